@@ -72,6 +72,10 @@ def parse():
     ap.add_argument("--triplet", action="store_true", help="also time the 2stg triplet step (f3: one triplet per optimiser step)")
     ap.add_argument("--ingest", action="store_true", help="also time the step fed with a NEW host batch every step (collate + "
                                                           "upload on a copy stream, double-buffered): `ingest` in the JSON line")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last of them computed (rank 0) as DIR/<name>.npy, float32: loss, "
+                         "head_hidden and logits (the forward's two outputs), param.<name> (every state_dict entry after the "
+                         "optimiser update) and grad.<name> (the gradient that update consumed)")
     return ap.parse_args()
 
 
@@ -321,6 +325,28 @@ def load_traffic():
         except (OSError, ValueError):
             continue
     return {}, None
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(d, model, trainer, head_hidden, logits, loss):
+    """--dump-outputs: what a caller of the timed step holds after it (the device has synchronised), as float32 .npy files"""
+    import numpy as np
+    arrays = {"loss": loss, "head_hidden": head_hidden, "logits": logits}
+    for name, t in model.state_dict().items():
+        arrays["param." + name] = t
+    names = [name for name, p in model.named_parameters() if p.requires_grad]      # = trainer.params, in the same order
+    for name, p, (o, n) in zip(names, trainer.params, trainer.views):
+        arrays["grad." + name] = trainer.flat_grad[o:o + n].view_as(p)
+    arrays = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit("--dump-outputs: %d bytes exceed the %d-byte limit" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(d, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), v)
+    print("dumped %d arrays (%d bytes) to %s" % (len(arrays), total, d), file=sys.stderr)
 
 
 # ----------------------------------------------------------------------------------------------- CPU baseline
@@ -700,8 +726,21 @@ def main():
     trainer.always_reduce = multi
 
     use_graph = not a.no_graph
+    # --dump-outputs: the forward's outputs and loss of every call recorded into a hipGraph (each replay rewrites those very
+    # tensors), and of the latest call run eagerly
+    captured, eager = [], []
+
+    def step_loss():
+        head_hidden, logits = model(x, g)
+        loss = model.loss(logits, label)
+        if a.dump_outputs:
+            if torch.cuda.is_current_stream_capturing():
+                captured.append((head_hidden.detach(), logits.detach(), loss))
+            else:
+                eager[:] = [(head_hidden.detach(), logits.detach(), loss)]
+        return loss
     # N = 1: one hipGraph for the whole step; N > 1: hipGraphs around the RCCL all-reduce (data_parallel.GraphedStep)
-    gstep = GraphedStep(trainer, lambda: model.loss(model(x, g)[1], label), warmup=3, use_graph=use_graph,
+    gstep = GraphedStep(trainer, step_loss, warmup=3, use_graph=use_graph,
                         steps_per_replay=1 if multi else max(1, a.steps_per_graph))
     stream = gstep.stream
     settle_steps = 0
@@ -731,6 +770,15 @@ def main():
             dist.barrier()
         torch.cuda.synchronize()
         elapsed = time.perf_counter() - t0
+        if a.dump_outputs and rank == 0:
+            if not use_graph:
+                last = eager[-1]
+            else:
+                # GraphedStep.run: graphs of k steps while they fit, single steps for the rest; the k-step graph is captured
+                # after the single-step one, so its calls are the last k recorded
+                k = gstep.steps_per_replay
+                last = captured[-1] if k == 1 or a.steps % k == 0 else captured[-1 - k]
+            dump_outputs(a.dump_outputs, model, trainer, *last)
         t = torch.tensor([elapsed], device=dev, dtype=torch.float64)
         per_rank = None
         if multi:

@@ -766,6 +766,46 @@ def test_bench_two_ranks_end_to_end_gloo():
     assert ar["us_alone"] > 0 and ar["bytes"] > 4 * 50000 and ar["backend"] == "gloo" and ar["buckets"] == 1
 
 
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_timed_step(tmp_path):
+    """`bench.py --dump-outputs DIR` writes what its LAST timed step computed.  W = 1 and K = 3 steps without settling at two steps per
+    graph launch: the timed steps are one 2-step replay and one single step, so the last step is not the 2-step graph's.  Judged against
+    the same four optimiser steps taken eagerly on the same model and batch."""
+    import json, subprocess
+    from two_stage_gnn_amd import dense_encoders as E, synthetic
+    from two_stage_gnn_amd.data_parallel import FlatTrainer
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--steps-per-graph", "2", "--settle-steps", "0", "--no-cpu-baseline", "--no-sweep", "--no-kernels", "--no-seeds",
+                        "--no-pyg", "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    d = json.loads(r.stdout.decode())
+    assert d["steps"] == 3 and d["steps_per_graph_launch"] == 2
+    got = {f[:-len(".npy")]: np.load(str(tmp_path / f)) for f in os.listdir(str(tmp_path))}
+    assert all(v.dtype == np.float32 for v in got.values())
+
+    class Args:
+        bias = True
+    dev = torch.device("cuda")
+    g, x, label = synthetic.to_device(synthetic.host_batch(seed=0, B=32, shape="DD", nmax=1000), dev)
+    torch.manual_seed(1234)                                          # bench.py's seed and model
+    model = E.GcnEncoderGraph(synthetic.SHAPES["DD"][2], 128, 128, 2, 3, bn=True, args=Args(), final_dim="number_classes").to(dev)
+    trainer = FlatTrainer(model, lr=1e-3, clip=2.0, defer_loss=True)
+    want = {}
+
+    def loss_fn():
+        want["head_hidden"], want["logits"] = model(x, g)
+        return model.loss(want["logits"], label)
+    for _ in range(4):
+        want["loss"] = trainer.step(loss_fn)
+    trainer.check()
+    want.update(("param." + k, v) for k, v in model.state_dict().items())
+    names = [k for k, p in model.named_parameters() if p.requires_grad]
+    want.update(("grad." + k, trainer.flat_grad[o:o + n].view_as(p)) for k, p, (o, n) in zip(names, trainer.params, trainer.views))
+    assert sorted(got) == sorted(want)
+    for k, v in want.items():
+        np.testing.assert_allclose(got[k], v.detach().float().cpu().numpy(), rtol=1e-5, atol=1e-6, err_msg=k)
+
+
 def _poison_worker(rank, world, port, q):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
     sys.path.insert(0, ROOT)
