@@ -24,7 +24,7 @@ typedef struct ihipStream_t* tsgnn_stream_t;
 extern "C" {
 #endif
 
-#define TSGNN_ABI_VERSION 1
+#define TSGNN_ABI_VERSION 2
 int tsgnn_abi_version(void);
 const char* tsgnn_strerror(int code);
 /* Diagnostic: name (template arguments included) of the device kernel that the calling thread's most recent entry-point call
@@ -289,15 +289,13 @@ int tsgnn_rowgemm_supported(const float* a, int64_t lda, const float* b, int64_t
 int tsgnn_rowgemm_f32(const float* a, int64_t lda, const float* b, int64_t ldb, int trans_b, const float* bias, float* c,
                       int64_t ldc, float* rinv, int64_t rows, int K, int N, int normalize, int64_t fill_rows,
                       tsgnn_stream_t stream);
-/* workgroups the row panels of a `rows`-row fused layer launch take on the current device: ceil(rows / 32) 32-row panels, or — when that
- * is a few more than the device has compute units — one full panel per unit and the remaining rows as 16-row units (a unit with two
- * full panels decided the launch: 1.3-1.4 x).  For callers that size a co-resident role of the same launch (encoders.py:33-40 backward:
- * the weight-gradient slab blocks beside the input-gradient panels). */
-int tsgnn_panel_blocks(int64_t rows);
-/* on = 0: the fused layer launches issued by this process keep plain 32-row panels until on = 1 again (process-wide, not per thread: a
- * backward's launches come from autograd's thread).  For capacity-padded batches — ingest.IngestPipeline captures its steps under it: the
- * rows beyond one panel per unit are mostly padding there.  Not for concurrent use by two trainers of one process. */
-int tsgnn_panel_split_hint(int on);
+/* workgroups the row panels of a `rows`-row fused layer launch take on the current device: ceil(rows / 32) 32-row panels, or — when
+ * panel_units != 0 and that is a few more than the device has compute units — one full panel per unit and the remaining rows as 16- or
+ * 8-row units (a unit with two full panels decided the launch: 1.3-1.4 x).  panel_units is the argument of that name of the fused layer
+ * launches (tsgnn_gather_rowgemm_st_f32, tsgnn_sage_layer_fwd_bn_f32, tsgnn_sage_layer_bwd_f32): a property of the batch, 0 for
+ * capacity-padded batches, whose rows beyond one panel per unit are mostly padding.  For callers that size a co-resident role of the
+ * same launch (encoders.py:33-40 backward: the weight-gradient slab blocks beside the input-gradient panels). */
+int tsgnn_panel_blocks(int64_t rows, int panel_units);
 /* Aggregation fused into the product (GraphConv.forward lines encoders.py:33-40 in one launch; and its input gradient
  * dX = (A dU) W^T for a symmetric A): the A operand of tsgnn_rowgemm_f32 is replaced by
  *   z[r,:] = sum_k x[ell[r*ell_w + k], :K]      (ell = fixed-width neighbour table of tsgnn_csr_to_ell, entries < 0 skipped,
@@ -314,10 +312,12 @@ int tsgnn_gather_rowgemm_f32(const int* ell, int ell_w, const int* tail_ptr, con
  * (sum_f relu(v), sum_f relu(v)^2) to sums[2 * row_slot[r]] as 64-bit fixed-point integers (2^-40 units: integer addition is
  * associative, so the totals do not depend on the order the panels finish in — bitwise reproducible) and the filler block leaves
  * the ghost row's two numbers in ghost[0..1].  sums [2 * nslots], 16-byte aligned, zero before the launch; row_slot[r] < 0: row r
- * belongs to no graph (padding of a capacity-padded batch).  Consumer: tsgnn_sage_layer_fwd_bn_f32. */
+ * belongs to no graph (padding of a capacity-padded batch).  panel_units: row panels as in tsgnn_panel_blocks.  Consumer:
+ * tsgnn_sage_layer_fwd_bn_f32. */
 int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* x, int64_t ldx, const float* b, int64_t ldb, const float* bias,
                                 float* c, int64_t ldc, float* rinv, float* zout, int64_t ldz, int64_t rows, int K, int N,
-                                int64_t fill_rows, const int* row_slot, unsigned long long* sums, float* ghost, tsgnn_stream_t stream);
+                                int64_t fill_rows, const int* row_slot, unsigned long long* sums, float* ghost, int panel_units,
+                                tsgnn_stream_t stream);
 /* tsgnn_sage_layer_fwd[_ro]_f32 for a layer whose INPUT's slot batch-norm has no launch of its own: x = the previous layer's
  * normalised pre-activations v, sums_in / ghost_in = what its statistics epilogue left, slot_count[n] = graphs with more than n
  * nodes.  Every row-panel block turns the sums into (mean, rstd) per slot — exact from the integers, ghost copies by their
@@ -326,18 +326,22 @@ int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, 
  * backward (tsgnn_slot_post_bwd_f32).  ell / tail_col: entry = slot << 20 | row, nslots <= 1024, rows < 2^20, n_ghost = nslots.
  * row_slot != NULL: this layer is followed by a batch-norm as well, its statistics go to sums_out / ghost_out (zero before);
  * packed_out != NULL: last layer, readout epilogue as in tsgnn_sage_layer_fwd_ro_f32 (not both).  ro_map (nullable): see
- * tsgnn_sage_layer_fwd_bn_plan; ignored unless ro_map_ch equals the chunk size the launch uses. */
+ * tsgnn_sage_layer_fwd_bn_plan; ignored unless ro_map_ch equals the chunk size the launch uses.  panel_units: row panels as in
+ * tsgnn_panel_blocks. */
 int tsgnn_sage_layer_fwd_bn_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias,
                                 float* v, int64_t ldv, float* rinv, float* zout, int64_t ldz, int64_t rows, int K, int64_t fill_rows,
                                 const int* graph_ptr, const int* slot_count, int B, int nslots, int n_ghost, unsigned long long* packed,
                                 unsigned long long* packed_out, const int* row_graph, const unsigned long long* sums_in,
                                 const float* ghost_in, float* mean_out, float* rstd_out, const int* row_slot,
-                                unsigned long long* sums_out, float* ghost_out, const int* ro_map, int ro_map_ch, tsgnn_stream_t stream);
-/* HOST function: slots per readout block (64 / 128 / 256) and row-panel blocks (filler included) of that launch — what a caller needs to
- * build ro_map: a permutation of the B * ceil(nslots / ro_ch) readout work items (graph * chunks + chunk) that puts the blocks scanning
- * a graph on the XCD whose row panels gather it (workgroups b, b + 8, ... share an XCD; the k-th readout block is workgroup n_gemm + k).
+                                unsigned long long* sums_out, float* ghost_out, const int* ro_map, int ro_map_ch, int panel_units,
+                                tsgnn_stream_t stream);
+/* HOST function: slots per readout block (64 / 128 / 256), row-panel blocks (filler included) and full 32-row panels ahead of the
+ * units (0: plain panels) of that launch with the same panel_units — what a caller needs to build ro_map: a permutation of the
+ * B * ceil(nslots / ro_ch) readout work items (graph * chunks + chunk) that puts the blocks scanning a graph on the XCD whose row
+ * panels gather it (workgroups b, b + 8, ... share an XCD; the k-th readout block is workgroup n_gemm + k).
  * Speed only: any permutation gives the same results. */
-int tsgnn_sage_layer_fwd_bn_plan(int64_t rows, int64_t fill_rows, int B, int nslots, int* ro_ch, int* n_gemm);
+int tsgnn_sage_layer_fwd_bn_plan(int64_t rows, int64_t fill_rows, int B, int nslots, int panel_units, int* ro_ch, int* n_gemm,
+                                 int* n_full);
 /* Forward of a hidden 128 -> 128 GraphConv layer in ONE launch together with the max-readout partial of its INPUT x (the
  * previous layer's output; both only read x): tsgnn_gather_rowgemm_f32(normalize = 1, fill_rows) + tsgnn_readout_partial_f32
  * over x into packed[B*128] (layout and ghost-row rule as there; n_real = rows). */
@@ -355,10 +359,11 @@ int tsgnn_sage_layer_fwd_ro_f32(const int* ell, int ell_w, const int* tail_ptr, 
 /* Backward of a hidden 128 -> 128 GraphConv layer's GEMM-shaped halves in ONE launch (both consume du): the weight / bias
  * gradient slabs of tsgnn_linear_wgrad_f32 (dw == NULL form: reduce ws later with tsgnn_wgrad_reduce_multi_f32; plan with
  * tsgnn_linear_wgrad_plan(rows, 128, 128, ...)) and dxs = (A du) w^T of tsgnn_gather_rowgemm_f32 (trans_b = 1, symmetric A).
- * A CU hosts one block of each grid, so the two run side by side instead of back to back. */
+ * A CU hosts one block of each grid, so the two run side by side instead of back to back.  panel_units: row panels as in
+ * tsgnn_panel_blocks. */
 int tsgnn_sage_layer_bwd_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* du, int64_t lddu, const float* w, int64_t ldw, float* dxs,
                              int64_t lddxs, const float* z, int64_t ldz, int64_t rows, int nslab, int64_t rows_per_slab,
-                             int64_t bias_only_rows, float* ws, tsgnn_stream_t stream);
+                             int64_t bias_only_rows, float* ws, int panel_units, tsgnn_stream_t stream);
 /* backward of the row normalisation: du = rinv * (dv - v (v.dv)) */
 int tsgnn_l2norm_bwd_f32(const float* v, int64_t ldv, const float* dv, int64_t lddv, const float* rinv, float* du,
                          int64_t lddu, int64_t rows, int F, tsgnn_stream_t stream);

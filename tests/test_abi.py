@@ -6,7 +6,7 @@ import os
 import pytest
 
 
-def test_header_parses_and_library_exports_every_symbol():
+def test_header_parses_and_library_exports_every_symbol_of_abi_2():
     from two_stage_gnn_amd import _native as nat
     decls = nat.parse_header()
     assert len(decls) >= 20 and "tsgnn_csr_spmm_f32" in decls
@@ -14,8 +14,23 @@ def test_header_parses_and_library_exports_every_symbol():
     L = ctypes.CDLL(nat.LIB_PATH)
     missing = [n for n in decls if not hasattr(L, n)]
     assert not missing, missing
-    assert nat.lib().tsgnn_abi_version() == 1
+    assert nat.lib().tsgnn_abi_version() == 2
     assert b"invalid" in nat.lib().tsgnn_strerror(-1)
+
+
+def test_panel_split_is_an_argument_not_process_state():
+    """the row-panel split travels with the batch (panel_units argument): no process-wide switch is declared or exported.  Without a
+    GPU the compute-unit count falls back to 256, which is also what an MI355X reports"""
+    from two_stage_gnn_amd import _native as nat
+    switch, flag = ("tsgnn_panel_split_" + s for s in ("hint", "on_"))      # (the round-4 switch and the variable it set)
+    assert switch not in nat.parse_header() and switch not in open(nat.HEADER).read()
+    blocks = nat.lib().tsgnn_panel_blocks
+    L = ctypes.CDLL(nat.LIB_PATH)
+    assert not hasattr(L, switch) and not hasattr(L, flag)
+    for rows, want in ((8151, 255), (8660, 315), (9200, 319), (20000, 625)):
+        assert blocks(rows, 1) == want, (rows, blocks(rows, 1))
+        assert blocks(rows, 0) == -(-rows // 32)
+    assert blocks(0, 1) == 0
 
 
 def test_invalid_arguments_are_rejected_without_a_gpu():

@@ -100,12 +100,13 @@ def _run(model, loss_fn, forward32, forward64, lr, clip=2.0, steps=3, defer_loss
     return report
 
 
-def test_panel_units_equal_plain_panels():
+def test_panel_units_batch_equals_plain_panel_batch():
     """rows beyond one 32-row panel per compute unit as 16- / 8-row units (csrc/rowgemm_body.h panel_split; the first layer's product, the
-    fused forward launches, the merged backward launches) against plain panels on the SAME batches (switched per process with
-    tsgnn_panel_split_hint): a row's arithmetic does not depend on the block that owns it, so logits, loss and the input-side results
-    are BITWISE equal; the weight gradients are sums over differently cut slabs (the slab count follows the panel blocks) and agree to
-    rounding.  Batches of 271 (8-row units) and 288 panels (16-row units)."""
+    fused forward launches, the merged backward launches) against plain panels on the SAME batches (two fresh batch objects of one seed,
+    one of them with panel_units = False): a row's arithmetic does not depend on the block that owns it, so logits, loss and the
+    input-side results are BITWISE equal; the weight gradients are sums over differently cut slabs (the slab count follows the panel
+    blocks) and agree to rounding.  The two batches run interleaved in one process (forward, forward, backward, backward): the split
+    travels with the batch, not with the order of the calls.  Batches of 271 (8-row units) and 288 panels (16-row units)."""
     from two_stage_gnn_amd import dense_encoders as E, synthetic, _native as nat
     dev = torch.device("cuda")
 
@@ -118,23 +119,35 @@ def test_panel_units_equal_plain_panels():
         ncu = torch.cuda.get_device_properties(dev).multi_processor_count
         if not (ncu < npan <= ncu + ncu // 2):
             pytest.skip("this device hosts every panel of the batch at once")
-        blocks = int(nat.lib().tsgnn_panel_blocks(int(g.n_rows)))
+        blocks = int(nat.lib().tsgnn_panel_blocks(int(g.n_rows), 1))
         assert blocks == (ncu & ~7) + -(-(g.n_rows - 32 * (ncu & ~7)) // want_unit), (blocks, npan)
-        out = []
-        for on in (1, 0):
-            nat.call_nostream("panel_split_hint", on)
-            try:
-                assert (int(nat.lib().tsgnn_panel_blocks(int(g.n_rows))) == npan) == (on == 0)
-                torch.manual_seed(11)
-                m = E.GcnEncoderGraph(89, 128, 128, 2, 3, bn=True, args=A(), final_dim="number_classes").to(dev)
-                g2, x2, _ = synthetic.to_device(hb, dev)              # (a fresh batch object: no cached launch plans)
-                logits = m(x2, g2)[1]
-                loss = m.loss(logits, label)
-                loss.backward()
+        assert int(nat.lib().tsgnn_panel_blocks(int(g.n_rows), 0)) == npan
+        runs = []
+        for units in (True, False):
+            torch.manual_seed(11)
+            m = E.GcnEncoderGraph(89, 128, 128, 2, 3, bn=True, args=A(), final_dim="number_classes").to(dev)
+            g2, x2, _ = synthetic.to_device(hb, dev)              # (a fresh batch object: no cached launch plans)
+            g2.panel_units = units
+            runs.append({"m": m, "g": g2, "x": x2})
+        prev = nat.trace
+        try:
+            for r in runs:                                        # forward of one batch, then of the other ...
+                nat.trace = r["fwd"] = []
+                r["logits"] = r["m"](r["x"], r["g"])[1]
+                r["loss"] = r["m"].loss(r["logits"], label)
+            for r in runs:                                        # ... then both backwards
+                nat.trace = r["bwd"] = []
+                r["loss"].backward()
                 torch.cuda.synchronize()
-                out.append((logits.detach().clone(), float(loss.detach()), [p.grad.detach().clone() for p in m.parameters() if p.grad is not None]))
-            finally:
-                nat.call_nostream("panel_split_hint", 1)
+        finally:
+            nat.trace = prev
+        for r, flag in zip(runs, ("true", "false")):
+            fwd = [k for _, _, k in r["fwd"]]
+            bwd = [k for _, _, k in r["bwd"]]
+            assert "rowgemm_gather_st_kernel<%s>" % flag in fwd, fwd
+            assert "sage_layer_bwd_kernel<true,%s>" % flag in bwd, bwd
+        out = [(r["logits"].detach(), float(r["loss"].detach()), [p.grad.detach() for p in r["m"].parameters() if p.grad is not None])
+               for r in runs]
         assert torch.equal(out[0][0], out[1][0]) and out[0][1] == out[1][1]
         for a, b in zip(out[0][2], out[1][2]):
             torch.testing.assert_close(a, b, rtol=2e-5, atol=1e-7 * float(b.abs().max() + 1e-30) + 1e-9)

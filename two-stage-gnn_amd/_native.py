@@ -151,7 +151,7 @@ def lib():
             raise RuntimeError("libtsgnn_hip.so does not export %s (declared in include/tsgnn.h); rebuild" % name)
         fn.restype = ret
         fn.argtypes = [p[0] for p in params]
-    if L.tsgnn_abi_version() != 1:
+    if L.tsgnn_abi_version() != 2:
         raise RuntimeError("libtsgnn_hip.so ABI version mismatch")
     _lib = L
     return L

@@ -45,6 +45,15 @@ extern thread_local char tsgnn_kname_[160];
 
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// compute units of the device current at first use, for the process (256 when the query fails): what launch geometries are sized by
+inline int device_cu_count() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    return (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
+  }();
+  return n;
+}
+
 // store of a value that THIS kernel will not read again (results handed to a later launch): -DTSGNN_NT_STORES=1 marks them
 // non-temporal.  Measured (round 3, A/B of two builds through TSGNN_LIB_PATH): the producers' own burst times drop (row panels
 // 10.0 -> 9.4 / 14.5 -> 13.8 / 13.1 -> 12.1 us: less to write back at the kernel boundary) and the replayed STEP does not move at all

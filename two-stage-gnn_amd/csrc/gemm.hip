@@ -463,12 +463,7 @@ int tsgnn_linear_wgrad_plan(int64_t rows, int K_in, int N, int64_t ldz, int64_t 
   if (K_in <= 0 || N <= 0 || K_in > 128 || N > 128 || (ldz % 4) || (lddu % 4) || (N % 4)) return TSGNN_OK;
   // one round of equal blocks: (slabs x blocks per slab) = number of CUs.  A grid a little over the CU count would
   // put two blocks on some CUs, and those decide the kernel time (measured: 286 blocks 9.9 us, 256 blocks 6.5 us).
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ncu = v;
-    else ncu = 256;
-  }
+  const int ncu = device_cu_count();
   const int tiles = ((K_in + 31) / 32) * ((N + 31) / 32);
   const int per_slab_blocks = tiles >= 8 ? 2 : 1;
   int64_t rps = ceil_div64(rows > 0 ? rows : 1, ncu / per_slab_blocks);
@@ -683,16 +678,6 @@ int tsgnn_wgrad_reduce_sets_f32(const int64_t* desc, tsgnn_stream_t stream) {
   return TSGNN_OK;
 }
 
-static int wgrad_blocks_cus() {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    if (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ncu = v;
-    else ncu = 256;
-  }
-  return ncu;
-}
-
 int tsgnn_wgrad_blocks_plan(int64_t rows, int K_in, int N, int64_t ldz, int64_t lddu, int* nslab, int64_t* rows_per_slab,
                             int64_t* ws_floats) {
   if (!nslab || !rows_per_slab || !ws_floats || rows < 0) return TSGNN_EINVAL;
@@ -702,7 +687,7 @@ int tsgnn_wgrad_blocks_plan(int64_t rows, int K_in, int N, int64_t ldz, int64_t 
   if (nsets > WB_MAXSETS) return TSGNN_OK;
   // two workgroups of 64 KB LDS fit a CU: (slabs x sets x 2 blocks per set) ~ 2 x CUs, every block in flight at once
   static const int per_cu = [] { const char* e = getenv("TSGNN_WGRAD_BLOCKS_PER_CU"); const int v = e ? atoi(e) : 2; return v > 0 ? v : 2; }();
-  int64_t ns = (int64_t)per_cu * wgrad_blocks_cus() / (2 * nsets);
+  int64_t ns = (int64_t)per_cu * device_cu_count() / (2 * nsets);
   if (ns < 1) ns = 1;
   int64_t rps = ceil_div64(rows > 0 ? rows : 1, ns);
   rps = ((rps + 31) / 32) * 32;                           // whole staged chunks

@@ -997,11 +997,7 @@ static int head2_bwd_launch(const float* out, int64_t ldo, const float* vec, con
     int du_chunk = 64;
     if (du) {
       dua = *du;                                         // (du->chunks carries the largest graph's bound: see the entry point)
-      static int ncu = 0;
-      if (ncu == 0) {
-        int dev = 0, v = 0;
-        ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-      }
+      const int ncu = device_cu_count();
       const int nodes = dua.chunks;                      // bound on the largest graph
       const int other = B + (E + 3) / 4 + 1;
       unsigned compact_blocks = 0;

@@ -43,7 +43,7 @@ extern "C" {
 
 int tsgnn_sage_layer_bwd_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* du, int64_t lddu, const float* w, int64_t ldw, float* dxs,
                              int64_t lddxs, const float* z, int64_t ldz, int64_t rows, int nslab, int64_t rows_per_slab,
-                             int64_t bias_only_rows, float* ws, tsgnn_stream_t stream) {
+                             int64_t bias_only_rows, float* ws, int panel_units, tsgnn_stream_t stream) {
   if (!ell || !du || !w || !dxs || !z || !ws || rows <= 0 || nslab <= 0 || rows_per_slab <= 0 || bias_only_rows < 0) return TSGNN_EINVAL;
   if (ell_w != 4 && ell_w != 8 && ell_w != 16) return TSGNN_EUNSUPPORTED;
   const uintptr_t al = reinterpret_cast<uintptr_t>(ell) | reinterpret_cast<uintptr_t>(du) | reinterpret_cast<uintptr_t>(w) |
@@ -54,12 +54,8 @@ int tsgnn_sage_layer_bwd_f32(const int* ell, int ell_w, const int* tail_ptr, con
   if ((tail_ptr == nullptr) != (tail_col == nullptr)) return TSGNN_EINVAL;
   RowGemmArgs ga{du, lddu, w, ldw, nullptr, dxs, lddxs, nullptr, rows, 128, 128, 0, 0, ell, ell_w, nullptr, 0, tail_ptr, tail_col};
   TnArgs gt{z, ldz, du, lddu, rows, rows_per_slab, 128, 128, ws, nullptr, bias_only_rows};
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  const unsigned n_tn = 2u * (unsigned)nslab, n_pan = panel_split(rows, ncu, &ga.n_full, &ga.unit);   // (a few more panels than CUs: 16-row units)
+  const int ncu = device_cu_count();
+  const unsigned n_tn = 2u * (unsigned)nslab, n_pan = panel_split(rows, ncu, panel_units, &ga.n_full, &ga.unit);   // (a few more panels than CUs: 16-row units)
   constexpr size_t la = rowgemm_lds_bytes<4, true, true>(), lt = tn_rows_lds_bytes<4, 4>();
   static const int panels_first = [] { const char* e = getenv("TSGNN_BWD_PANELS_FIRST"); return e ? atoi(e) : 1; }();
   // the slab blocks wait `delay` x ~0.43 us before their first request: with at most one row panel per CU the panels' two dependent gather

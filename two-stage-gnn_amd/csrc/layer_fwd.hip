@@ -57,13 +57,13 @@ __global__ __launch_bounds__(256, 2) void sage_layer_fwd_bn_kernel(RowGemmArgs g
 
 extern "C" {
 
-/* slots per readout block and row-panel blocks (filler included) of a tsgnn_sage_layer_fwd_bn_f32 launch: what a caller needs to build ro_map */
-int tsgnn_sage_layer_fwd_bn_plan(int64_t rows, int64_t fill_rows, int B, int nslots, int* ro_ch, int* n_gemm) {
-  if (!ro_ch || !n_gemm || rows <= 0 || B <= 0 || nslots <= 0) return TSGNN_EINVAL;
-  int dev = 0, v = 0;
-  const int ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  int n_full_ = 0, unit_ = 16;
-  const unsigned ng = panel_split(rows, ncu, &n_full_, &unit_) + (fill_rows > 0 ? 1u : 0u);
+/* slots per readout block, row-panel blocks (filler included) and full 32-row panels ahead of the units (0: plain panels) of a
+ * tsgnn_sage_layer_fwd_bn_f32 launch: what a caller needs to build ro_map */
+int tsgnn_sage_layer_fwd_bn_plan(int64_t rows, int64_t fill_rows, int B, int nslots, int panel_units, int* ro_ch, int* n_gemm, int* n_full) {
+  if (!ro_ch || !n_gemm || !n_full || rows <= 0 || B <= 0 || nslots <= 0) return TSGNN_EINVAL;
+  const int ncu = device_cu_count();
+  int unit_ = 16;
+  const unsigned ng = panel_split(rows, ncu, panel_units, n_full, &unit_) + (fill_rows > 0 ? 1u : 0u);
   int ch = 64;
   while (ch < 256 && ng + (unsigned)((nslots + ch - 1) / ch) * (unsigned)B > 2u * (unsigned)ncu) ch *= 2;
   *ro_ch = ch; *n_gemm = (int)ng;
@@ -85,7 +85,8 @@ int tsgnn_sage_layer_fwd_bn_f32(const int* ell, int ell_w, const int* tail_ptr, 
                                 const int* graph_ptr, const int* slot_count, int B, int nslots, int n_ghost, unsigned long long* packed,
                                 unsigned long long* packed_out, const int* row_graph, const unsigned long long* sums_in,
                                 const float* ghost_in, float* mean_out, float* rstd_out, const int* row_slot,
-                                unsigned long long* sums_out, float* ghost_out, const int* ro_map, int ro_map_ch, tsgnn_stream_t stream) {
+                                unsigned long long* sums_out, float* ghost_out, const int* ro_map, int ro_map_ch, int panel_units,
+                                tsgnn_stream_t stream) {
   if (!ell || !x || !w || !v || !rinv || !graph_ptr || !slot_count || !packed || !sums_in || !ghost_in || !mean_out || !rstd_out ||
       rows <= 0 || fill_rows < 0 || K <= 0 || B <= 0 || nslots <= 0 || (n_ghost != 0 && n_ghost != nslots) || (packed_out && !row_graph) ||
       (row_slot && (!sums_out || !ghost_out)))
@@ -107,12 +108,8 @@ int tsgnn_sage_layer_fwd_bn_f32(const int* ell, int ell_w, const int* tail_ptr, 
   BnReadArgs bn{sums_in, ghost_in, K, mean_out, rstd_out};
   // slots per readout block: 64 while [panels + readout blocks] fit two blocks per compute unit (what the registers allow), else 128
   // or 256 — DD seed 2: 266 panels + 256 readout blocks = 523 > 512 ran a third round for eleven blocks (13.9 -> 17.8 us)
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  const unsigned n_gemm = panel_split(rows, ncu, &ga.n_full, &ga.unit) + (fill_rows > 0 ? 1u : 0u);   // (a few more panels than CUs: 16-row units)
+  const int ncu = device_cu_count();
+  const unsigned n_gemm = panel_split(rows, ncu, panel_units, &ga.n_full, &ga.unit) + (fill_rows > 0 ? 1u : 0u);   // (a few more panels than CUs: 16-row units)
   int ro_ch = 64;
   while (ro_ch < 256 && n_gemm + (unsigned)((nslots + ro_ch - 1) / ro_ch) * (unsigned)B > 2u * (unsigned)ncu) ro_ch *= 2;
   const unsigned ro_gx = (unsigned)((nslots + ro_ch - 1) / ro_ch);

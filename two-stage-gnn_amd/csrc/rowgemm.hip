@@ -20,23 +20,9 @@
 #include <cstdlib>
 #include "rowgemm_body.h"
 #include "ingest_rider.h"
-
-int tsgnn_panel_split_on_ = 1;
 #include "rowgemm_big_body.h"
 
 namespace {
-
-inline int device_cu_count() {
-  static const int n = [] {
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-      hipDeviceProp_t p;
-      if (hipGetDeviceProperties(&p, dev) == hipSuccess && p.multiProcessorCount > 0) cus = p.multiProcessorCount;
-    }
-    return cus;
-  }();
-  return n;
-}
 
 inline unsigned ks2_max_blocks() {                       // TSGNN_KS2_MAX_BLOCKS: up to how many row panels the two-group kernel is used
   static const unsigned n = [] { const char* e = getenv("TSGNN_KS2_MAX_BLOCKS"); return e ? (unsigned)atoi(e) : (unsigned)device_cu_count(); }();
@@ -271,7 +257,8 @@ int tsgnn_rowgemm_f32(const float* a, int64_t lda, const float* b, int64_t ldb, 
  * graph (padding of a capacity-padded batch).  The consumer is tsgnn_sage_layer_fwd_bn_f32. */
 int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* x, int64_t ldx, const float* b, int64_t ldb, const float* bias,
                                 float* c, int64_t ldc, float* rinv, float* zout, int64_t ldz, int64_t rows, int K, int N,
-                                int64_t fill_rows, const int* row_slot, unsigned long long* sums, float* ghost, tsgnn_stream_t stream) {
+                                int64_t fill_rows, const int* row_slot, unsigned long long* sums, float* ghost, int panel_units,
+                                tsgnn_stream_t stream) {
   if (!ell || !x || !b || !c || !row_slot || !sums || !ghost || rows <= 0 || fill_rows < 0 || K <= 0 || N <= 0 || ldx < K || ldc < N)
     return TSGNN_EINVAL;
   if (ell_w != 4 && ell_w != 8 && ell_w != 16) return TSGNN_EUNSUPPORTED;
@@ -285,14 +272,8 @@ int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, 
   g.st_row_slot = row_slot; g.st_sums = sums; g.st_ghost = ghost;
   unsigned nblk = (unsigned)(ceil_div64(rows, 32) + (fill_rows > 0 ? 1 : 0));
   const bool ks2 = K > KC && nblk <= ks2_max_blocks() && rowgemm_ks2_enabled();
-  if (!ks2) {                                            // (the one-group kernel: a few more panels than CUs go as 16-row units)
-    static int ncu = 0;
-    if (ncu == 0) {
-      int dev = 0, v = 0;
-      ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-    }
-    nblk = panel_split(rows, ncu, &g.n_full, &g.unit) + (fill_rows > 0 ? 1u : 0u);
-  }
+  if (!ks2)                                              // (the one-group kernel: a few more panels than CUs go as 16-row units)
+    nblk = panel_split(rows, device_cu_count(), panel_units, &g.n_full, &g.unit) + (fill_rows > 0 ? 1u : 0u);
   if (ks2) {
     constexpr size_t lds2 = rowgemm_lds_bytes<4, false, true, 2>();
     static bool attr = false;
@@ -313,24 +294,13 @@ int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, 
   return TSGNN_OK;
 }
 
-/* on = 0: the fused layer launches of this PROCESS keep plain 32-row panels until it is switched back on (default on) */
-int tsgnn_panel_split_hint(int on) {
-  tsgnn_panel_split_on_ = on ? 1 : 0;
-  return TSGNN_OK;
-}
-
-/* workgroups the row panels of a `rows`-row launch take on the current device (rowgemm_body.h panel_split: 32-row panels, or — a few more
- * panels than compute units — one full panel per unit and the rest of the rows in 16-row units); callers that size a co-resident role
- * (the merged backward launch's slab blocks) plan with this */
-int tsgnn_panel_blocks(int64_t rows) {
+/* workgroups the row panels of a `rows`-row launch take on the current device (rowgemm_body.h panel_split: 32-row panels, or — panel_units
+ * != 0 and a few more panels than compute units — one full panel per unit and the rest of the rows in 16-row units); callers that size a
+ * co-resident role (the merged backward launch's slab blocks) plan with this */
+int tsgnn_panel_blocks(int64_t rows, int panel_units) {
   if (rows <= 0) return 0;
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
   int nf = 0, un = 16;
-  return (int)panel_split(rows, ncu, &nf, &un);
+  return (int)panel_split(rows, device_cu_count(), panel_units, &nf, &un);
 }
 
 int tsgnn_gather_rowgemm_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* x, int64_t ldx, const float* b, int64_t ldb, int trans_b,

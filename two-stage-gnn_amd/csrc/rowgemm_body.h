@@ -4,8 +4,6 @@
 #pragma once
 #include "common.h"
 #include <type_traits>
-
-extern int tsgnn_panel_split_on_;                       // rowgemm.hip; see panel_split() below
 #include <cstdlib>
 
 namespace {
@@ -63,14 +61,13 @@ inline int panel_unit_rows(int64_t rows, int ncu) {
   if (forced) return forced;
   return ((rows + 31) / 32 - ncu) <= ncu / 16 ? 8 : 16;
 }
-// 0: launches keep plain 32-row panels (tsgnn_panel_split_hint; process-wide — a backward's launches are issued by autograd's own
-// thread, so a thread-local switch would miss them: capacity-padded batches, whose rows beyond one panel
-// per CU are mostly PADDING — cut into units they cost a block's fixed work each and gather nothing: the ingest step 0.1494 -> 0.1541 ms)
-inline unsigned panel_split(int64_t rows, int ncu, int* n_full, int* unit) {
-  static const bool on = [] { const char* e = getenv("TSGNN_HALF_PANELS"); return e ? atoi(e) != 0 : true; }();
+// panel_units = 0: plain 32-row panels.  The caller passes the batch's own choice (GraphBatch.panel_units): capacity-padded batches
+// (ingest.CapacityBatch) keep plain panels, because their rows beyond one panel per CU are mostly PADDING — cut into units they cost
+// a block's fixed work each and gather nothing (the ingest step 0.1494 -> 0.1541 ms)
+inline unsigned panel_split(int64_t rows, int ncu, int panel_units, int* n_full, int* unit) {
   const int64_t P = (rows + 31) / 32;
   *n_full = 0; *unit = 32;
-  if (!on || !tsgnn_panel_split_on_ || ncu < 8) return (unsigned)P;
+  if (!panel_units || ncu < 8) return (unsigned)P;
   // (small batches — PROTEINS b64: 77 panels — cut entirely into 16- or 8-row units to occupy more CUs: 116.9 -> 117.2 / 125.4 us per
   // step, measured and left out: a block's fixed work — all of W, a whole MFMA chain — does not shrink with its rows)
   if (P <= ncu || P - ncu > ncu / 2) return (unsigned)P;

@@ -445,12 +445,7 @@ constexpr int PG_SMALL_NODES = 256;       // batches whose graphs all fit this M
 // sooner (more lane groups per phase): IMDB-B b128, the level-0 kernels 13.8 -> 10.2 us forward, 11.2 -> 7.2 us backward, the step
 // 132.3 -> 123.3 us (measured with the threshold forced either way).
 inline bool pg_small_block(int max_seg, int B) {
-  static int ncu = 0;
-  if (ncu == 0) {
-    int dev = 0, v = 0;
-    ncu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-  }
-  return max_seg <= PG_SMALL_NODES && B > 2 * ncu;
+  return max_seg <= PG_SMALL_NODES && B > 2 * device_cu_count();
 }
 #ifndef TSGNN_PG_RGROUPS
 #define TSGNN_PG_RGROUPS 8

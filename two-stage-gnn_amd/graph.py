@@ -14,7 +14,6 @@ Row layouts
             drop-in ``GraphConv.forward(x[B,N,F], adj[B,N,N])`` whose output must be padded too).
 Feature matrices have ``total_rows = n_rows + n_ghost`` rows; ghost rows have empty neighbour lists.
 """
-import os
 import numpy as np
 import torch
 
@@ -58,6 +57,9 @@ class GraphBatch:
         self.symmetric = False
         self._t = None
         self.device = None
+        # rows beyond one 32-row panel per compute unit may go as 16- / 8-row units in the fused layer launches (the panel_units
+        # argument, csrc/rowgemm_body.h panel_split).  Fixed when the batch is built: launch plans are cached per batch.
+        self.panel_units = True
 
     @property
     def total_rows(self):
@@ -303,13 +305,12 @@ class GraphBatch:
         if key not in cache:
             ch = np.zeros(1, dtype=np.int32)
             ng = np.zeros(1, dtype=np.int32)
-            nat.call_nostream("sage_layer_fwd_bn_plan", int(self.n_rows), int(fill_rows), int(self.B), int(nslots), ch.ctypes.data, ng.ctypes.data)
-            ch, ng = int(ch[0]), int(ng[0])
+            nf = np.zeros(1, dtype=np.int32)
+            nat.call_nostream("sage_layer_fwd_bn_plan", int(self.n_rows), int(fill_rows), int(self.B), int(nslots), int(self.panel_units),
+                              ch.ctypes.data, ng.ctypes.data, nf.ctypes.data)
+            ch, ng, nf = int(ch[0]), int(ng[0]), int(nf[0])
             chunks = -(-int(nslots) // ch)
-            npan = -(-self.n_rows // 32)
-            ncu = torch.cuda.get_device_properties(self.device).multi_processor_count
-            if npan > ncu and npan - ncu <= ncu // 2 and os.environ.get("TSGNN_HALF_PANELS", "1") != "0":
-                npan = ncu & ~7            # (rowgemm_body.h panel_split: the full panels; the rows behind them go as 16-row units on any XCD)
+            npan = nf or -(-self.n_rows // 32)     # (with units: the full panels; the rows behind them go as units on any XCD)
             q, r = divmod(npan, 8)
             start = np.zeros(9, dtype=np.int64)
             for x in range(8):

@@ -111,6 +111,8 @@ class CapacityBatch:
         g.symmetric = True
         g.sizes = None
         g.ghost_slots_fixed = self.nmax if ghost_slots is None else int(ghost_slots)
+        # plain 32-row panels: the rows beyond one panel per CU are mostly padding here (csrc/rowgemm_body.h, panel_split)
+        g.panel_units = False
         # the neighbour table of this batch is rewritten on the device every step, and so is its slot-annotated copy (the operand
         # of the fused slot batch-norm path, GraphBatch.ell_slots): the expansion writes both
         self.ell_slots = torch.full((R * ELL_W,), -1, dtype=torch.int32, device=device)
@@ -311,15 +313,9 @@ class IngestPipeline:
                     nat.call("ingest_flush_pull_rider")       # (a model without such a launch: the riders as launches of their own)
                     return out
                 return loss
-        # capacity-padded batches keep plain 32-row panels: their rows beyond one panel per CU are mostly padding (csrc/rowgemm_body.h,
-        # panel_split; the decision is taken when the launches are captured)
-        nat.call_nostream("panel_split_hint", 0)
-        try:
-            for p, s in enumerate(self.slots):
-                fn = make_loss_ride(s, self.slots[(p + 1) % depth]) if self.ride else make_loss(s)
-                self.steps.append(GraphedStep(trainer, fn, warmup=2, stream=self.compute))
-        finally:
-            nat.call_nostream("panel_split_hint", 1)
+        for p, s in enumerate(self.slots):
+            fn = make_loss_ride(s, self.slots[(p + 1) % depth]) if self.ride else make_loss(s)
+            self.steps.append(GraphedStep(trainer, fn, warmup=2, stream=self.compute))
 
     def run(self, schedule=None, workers=2, ticks=None):
         """enqueue one step per entry of the schedule; returns after the last step is enqueued (caller synchronises).

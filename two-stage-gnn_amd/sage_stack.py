@@ -79,7 +79,7 @@ def _cu_count(dev):
     return n
 
 
-def _slabs_beside_panels(nslab, rps, need, rows, K, N, dev):
+def _slabs_beside_panels(nslab, rps, need, rows, K, N, dev, panel_units):
     """The merged backward launch hosts two slab blocks per slab AND one block per 32-row panel; a CU keeps two of these blocks
     (registers).  The plan sizes the slabs to one block per CU, which is right while the panels fit the CUs too; with more
     panels than CUs the launch would need a THIRD block on some CUs, which waits for a free slot (DD seed 6, 288 panels:
@@ -90,10 +90,8 @@ def _slabs_beside_panels(nslab, rps, need, rows, K, N, dev):
         rps = (-(-rows // NSLAB_MAX) + 7) // 8 * 8
         nslab = -(-rows // rps)
         need = nslab * (K + 1) * N
-    ncu = _ncu.get(dev)
-    if ncu is None:
-        ncu = _ncu[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
-    npan = int(nat.lib().tsgnn_panel_blocks(int(rows)))         # (32-row panels, or 16-row units for the rows beyond one panel per CU)
+    ncu = _cu_count(dev)
+    npan = int(nat.lib().tsgnn_panel_blocks(int(rows), int(panel_units)))   # (32-row panels, or units for the rows beyond one panel per CU)
     if npan <= ncu or 2 * nslab + npan <= 2 * ncu:
         return nslab, rps, need
     cap = max(32, (2 * ncu - npan) // 2)
@@ -213,7 +211,7 @@ class _SageStack(torch.autograd.Function):
                 g_out = ghost[2 * l:2 * l + 2] if l < L - 1 else None
                 if l == 0:
                     nat.call("gather_rowgemm_st_f32", ell, ell_w, tp, tc, x, x.stride(0), Ws[0], Ws[0].stride(0), bs[0], v, v.stride(0), rinv, z,
-                             z.stride(0), g.n_rows, K, N, gs, g.row_slot, s_out, g_out)
+                             z.stride(0), g.n_rows, K, N, gs, g.row_slot, s_out, g_out, int(g.panel_units))
                     mean = rstd = None
                 else:
                     pm, pr_ = saved[l - 1][3], saved[l - 1][4]
@@ -223,7 +221,7 @@ class _SageStack(torch.autograd.Function):
                              packed[(l - 1) * B * Fh:(l - 1) * B * Fh + B * Fh],
                              packed[l * B * Fh:l * B * Fh + (B + 1) * N] if last else None, g.row_graph,
                              sums[(l - 1) * 2 * sn:l * 2 * sn], ghost[2 * (l - 1):2 * l], pm, pr_,
-                             None if last else g.row_slot, s_out, g_out, ro_map, ro_ch)
+                             None if last else g.row_slot, s_out, g_out, ro_map, ro_ch, int(g.panel_units))
                 if l < L - 1:
                     mean = torch.empty(g.nmax, dtype=torch.float32, device=dev)     # written by the NEXT launch's readout blocks
                     rstd = torch.empty(g.nmax, dtype=torch.float32, device=dev)
@@ -469,7 +467,7 @@ class _SageStack(torch.autograd.Function):
                     and _gather_ok(g, du) and z.data_ptr() % 16 == 0 and du.data_ptr() % 16 == 0 and W.data_ptr() % 16 == 0
                     and W.stride(0) % 4 == 0):
                 nslab, rps, need = mp.wgrad_plan(g.n_rows, K, N, z.stride(0), du.stride(0))
-                nslab, rps, need = _slabs_beside_panels(nslab, rps, need, g.n_rows, K, N, dev)
+                nslab, rps, need = _slabs_beside_panels(nslab, rps, need, g.n_rows, K, N, dev, g.panel_units)
                 if 0 < nslab < 512:
                     # weight-gradient slabs and dX = (A dU) W^T side by side in one launch (both only need dU)
                     ell, ell_w, tail = g.ell()
@@ -477,7 +475,7 @@ class _SageStack(torch.autograd.Function):
                     ws = torch.empty(need, dtype=torch.float32, device=dev)
                     dxs = torch.empty(R, K, dtype=torch.float32, device=dev)
                     nat.call("sage_layer_bwd_f32", ell, ell_w, tp, tc, du, du.stride(0), W, W.stride(0), dxs, dxs.stride(0), z, z.stride(0),
-                             g.n_rows, nslab, rps, bo, ws)
+                             g.n_rows, nslab, rps, bo, ws, int(g.panel_units))
                     dw, sw = mp._sink_or_new(ctx.params[2 * l], (K, N), dev)
                     db, sb = mp._sink_or_new(ctx.params[2 * l + 1], (N,), dev) if want_b else (None, False)
                     pending.append((ws, nslab, K, N, dw, db))
