@@ -771,6 +771,25 @@ int tsgnn_sag_pool_graph_bwd_f32(const float* y, int64_t ldy, const float* score
                                  float* dws, float* dbs, const float* dagg_next, int64_t lddagg, const int* rowptr_n,
                                  const int* rowend_n, const int* col_n, const float* dinv_n, const float* self_w_n,
                                  tsgnn_stream_t stream);
+/* The GraphConv-scorer forms of the two per-graph level kernels (PyG SAGPooling's default GNN, unit edge weights, symmetric adjacency):
+ *   score_i = w_rel . sum_{j in N(i)} relu(y_j) + w_root . relu(y_i) + b      (w_rel / b = gnn.lin_l.{weight, bias}, w_root = gnn.lin_r.weight;
+ *                                                                             b nullable)
+ * in place of the GCNConv score layer; top-k, perm / new_id, xp / cnt, out / arg are those of tsgnn_sag_pool_graph_f32.  rowptr_new,
+ * rowend_new, col_new (all or none): the filtered adjacency as there, without next-level coefficients (the scorer needs none).
+ * Backward: du as tsgnn_sag_pool_graph_bwd_f32 (dxp nullable) with du_r = (dtot_r gate_r + dt_r w_rel + dscore_r w_root) [y_r > 0],
+ * dt = A dscore; part: B rows of 2F + 4 floats [sum_r dt_r relu(y_r) (F) | sum_r dscore_r | 3 unused | sum_r dscore_r relu(y_r) (F)]
+ * (dw_rel, db, dw_root), summed by a partial-row set of tsgnn_sage_wgrad_reduce_oi_f32 (N = 2F + 4, n_db = F, db = dw_rel, tail = db,
+ * dw_oi = dw_root, lddw = F + 4).  Same size limits as the GCN forms; other shapes: TSGNN_EUNSUPPORTED. */
+int tsgnn_sag_pool_graph_gc_f32(const float* y, int64_t ldy, const int* rowptr, const int* rowend, const int* col, const float* w_rel,
+                                const float* w_root, const float* b, const int* graph_ptr, const int* graph_ptr_new, int B, int max_seg,
+                                int F, float* score, int* perm, int* new_id, float* xp, int64_t ldo, int* cnt, float* out,
+                                int64_t ldout, int* arg, int accumulate, int* rowptr_new, int* rowend_new, int* col_new,
+                                tsgnn_stream_t stream);
+int tsgnn_sag_pool_graph_gc_bwd_f32(const float* y, int64_t ldy, const float* score, const int* new_id, const int* graph_ptr,
+                                    const int* graph_ptr_new, const int* arg, const float* dxp, int64_t lddxp, const float* dread,
+                                    int64_t lddr, const int* rowptr, const int* rowend, const int* col, const float* w_rel,
+                                    const float* w_root, int B, int max_seg, int F, float* du, int64_t lddu, float* part,
+                                    tsgnn_stream_t stream);
 /* fixed-order sum of nb partial rows part[nb][F + 4] (columns 0..F-1: dw_s, column F: db_s) -> dws[F], dbs[1] */
 int tsgnn_sag_du_reduce_f32(float* part, int nb, int F, float* dws, float* dbs, tsgnn_stream_t stream);
 /* tsgnn_linear_wgrad_f32 (dw != NULL) whose reduction launch carries that sum as one extra block (nb <= 256): the conv layer's
@@ -1083,7 +1102,8 @@ int tsgnn_sage_readout_decode_f32(unsigned long long* packed, unsigned long long
  * (dw == NULL form) summed in slab order into nn.Linear's layout dw_oi[n * lddw + k] (kn = 1: GCNConv's [in, out], dw[k * lddw + n])
  * (+ db[n < n_db], nullable; n_db = N for a weight set): all layers' weight gradients in one launch.  K = 0: a set of partial ROWS [nslab][N] only, column sums to db[0 .. n_db)
  * and column n_db to tail[0] (nullable) — the SAGPool score layer's partial rows [nb][F + 4] of tsgnn_sag_pool_graph_bwd_f32
- * (Code/sag/layers.py:18 weight / bias gradients), i.e. tsgnn_sag_du_reduce_f32 riding in this launch.
+ * (Code/sag/layers.py:18 weight / bias gradients), i.e. tsgnn_sag_du_reduce_f32 riding in this launch.  dw_oi (nullable) of a K = 0 set
+ * takes columns [lddw, lddw + n_db): the GraphConv scorer's rows [nb][2F + 4] of tsgnn_sag_pool_graph_gc_bwd_f32 with lddw = F + 4.
  * normparts (nullable; tsgnn_sage_wgrad_reduce_oi_blocks(desc) entries): block k's sum of squares of what it wrote; step_state
  * (nullable): step_state[0] += 1 — both as tsgnn_wgrad_reduce_multi_f32, for tsgnn_adam_from_partials_f32 */
 int tsgnn_sage_wgrad_reduce_oi_blocks(const int64_t* desc);

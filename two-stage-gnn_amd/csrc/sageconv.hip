@@ -113,7 +113,9 @@ __global__ __launch_bounds__(256) void sage_conv_pack_kernel(PackArgs a) {
 
 struct OiSet {
   const float* ws; int nslab, K, N;     // slabs [nslab][K + 1][N] (row K = bias partial); K = 0: rows of partial column sums only
-  float* dw; int64_t lddw;              // dw[n * lddw + k]  (nn.Linear's [out, in]; kn = 1: dw[k * lddw + n], GCNConv's [in, out]); unused when K = 0
+  float* dw; int64_t lddw;              // dw[n * lddw + k]  (nn.Linear's [out, in]; kn = 1: dw[k * lddw + n], GCNConv's [in, out]);
+                                        // K = 0 (nullable): columns lddw .. lddw + n_db - 1 go to dw[0 .. n_db) (the GraphConv
+                                        // scorer's partial rows [nb][2F + 4]: dw_root from column F + 4)
   int kn;
   float* db;                            // nullable [n_db]
   int n_db;                             // columns of the bias row that go to db (N for a weight set)
@@ -160,6 +162,7 @@ __global__ __launch_bounds__(256) void sage_wgrad_reduce_oi_kernel(OiArgs a) {
     if (k < s.K) { s.dw[s.kn ? (int64_t)k * s.lddw + n : (int64_t)n * s.lddw + k] = v; sq = v * v; }
     else if (s.db && n < s.n_db) { s.db[n] = v; sq = v * v; }
     else if (s.tail && n == s.n_db) { s.tail[0] = v; sq = v * v; }
+    else if (s.K == 0 && s.dw && n >= s.lddw && n < s.lddw + s.n_db) { s.dw[n - s.lddw] = v; sq = v * v; }
   }
   if (a.normparts) {                                    // this block's share of |grad|^2 (summed in fixed order by the optimiser)
     sq = wave_sum(sq);
@@ -298,9 +301,10 @@ int tsgnn_sage_readout_decode_f32(unsigned long long* packed, unsigned long long
 
 /* desc (HOST memory): [nsets <= 12, nsets x (ws, nslab, K, N, dw_oi, lddw, db, n_db, tail, kn)] — slab sets in the layout of
  * tsgnn_linear_wgrad_f32 (dw == NULL form), summed in slab order and written transposed: dw_oi[n * lddw + k] (kn = 1: as they lie,
- * dw[k * lddw + n]); db nullable, takes the first n_db columns of the bias row (n_db = N for a weight set).  K = 0: a set of partial ROWS [nslab][N] only (dw_oi unused) whose
+ * dw[k * lddw + n]); db nullable, takes the first n_db columns of the bias row (n_db = N for a weight set).  K = 0: a set of partial ROWS [nslab][N] only whose
  * column sums go to db[0 .. n_db) and, column n_db, to tail[0] when tail != NULL (the SAGPool score layer's per-graph partial rows
- * [nb][F + 4] left by tsgnn_sag_pool_graph_bwd_f32: the work of tsgnn_sag_du_reduce_f32 riding in this launch). */
+ * [nb][F + 4] left by tsgnn_sag_pool_graph_bwd_f32: the work of tsgnn_sag_du_reduce_f32 riding in this launch); dw_oi (nullable) then takes
+ * columns [lddw, lddw + n_db) (the GraphConv scorer's rows [nb][2F + 4] of tsgnn_sag_pool_graph_gc_bwd_f32: lddw = F + 4). */
 int tsgnn_sage_wgrad_reduce_oi_blocks(const int64_t* desc) {
   if (!desc || desc[0] <= 0 || desc[0] > OI_MAX_SETS) return -1;
   int blocks = 0;
@@ -324,6 +328,7 @@ int tsgnn_sage_wgrad_reduce_oi_f32(const int64_t* desc, float* normparts, float*
     if (!s.ws || s.nslab <= 0 || s.K < 0 || s.N <= 0 || s.n_db < 0 || s.n_db > s.N) return TSGNN_EINVAL;
     if (s.K > 0 && (!s.dw || s.lddw < (s.kn ? s.N : s.K))) return TSGNN_EINVAL;
     if (s.tail && s.n_db >= s.N) return TSGNN_EINVAL;
+    if (s.K == 0 && s.dw && (s.lddw <= s.n_db || s.lddw + s.n_db > s.N)) return TSGNN_EINVAL;
     s.first_block = blocks;
     blocks += ((s.K + 1) * s.N + 63) / 64;
   }

@@ -437,6 +437,9 @@ __device__ __forceinline__ float4 prop_row(const int* __restrict__ rowptr, const
 //   cnt[p] = kept neighbours of perm[p]  (input of the CSR filter's scan)
 // in one launch instead of four (score propagate, top-k, gather, readout), with the relabelling map and the scores staying
 // in LDS between the phases.
+// GC = true: PyG SAGPooling's GraphConv(C -> 1) scorer instead (unit weights, no normalisation):
+//   t_j = relu(y_j) . w_rel,  u_j = relu(y_j) . w_root,  s_i = sum_{j in N(i)} t_j + u_i + b
+// u lives where the next level's gcn_norm coefficients (dvn / swn) would: that scorer needs none.  The other phases are the same.
 constexpr int PG_THREADS = 1024;
 constexpr int PG_MAX_NODES = 4096;
 constexpr int PG_SMALL_NODES = 256;       // batches whose graphs all fit this MAY run the per-graph kernels with 256-thread workgroups ...
@@ -467,11 +470,12 @@ struct PoolGraphArgs {
   int* rowptr_new; int* rowend_new; int* col_new; float* dinv_new; float* self_w_new;
   // with the filter: the NEXT level's aggregation A^' xp (nullable) — one launch less per level (gcn_propagate on the pooled rows)
   float* agg_next; int64_t ldagg;
+  const float* w_root;                      // GC scorer only: lin_r's weight (w_s = lin_l's weight, b_s = its bias); dinv / self_w unused
 };
 
 // BT threads per workgroup: 1,024 for graphs of up to 4,096 nodes, 256 when no graph of the batch exceeds 256 nodes (TU graphs:
 // four times the resident graphs per CU; at 8,192 IMDB-B graphs per launch 266 -> see profiles)
-template <int G, int BT>
+template <int G, int BT, bool GC>
 __global__ __launch_bounds__(BT) void sag_pool_graph_kernel(PoolGraphArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long pg_smem[];
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -500,6 +504,9 @@ __global__ __launch_bounds__(BT) void sag_pool_graph_kernel(PoolGraphArgs a) {
   const bool live = lig < nvec;
   const int co = live ? 4 * lig : 0;
   const float4 wv = live ? ld4(a.w_s + co) : make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 wr = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (GC) wr = live ? ld4(a.w_root + co) : wr;
+  float* uu = dvn;                                                      // [np] GC: u_j = relu(y_j) . w_root
   // (1) t_j = relu(y_j) . w_s   (four rows per lane group in flight: one round trip for up to 4 * NG rows)
   for (int j0 = grp; j0 < n; j0 += 4 * NG) {
     float4 v[4];
@@ -513,6 +520,10 @@ __global__ __launch_bounds__(BT) void sag_pool_graph_kernel(PoolGraphArgs a) {
       const int j = j0 + u * NG;
       const float d = group_sum<G>(dot4(relu4(v[u]), wv));
       if (lig == 0 && j < n) t[j] = d;
+      if constexpr (GC) {
+        const float e = group_sum<G>(dot4(relu4(v[u]), wr));
+        if (lig == 0 && j < n) uu[j] = e;
+      }
     }
   }
   __syncthreads();
@@ -532,10 +543,16 @@ __global__ __launch_bounds__(BT) void sag_pool_graph_kernel(PoolGraphArgs a) {
       const int e1 = a.rowend ? a.rowend[r] : a.rowptr[r + 1];
       for (int e = a.rowptr[r] + sub; e < e1; e += EG) {
         const int c = a.col[e];
-        if ((unsigned)(c - g0) < (unsigned)n) acc = fmaf(a.dinv[c], t[c - g0], acc);   // graphs of a batch are disjoint (PyG collate)
+        if constexpr (GC) {
+          if ((unsigned)(c - g0) < (unsigned)n) acc += t[c - g0];
+        } else {
+          if ((unsigned)(c - g0) < (unsigned)n) acc = fmaf(a.dinv[c], t[c - g0], acc);   // graphs of a batch are disjoint (PyG collate)
+        }
       }
       acc = group_sum<EG>(acc);
-      const float sc = fmaf(a.dinv[r], acc, a.self_w[r] * t[j]) + bs;
+      float sc;
+      if constexpr (GC) sc = (acc + uu[j]) + bs;
+      else sc = fmaf(a.dinv[r], acc, a.self_w[r] * t[j]) + bs;
       if (sub == 0) a.score[r] = sc;
       key = ((unsigned long long)f32_ordered(sc) << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)j);
     }
@@ -682,6 +699,13 @@ __global__ __launch_bounds__(BT) void sag_pool_graph_kernel(PoolGraphArgs a) {
         }
         o += __popc(gm);
       }
+      if constexpr (GC) {                                               // no coefficients for the next level
+        if (sub == 0) {
+          a.rowptr_new[k0 + p] = o0;
+          a.rowend_new[k0 + p] = o;
+        }
+        continue;
+      }
       has_self = (((unsigned)(__ballot(has_self) >> gsh)) & ((1u << EG) - 1u)) != 0u;
       if (sub == 0) {
         a.rowptr_new[k0 + p] = o0;
@@ -696,7 +720,7 @@ __global__ __launch_bounds__(BT) void sag_pool_graph_kernel(PoolGraphArgs a) {
   }
   __syncthreads();
   TR(7);
-  if (a.agg_next != nullptr) {                              // pooled rows, their CSR and coefficients were written above by this block
+  if (!GC && a.agg_next != nullptr) {                       // pooled rows, their CSR and coefficients were written above by this block
     // prop_row's arithmetic with the row bounds and coefficients from LDS: entries -> pooled rows are the only global hops
     for (int p = grp; p < k; p += NG) {
       const int e0 = rpn[p], e1 = ren[p];
@@ -911,6 +935,9 @@ inline void launch_du_reduce(float* part, int nb, int F, float* dws, float* dbs,
 // ---------------------------------------------------------------- backward of the level tail, one workgroup per graph
 // pool_bwd -> dt = A^ dscore -> du also touch one graph's rows only: with dscore and dt in LDS the three phases are one launch
 // (sag_pool_bwd + sag_du otherwise), followed by the fixed-order reduction of the per-graph partial sums of dw_s / db_s.
+// GC = true: the GraphConv scorer (see sag_pool_graph_kernel):  dt = A dscore (unit weights, symmetric),
+//   du_r = (dtot_r gate_r + dt_r w_rel + dscore_r w_root) [y_r > 0],  and a partial row of 2F + 4 floats per graph:
+//   [sum dt relu(y) (F) | sum dscore | 3 unused | sum dscore relu(y) (F)]  (dw_rel, db, dw_root)
 struct PoolGraphBwdArgs {
   const float* y; int64_t ldy; const float* score; const int* new_id;
   const int* gp; const int* gp_new; const int* arg;
@@ -921,8 +948,9 @@ struct PoolGraphBwdArgs {
   // formed per kept row here (symmetric adjacency), one launch less per level
   const float* dagg_next; int64_t lddagg;
   const int* rowptr_n; const int* rowend_n; const int* col_n; const float* dinv_n; const float* self_w_n;
+  const float* w_root;                        // GC scorer only (w_s = w_rel); dinv / self_w unused
 };
-template <int G, int BT>
+template <int G, int BT, bool GC>
 __global__ __launch_bounds__(BT) void sag_pool_graph_bwd_kernel(PoolGraphBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float pb_smem[];
   constexpr int NG = BT / G;
@@ -938,6 +966,7 @@ __global__ __launch_bounds__(BT) void sag_pool_graph_bwd_kernel(PoolGraphBwdArgs
   int* rowof = nidl + n4;                     // [kb] old row (offset in the graph) of kept row q
   float* dvn = reinterpret_cast<float*>(rowof + n4);   // [kb] next level's dinv of kept row q
   float* racc = dvn + n4;                     // [NG][F] partial dw_s
+  float* racc2 = racc + NG * F;               // [NG][F] GC: partial dw_root
   const int lig = tid & (G - 1), grp = tid / G;
   const bool live = lig < nvec;
   const int co = live ? 4 * lig : 0;
@@ -1020,17 +1049,27 @@ __global__ __launch_bounds__(BT) void sag_pool_graph_bwd_kernel(PoolGraphBwdArgs
       float acc = 0.f;
       for (int e = a.rowptr[r] + sub; e < e1; e += EG) {
         const int c = a.col[e];
-        if ((unsigned)(c - g0) < (unsigned)n) acc = fmaf(a.dinv[c], ds[c - g0], acc);
+        if constexpr (GC) {
+          if ((unsigned)(c - g0) < (unsigned)n) acc += ds[c - g0];
+        } else {
+          if ((unsigned)(c - g0) < (unsigned)n) acc = fmaf(a.dinv[c], ds[c - g0], acc);
+        }
       }
       acc = group_sum<EG>(acc);
-      if (sub == 0) dt[j] = fmaf(a.dinv[r], acc, a.self_w[r] * ds[j]);
+      if constexpr (GC) {
+        if (sub == 0) dt[j] = acc;
+      } else {
+        if (sub == 0) dt[j] = fmaf(a.dinv[r], acc, a.self_w[r] * ds[j]);
+      }
     }
   }
   __syncthreads();
   TR(2);
   // (C) du = (du + dt w_s) [y > 0]; partial sums of dw_s = sum dt relu(y)   (two rows per lane group in flight)
   const float4 w = live ? ld4(a.w_s + co) : make_float4(0.f, 0.f, 0.f, 0.f);
-  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+  float4 wr = make_float4(0.f, 0.f, 0.f, 0.f);
+  if constexpr (GC) wr = live ? ld4(a.w_root + co) : wr;
+  float4 acc = make_float4(0.f, 0.f, 0.f, 0.f), acc2 = acc;
   for (int j0 = grp; j0 < n; j0 += 2 * NG) {
     float4 v[2], d[2];
 #pragma unroll
@@ -1045,6 +1084,11 @@ __global__ __launch_bounds__(BT) void sag_pool_graph_bwd_kernel(PoolGraphBwdArgs
       const int j = j0 + u * NG;
       if (live && j < n) {
         const float t = dt[j];
+        if constexpr (GC) {
+          const float sj = ds[j];
+          d[u] = make_float4(fmaf(sj, wr.x, d[u].x), fmaf(sj, wr.y, d[u].y), fmaf(sj, wr.z, d[u].z), fmaf(sj, wr.w, d[u].w));
+          fma4(acc2, sj, relu4(v[u]));
+        }
         float4 o;
         o.x = v[u].x > 0.f ? fmaf(t, w.x, d[u].x) : 0.f;
         o.y = v[u].y > 0.f ? fmaf(t, w.y, d[u].y) : 0.f;
@@ -1056,18 +1100,27 @@ __global__ __launch_bounds__(BT) void sag_pool_graph_bwd_kernel(PoolGraphBwdArgs
     }
   }
   if (live) *reinterpret_cast<float4*>(racc + grp * F + co) = acc;
+  if constexpr (GC) {
+    if (live) *reinterpret_cast<float4*>(racc2 + grp * F + co) = acc2;
+  }
   __syncthreads();
   TR(3);
   // (D) this graph's partial sums, groups in order
+  constexpr int PW = GC ? 2 : 1;                                        // F-wide sums per partial row
   for (int f = tid; f < F; f += BT) {
     float sum = 0.f;
     for (int q = 0; q < NG; ++q) sum += racc[q * F + f];
-    a.part[(int64_t)b * (F + 4) + f] = sum;
+    a.part[(int64_t)b * (PW * F + 4) + f] = sum;
+    if constexpr (GC) {
+      float s2 = 0.f;
+      for (int q = 0; q < NG; ++q) s2 += racc2[q * F + f];
+      a.part[(int64_t)b * (2 * F + 4) + F + 4 + f] = s2;
+    }
   }
   if (tid == 0) {
     float sum = 0.f;
     for (int j = 0; j < n; ++j) sum += ds[j];
-    a.part[(int64_t)b * (F + 4) + F] = sum;
+    a.part[(int64_t)b * (PW * F + 4) + F] = sum;
   }
   TR(4);
   TR_END();
@@ -1124,6 +1177,63 @@ constexpr int64_t PROP_RB_MIN_ROWS = 262144;   // below this the batch is cache-
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 inline int group_of(int F) { const int nv = F / 4; return nv <= 8 ? 8 : nv <= 16 ? 16 : nv <= 32 ? 32 : 64; }
+
+// dynamic LDS of sag_pool_graph_kernel: keys / t / nid [np], the readout partials, the rank sort's second key array, the pooled
+// rows' bounds and coefficients [4][np] (the GC scorer keeps u in the coefficients' place).  At max_seg = 4,096, F = 256:
+// 64 + 24 + 64 KiB = 152 KiB of the 160 KiB a workgroup may have.
+inline size_t pool_graph_lds(int max_seg, int F) {
+  int np = 1;
+  while (np < max_seg) np <<= 1;
+  return (size_t)np * (8 + 4 + 4) + (size_t)PG_RGROUPS * F * 12 + (np <= PG_RANK_MAX ? (size_t)np * 8 : 0) + (size_t)np * 16;
+}
+
+template <int G, bool GC>
+void launch_pool_graph_g(const PoolGraphArgs& a, int B, int max_seg, size_t lds, hipStream_t stream) {
+  if (pg_small_block(max_seg, B)) {
+    sag_pool_graph_kernel<G, 256, GC><<<(unsigned)B, 256, lds, stream>>>(a);
+  } else {
+    if (lds > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sag_pool_graph_kernel<G, PG_THREADS, GC>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    sag_pool_graph_kernel<G, PG_THREADS, GC><<<(unsigned)B, PG_THREADS, lds, stream>>>(a);
+  }
+}
+
+template <bool GC>
+void launch_pool_graph(const PoolGraphArgs& a, int B, int max_seg, size_t lds, hipStream_t stream) {
+  switch (group_of(a.F)) {
+    case 8: launch_pool_graph_g<8, GC>(a, B, max_seg, lds, stream); break;
+    case 16: launch_pool_graph_g<16, GC>(a, B, max_seg, lds, stream); break;
+    case 32: launch_pool_graph_g<32, GC>(a, B, max_seg, lds, stream); break;
+    default: launch_pool_graph_g<64, GC>(a, B, max_seg, lds, stream); break;
+  }
+}
+
+// dynamic LDS of sag_pool_graph_bwd_kernel: five [n] arrays and the lane groups' partial dw rows (two sets for the GC scorer).
+// At max_seg = 4,096, F = 256, 1,024 threads: 80 + 16 KiB (GC: 80 + 32 KiB).
+template <int G, bool GC>
+void launch_pool_graph_bwd_g(const PoolGraphBwdArgs& a, int B, int max_seg, hipStream_t stream) {
+  const int bt = pg_small_block(max_seg, B) ? 256 : PG_THREADS;
+  const size_t lds = sizeof(float) * (5 * (size_t)((max_seg + 3) & ~3) + (GC ? 2 : 1) * (size_t)(bt / G) * a.F);
+  if (bt == 256) {
+    sag_pool_graph_bwd_kernel<G, 256, GC><<<(unsigned)B, 256, lds, stream>>>(a);
+  } else {
+    if (lds > 64 * 1024)
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sag_pool_graph_bwd_kernel<G, PG_THREADS, GC>),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    sag_pool_graph_bwd_kernel<G, PG_THREADS, GC><<<(unsigned)B, PG_THREADS, lds, stream>>>(a);
+  }
+}
+
+template <bool GC>
+void launch_pool_graph_bwd(const PoolGraphBwdArgs& a, int B, int max_seg, hipStream_t stream) {
+  switch (group_of(a.F)) {
+    case 8: launch_pool_graph_bwd_g<8, GC>(a, B, max_seg, stream); break;
+    case 16: launch_pool_graph_bwd_g<16, GC>(a, B, max_seg, stream); break;
+    case 32: launch_pool_graph_bwd_g<32, GC>(a, B, max_seg, stream); break;
+    default: launch_pool_graph_bwd_g<64, GC>(a, B, max_seg, stream); break;
+  }
+}
 
 }  // namespace
 
@@ -1264,29 +1374,31 @@ int tsgnn_sag_pool_graph_f32(const float* y, int64_t ldy, const int* rowptr, con
   if (!tsgnn_sag_supported(F) || max_seg > PG_MAX_NODES || ldy % 4 || ldo % 4 || !aligned16(y) || !aligned16(xp) || !aligned16(w_s))
     return TSGNN_EUNSUPPORTED;
   if (max_seg == 0) return TSGNN_OK;
-  int np = 1;
-  while (np < max_seg) np <<= 1;
-  const size_t lds = (size_t)np * (8 + 4 + 4) + (size_t)PG_RGROUPS * F * 12 + (np <= PG_RANK_MAX ? (size_t)np * 8 : 0) + (size_t)np * 16;
+  const size_t lds = pool_graph_lds(max_seg, F);
   PoolGraphArgs a{y, ldy, rowptr, rowend, col, dinv, self_w, w_s, b_s, graph_ptr, graph_ptr_new, score, perm, new_id, xp, ldo, cnt,
-                  out, ldout, arg, accumulate, F, rowptr_new, rowend_new, col_new, dinv_new, self_w_new, agg_next, ldagg};
-#define PG_LAUNCH(GG)                                                                                                          \
-  do {                                                                                                                         \
-    if (pg_small_block(max_seg, B)) {                                                                                          \
-      sag_pool_graph_kernel<GG, 256><<<(unsigned)B, 256, lds, stream>>>(a);                                                    \
-    } else {                                                                                                                   \
-      if (lds > 64 * 1024)                                                                                                     \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sag_pool_graph_kernel<GG, PG_THREADS>),                        \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                       \
-      sag_pool_graph_kernel<GG, PG_THREADS><<<(unsigned)B, PG_THREADS, lds, stream>>>(a);                                      \
-    }                                                                                                                          \
-  } while (0)
-  switch (group_of(F)) {
-    case 8: PG_LAUNCH(8); break;
-    case 16: PG_LAUNCH(16); break;
-    case 32: PG_LAUNCH(32); break;
-    default: PG_LAUNCH(64); break;
-  }
-#undef PG_LAUNCH
+                  out, ldout, arg, accumulate, F, rowptr_new, rowend_new, col_new, dinv_new, self_w_new, agg_next, ldagg, nullptr};
+  launch_pool_graph<false>(a, B, max_seg, lds, stream);
+  TSGNN_CHECK_LAUNCH();
+  return TSGNN_OK;
+}
+
+/* the GraphConv-scorer form (PyG SAGPooling's default GNN): score_i = w_rel . sum_{j in N(i)} relu(y_j) + w_root . relu(y_i) + b */
+int tsgnn_sag_pool_graph_gc_f32(const float* y, int64_t ldy, const int* rowptr, const int* rowend, const int* col, const float* w_rel,
+                                const float* w_root, const float* b, const int* graph_ptr, const int* graph_ptr_new, int B, int max_seg,
+                                int F, float* score, int* perm, int* new_id, float* xp, int64_t ldo, int* cnt, float* out,
+                                int64_t ldout, int* arg, int accumulate, int* rowptr_new, int* rowend_new, int* col_new,
+                                tsgnn_stream_t stream) {
+  if ((col_new != nullptr) != (rowptr_new != nullptr) || (col_new != nullptr) != (rowend_new != nullptr)) return TSGNN_EINVAL;
+  if (!y || !rowptr || !col || !w_rel || !w_root || !graph_ptr || !graph_ptr_new || !score || !perm || !new_id || !xp || !cnt || !out ||
+      !arg || B <= 0 || max_seg < 0 || ldy < F || ldo < F || ldout < 2 * F)
+    return TSGNN_EINVAL;
+  if (!tsgnn_sag_supported(F) || max_seg > PG_MAX_NODES || ldy % 4 || ldo % 4 || !aligned16(y) || !aligned16(xp) || !aligned16(w_rel) ||
+      !aligned16(w_root))
+    return TSGNN_EUNSUPPORTED;
+  if (max_seg == 0) return TSGNN_OK;
+  PoolGraphArgs a{y, ldy, rowptr, rowend, col, nullptr, nullptr, w_rel, b, graph_ptr, graph_ptr_new, score, perm, new_id, xp, ldo, cnt,
+                  out, ldout, arg, accumulate, F, rowptr_new, rowend_new, col_new, nullptr, nullptr, nullptr, 0, w_root};
+  launch_pool_graph<true>(a, B, max_seg, pool_graph_lds(max_seg, F), stream);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -1350,29 +1462,31 @@ int tsgnn_sag_pool_graph_bwd_f32(const float* y, int64_t ldy, const float* score
     return TSGNN_EUNSUPPORTED;
   if (max_seg == 0) return TSGNN_OK;
   PoolGraphBwdArgs a{y, ldy, score, new_id, graph_ptr, graph_ptr_new, arg, dxp, lddxp, dread, lddr, rowptr, rowend, col, dinv, self_w,
-                     w_s, du, lddu, part, F, dagg_next, lddagg, rowptr_n, rowend_n, col_n, dinv_n, self_w_n};
-  const int G_ = group_of(F);
-  const int bt = pg_small_block(max_seg, B) ? 256 : PG_THREADS;
-  const size_t lds = sizeof(float) * (5 * (size_t)((max_seg + 3) & ~3) + (size_t)(bt / G_) * F);
-#define PGB_LAUNCH(GG)                                                                                                             \
-  do {                                                                                                                             \
-    if (bt == 256) {                                                                                                               \
-      sag_pool_graph_bwd_kernel<GG, 256><<<(unsigned)B, 256, lds, stream>>>(a);                                                    \
-    } else {                                                                                                                       \
-      if (lds > 64 * 1024)                                                                                                         \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sag_pool_graph_bwd_kernel<GG, PG_THREADS>),                        \
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                                           \
-      sag_pool_graph_bwd_kernel<GG, PG_THREADS><<<(unsigned)B, PG_THREADS, lds, stream>>>(a);                                      \
-    }                                                                                                                              \
-  } while (0)
-  switch (G_) {
-    case 8: PGB_LAUNCH(8); break;
-    case 16: PGB_LAUNCH(16); break;
-    case 32: PGB_LAUNCH(32); break;
-    default: PGB_LAUNCH(64); break;
-  }
-#undef PGB_LAUNCH
+                     w_s, du, lddu, part, F, dagg_next, lddagg, rowptr_n, rowend_n, col_n, dinv_n, self_w_n, nullptr};
+  launch_pool_graph_bwd<false>(a, B, max_seg, stream);
   if (dws != nullptr) launch_du_reduce(part, (int)B, F, dws, dbs, stream);   // NULL: reduced by tsgnn_linear_wgrad_du_f32
+  TSGNN_CHECK_LAUNCH();
+  return TSGNN_OK;
+}
+
+/* the GraphConv-scorer form: part gets B rows of 2F + 4 floats [dw_rel (F) | db | 3 unused | dw_root (F)], summed by a partial-row
+ * set of tsgnn_sage_wgrad_reduce_oi_f32 (dw = dw_root at column offset F + 4) */
+int tsgnn_sag_pool_graph_gc_bwd_f32(const float* y, int64_t ldy, const float* score, const int* new_id, const int* graph_ptr,
+                                    const int* graph_ptr_new, const int* arg, const float* dxp, int64_t lddxp, const float* dread,
+                                    int64_t lddr, const int* rowptr, const int* rowend, const int* col, const float* w_rel,
+                                    const float* w_root, int B, int max_seg, int F, float* du, int64_t lddu, float* part,
+                                    tsgnn_stream_t stream) {
+  if (!y || !score || !new_id || !graph_ptr || !graph_ptr_new || !arg || !dread || !rowptr || !col || !w_rel || !w_root || !du || !part ||
+      B <= 0 || max_seg < 0 || ldy < F || lddu < F || lddr < 2 * F || (dxp && lddxp < F))
+    return TSGNN_EINVAL;
+  if (!tsgnn_sag_supported(F) || max_seg > PG_MAX_NODES || ldy % 4 || lddu % 4 || lddr % 4 || (dxp && (lddxp % 4 || !aligned16(dxp))) ||
+      !aligned16(y) || !aligned16(du) || !aligned16(dread) || !aligned16(arg) || !aligned16(w_rel) || !aligned16(w_root) ||
+      !aligned16(part))
+    return TSGNN_EUNSUPPORTED;
+  if (max_seg == 0) return TSGNN_OK;
+  PoolGraphBwdArgs a{y, ldy, score, new_id, graph_ptr, graph_ptr_new, arg, dxp, lddxp, dread, lddr, rowptr, rowend, col, nullptr, nullptr,
+                     w_rel, du, lddu, part, F, nullptr, 0, nullptr, nullptr, nullptr, nullptr, nullptr, w_root};
+  launch_pool_graph_bwd<true>(a, B, max_seg, stream);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }

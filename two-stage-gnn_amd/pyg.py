@@ -735,14 +735,23 @@ class GatNet(nn.Module):
 class SagePoolNet(nn.Module):
     """BASELINE config 4 as worded ("IMDB-BINARY SAGPool (ratio 0.5) + SAGEConv h=128 batch=128"): Code/sag/network.py:9-53 with its
     GCNConv layers replaced by SAGEConv and its pooling by PyG's SAGPooling (GraphConv scorer) — conv + ReLU, pool, [gmp || gap] per
-    level, summed; lin1-3; log_softmax.  The conv layers are the fused SAGEConv launches; the pooling levels are composed from the
-    drop-in operators (top-k / filter_adj size their outputs from the data: three host round trips per level, like PyG).  The
-    sync-free single-node form exists for the reference's own SAGPool + GCNConv network (sag_layers.Net, sag_stack.py); carrying the
-    mean aggregation and the GraphConv scorer through those per-graph kernels is listed as open in DESIGN.md."""
+    level, summed; lin1-3; log_softmax.
 
-    def __init__(self, num_features, nhid, num_classes, pooling_ratio=0.5, dropout_ratio=0.0):
+    ``fused=True`` (default): the three levels run as ONE sync-free autograd node, sag_stack_sage._SagSageStack with the GraphConv
+    scorer (two per-graph launches per level each way, no host round trip: the step can be captured in a hipGraph / GraphedStep), when
+    every one of these holds (``fused_route``):
+      - nhid % 4 == 0 and the per-graph kernels take nhid (sag_stack.supported);
+      - every SAGEConv has a lin_l bias, root_weight and no normalize;
+      - every SAGPooling has ratio = pooling_ratio, a GraphConv(aggr="add") scorer with a lin_l bias, min_score None, multiplier 1,
+        nonlinearity torch.tanh;
+      - the edge list is unit-weight and symmetric, and no graph has more than tsgnn_sag_pool_graph_max_nodes() nodes.
+    Anything else, and ``fused=False``, composes the drop-in operators level by level (top-k / filter_adj size their outputs from the
+    data: three host round trips per level, like PyG).  ``last_perms``: per level, int64 rows of that level, grouped by graph, descending
+    score within a graph, on both paths (the fused path converts its int32 buffers when read)."""
+
+    def __init__(self, num_features, nhid, num_classes, pooling_ratio=0.5, dropout_ratio=0.0, fused=True):
         super().__init__()
-        self.nhid, self.pooling_ratio, self.dropout_ratio = nhid, pooling_ratio, dropout_ratio
+        self.nhid, self.pooling_ratio, self.dropout_ratio, self.fused = nhid, pooling_ratio, dropout_ratio, fused
         self.convs = nn.ModuleList([SAGEConv(num_features if l == 0 else nhid, nhid) for l in range(3)])
         self.pools = nn.ModuleList([SAGPooling(nhid, ratio=pooling_ratio) for _ in range(3)])
         dev = _default_device()
@@ -751,7 +760,61 @@ class SagePoolNet(nn.Module):
         self.lin3 = nn.Linear(nhid // 2, num_classes).to(dev)
         self.last_perms = None
 
+    @property
+    def last_perms(self):
+        if self._perms_fused is not None:
+            return [p.long() for p in self._perms_fused]
+        return self._perms
+
+    @last_perms.setter
+    def last_perms(self, v):
+        self._perms, self._perms_fused = v, None
+
+    def _modules_fusable(self):
+        from . import sag_stack
+        convs_ok = all(c.lin_l.bias is not None and c.root_weight and not c.normalize for c in self.convs)
+        pools_ok = all(isinstance(p.gnn, GraphConv) and p.gnn.aggr == "add" and p.gnn.lin_l.bias is not None and p.min_score is None
+                       and p.multiplier == 1 and p.nonlinearity is torch.tanh and p.ratio == self.pooling_ratio for p in self.pools)
+        return self.fused and self.nhid % 4 == 0 and sag_stack.supported(self.nhid) and convs_ok and pools_ok
+
+    def fused_route(self, data):
+        """(graph, plan) when forward(data) takes the one-node stack, else None (see the class docstring).  Host work on the first call
+        for an edge list / batch only (symmetry check, graph sizes), as the composed path's."""
+        if not self._modules_fusable():
+            return None
+        from . import sag_stack
+        x, edge_index = data.x, data.edge_index
+        if x.dim() != 2 or x.size(1) != self.convs[0].in_channels:
+            return None
+        g = edge_index if isinstance(edge_index, GraphBatch) else graph_of(edge_index, x.size(0), check_symmetry=True)
+        if g.val is not None or not g.symmetric:
+            return None
+        sizes = segment_sizes(getattr(data, "batch", None), x.size(0))
+        if int(sizes.max()) > int(nat.lib().tsgnn_sag_pool_graph_max_nodes()):
+            return None
+        return g, sag_stack.SagPlan.get(sizes, self.pooling_ratio, x.device, depth=3)
+
     def forward(self, data):
+        route = self.fused_route(data)
+        if route is not None:
+            from . import sag_stack_sage
+            g, plan = route
+            params, perms = [], []
+            for conv, pool in zip(self.convs, self.pools):
+                params += [conv.lin_l.weight, conv.lin_l.bias, conv.lin_r.weight, pool.gnn.lin_l.weight, pool.gnn.lin_l.bias,
+                           pool.gnn.lin_r.weight]
+            out = sag_stack_sage.sag_sage_stack(data.x, g, plan, params, scorer="graphconv", perms_out=perms)
+            self._perms, self._perms_fused = None, perms
+        else:
+            out = self._levels_composed(data)
+        if mp.mlp3_ok(out, self.lin1, self.lin2, self.lin3):
+            return mp.mlp3_log_softmax(out, self.lin1, self.lin2, self.lin3, self.dropout_ratio, self.training)
+        h = relu(mp.linear_oi(out, self.lin1.weight, self.lin1.bias))
+        h = torch.nn.functional.dropout(h, p=self.dropout_ratio, training=self.training)
+        h = relu(mp.linear_oi(h, self.lin2.weight, self.lin2.bias))
+        return torch.nn.functional.log_softmax(mp.linear_oi(h, self.lin3.weight, self.lin3.bias), dim=-1)
+
+    def _levels_composed(self, data):
         x, edge_index = data.x, data.edge_index
         batch = getattr(data, "batch", None)
         if batch is None:
@@ -764,9 +827,4 @@ class SagePoolNet(nn.Module):
             r = torch.cat([global_max_pool(x, batch), global_mean_pool(x, batch)], dim=1)
             out = r if out is None else out + r
         self.last_perms = perms
-        if mp.mlp3_ok(out, self.lin1, self.lin2, self.lin3):
-            return mp.mlp3_log_softmax(out, self.lin1, self.lin2, self.lin3, self.dropout_ratio, self.training)
-        h = relu(mp.linear_oi(out, self.lin1.weight, self.lin1.bias))
-        h = torch.nn.functional.dropout(h, p=self.dropout_ratio, training=self.training)
-        h = relu(mp.linear_oi(h, self.lin2.weight, self.lin2.bias))
-        return torch.nn.functional.log_softmax(mp.linear_oi(h, self.lin3.weight, self.lin3.bias), dim=-1)
+        return out
