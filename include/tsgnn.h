@@ -824,6 +824,14 @@ int tsgnn_row_softmax_ent_fwd_f32(const float* x, int64_t ldx, int64_t rows, int
                                   float* hpart, tsgnn_stream_t stream);
 int tsgnn_row_softmax_ent_bwd_f32(const float* y, int64_t ldy, const float* ds, int64_t ldds, const float* mask, const float* g_ent,
                                   float g_scale, float eps, int64_t rows, int C, float* dx, int64_t lddx, tsgnn_stream_t stream);
+/* its link loss ||adj - s s^T||_F / n_adj in closed form, d2 = ||adj||^2 - 2 tr(ao) + ||G||^2 with ao = s^T adj s and G = s^T s
+ * ([B, K, K]) accumulated in fp64 (part: nblk doubles of scratch, 1 <= nblk <= 65535): link[0] = sqrt(d2) / n_adj (fp32) and
+ * coef[0] = d link / d d2 (fp64), both 0 where d2 <= 0.  The backward: dG = 2 g G, dao = -2 g I per graph, dadj = 2 g adj
+ * (nullable) with g = g_link[0] * coef[0] (g_link: device scalar). */
+int tsgnn_diffpool_link_fwd_f32(const float* adj, int64_t n_adj, const float* ao, const float* G, int B, int K, double* part, int nblk,
+                                float* link, double* coef, tsgnn_stream_t stream);
+int tsgnn_diffpool_link_bwd_f32(const float* g_link, const double* coef, const float* G, int B, int K, const float* adj, int64_t n_adj,
+                                float* dG, float* dao, float* dadj, tsgnn_stream_t stream);
 
 /* ---------------------------------------------------------------- fused slot kernels of the GraphSage stack (sage_fused.hip) */
 

@@ -40,6 +40,8 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     assert L.tsgnn_csr_spmm_f32(None, None, None, None, None, 4, None, 4, 10, 4, 0.0, 0, 0, None) == -1
     assert L.tsgnn_linear_l2norm_f32(None, 1, None, 1, None, None, 1, None, 1, 1, 1, 1, None) == -1
     assert L.tsgnn_exclusive_scan_i32(None, -1, None, None, None) == -1
+    assert L.tsgnn_diffpool_link_fwd_f32(None, 16, None, None, 1, 2, None, 512, None, None, None) == -1
+    assert L.tsgnn_diffpool_link_bwd_f32(None, None, None, 1, 2, None, 16, None, None, None, None) == -1
 
 
 def test_product_path_refuses_cpu_tensors():

@@ -6,6 +6,8 @@
 // top-k: one workgroup per graph sorts 64-bit keys (order-preserving score bits << 32 | ~index) in LDS
 // with a bitonic network: descending score, ties -> smaller node index (deterministic, unlike
 // torch.sort's unstable order).  Integer / byte work; nothing here is GEMM-shaped.
+#include <algorithm>
+
 #include "common.h"
 #include "../../include/tsgnn.h"
 
@@ -208,6 +210,76 @@ __global__ __launch_bounds__(256) void row_softmax_ent_bwd(const float* __restri
   }
 }
 
+// dense_diff_pool's link loss in closed form: d2 = sum adj^2 - 2 tr(ao) + sum G^2 over the batch (ao = s^T adj s, G = s^T s, both
+// [B, K, K]).  Products and sums in fp64 (the square of an fp32 value is exact there); the terms cancel when s s^T reproduces adj.
+// part[block] = the block's share, summed in a fixed order by diffpool_link_fin: the result does not depend on scheduling.
+constexpr int LINK_THREADS = 256;
+
+__device__ __forceinline__ double block_sum_f64(double v, double* red) {
+  red[threadIdx.x] = v;
+  __syncthreads();
+  for (int w = LINK_THREADS / 2; w > 0; w >>= 1) {
+    if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+    __syncthreads();
+  }
+  return red[0];
+}
+
+__global__ __launch_bounds__(LINK_THREADS) void diffpool_link_part(const float* __restrict__ adj, int64_t n_adj,
+                                                                   const float* __restrict__ ao, const float* __restrict__ G, int64_t BK,
+                                                                   int K, double* __restrict__ part) {
+  __shared__ double red[LINK_THREADS];
+  const int64_t stride = (int64_t)gridDim.x * LINK_THREADS;
+  const int64_t t0 = (int64_t)blockIdx.x * LINK_THREADS + threadIdx.x;
+  double acc = 0.0;
+  int64_t tail = 0;
+  if ((reinterpret_cast<uintptr_t>(adj) & 15) == 0) {
+    const float4* a4 = reinterpret_cast<const float4*>(adj);
+    for (int64_t i = t0; i < (n_adj >> 2); i += stride) {
+      const float4 v = a4[i];
+      acc = fma((double)v.x, (double)v.x, acc);
+      acc = fma((double)v.y, (double)v.y, acc);
+      acc = fma((double)v.z, (double)v.z, acc);
+      acc = fma((double)v.w, (double)v.w, acc);
+    }
+    tail = n_adj & ~(int64_t)3;
+  }
+  for (int64_t i = tail + t0; i < n_adj; i += stride) acc = fma((double)adj[i], (double)adj[i], acc);
+  for (int64_t i = t0; i < BK * K; i += stride) acc = fma((double)G[i], (double)G[i], acc);
+  for (int64_t i = t0; i < BK; i += stride) acc -= 2.0 * (double)ao[i * K + i % K];      // (b, k, k) = (b K + k) K + k
+  const double s = block_sum_f64(acc, red);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+// link = sqrt(d2) / numel and coef = d link / d d2 = 0.5 / (sqrt(d2) numel); both 0 where d2 <= 0 (torch.norm's gradient at 0)
+__global__ __launch_bounds__(LINK_THREADS) void diffpool_link_fin(const double* __restrict__ part, int nblk, int64_t numel,
+                                                                  float* __restrict__ link, double* __restrict__ coef) {
+  __shared__ double red[LINK_THREADS];
+  double acc = 0.0;
+  for (int i = threadIdx.x; i < nblk; i += LINK_THREADS) acc += part[i];
+  const double d2 = block_sum_f64(acc, red);
+  if (threadIdx.x == 0) {
+    const double r = d2 > 0.0 ? sqrt(d2) : 0.0;
+    link[0] = (float)(r / (double)numel);
+    coef[0] = d2 > 0.0 ? 0.5 / (r * (double)numel) : 0.0;
+  }
+}
+// g = g_link[0] * coef[0] = d loss / d d2:  dG = 2 g G,  dao = -2 g on the diagonal (0 elsewhere),  dadj = 2 g adj (nullable)
+__global__ __launch_bounds__(LINK_THREADS) void diffpool_link_bwd(const float* __restrict__ g_link, const double* __restrict__ coef,
+                                                                  const float* __restrict__ G, int64_t BK, int K,
+                                                                  const float* __restrict__ adj, int64_t n_adj, float* __restrict__ dG,
+                                                                  float* __restrict__ dao, float* __restrict__ dadj) {
+  const float g2 = (float)(2.0 * (double)g_link[0] * coef[0]);
+  const int64_t nG = BK * K;
+  const int64_t n = dadj ? (nG > n_adj ? nG : n_adj) : nG;
+  for (int64_t i = (int64_t)blockIdx.x * LINK_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * LINK_THREADS) {
+    if (i < nG) {
+      dG[i] = g2 * G[i];
+      dao[i] = (i % K == (i / K) % K) ? -g2 : 0.f;
+    }
+    if (dadj && i < n_adj) dadj[i] = g2 * adj[i];
+  }
+}
+
 }  // namespace
 
 extern "C" {
@@ -230,6 +302,31 @@ int tsgnn_row_softmax_ent_bwd_f32(const float* y, int64_t ldy, const float* ds, 
   if (!y || !dx || rows < 0 || C <= 0 || ldy < C || lddx < C || (ds && ldds < C)) return TSGNN_EINVAL;
   if (rows == 0) return TSGNN_OK;
   row_softmax_ent_bwd<<<(unsigned)ceil_div64(rows, 4), 256, 0, stream>>>(y, ldy, ds, ldds, mask, g_ent, g_scale, eps, rows, C, dx, lddx);
+  TSGNN_CHECK_LAUNCH();
+  return TSGNN_OK;
+}
+
+/* dense_diff_pool's link loss ||adj - s s^T||_F / n_adj from d2 = ||adj||^2 - 2 tr(ao) + ||G||^2 accumulated in fp64: adj [n_adj],
+ * ao = s^T adj s and G = s^T s [B, K, K], all contiguous; part [nblk] fp64 scratch (nblk blocks share the reduction).  link[0] (fp32)
+ * = sqrt(d2) / n_adj and coef[0] (fp64) = d link / d d2, both 0 where d2 <= 0.  Two launches, no host sync. */
+int tsgnn_diffpool_link_fwd_f32(const float* adj, int64_t n_adj, const float* ao, const float* G, int B, int K, double* part, int nblk,
+                                float* link, double* coef, tsgnn_stream_t stream) {
+  if (!adj || !ao || !G || !part || !link || !coef || n_adj <= 0 || B < 0 || K <= 0 || nblk <= 0 || nblk > 65535) return TSGNN_EINVAL;
+  diffpool_link_part<<<(unsigned)nblk, LINK_THREADS, 0, stream>>>(adj, n_adj, ao, G, (int64_t)B * K, K, part);
+  TSGNN_CHECK_LAUNCH();
+  diffpool_link_fin<<<1, LINK_THREADS, 0, stream>>>(part, nblk, n_adj, link, coef);
+  TSGNN_CHECK_LAUNCH();
+  return TSGNN_OK;
+}
+/* its backward from g_link[0] (device scalar, the gradient arriving at link) and the forward's coef: dG = 2 g G, dao = -2 g I per
+ * graph, dadj = 2 g adj (nullable) with g = g_link[0] coef[0]; dG, dao [B, K, K] and dadj [n_adj] contiguous */
+int tsgnn_diffpool_link_bwd_f32(const float* g_link, const double* coef, const float* G, int B, int K, const float* adj, int64_t n_adj,
+                                float* dG, float* dao, float* dadj, tsgnn_stream_t stream) {
+  if (!g_link || !coef || !G || !dG || !dao || B < 0 || K <= 0 || n_adj < 0 || (dadj && !adj)) return TSGNN_EINVAL;
+  const int64_t n = dadj ? std::max((int64_t)B * K * K, n_adj) : (int64_t)B * K * K;
+  if (n == 0) return TSGNN_OK;
+  diffpool_link_bwd<<<(unsigned)std::min<int64_t>(ceil_div64(n, LINK_THREADS), 2048), LINK_THREADS, 0, stream>>>(
+      g_link, coef, G, (int64_t)B * K, K, adj, n_adj, dG, dao, dadj);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }

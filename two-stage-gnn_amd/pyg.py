@@ -603,6 +603,32 @@ class _SoftmaxEntropy(torch.autograd.Function):
         return dx, None, None
 
 
+_LINK_PARTS = 512        # blocks sharing the fp64 reduction of the link loss (config 5: 8 K adjacency floats each)
+
+
+class _LinkLoss(torch.autograd.Function):
+    """dense_diff_pool's link loss ||adj - s s^T||_F / adj.numel() from ao = s^T adj s and G = s^T s without the [B, N, N] product:
+    d2 = ||adj||^2 - 2 tr(ao) + ||G||^2 accumulated in fp64, two launches forward and one backward (tsgnn_diffpool_link_{fwd,bwd}_f32)"""
+
+    @staticmethod
+    def forward(ctx, adj, ao, G):
+        adj, ao, G = adj.contiguous(), ao.contiguous(), G.contiguous()
+        part = torch.empty(_LINK_PARTS, dtype=torch.float64, device=adj.device)
+        link = torch.empty((), dtype=torch.float32, device=adj.device)
+        coef = torch.empty(1, dtype=torch.float64, device=adj.device)
+        nat.call("diffpool_link_fwd_f32", adj, adj.numel(), ao, G, G.size(0), G.size(1), part, _LINK_PARTS, link, coef)
+        ctx.save_for_backward(adj, G, coef)
+        return link
+
+    @staticmethod
+    def backward(ctx, g):
+        adj, G, coef = ctx.saved_tensors
+        dG, dao = torch.empty_like(G), torch.empty_like(G)
+        dadj = torch.empty_like(adj) if ctx.needs_input_grad[0] else None
+        nat.call("diffpool_link_bwd_f32", g.contiguous(), coef, G, G.size(0), G.size(1), adj, adj.numel(), dG, dao, dadj)
+        return dadj, dao, dG
+
+
 def dense_diff_pool(x, adj, s, mask=None, eps=1e-15):
     """PyG dense_diff_pool: (s^T x, s^T adj s, link loss, entropy loss) with s = softmax(s, -1) [* mask].
 
@@ -610,7 +636,13 @@ def dense_diff_pool(x, adj, s, mask=None, eps=1e-15):
     [B, N, N] product s s^T (config 5: 16 x 512 x 512 x 64 x 2 = 0.54 GFLOP and three 16 MB tensors for one scalar):
         ||adj - s s^T||^2 = ||adj||^2 - 2 tr(s^T adj s) + ||s^T s||^2        (<adj, s s^T> = tr(s^T adj s);  ||s s^T||_F = ||s^T s||_F)
     with tr(s^T adj s) read off the pooled adjacency that is computed anyway and G = s^T s a [B, K, K] product; its gradient reaches s
-    (and adj) through those two products' own backward.  Softmax, mask and the entropy term are one launch each way."""
+    (and adj) through those two products' own backward.  Softmax, mask and the entropy term are one launch each way.
+
+    The three terms are accumulated in fp64 (_LinkLoss), but tr(s^T adj s) and G are fp32 products and the terms cancel when s s^T
+    reproduces adj, so the link loss is good to an absolute bound, not a relative one:
+        |link - ||adj - s s^T||_F / numel|  <=  8 sqrt(eps32 (||adj||^2 + 2 |tr(s^T adj s)| + ||s^T s||^2)) / numel,   eps32 = 2^-23.
+    Where the computed d2 = ||adj - s s^T||^2 is <= 0 the link loss is 0 and passes no gradient (torch.norm's choice at 0, where
+    sqrt' is inf); elsewhere its gradient is 0.5 / sqrt(d2) times d2's.  The choice is made on the device: no host sync, capture-safe."""
     from .diffpool import bmm, diffpool_contract_dense
     x = x.unsqueeze(0) if x.dim() == 2 else x
     adj = adj.unsqueeze(0) if adj.dim() == 2 else adj
@@ -623,8 +655,7 @@ def dense_diff_pool(x, adj, s, mask=None, eps=1e-15):
         x = x * mask.view(B, N, 1).to(x.dtype)
     out, out_adj = diffpool_contract_dense(s, x, adj)
     G = bmm(s, s, trans_a=True)                                                   # s^T s  [B, K, K]
-    d2 = (adj * adj).sum() - 2.0 * torch.diagonal(out_adj, dim1=1, dim2=2).sum() + (G * G).sum()
-    link = torch.sqrt(torch.clamp(d2, min=0.0)) / adj.numel()
+    link = _LinkLoss.apply(adj, out_adj, G)
     ent = h / (B * N)
     return out, out_adj, link, ent
 
