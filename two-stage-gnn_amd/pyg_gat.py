@@ -85,8 +85,19 @@ class _Pack(torch.autograd.Function):
         return (None,) + tuple(res)
 
 
+PACK_MAX = 4        # layers per pack / unpack launch (GC_LMAX of csrc/gatconv.hip)
+
+
 def pack_layers(convs):
-    """convs: list (<= 4) of pyg.GATConv -> tuple of W' (one per layer)"""
+    """convs: list of pyg.GATConv -> tuple of W' (one per layer): one pack launch forward and one unpack launch backward per group of
+    up to PACK_MAX consecutive layers (a net of at most PACK_MAX layers: one launch each way)"""
+    outs = ()
+    for i in range(0, len(convs), PACK_MAX):
+        outs += _pack_group(convs[i:i + PACK_MAX])
+    return outs
+
+
+def _pack_group(convs):
     params = []
     for c in convs:
         params += [c.lin_l.weight, c.att_l, c.att_r]
