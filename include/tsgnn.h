@@ -223,10 +223,23 @@ int tsgnn_linear_wgrad_plan(int64_t rows, int K_in, int N, int64_t ldz, int64_t 
                             int64_t* ws_floats);
 int tsgnn_linear_wgrad_f32(const float* z, int64_t ldz, const float* du, int64_t lddu, int64_t rows, int K_in, int N, int nslab,
                            int64_t rows_per_slab, int64_t bias_only_rows, float* ws, float* dw, float* db, tsgnn_stream_t stream);
-/* dw == NULL above leaves the slabs in ws; this reduces up to four such slab sets (all layers of one backward pass) in ONE
- * launch.  Unused sets: ws == NULL.  normparts (nullable): block k of the launch (sum over sets of ceil((K+1)*N/64) blocks)
- * stores the sum of squares of the gradient entries it wrote; step_state (nullable): step_state[0] += 1 (both feed
- * tsgnn_adam_from_partials_f32). */
+/* dw == NULL above leaves the slabs in ws.  The fixed-order reduction of slab sets into dw / db is one launcher,
+ * tsgnn_wgrad_reduce_sets_f32 (below): desc (HOST memory, read during the call) = [n <= 12, n x 11 words]
+ *   (ws, nslab, K, N, dw, lddw, db, n_db, tail, kn, blocked)
+ * slabs ws [nslab][K + 1][N] (row K = the bias partial), summed in slab order: row k < K -> dw[n * lddw + k] (nn.Linear's [out, in];
+ * kn = 1: dw[k * lddw + n], [in, out]); row K: columns [0, n_db) -> db (nullable; n_db = N for a weight set), column n_db -> tail[0]
+ * (nullable).  K = 0: partial ROWS [nslab][N] only — the SAGPool score layer's per-graph rows [nb][F + 4] of
+ * tsgnn_sag_pool_graph_bwd_f32 (db = dw_s, n_db = F, tail = db_s); dw (nullable) then takes columns [lddw, lddw + n_db) — the
+ * GraphConv scorer's rows [nb][2F + 4] of tsgnn_sag_pool_graph_gc_bwd_f32 with lddw = F + 4.  blocked = 1: the slabs of
+ * tsgnn_wgrad_blocks_slabs_f32 / tsgnn_gat_bwd_products_f32 / tsgnn_linear_bwd_products_f32 for a K x N (<= 512 x 512) matrix;
+ * tail must be NULL and n_db = N when db is given.  Every set reduces in one launch of 12 sets at most (a blocked record counts one
+ * set per 128 x 128 block; more sets take more launches).  normparts (nullable): tsgnn_wgrad_reduce_sets_blocks(desc) entries,
+ * block k's sum of squares of the entries it wrote; step_state (nullable): step_state[0] += 1 once — both for
+ * tsgnn_adam_from_partials_f32.  A bad record: TSGNN_EINVAL before anything is launched (tsgnn_wgrad_reduce_sets_blocks: -1).
+ * tsgnn_wgrad_reduce_multi_f32 is the same launch for up to four [K][N] sets given positionally (unused: ws == NULL; kn = 1,
+ * lddw = n_db = N): bench.py's per-kernel table reads its arguments by position. */
+int tsgnn_wgrad_reduce_sets_blocks(const int64_t* desc);
+int tsgnn_wgrad_reduce_sets_f32(const int64_t* desc, float* normparts, float* step_state, tsgnn_stream_t stream);
 int tsgnn_wgrad_reduce_multi_f32(const float* ws0, int nslab0, int K0, int N0, float* dw0, float* db0, const float* ws1, int nslab1,
                                  int K1, int N1, float* dw1, float* db1, const float* ws2, int nslab2, int K2, int N2, float* dw2,
                                  float* db2, const float* ws3, int nslab3, int K3, int N3, float* dw3, float* db3,
@@ -778,8 +791,8 @@ int tsgnn_sag_pool_graph_bwd_f32(const float* y, int64_t ldy, const float* score
  * rowend_new, col_new (all or none): the filtered adjacency as there, without next-level coefficients (the scorer needs none).
  * Backward: du as tsgnn_sag_pool_graph_bwd_f32 (dxp nullable) with du_r = (dtot_r gate_r + dt_r w_rel + dscore_r w_root) [y_r > 0],
  * dt = A dscore; part: B rows of 2F + 4 floats [sum_r dt_r relu(y_r) (F) | sum_r dscore_r | 3 unused | sum_r dscore_r relu(y_r) (F)]
- * (dw_rel, db, dw_root), summed by a partial-row set of tsgnn_sage_wgrad_reduce_oi_f32 (N = 2F + 4, n_db = F, db = dw_rel, tail = db,
- * dw_oi = dw_root, lddw = F + 4).  Same size limits as the GCN forms; other shapes: TSGNN_EUNSUPPORTED. */
+ * (dw_rel, db, dw_root), summed by a partial-row set of tsgnn_wgrad_reduce_sets_f32 (N = 2F + 4, n_db = F, db = dw_rel, tail = db,
+ * dw = dw_root, lddw = F + 4).  Same size limits as the GCN forms; other shapes: TSGNN_EUNSUPPORTED. */
 int tsgnn_sag_pool_graph_gc_f32(const float* y, int64_t ldy, const int* rowptr, const int* rowend, const int* col, const float* w_rel,
                                 const float* w_root, const float* b, const int* graph_ptr, const int* graph_ptr_new, int B, int max_seg,
                                 int F, float* score, int* perm, int* new_id, float* xp, int64_t ldo, int* cnt, float* out,
@@ -998,7 +1011,6 @@ int tsgnn_slot_post_bwd_pair_f32(const int* graph_ptr, const int* slot_count, in
                                  const float* dxs2_0, const float* dxs2_1, int64_t lddxs2, int F, int relu, int bn, const float* mean0,
                                  const float* mean1, const float* rstd0, const float* rstd1, const float* rinv0, const float* rinv1,
                                  float* du0, float* du1, int64_t lddu, tsgnn_stream_t stream);
-int tsgnn_wgrad_reduce_sets_f32(const int64_t* desc, tsgnn_stream_t stream);
 
 /* ---- several independent problems of the GraphConv layer kernels in one launch (csrc/multi.hip): up to two weight-gradient slab
  * problems (arguments of tsgnn_linear_wgrad_f32, dw = db = NULL) and up to two gather products (arguments of
@@ -1016,26 +1028,17 @@ int tsgnn_sage_multi_f32(const int64_t* desc, tsgnn_stream_t stream);
 int tsgnn_sage_multi_zero_f32(const int64_t* desc, float* zero0, int64_t n0, float* zero1, int64_t n1, tsgnn_stream_t stream);
 
 /* ---- backward of a GAT layer's packed projection hp = x W' (csrc/gat_products.hip; encoders_GAT.py:29-36): the slab partials of
- * dW'[K_in, N] = x[:, :K_in]^T du into ws (plan: tsgnn_wgrad_blocks_plan(rows, K_in, N, ldx, lddu); reduce:
- * tsgnn_wgrad_blocks_reduce_f32) and dx[rows, K_in] = du[rows, N] . wp[K_in, N]^T in ONE launch — the same blocks as
+ * dW'[K_in, N] = x[:, :K_in]^T du into ws (plan: tsgnn_wgrad_blocks_plan(rows, K_in, N, ldx, lddu); reduce: a blocked record of
+ * tsgnn_wgrad_reduce_sets_f32) and dx[rows, K_in] = du[rows, N] . wp[K_in, N]^T in ONE launch — the same blocks as
  * tsgnn_wgrad_blocks_f32's slab launch + tsgnn_rowgemm_f32(trans_b = 1), same bits.  128 < K_in <= 512, N <= 512, N % 4 == 0. */
 int tsgnn_gat_bwd_products_f32(const float* x, int64_t ldx, const float* du, int64_t lddu, int64_t rows, int K_in, int N, const float* wp,
                                int64_t ldwp, float* dx, int64_t lddx, int nslab, int64_t rows_per_slab, float* ws, tsgnn_stream_t stream);
-int tsgnn_wgrad_blocks_reduce_f32(const float* ws, int nslab, int K_in, int N, float* dw, int64_t lddw, tsgnn_stream_t stream);
-/* K_in, N <= 128 (one 128 x 128 set: the slab layout of tsgnn_linear_wgrad_f32): the reduction of tsgnn_linear_wgrad_du_f32 alone
- * (part nullable) — the SAGPool conv layers (Code/sag/network.py:19-23) run their slabs beside dagg = du W^T in tsgnn_gat_bwd_products_f32 */
-int tsgnn_linear_wgrad_du_reduce_f32(const float* ws, int nslab, int K_in, int N, float* dw, float* db, float* part, int nb, int F_du,
-                                     float* dws, float* dbs, tsgnn_stream_t stream);
 /* the same pairing for a torch.nn.Linear y = x W^T + b with W [N = out, K_in = in] (DiffPool's assignment predictor, encoders.py:362-372):
  * the slab partials of (dW^T, db) from x and dy into ws and dx[rows, K_in] = dy[rows, N] . W in one launch; the reduction into
  * nn.Linear's layout dw_oi[N][K_in] + db[N] (nullable).  K_in, N <= 512, both multiples of 4. */
 int tsgnn_linear_bwd_products_f32(const float* x, int64_t ldx, const float* dy, int64_t lddy, int64_t rows, int K_in, int N, const float* w,
                                   int64_t ldw, float* dx, int64_t lddx, int nslab, int64_t rows_per_slab, float* ws, tsgnn_stream_t stream);
-int tsgnn_wgrad_blocks_reduce_oi_f32(const float* ws, int nslab, int K_in, int N, float* dw_oi, int64_t lddw, float* db, tsgnn_stream_t stream);
-/* two such reductions in one launch (both layers of a GAT encoder's backward); the slab-only form of the blocked weight gradient:
- * tsgnn_wgrad_blocks_slabs_f32 = tsgnn_wgrad_blocks_f32 without its reduction. */
-int tsgnn_wgrad_blocks_reduce2_f32(const float* ws0, int nslab0, int K0, int N0, float* dw0, int64_t lddw0, const float* ws1, int nslab1,
-                                   int K1, int N1, float* dw1, int64_t lddw1, tsgnn_stream_t stream);
+/* the slab-only form of the blocked weight gradient: tsgnn_wgrad_blocks_slabs_f32 = tsgnn_wgrad_blocks_f32 without its reduction */
 int tsgnn_wgrad_blocks_slabs_f32(const float* z, int64_t ldz, const float* du, int64_t lddu, int64_t rows, int K_in, int N, int nslab,
                                  int64_t rows_per_slab, float* ws, tsgnn_stream_t stream);
 
@@ -1106,16 +1109,6 @@ int tsgnn_sage_relu_readout_bwd_f32(const float* h, int64_t ldh, const float* dx
  * maximum; packed / sums [L, B, F] as left by tsgnn_sage_conv_f32's epilogue, zero again afterwards */
 int tsgnn_sage_readout_decode_f32(unsigned long long* packed, unsigned long long* sums, const int* graph_ptr, int B, int L, int F, float* read,
                                   int64_t ldr, int* arg, tsgnn_stream_t stream);
-/* desc (HOST memory): [nsets <= 12, nsets x (ws, nslab, K, N, dw_oi, lddw, db, n_db, tail, kn)]: slab sets of tsgnn_linear_wgrad_f32
- * (dw == NULL form) summed in slab order into nn.Linear's layout dw_oi[n * lddw + k] (kn = 1: GCNConv's [in, out], dw[k * lddw + n])
- * (+ db[n < n_db], nullable; n_db = N for a weight set): all layers' weight gradients in one launch.  K = 0: a set of partial ROWS [nslab][N] only, column sums to db[0 .. n_db)
- * and column n_db to tail[0] (nullable) — the SAGPool score layer's partial rows [nb][F + 4] of tsgnn_sag_pool_graph_bwd_f32
- * (Code/sag/layers.py:18 weight / bias gradients), i.e. tsgnn_sag_du_reduce_f32 riding in this launch.  dw_oi (nullable) of a K = 0 set
- * takes columns [lddw, lddw + n_db): the GraphConv scorer's rows [nb][2F + 4] of tsgnn_sag_pool_graph_gc_bwd_f32 with lddw = F + 4.
- * normparts (nullable; tsgnn_sage_wgrad_reduce_oi_blocks(desc) entries): block k's sum of squares of what it wrote; step_state
- * (nullable): step_state[0] += 1 — both as tsgnn_wgrad_reduce_multi_f32, for tsgnn_adam_from_partials_f32 */
-int tsgnn_sage_wgrad_reduce_oi_blocks(const int64_t* desc);
-int tsgnn_sage_wgrad_reduce_oi_f32(const int64_t* desc, float* normparts, float* step_state, tsgnn_stream_t stream);
 /* desc (HOST memory): [njobs <= 16, njobs x (src, lds, rows, cols, dst, ldd, dst_cols)]: dst[r, 0 .. dst_cols) = src[r, 0 .. cols) then
  * zeros — the [W_l | W_r] images of every level of a SAGEConv stack placed and zero-padded in ONE launch (host glue of the reference's
  * network with PyG SAGEConv layers; no reference line) */

@@ -20,7 +20,8 @@ for what in "$@"; do
              rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_dp -- python3 scripts/prof_diffpool.py > /dev/null 2>&1 && cp $O/rocprof_dp/*/*kernel_stats.csv $O/diffpool_kernel_stats.csv ;;
     diffpool_replay) rm -rf $O/rocprof_dpr
              rocprofv3 --kernel-trace --output-format csv -d $O/rocprof_dpr -- python3 scripts/diffpool_step.py > /dev/null 2>&1 &&
-             python3 scripts/replay_trace.py $(ls $O/rocprof_dpr/*/*kernel_trace.csv | head -1) tn_rows_reduce_multi > $O/diffpool_replay_timeline.txt; rm -rf $O/rocprof_dpr ;;
+             # (anchor: a kernel that runs once per step — the weight-gradient reduction also runs inside the assignment predictor's backward)
+             python3 scripts/replay_trace.py $(ls $O/rocprof_dpr/*/*kernel_trace.csv | head -1) head2_fwd_kernel > $O/diffpool_replay_timeline.txt; rm -rf $O/rocprof_dpr ;;
     gat_replay) rm -rf $O/rocprof_gr
              rocprofv3 --kernel-trace --output-format csv -d $O/rocprof_gr -- python3 scripts/gat_step.py > /dev/null 2>&1 &&
              python3 scripts/replay_trace.py $(ls $O/rocprof_gr/*/*kernel_trace.csv | head -1) gat_unpack_kernel > $O/gat_replay_timeline.txt; rm -rf $O/rocprof_gr ;;

@@ -75,7 +75,7 @@ def test_new_entry_points_validate_on_the_host():
     bad = np.zeros(64, dtype=np.int64)
     assert L.tsgnn_gat_pack_f32(bad.ctypes.data, None) == -1                          # zero layers
     assert L.tsgnn_sage_multi_f32(bad.ctypes.data, None) == -1                        # no problems
-    assert L.tsgnn_wgrad_reduce_sets_f32(None, None) == -1
+    assert L.tsgnn_wgrad_reduce_sets_f32(None, None, None, None) == -1
     ns, rps, need = np.zeros(1, np.int32), np.zeros(1, np.int64), np.zeros(1, np.int64)
     assert L.tsgnn_wgrad_blocks_plan(8518, 256, 264, 256, 264, ns.ctypes.data, rps.ctypes.data, need.ctypes.data) == 0
     assert ns[0] > 0 and ns[0] * rps[0] >= 8518 and rps[0] % 32 == 0 and need[0] == 6 * ns[0] * 129 * 128
@@ -97,12 +97,58 @@ def test_new_entry_points_validate_on_the_host():
     assert L.tsgnn_margin_rank_bwd_f32(None, None, 1, None, None, None) == -1
     assert L.tsgnn_row_post_bwd_f32(None, 3, 10, 12, None, 8, None, 8, None, 8, None, 8, 1, 1, None, None, None, None, 8, None) == -1
     assert L.tsgnn_gat_bwd_products_f32(None, 256, None, 264, 100, 256, 264, None, 264, None, 256, 4, 32, None, None) == -1
-    assert L.tsgnn_wgrad_blocks_reduce_f32(None, 4, 256, 264, None, 264, None) == -1
-    assert L.tsgnn_wgrad_blocks_reduce2_f32(None, 4, 256, 264, None, 264, None, 4, 92, 264, None, 264, None) == -1
+    blocked = [0, 4, 256, 264, 0, 264, 0, 264, 0, 1, 1]                              # (ws, nslab, K, N, dw, lddw, db, n_db, tail, kn, blocked)
+    one, two = np.asarray([1] + blocked, np.int64), np.asarray([2] + blocked + blocked[:2] + [92] + blocked[3:], np.int64)
+    assert L.tsgnn_wgrad_reduce_sets_f32(one.ctypes.data, None, None, None) == -1
+    assert L.tsgnn_wgrad_reduce_sets_f32(two.ctypes.data, None, None, None) == -1
     assert L.tsgnn_wgrad_blocks_slabs_f32(None, 256, None, 264, 100, 256, 264, 4, 32, None, None) == -1
     off = np.zeros(10, dtype=np.int64)
     assert L.tsgnn_ingest_compact_layout(4, 64, 256, 1024, 64, off.ctypes.data) == 0
     assert off[1] - off[0] == 8 and all(int(o) % 4 == 0 for o in off)                   # header: 4 sizes + sequence word + 3 spare
+
+
+def test_wgrad_reduce_descriptor_rejects_bad_records():
+    """the weight-gradient reduction's descriptor parser (tsgnn_wgrad_reduce_sets_*): block counts of good records, and every bad record
+    refused on the host — the whole descriptor, before anything is launched"""
+    import numpy as np
+    from two_stage_gnn_amd import _native as nat
+    L = nat.lib()
+    P = 1 << 20                                                                          # (pointers are only tested for NULL here)
+
+    def rec(ws=P, nslab=4, K=6, N=8, dw=P, lddw=6, db=P, n_db=8, tail=0, kn=0, blocked=0):
+        return [ws, nslab, K, N, dw, lddw, db, n_db, tail, kn, blocked]
+
+    def blocks(*recs):
+        d = np.asarray([len(recs)] + sum(recs, []), np.int64)                        # (referenced until the call has read it)
+        return L.tsgnn_wgrad_reduce_sets_blocks(d.ctypes.data)
+
+    def launch(*recs):
+        d = np.asarray([len(recs)] + sum(recs, []), np.int64)
+        return L.tsgnn_wgrad_reduce_sets_f32(d.ctypes.data, None, None, None)
+
+    assert blocks() == 0 and blocks(rec()) == 1
+    assert blocks(rec(K=128, N=128, lddw=128, n_db=128)) == 258
+    assert blocks(rec(K=128, N=128, lddw=128, db=0)) == 258                           # the grid covers the bias row with or without db
+    assert blocks(rec(K=0, N=132, dw=0, lddw=0, n_db=128, tail=P)) == 3               # score-layer rows [nb][F + 4]
+    assert blocks(rec(K=0, N=260, lddw=132, n_db=128, tail=P)) == 5                   # GraphConv scorer rows, dw_root from column F + 4
+    assert blocks(rec(K=256, N=264, lddw=264, db=0, n_db=264, kn=1, blocked=1)) == 2 * (258 + 258 + 17)   # 2 x 3 blocks of 128 x 128
+    assert blocks(*[rec()] * 12) == 12
+    assert L.tsgnn_wgrad_reduce_sets_blocks(None) == -1
+    bad = [rec(ws=0), rec(nslab=0), rec(K=-1), rec(N=0), rec(n_db=9), rec(n_db=-1), rec(kn=2), rec(blocked=2), rec(dw=0),
+           rec(lddw=5), rec(kn=1, lddw=7), rec(tail=P), rec(K=0, lddw=8, n_db=8), rec(K=0, N=20, lddw=8, n_db=8),
+           rec(K=0, N=20, lddw=12, n_db=9), rec(K=1 << 16, N=1 << 16, lddw=1 << 16, n_db=1 << 16),
+           rec(K=0, N=20, lddw=12, n_db=8, blocked=1), rec(K=520, N=8, lddw=520, blocked=1), rec(K=8, N=520, lddw=8, n_db=520, blocked=1),
+           rec(tail=P, n_db=4, blocked=1), rec(n_db=4, blocked=1)]
+    for r in bad:
+        assert blocks(r) == -1 and launch(r) == -1, r
+        assert blocks(rec(), r) == -1 and launch(rec(), r) == -1, r                  # one bad record refuses the whole descriptor
+    assert blocks(*[rec()] * 13) == -1 and launch(*[rec()] * 13) == -1               # at most 12 records per call
+    n = np.asarray([-1], np.int64)
+    assert L.tsgnn_wgrad_reduce_sets_blocks(n.ctypes.data) == -1
+    # the positional form: a used set (ws != NULL) needs K > 0, a weight destination and slabs
+    assert L.tsgnn_wgrad_reduce_multi_f32(P, 4, 0, 8, P, None, *([None, 0, 0, 0, None, None] * 3), None, None, None) == -1
+    assert L.tsgnn_wgrad_reduce_multi_f32(P, 4, 6, 8, None, None, *([None, 0, 0, 0, None, None] * 3), None, None, None) == -1
+    assert L.tsgnn_wgrad_reduce_multi_f32(P, 0, 6, 8, P, None, *([None, 0, 0, 0, None, None] * 3), None, None, None) == -1
 
 
 def test_paired_launch_records_merge_in_order(monkeypatch):

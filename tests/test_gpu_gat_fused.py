@@ -159,7 +159,7 @@ def test_fused_path_is_the_one_that_runs():
     # (the input features need no gradient): the blocked weight gradient's slabs alone; ONE reduction launch for both layers, issued
     # by the parameter unpack
     assert names.count("gat_bwd_products_f32") == 1 and names.count("wgrad_blocks_slabs_f32") == 1
-    assert names.count("wgrad_blocks_reduce2_f32") == 1 and names.index("wgrad_blocks_reduce2_f32") == names.index("gat_unpack_f32") - 1
+    assert names.count("wgrad_reduce_sets_f32") == 1 and names.index("wgrad_reduce_sets_f32") == names.index("gat_unpack_f32") - 1
     assert not any(n in names for n in ("edge_softmax_fwd_f32", "csr_sddmm_heads_f32", "node_scores2_f32"))
 
 

@@ -587,10 +587,103 @@ def test_row_post_bwd_against_autograd(T, F, ln, relu, with_dxs):
     torch.testing.assert_close(du.cpu().double(), u.grad, rtol=2e-4, atol=2e-5)
 
 
+def _fixed_order_sum(x):
+    """float32 emulation of the reduction's order over x[nslab, E]: four groups of contiguous slab ranges, four accumulators each,
+    (a0 + a1) + (a2 + a3), the groups added in order"""
+    nslab = x.shape[0]
+    per = (nslab + 3) // 4
+    g = []
+    for grp in range(4):
+        a = [np.zeros(x.shape[1], np.float32) for _ in range(4)]
+        s, s1 = grp * per, min(nslab, grp * per + per)
+        while s + 4 <= s1:
+            for u in range(4):
+                a[u] = a[u] + x[s + u]
+            s += 4
+        while s < s1:
+            a[0] = a[0] + x[s]
+            s += 1
+        g.append((a[0] + a[1]) + (a[2] + a[3]))
+    return (g[0] + g[1]) + (g[2] + g[3])
+
+
+def test_wgrad_reduce_every_set_kind_bitwise(T):
+    """mp.wgrad_reduce (tsgnn_wgrad_reduce_sets_f32): [K, N] and [N, K] (lddw > K) sets, blocked matrices in both layouts, score-layer
+    rows with a tail and GraphConv-scorer rows with a dw column offset — 14 sets, two launches — against the fixed order in float32,
+    bit for bit; |grad|^2 shares per block and ONE step-counter advance"""
+    mp, _ = T
+    WB = 129 * 128                                               # slab floats of a 128 x 128 output block (blocked matrices)
+    g = torch.Generator().manual_seed(11)
+    F = 20
+    dev = torch.device("cuda")
+    # (name, nslab, K, N, kn, lddw, with_db, n_db, with_tail, blocked)
+    kinds = [("kn", 1, 6, 8, 1, 8, True, 8, False, False), ("oi", 3, 5, 12, 0, 8, True, 12, False, False),
+             ("blk_kn", 4, 200, 264, 1, 268, True, 264, False, True), ("blk_oi", 5, 132, 140, 0, 136, False, 140, False, True),
+             ("rows", 17, 0, F + 4, 0, 0, True, F, True, False), ("gc_rows", 5, 0, 2 * F + 4, 0, F + 4, True, F, True, False)]
+    sets, host, outs = [], [], []
+    for name, nslab, K, N, kn, lddw, with_db, n_db, with_tail, blocked in kinds:
+        nblk = ((K + 127) // 128) * ((N + 127) // 128) if blocked else 1
+        ws = torch.randn(nblk * nslab * (WB if blocked else (K + 1) * N), generator=g)
+        if K > 0:
+            dw = torch.full((K, lddw) if kn else (N, lddw), 7.0, device=dev)
+        else:
+            dw = torch.full((n_db + 2,), 7.0, device=dev) if name == "gc_rows" else None
+        db = torch.full((n_db + 3,), 7.0, device=dev) if with_db else None
+        tail = torch.full((2,), 7.0, device=dev) if with_tail else None
+        sets.append(mp.wgrad_set(ws.to(dev), nslab, K, N, dw, db, n_db=n_db, tail=tail, kn=kn, lddw=lddw, blocked=blocked))
+        host.append((name, ws.numpy(), nslab, K, N, kn, lddw, n_db, blocked))
+        outs.append((dw, db, tail))
+    sink = mp.GradSink()
+    sink.norm_parts = torch.full((4096,), -1.0, device=dev)
+    sink.step_state = torch.full((4,), 5.0, device=dev)
+    sink.norm_enabled = True
+    assert mp.wgrad_reduce(sets, norm_sink=sink) and sink.stepped
+    torch.cuda.synchronize()
+    parts = sink.norm_parts.cpu().numpy()
+    assert float(sink.step_state[0]) == 6.0 and float(sink.step_state[1]) == 5.0          # one advance for both launches
+    blk = 0
+    for (name, ws, nslab, K, N, kn, lddw, n_db, blocked), (dw, db, tail) in zip(host, outs):
+        want_dw = np.full(tuple(dw.shape), 7.0, np.float32) if dw is not None else None
+        want_db = np.full(tuple(db.shape), 7.0, np.float32) if db is not None else None
+        want_tail = np.full(2, 7.0, np.float32) if tail is not None else None
+        NB = (N + 127) // 128 if blocked else 1
+        for t in range((((K + 127) // 128) * NB) if blocked else 1):
+            kb, nb = divmod(t, NB)
+            kc, nc = (min(128, K - 128 * kb), min(128, N - 128 * nb)) if blocked else (K, N)
+            x = ws[t * nslab * WB:][:nslab * (kc + 1) * nc].reshape(nslab, (kc + 1) * nc)     # block t's slabs, packed [nslab][kc + 1][nc]
+            img = _fixed_order_sum(x).reshape(kc + 1, nc)
+            wrote = np.zeros((kc + 1, nc), bool)
+            wrote[:kc] = True
+            r0, c0 = (128 * kb, 128 * nb) if blocked else (0, 0)
+            if kc > 0:
+                if kn:
+                    want_dw[r0:r0 + kc, c0:c0 + nc] = img[:kc]
+                else:
+                    want_dw[c0:c0 + nc, r0:r0 + kc] = img[:kc].T
+            if want_db is not None and kb == 0:
+                want_db[c0:c0 + min(nc, n_db)] = img[kc, :n_db]
+                wrote[kc, :n_db] = True
+            if want_tail is not None:
+                want_tail[0] = img[kc, n_db]
+                wrote[kc, n_db] = True
+            if K == 0 and want_dw is not None:
+                want_dw[:n_db] = img[0, lddw:lddw + n_db]
+                wrote[0, lddw:lddw + n_db] = True
+            sq = np.where(wrote, img.astype(np.float64) ** 2, 0.0).reshape(-1)
+            nb_set = -(-sq.size // 64)
+            np.testing.assert_allclose(parts[blk:blk + nb_set], np.add.reduceat(sq, np.arange(0, sq.size, 64)), rtol=3e-5, atol=1e-30,
+                                       err_msg=name)
+            blk += nb_set
+        for got, want in ((dw, want_dw), (db, want_db), (tail, want_tail)):
+            if got is not None:
+                assert np.array_equal(got.cpu().numpy(), want), name
+    assert sink.norm_used == blk and float(parts[blk]) == -1.0                             # the slots the library counted, no more
+
+
 @pytest.mark.parametrize("R_,K,N,bias", [(8183, 192, 64, True), (1024, 192, 64, True), (500, 64, 128, False), (300, 260, 200, True)])
 def test_linear_backward_products_merged_equals_separate(T, R_, K, N, bias):
     """torch.nn.Linear's backward with the weight-gradient slabs beside the input-gradient product in one launch
-    (tsgnn_linear_bwd_products_f32 + tsgnn_wgrad_blocks_reduce_oi_f32; DiffPool's assignment predictor) == the separate launches,
+    (tsgnn_linear_bwd_products_f32 + a blocked tsgnn_wgrad_reduce_sets_f32 record; DiffPool's assignment predictor) == the separate launches,
     bit for bit, and torch"""
     mp, _ = T
     from two_stage_gnn_amd import _native as nat

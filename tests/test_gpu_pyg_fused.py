@@ -234,8 +234,8 @@ def test_propagate_mean_both_forms(feat, ld, with_rowend):
 
 def test_copy2d_multi_and_score_rows_in_the_reduction():
     """tsgnn_copy2d_multi_f32 (zero-padded placement of several matrices in one launch) and the K = 0 sets of
-    tsgnn_sage_wgrad_reduce_oi_f32 (column sums of the score layer's partial rows beside the weight slabs, with |grad|^2 shares)"""
-    from two_stage_gnn_amd import _native as nat, pyg_sage as ps
+    tsgnn_wgrad_reduce_sets_f32 (column sums of the score layer's partial rows beside the weight slabs)"""
+    from two_stage_gnn_amd import _native as nat, message_passing as mp
     dev = torch.device("cuda")
     g = torch.Generator().manual_seed(3)
     srcs = [torch.randn(128, 1, generator=g), torch.randn(128, 128, generator=g), torch.randn(64, 7, generator=g)]
@@ -260,8 +260,7 @@ def test_copy2d_multi_and_score_rows_in_the_reduction():
     dw, db = torch.zeros(N, K, device=dev), torch.zeros(N, device=dev)
     dws, dbs = torch.zeros(F + 3, device=dev), torch.zeros(2, device=dev)
     wsd, partd = ws.to(dev), part.to(dev)
-    sets = [(wsd, nslab, K, N, dw, db), (partd, nb, 0, F + 4, None, dws, F, dbs)]
-    ps.reduce_oi(sets)
+    mp.wgrad_reduce([mp.wgrad_set(wsd, nslab, K, N, dw, db), mp.wgrad_set(partd, nb, 0, F + 4, None, dws, n_db=F, tail=dbs)])
     torch.cuda.synchronize()
     tot = ws.double().sum(0)
     torch.testing.assert_close(dw.cpu().double(), tot[:K].t(), rtol=1e-5, atol=1e-5)

@@ -58,7 +58,7 @@ def _level_case(case, F):
 
 @pytest.mark.parametrize("case,F", [("mixed", 8), ("mixed", 32), ("mixed", 64), ("mixed", 128), ("many", 32)])
 def test_graphconv_pool_kernels_vs_torch(case, F):
-    from two_stage_gnn_amd import _native as nat, pyg_sage as ps, sag_stack as SS
+    from two_stage_gnn_amd import _native as nat, message_passing as mp, sag_stack as SS
     from two_stage_gnn_amd.graph import GraphBatch
     dev = torch.device("cuda")
     sizes, ei, y = _level_case(case, F)
@@ -125,7 +125,7 @@ def test_graphconv_pool_kernels_vs_torch(case, F):
     nat.call("sag_pool_graph_gc_bwd_f32", yd, F, score, new_id, L.gp, Ln.gp, arg, dxp.to(dev), F, dread.to(dev), 2 * F, g.rowptr, None,
              g.col, w_rel.to(dev), w_root.to(dev), B, L.max_seg, F, du, F, part)
     dwrel, dwroot, db = torch.zeros(1, F, device=dev), torch.zeros(1, F, device=dev), torch.zeros(1, device=dev)
-    ps.reduce_oi([(part, B, 0, 2 * F + 4, dwroot, dwrel, F, db, 0, F + 4)])
+    mp.wgrad_reduce([mp.wgrad_set(part, B, 0, 2 * F + 4, dwroot, dwrel, n_db=F, tail=db, lddw=F + 4)])
     torch.cuda.synchronize()
     yv = y.double().requires_grad_(True)
     wl, wr, bb = w_rel.double().requires_grad_(True), w_root.double().requires_grad_(True), b.double().requires_grad_(True)

@@ -8,7 +8,7 @@
 // 512 slots of the chip, and the 22 that wait run on a nearly empty machine (18.1 us at 256 panels, 23.7 at 257); the
 // slab launch ends the same way.  Launched together — the input-gradient blocks first, the slab blocks behind them — the slab blocks
 // fill the slots as the panels drain, one kernel boundary is gone, and the layer below gets dx no later than before.  The slabs are
-// reduced by tsgnn_wgrad_blocks_reduce_f32 as after a launch of their own (same bits as the separate launches: same blocks, same order).
+// reduced by tsgnn_wgrad_reduce_sets_f32 as after a launch of their own (same bits as the separate launches: same blocks, same order).
 #include "common.h"
 #include "../../include/tsgnn.h"
 #include "rowgemm_body.h"
@@ -39,10 +39,10 @@ __global__ __launch_bounds__(256) void gat_bwd_products_kernel(RowGemmArgs g, Wg
 
 extern "C" {
 
-/* dw_slabs (ws) <- the slab partials of dW'[K_in, N] = x[:, :K_in]^T du  (reduce with tsgnn_wgrad_blocks_reduce_f32; plan with
+/* dw_slabs (ws) <- the slab partials of dW'[K_in, N] = x[:, :K_in]^T du  (reduce with a blocked record of tsgnn_wgrad_reduce_sets_f32; plan with
  * tsgnn_wgrad_blocks_plan(rows, K_in, N, ldx, lddu)) and dx[rows, K_in] = du[rows, N] . wp[K_in, N]^T, one launch.
  * K_in, N <= 512, both multiples of 4, 16-byte aligned rows everywhere.  (K_in = N = 128: the slabs have tsgnn_linear_wgrad_f32's
- * layout [nslab][K_in + 1][N] — the SAGPool conv layers reduce them with tsgnn_linear_wgrad_du_reduce_f32.) */
+ * layout [nslab][K_in + 1][N] — the SAGPool conv layers reduce them as a plain record of tsgnn_wgrad_reduce_sets_f32.) */
 int tsgnn_gat_bwd_products_f32(const float* x, int64_t ldx, const float* du, int64_t lddu, int64_t rows, int K_in, int N, const float* wp,
                                int64_t ldwp, float* dx, int64_t lddx, int nslab, int64_t rows_per_slab, float* ws, tsgnn_stream_t stream) {
   if (!x || !du || !wp || !dx || !ws || rows <= 0 || K_in <= 0 || N <= 0 || nslab <= 0 || rows_per_slab <= 0 || ldx < K_in || lddu < N ||
@@ -73,7 +73,7 @@ int tsgnn_gat_bwd_products_f32(const float* x, int64_t ldx, const float* du, int
 }
 
 /* The same pairing for a torch.nn.Linear y = x W^T + b with W [N = out, K_in = in] (message_passing._LinearOI: DiffPool's assignment
- * predictor, encoders.py:362-372): the slab partials of (dW^T, db) from x and dy into ws (reduce with tsgnn_wgrad_blocks_reduce_oi_f32)
+ * predictor, encoders.py:362-372): the slab partials of (dW^T, db) from x and dy into ws (reduce with a blocked record of tsgnn_wgrad_reduce_sets_f32)
  * and dx[rows, K_in] = dy[rows, N] . W in one launch.  K_in, N <= 512, K_in % 4 == 0, N % 4 == 0. */
 int tsgnn_linear_bwd_products_f32(const float* x, int64_t ldx, const float* dy, int64_t lddy, int64_t rows, int K_in, int N, const float* w,
                                   int64_t ldw, float* dx, int64_t lddx, int nslab, int64_t rows_per_slab, float* ws, tsgnn_stream_t stream) {

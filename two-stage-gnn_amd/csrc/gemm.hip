@@ -14,6 +14,7 @@
 // Tile: 64x64 per 256-thread block (4 waves, 2x2, one 32x32 MFMA tile each), K chunk 32, operands
 // staged through LDS with +1 padding (conflict-free ds_read_b32 for both fragment shapes).
 #include "common.h"
+#include <algorithm>
 #include <cstdlib>
 #include <type_traits>
 #include "../../include/tsgnn.h"
@@ -233,55 +234,14 @@ __global__ __launch_bounds__(256) void gemm_tn_rows_kernel(TnArgs g) {
   tn_rows_body<MT, NTt, NY>(g, tn_smem, blockIdx.x, blockIdx.y, gridDim.x);
 }
 
-// out[e] = sum_s slabs[s][e]; e < K_in*N -> dW, else -> db.  64 outputs x 4 slab groups per block.
-__global__ __launch_bounds__(256) void tn_rows_reduce(const float* __restrict__ slabs, int nslab, int64_t per_slab, int64_t n_w,
-                                                      float* __restrict__ dw, float* __restrict__ db,
-                                                      const int* __restrict__ seg_slab_ptr) {
-  __shared__ float lds[4][64];
+// The fixed-order slab sum that every weight gradient of the library goes through: entry e of slabs[0 .. nslab) (stride per_slab).
+// Four wave groups take contiguous slab ranges, four accumulators each, and meet in LDS in group order: the same bits every run
+// (scripts/repeat_steps.py, repeat_diffpool.py).  All 256 threads of the block call it (it holds a barrier); every lane gets the sum.
+__device__ __forceinline__ float slab_sum(const float* __restrict__ slabs, int nslab, int64_t per_slab, int64_t e, bool ok,
+                                          float (*lds)[64]) {
   const int e_l = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int64_t e = (int64_t)blockIdx.x * 64 + e_l;
-  // blockIdx.y = segment (graph): sums only that segment's slabs into dw[seg]
-  const int sb = seg_slab_ptr ? seg_slab_ptr[blockIdx.y] : 0;
-  const int se = seg_slab_ptr ? seg_slab_ptr[blockIdx.y + 1] : nslab;
-  dw += (int64_t)blockIdx.y * n_w;
   float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (e < per_slab) {
-    const int per = (se - sb + 3) / 4;
-    const int s0 = sb + grp * per, s1 = min(se, s0 + per);
-    int s = s0;
-    for (; s + 4 <= s1; s += 4) {
-      a0 += slabs[(int64_t)s * per_slab + e];
-      a1 += slabs[(int64_t)(s + 1) * per_slab + e];
-      a2 += slabs[(int64_t)(s + 2) * per_slab + e];
-      a3 += slabs[(int64_t)(s + 3) * per_slab + e];
-    }
-    for (; s < s1; ++s) a0 += slabs[(int64_t)s * per_slab + e];
-  }
-  lds[grp][e_l] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (grp == 0 && e < per_slab) {
-    const float v = (lds[0][e_l] + lds[1][e_l]) + (lds[2][e_l] + lds[3][e_l]);
-    if (e < n_w) dw[e] = v;
-    else if (db) db[e - n_w] = v;
-  }
-}
-
-
-// tn_rows_reduce with one passenger: the last block adds up the per-graph partial rows of the SAGPool score-layer gradients
-// (du_reduce_body) — both reductions wait for the same producer launch, so they share one launch (4 us per pooled level)
-__global__ __launch_bounds__(256) void tn_rows_reduce_du(const float* __restrict__ slabs, int nslab, int64_t per_slab, int64_t n_w,
-                                                         float* __restrict__ dw, float* __restrict__ db, float* __restrict__ part, int nb,
-                                                         int F_du, float* __restrict__ dws, float* __restrict__ dbs) {
-  __shared__ float4 s_part[256];
-  if (blockIdx.x == gridDim.x - 1) {
-    du_reduce_body(part, nb, F_du, dws, dbs, nb, 1, 0, s_part);
-    return;
-  }
-  float (*lds)[64] = reinterpret_cast<float (*)[64]>(s_part);      // [4][64]
-  const int e_l = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int64_t e = (int64_t)blockIdx.x * 64 + e_l;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (e < per_slab) {                                                 // the arithmetic (and order) of tn_rows_reduce
+  if (ok) {
     const int per = (nslab + 3) / 4;
     const int s0 = grp * per, s1 = min(nslab, s0 + per);
     int s = s0;
@@ -295,53 +255,76 @@ __global__ __launch_bounds__(256) void tn_rows_reduce_du(const float* __restrict
   }
   lds[grp][e_l] = (a0 + a1) + (a2 + a3);
   __syncthreads();
-  if (grp == 0 && e < per_slab) {
-    const float v = (lds[0][e_l] + lds[1][e_l]) + (lds[2][e_l] + lds[3][e_l]);
+  return (lds[0][e_l] + lds[1][e_l]) + (lds[2][e_l] + lds[3][e_l]);
+}
+
+// per-graph sums of ragged slabs (tsgnn_ragged_tn_f32): block (x, g) sums graph g's slabs [seg_slab_ptr[g], seg_slab_ptr[g + 1])
+// for 64 entries of the [K][N] image (n_w = K * N) into out[g]
+__global__ __launch_bounds__(256) void tn_rows_reduce(const float* __restrict__ slabs, int64_t per_slab, int64_t n_w, float* __restrict__ out,
+                                                      const int* __restrict__ seg_slab_ptr) {
+  __shared__ float lds[4][64];
+  const int64_t e = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  const int sb = seg_slab_ptr[blockIdx.y], se = seg_slab_ptr[blockIdx.y + 1];
+  const float v = slab_sum(slabs + (int64_t)sb * per_slab, se - sb, per_slab, e, e < per_slab, lds);
+  if (threadIdx.x < 64 && e < n_w) out[(int64_t)blockIdx.y * n_w + e] = v;
+}
+
+// the slab sum of one [K_in + 1][N] set (dw[K_in][N], db[N]) with one passenger: the last block adds up the per-graph partial rows of
+// the SAGPool score-layer gradients (du_reduce_body, an order of its own) — both reductions wait for the same producer launch, so they
+// share one launch (4 us per pooled level)
+__global__ __launch_bounds__(256) void tn_rows_reduce_du(const float* __restrict__ slabs, int nslab, int64_t per_slab, int64_t n_w,
+                                                         float* __restrict__ dw, float* __restrict__ db, float* __restrict__ part, int nb,
+                                                         int F_du, float* __restrict__ dws, float* __restrict__ dbs) {
+  __shared__ float4 s_part[256];
+  if (blockIdx.x == gridDim.x - 1) {
+    du_reduce_body(part, nb, F_du, dws, dbs, nb, 1, 0, s_part);
+    return;
+  }
+  const int64_t e = (int64_t)blockIdx.x * 64 + (threadIdx.x & 63);
+  const float v = slab_sum(slabs, nslab, per_slab, e, e < per_slab, reinterpret_cast<float (*)[64]>(s_part));
+  if (threadIdx.x < 64 && e < per_slab) {
     if (e < n_w) dw[e] = v;
     else if (db) db[e - n_w] = v;
   }
 }
 
-struct ReduceSet { const float* slabs; int nslab; int64_t per_slab; int64_t n_w; float* dw; float* db; int64_t first_block; };
-constexpr int RM_SETS = 8;
-struct ReduceMulti { ReduceSet s[RM_SETS]; int n; float* normparts; float* step_state; };
-// several independent slab sets (the layers of one backward pass) reduced by ONE launch
+// One slab set of the weight-gradient reduction: slabs [nslab][K + 1][N], row K = the bias partial (K = 0: partial rows only).
+struct ReduceSet {
+  const float* ws; int nslab, K, N;
+  float* dw; int64_t lddw; int kn;      // row k < K: dw[n * lddw + k] (nn.Linear's [out, in]); kn = 1: dw[k * lddw + n]
+  float* db; int n_db; float* tail;     // row K: columns [0, n_db) -> db, column n_db -> tail[0] (both nullable);
+                                        // K = 0: columns [lddw, lddw + n_db) -> dw (nullable)
+};
+constexpr int RM_SETS = 12;
+// (the sets' first blocks side by side: the lookup of a block's set reads one cache line — spread over the set records, 0.2 us more)
+struct ReduceMulti { int first_block[RM_SETS]; ReduceSet s[RM_SETS]; int n; float* normparts; float* step_state; };
+
+// all the weight gradients of a backward pass in one launch: block -> 64 consecutive entries (k, n) of one set's [K + 1][N] slab image,
+// n fastest (coalesced slab reads)
 __global__ __launch_bounds__(256) void tn_rows_reduce_multi(ReduceMulti m) {
   __shared__ float lds[4][64];
-  int k = 0;
+  int si = 0;
 #pragma unroll
-  for (int t = 1; t < RM_SETS; ++t) if (t < m.n && (int64_t)blockIdx.x >= m.s[t].first_block) k = t;
-  const ReduceSet r = m.s[k];
-  const int e_l = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int64_t e = ((int64_t)blockIdx.x - r.first_block) * 64 + e_l;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (e < r.per_slab) {
-    const int per = (r.nslab + 3) / 4;
-    const int s0 = grp * per, s1 = min(r.nslab, s0 + per);
-    int s = s0;
-    for (; s + 4 <= s1; s += 4) {
-      a0 += r.slabs[(int64_t)s * r.per_slab + e];
-      a1 += r.slabs[(int64_t)(s + 1) * r.per_slab + e];
-      a2 += r.slabs[(int64_t)(s + 2) * r.per_slab + e];
-      a3 += r.slabs[(int64_t)(s + 3) * r.per_slab + e];
-    }
-    for (; s < s1; ++s) a0 += r.slabs[(int64_t)s * r.per_slab + e];
+  for (int t = 1; t < RM_SETS; ++t) if (t < m.n && (int)blockIdx.x >= m.first_block[t]) si = t;
+  const ReduceSet& r = m.s[si];
+  const int e_l = threadIdx.x & 63;
+  const int64_t per_slab = (int64_t)(r.K + 1) * r.N;
+  const int64_t e = (int64_t)((int)blockIdx.x - m.first_block[si]) * 64 + e_l;
+  const float v = slab_sum(r.ws, r.nslab, per_slab, e, e < per_slab, lds);
+  if (threadIdx.x >= 64) return;                         // wave 0: one entry per lane
+  float sq = 0.f;
+  if (e < per_slab) {
+    const int k = (int)e / r.N, n = (int)e % r.N;      // (e < per_slab <= INT32_MAX: reduce_plan)
+    if (k < r.K) { r.dw[r.kn ? (int64_t)k * r.lddw + n : (int64_t)n * r.lddw + k] = v; sq = v * v; }
+    else if (r.db && n < r.n_db) { r.db[n] = v; sq = v * v; }
+    else if (r.tail && n == r.n_db) { r.tail[0] = v; sq = v * v; }
+    else if (r.K == 0 && r.dw && n >= r.lddw && n < r.lddw + r.n_db) { r.dw[n - r.lddw] = v; sq = v * v; }
   }
-  lds[grp][e_l] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (grp == 0) {                                        // wave 0: one element per lane
-    float sq = 0.f;
-    if (e < r.per_slab) {
-      const float v = (lds[0][e_l] + lds[1][e_l]) + (lds[2][e_l] + lds[3][e_l]);
-      if (e < r.n_w) { r.dw[e] = v; sq = v * v; }
-      else if (r.db) { r.db[e - r.n_w] = v; sq = v * v; }
-    }
-    if (m.normparts) {                                   // this block's share of |grad|^2 (summed in fixed order by the optimiser)
-      sq = wave_sum(sq);
-      if (e_l == 0) m.normparts[blockIdx.x] = sq;
-    }
-    if (m.step_state && blockIdx.x == 0 && e_l == 0) m.step_state[0] += 1.f;   // optimiser step counter, ahead of the update kernel
+  if (m.normparts) {                                     // this block's share of |grad|^2 (summed in fixed order by the optimiser)
+    sq = wave_sum(sq);
+    if (e_l == 0) m.normparts[blockIdx.x] = sq;
   }
+  if (m.step_state && blockIdx.x == 0 && e_l == 0) m.step_state[0] += 1.f;   // optimiser step counter, ahead of the update kernel
 }
 
 // ---- blocked weight gradient: dW[K_in, N] for K_in, N up to 512 as 128 x 128 output blocks ("sets"), all of them and all of
@@ -352,56 +335,79 @@ __global__ __launch_bounds__(256) void wgrad_blocks_kernel(WgradBlocks w) {
   extern __shared__ __attribute__((aligned(16))) float tn_smem[];
   wgrad_blocks_role<NY>(w, tn_smem, blockIdx.x, blockIdx.y, gridDim.x);
 }
-struct WgradBlocksReduce {
-  const float* slabs; int nslab; int64_t set_stride;
-  int K_in, N, NB, nsets;
-  float* dw; int64_t lddw;
-  int oi; float* db;                                    // oi: dw is [N][K_in] (torch.nn.Linear's layout); db [N] nullable (oi form)
-  int first_block[WB_MAXSETS + 1];
-};
-__device__ __forceinline__ void wgrad_blocks_reduce_body(const WgradBlocksReduce& r, const int bx) {
-  __shared__ float lds[4][64];
-  int set = 0;
-#pragma unroll
-  for (int t = 1; t < WB_MAXSETS; ++t) if (t < r.nsets && bx >= r.first_block[t]) set = t;
-  const int kb = set / r.NB, nb = set % r.NB;
-  const int kc = min(128, r.K_in - 128 * kb), nc = min(128, r.N - 128 * nb);
-  const int64_t per_slab = (int64_t)(kc + 1) * nc;
-  const float* slabs = r.slabs + (int64_t)set * r.set_stride;
-  const int e_l = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int64_t e = ((int64_t)bx - r.first_block[set]) * 64 + e_l;
-  const bool ok = e < ((r.db && kb == 0) ? per_slab : (int64_t)kc * nc);   // (the slabs' last row is colsum(du) of the column block)
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (ok) {                                             // the arithmetic (and order) of tn_rows_reduce
-    const int per = (r.nslab + 3) / 4;
-    const int s0 = grp * per, s1 = min(r.nslab, s0 + per);
-    int s = s0;
-    for (; s + 4 <= s1; s += 4) {
-      a0 += slabs[(int64_t)s * per_slab + e];
-      a1 += slabs[(int64_t)(s + 1) * per_slab + e];
-      a2 += slabs[(int64_t)(s + 2) * per_slab + e];
-      a3 += slabs[(int64_t)(s + 3) * per_slab + e];
+}  // namespace
+
+// ---- the one host path into tn_rows_reduce_multi.  desc (HOST memory): [n <= RM_SETS, n x RS_WORDS] records (tsgnn.h,
+// tsgnn_wgrad_reduce_sets_f32); a blocked record expands into one set per 128 x 128 output block.  A set's block count is
+// ceil((K + 1) * N / 64), its whole slab image whether or not it writes the bias row: the launches' grid and the norm-share slots
+// (tsgnn_wgrad_reduce_sets_blocks) both come from here.
+constexpr int RS_WORDS = 11;
+struct ReducePlan { ReduceSet s[RM_SETS * WB_MAXSETS]; int64_t first_block[RM_SETS * WB_MAXSETS + 1]; int n; };
+
+static int reduce_plan(const int64_t* desc, ReducePlan& p) {
+  if (!desc || desc[0] < 0 || desc[0] > RM_SETS) return TSGNN_EINVAL;
+  p.n = 0;
+  p.first_block[0] = 0;
+  auto add = [&p](const ReduceSet& r) {
+    p.first_block[p.n + 1] = p.first_block[p.n] + ceil_div64((int64_t)(r.K + 1) * r.N, 64);
+    p.s[p.n++] = r;
+  };
+  for (int t = 0; t < (int)desc[0]; ++t) {
+    const int64_t* d = desc + 1 + RS_WORDS * t;
+    const float* ws = reinterpret_cast<const float*>(d[0]);
+    const int64_t nslab = d[1], K = d[2], N = d[3], lddw = d[5], n_db = d[7], kn = d[9], blocked = d[10];
+    float* dw = reinterpret_cast<float*>(d[4]);
+    float* db = reinterpret_cast<float*>(d[6]);
+    float* tail = reinterpret_cast<float*>(d[8]);
+    if (!ws || nslab <= 0 || nslab > INT32_MAX || K < 0 || N <= 0 || (K + 1) * N > INT32_MAX || n_db < 0 || n_db > N) return TSGNN_EINVAL;
+    if ((kn != 0 && kn != 1) || (blocked != 0 && blocked != 1)) return TSGNN_EINVAL;
+    if (K > 0 && (!dw || lddw < (kn ? N : K))) return TSGNN_EINVAL;
+    if (tail && n_db >= N) return TSGNN_EINVAL;
+    if (K == 0 && dw && (lddw <= n_db || lddw + n_db > N)) return TSGNN_EINVAL;
+    if (!blocked) {
+      add(ReduceSet{ws, (int)nslab, (int)K, (int)N, dw, lddw, (int)kn, db, (int)n_db, tail});
+      continue;
     }
-    for (; s < s1; ++s) a0 += slabs[(int64_t)s * per_slab + e];
+    // slabs of tsgnn_wgrad_blocks_*: block (kb, nb) at ws + (kb * NB + nb) * nslab * WB_SET_FLOATS, [nslab][kc + 1][nc]
+    const int KB = (int)(K + 127) / 128, NB = (int)(N + 127) / 128;
+    if (K == 0 || K > 512 || N > 512 || KB * NB > WB_MAXSETS || tail || (db && n_db != N)) return TSGNN_EINVAL;
+    for (int kb = 0; kb < KB; ++kb)
+      for (int nb = 0; nb < NB; ++nb) {
+        const int kc = (int)std::min<int64_t>(128, K - 128 * kb), nc = (int)std::min<int64_t>(128, N - 128 * nb);
+        float* dwb = dw + (kn ? 128 * kb * lddw + 128 * nb : 128 * nb * lddw + 128 * kb);
+        add(ReduceSet{ws + (kb * NB + nb) * nslab * WB_SET_FLOATS, (int)nslab, kc, nc, dwb, lddw, (int)kn, (db && kb == 0) ? db + 128 * nb : nullptr,
+                      nc, nullptr});
+      }
   }
-  lds[grp][e_l] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (grp == 0 && ok) {
-    const int k = (int)(e / nc), n = (int)(e % nc);
-    const float v = (lds[0][e_l] + lds[1][e_l]) + (lds[2][e_l] + lds[3][e_l]);
-    if (k == kc) r.db[128 * nb + n] = v;
-    else if (r.oi) r.dw[(int64_t)(128 * nb + n) * r.lddw + 128 * kb + k] = v;
-    else r.dw[(int64_t)(128 * kb + k) * r.lddw + 128 * nb + n] = v;
-  }
-}
-__global__ __launch_bounds__(256) void wgrad_blocks_reduce(WgradBlocksReduce r) { wgrad_blocks_reduce_body(r, (int)blockIdx.x); }
-// the reductions of TWO blocked weight gradients (the two layers of a GAT encoder) in one launch: blocks [0, n0) work on r0
-__global__ __launch_bounds__(256) void wgrad_blocks_reduce2(WgradBlocksReduce r0, WgradBlocksReduce r1, int n0) {
-  if ((int)blockIdx.x < n0) wgrad_blocks_reduce_body(r0, (int)blockIdx.x);
-  else wgrad_blocks_reduce_body(r1, (int)blockIdx.x - n0);
+  return TSGNN_OK;
 }
 
-}  // namespace
+// RM_SETS sets per launch; normparts continues from launch to launch, the step counter moves in the first
+static int reduce_launch(const ReducePlan& p, float* normparts, float* step_state, tsgnn_stream_t stream) {
+  for (int i = 0; i < p.n; i += RM_SETS) {
+    ReduceMulti m{};
+    m.n = std::min(RM_SETS, p.n - i);
+    const int64_t b0 = p.first_block[i], b1 = p.first_block[i + m.n];
+    for (int t = 0; t < m.n; ++t) {
+      m.s[t] = p.s[i + t];
+      m.first_block[t] = (int)(p.first_block[i + t] - b0);
+    }
+    m.normparts = normparts ? normparts + b0 : nullptr;
+    m.step_state = i == 0 ? step_state : nullptr;
+    tn_rows_reduce_multi<<<(unsigned)(b1 - b0), 256, 0, stream>>>(m);
+  }
+  TSGNN_CHECK_LAUNCH();
+  return TSGNN_OK;
+}
+
+// one matrix's slabs -> dw (+ db): the reduction of tsgnn_linear_wgrad_f32 / tsgnn_wgrad_blocks_f32 / _oi_f32 with dw != NULL
+static int reduce_one(const float* ws, int nslab, int K, int N, float* dw, int64_t lddw, int kn, float* db, int blocked, tsgnn_stream_t stream) {
+  const int64_t desc[1 + RS_WORDS] = {1, (int64_t)(uintptr_t)ws, nslab, K, N, (int64_t)(uintptr_t)dw, lddw, (int64_t)(uintptr_t)db, N, 0, kn,
+                                      blocked};
+  ReducePlan p;
+  const int rc = reduce_plan(desc, p);
+  return rc != TSGNN_OK ? rc : reduce_launch(p, nullptr, nullptr, stream);
+}
 
 extern "C" {
 
@@ -475,8 +481,7 @@ int tsgnn_linear_wgrad_plan(int64_t rows, int K_in, int N, int64_t ldz, int64_t 
   return TSGNN_OK;
 }
 
-/* reduce up to four slab sets (written by tsgnn_linear_wgrad_f32 with dw == NULL) in ONE launch: the weight gradients of all
- * layers of a backward pass.  Unused sets: ws == NULL. */
+/* up to four plain slab sets [K][N] in positional arguments (unused: ws == NULL): records of tsgnn_wgrad_reduce_sets_f32 */
 int tsgnn_wgrad_reduce_multi_f32(const float* ws0, int nslab0, int K0, int N0, float* dw0, float* db0, const float* ws1, int nslab1,
                                  int K1, int N1, float* dw1, float* db1, const float* ws2, int nslab2, int K2, int N2, float* dw2,
                                  float* db2, const float* ws3, int nslab3, int K3, int N3, float* dw3, float* db3,
@@ -485,25 +490,15 @@ int tsgnn_wgrad_reduce_multi_f32(const float* ws0, int nslab0, int K0, int N0, f
   const int ns[4] = {nslab0, nslab1, nslab2, nslab3}, Ks[4] = {K0, K1, K2, K3}, Ns[4] = {N0, N1, N2, N3};
   float* dws[4] = {dw0, dw1, dw2, dw3};
   float* dbs[4] = {db0, db1, db2, db3};
-  ReduceMulti m;
-  m.n = 0;
-  int64_t blocks = 0;
+  int64_t desc[1 + 4 * RS_WORDS] = {0};
   for (int t = 0; t < 4; ++t) {
     if (!ws[t]) continue;
-    if (ns[t] <= 0 || Ks[t] <= 0 || Ns[t] <= 0 || !dws[t]) return TSGNN_EINVAL;
-    const int64_t per_slab = (int64_t)(Ks[t] + 1) * Ns[t];
-    m.s[m.n] = ReduceSet{ws[t], ns[t], per_slab, (int64_t)Ks[t] * Ns[t], dws[t], dbs[t], blocks};
-    blocks += ceil_div64(per_slab, 64);
-    ++m.n;
+    if (Ks[t] <= 0) return TSGNN_EINVAL;
+    const int64_t r[RS_WORDS] = {(int64_t)(uintptr_t)ws[t], ns[t], Ks[t], Ns[t], (int64_t)(uintptr_t)dws[t], Ns[t], (int64_t)(uintptr_t)dbs[t],
+                                 Ns[t], 0, 1, 0};
+    std::copy(r, r + RS_WORDS, desc + 1 + RS_WORDS * desc[0]++);
   }
-  if (m.n == 0) return TSGNN_OK;
-  for (int t = m.n; t < RM_SETS; ++t) m.s[t] = m.s[0];
-  m.normparts = normparts;
-  m.step_state = step_state;
-  TSGNN_KNAME("tn_rows_reduce_multi");
-  tn_rows_reduce_multi<<<(unsigned)blocks, 256, 0, stream>>>(m);
-  TSGNN_CHECK_LAUNCH();
-  return TSGNN_OK;
+  return tsgnn_wgrad_reduce_sets_f32(desc, normparts, step_state, stream);
 }
 
 /* dW[K_in,N] = z[:, :K_in]^T . du ; db[N] = colsum(du) (db nullable).  Plan with tsgnn_linear_wgrad_plan.
@@ -530,12 +525,11 @@ static int linear_wgrad_launch(const float* z, int64_t ldz, const float* du, int
     case 41: TSGNN_TN(4, 1); break; case 42: TSGNN_TN(4, 2); break; case 43: TSGNN_TN(4, 3); break; default: TSGNN_TN(4, 4); break;
   }
 #undef TSGNN_TN
+  if (dw && !du_part) return reduce_one(ws, nslab, K_in, N, dw, N, 1, db, 0, stream);
   const int64_t per_slab = (int64_t)(K_in + 1) * N;
-  if (dw && du_part)
+  if (dw)
     tn_rows_reduce_du<<<(unsigned)ceil_div64(per_slab, 64) + 1, 256, 0, stream>>>(ws, nslab, per_slab, (int64_t)K_in * N, dw, db, du_part,
                                                                                    du_nb, du_F, du_dws, du_dbs);
-  else if (dw)
-    tn_rows_reduce<<<(unsigned)ceil_div64(per_slab, 64), 256, 0, stream>>>(ws, nslab, per_slab, (int64_t)K_in * N, dw, db, nullptr);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -557,24 +551,6 @@ int tsgnn_linear_wgrad_du_f32(const float* z, int64_t ldz, const float* du, int6
   return linear_wgrad_launch(z, ldz, du, lddu, rows, K_in, N, nslab, rows_per_slab, 0, ws, dw, db, part, nb, F_du, dws, dbs, stream);
 }
 
-
-/* only the reduction of tsgnn_linear_wgrad_du_f32 (part nullable: tsgnn_linear_wgrad_f32's), for slabs [nslab][K_in + 1][N] another
- * launch produced (tsgnn_gat_bwd_products_f32: the slab blocks beside the input-gradient product) */
-int tsgnn_linear_wgrad_du_reduce_f32(const float* ws, int nslab, int K_in, int N, float* dw, float* db, float* part, int nb, int F_du,
-                                     float* dws, float* dbs, tsgnn_stream_t stream) {
-  if (!ws || !dw || nslab <= 0 || K_in <= 0 || N <= 0 || K_in > 128 || N > 128) return TSGNN_EINVAL;
-  if (part && (!dws || !dbs || nb <= 0 || nb > 256 || F_du <= 0 || (F_du % 4) || (reinterpret_cast<uintptr_t>(part) & 15) ||
-               (reinterpret_cast<uintptr_t>(dws) & 15)))
-    return TSGNN_EINVAL;
-  const int64_t per_slab = (int64_t)(K_in + 1) * N;
-  if (part)
-    tn_rows_reduce_du<<<(unsigned)ceil_div64(per_slab, 64) + 1, 256, 0, stream>>>(ws, nslab, per_slab, (int64_t)K_in * N, dw, db, part, nb,
-                                                                                   F_du, dws, dbs);
-  else
-    tn_rows_reduce<<<(unsigned)ceil_div64(per_slab, 64), 256, 0, stream>>>(ws, nslab, per_slab, (int64_t)K_in * N, dw, db, nullptr);
-  TSGNN_CHECK_LAUNCH();
-  return TSGNN_OK;
-}
 
 /* Ragged batched  out[b][K,N] = S[rows_b, :K]^T . X[rows_b, :N]  (DiffPool's S^T Z and S^T (A S), encoders.py:374-375):
  * every graph is cut into row slabs (slab_row_ptr[nslab+1], graph b owns slabs [seg_slab_ptr[b], seg_slab_ptr[b+1])),
@@ -603,7 +579,7 @@ int tsgnn_ragged_tn_f32(const float* s_mat, int64_t lds_, const float* x, int64_
 #undef TSGNN_RT
   const int64_t per_slab = (int64_t)(K + 1) * N;
   dim3 rgrid((unsigned)ceil_div64((int64_t)K * N, 64), (unsigned)nseg);
-  tn_rows_reduce<<<rgrid, 256, 0, stream>>>(ws, nslab, per_slab, (int64_t)K * N, out, nullptr, seg_slab_ptr);
+  tn_rows_reduce<<<rgrid, 256, 0, stream>>>(ws, per_slab, (int64_t)K * N, out, seg_slab_ptr);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -648,34 +624,17 @@ int tsgnn_colsum_f32(const float* x, int64_t ld, int64_t rows, int F, float* out
   return TSGNN_OK;
 }
 
-/* the same for up to 8 slab sets described in HOST memory: desc = [n, n x (ws, nslab, K, N, dw, db)] (the gradients of two
- * stacks that share their launches, sage_stack._SageStackPair) */
-int tsgnn_wgrad_reduce_sets_f32(const int64_t* desc, tsgnn_stream_t stream) {
-  if (!desc) return TSGNN_EINVAL;
-  const int n = (int)desc[0];
-  if (n < 0 || n > RM_SETS) return TSGNN_EINVAL;
-  if (n == 0) return TSGNN_OK;
-  ReduceMulti m;
-  m.n = n;
-  int64_t blocks = 0;
-  for (int t = 0; t < n; ++t) {
-    const int64_t* d = desc + 1 + 6 * t;
-    const float* ws = reinterpret_cast<const float*>(d[0]);
-    const int nslab = (int)d[1], K = (int)d[2], N = (int)d[3];
-    float* dw = reinterpret_cast<float*>(d[4]);
-    float* db = reinterpret_cast<float*>(d[5]);
-    if (!ws || !dw || nslab <= 0 || K <= 0 || N <= 0) return TSGNN_EINVAL;
-    const int64_t per_slab = (int64_t)(K + 1) * N;
-    m.s[t] = ReduceSet{ws, nslab, per_slab, (int64_t)K * N, dw, db, blocks};
-    blocks += ceil_div64(per_slab, 64);
-  }
-  for (int t = n; t < RM_SETS; ++t) m.s[t] = m.s[0];
-  m.normparts = nullptr;
-  m.step_state = nullptr;
+int tsgnn_wgrad_reduce_sets_blocks(const int64_t* desc) {
+  ReducePlan p;
+  return reduce_plan(desc, p) == TSGNN_OK ? (int)p.first_block[p.n] : TSGNN_EINVAL;
+}
+
+int tsgnn_wgrad_reduce_sets_f32(const int64_t* desc, float* normparts, float* step_state, tsgnn_stream_t stream) {
+  ReducePlan p;
+  const int rc = reduce_plan(desc, p);
+  if (rc != TSGNN_OK) return rc;
   TSGNN_KNAME("tn_rows_reduce_multi");
-  tn_rows_reduce_multi<<<(unsigned)blocks, 256, 0, stream>>>(m);
-  TSGNN_CHECK_LAUNCH();
-  return TSGNN_OK;
+  return reduce_launch(p, normparts, step_state, stream);
 }
 
 int tsgnn_wgrad_blocks_plan(int64_t rows, int K_in, int N, int64_t ldz, int64_t lddu, int* nslab, int64_t* rows_per_slab,
@@ -697,8 +656,6 @@ int tsgnn_wgrad_blocks_plan(int64_t rows, int K_in, int N, int64_t ldz, int64_t 
   return TSGNN_OK;
 }
 
-static int wgrad_blocks_reduce_launch(const float* ws, int nslab, int K_in, int N, float* dw, int64_t lddw, int oi, float* db,
-                                      tsgnn_stream_t stream);
 static int wgrad_blocks_launch(const float* z, int64_t ldz, const float* du, int64_t lddu, int64_t rows, int K_in, int N, int nslab,
                                int64_t rows_per_slab, float* ws, float* dw, int64_t lddw, int oi, float* db, tsgnn_stream_t stream) {
   if (!z || !du || !ws || rows < 0 || nslab <= 0 || rows_per_slab <= 0 || K_in <= 0 || N <= 0 || (dw && lddw < (oi ? K_in : N))) return TSGNN_EINVAL;
@@ -716,63 +673,8 @@ static int wgrad_blocks_launch(const float* z, int64_t ldz, const float* du, int
   }
   TSGNN_KNAME("wgrad_blocks_kernel<2>");
   wgrad_blocks_kernel<2><<<dim3((unsigned)nslab, (unsigned)(2 * nsets)), 256, lds, stream>>>(w);
-  if (!dw) {                                              // slabs only: the caller reduces them later (tsgnn_wgrad_blocks_reduce[2]_f32)
-    TSGNN_CHECK_LAUNCH();
-    return TSGNN_OK;
-  }
-  return wgrad_blocks_reduce_launch(ws, nslab, K_in, N, dw, lddw, oi, db, stream);
-}
-
-static WgradBlocksReduce wgrad_blocks_reduce_args(const float* ws, int nslab, int K_in, int N, float* dw, int64_t lddw, int oi, float* db,
-                                                  int* nblocks) {
-  const int KB = (K_in + 127) / 128, NB = (N + 127) / 128, nsets = KB * NB;
-  WgradBlocksReduce r{ws, nslab, (int64_t)nslab * WB_SET_FLOATS, K_in, N, NB, nsets, dw, lddw, oi, db, {0}};
-  int blocks = 0;
-  for (int t = 0; t < nsets; ++t) {
-    r.first_block[t] = blocks;
-    const int kc = K_in - 128 * (t / NB) < 128 ? K_in - 128 * (t / NB) : 128, nc = N - 128 * (t % NB) < 128 ? N - 128 * (t % NB) : 128;
-    blocks += (((db && t / NB == 0) ? kc + 1 : kc) * nc + 63) / 64;
-  }
-  for (int t = nsets; t <= WB_MAXSETS; ++t) r.first_block[t] = blocks;
-  *nblocks = blocks;
-  return r;
-}
-static int wgrad_blocks_reduce_launch(const float* ws, int nslab, int K_in, int N, float* dw, int64_t lddw, int oi, float* db,
-                                      tsgnn_stream_t stream) {
-  int blocks = 0;
-  const WgradBlocksReduce r = wgrad_blocks_reduce_args(ws, nslab, K_in, N, dw, lddw, oi, db, &blocks);
-  wgrad_blocks_reduce<<<(unsigned)blocks, 256, 0, stream>>>(r);
-  TSGNN_CHECK_LAUNCH();
-  return TSGNN_OK;
-}
-
-/* the fixed-order reduction of slabs a blocked weight-gradient launch left in ws (tsgnn_gat_bwd_products_f32) */
-int tsgnn_wgrad_blocks_reduce_f32(const float* ws, int nslab, int K_in, int N, float* dw, int64_t lddw, tsgnn_stream_t stream) {
-  if (!ws || !dw || nslab <= 0 || K_in <= 0 || N <= 0 || K_in > 512 || N > 512 || lddw < N) return TSGNN_EINVAL;
-  if (((K_in + 127) / 128) * ((N + 127) / 128) > WB_MAXSETS) return TSGNN_EINVAL;
-  return wgrad_blocks_reduce_launch(ws, nslab, K_in, N, dw, lddw, 0, nullptr, stream);
-}
-
-/* the same into torch.nn.Linear's layout: dw_oi[N][K_in], db[N] (nullable) — after tsgnn_linear_bwd_products_f32 */
-int tsgnn_wgrad_blocks_reduce_oi_f32(const float* ws, int nslab, int K_in, int N, float* dw_oi, int64_t lddw, float* db, tsgnn_stream_t stream) {
-  if (!ws || !dw_oi || nslab <= 0 || K_in <= 0 || N <= 0 || K_in > 512 || N > 512 || lddw < K_in) return TSGNN_EINVAL;
-  if (((K_in + 127) / 128) * ((N + 127) / 128) > WB_MAXSETS) return TSGNN_EINVAL;
-  return wgrad_blocks_reduce_launch(ws, nslab, K_in, N, dw_oi, lddw, 1, db, stream);
-}
-
-/* two such reductions in one launch (the two layers of a GAT encoder's backward) */
-int tsgnn_wgrad_blocks_reduce2_f32(const float* ws0, int nslab0, int K0, int N0, float* dw0, int64_t lddw0, const float* ws1, int nslab1,
-                                   int K1, int N1, float* dw1, int64_t lddw1, tsgnn_stream_t stream) {
-  if (!ws0 || !dw0 || !ws1 || !dw1 || nslab0 <= 0 || nslab1 <= 0 || K0 <= 0 || N0 <= 0 || K1 <= 0 || N1 <= 0 || K0 > 512 || N0 > 512 ||
-      K1 > 512 || N1 > 512 || lddw0 < N0 || lddw1 < N1)
-    return TSGNN_EINVAL;
-  if (((K0 + 127) / 128) * ((N0 + 127) / 128) > WB_MAXSETS || ((K1 + 127) / 128) * ((N1 + 127) / 128) > WB_MAXSETS) return TSGNN_EINVAL;
-  int n0 = 0, n1 = 0;
-  const WgradBlocksReduce r0 = wgrad_blocks_reduce_args(ws0, nslab0, K0, N0, dw0, lddw0, 0, nullptr, &n0);
-  const WgradBlocksReduce r1 = wgrad_blocks_reduce_args(ws1, nslab1, K1, N1, dw1, lddw1, 0, nullptr, &n1);
-  TSGNN_KNAME("wgrad_blocks_reduce2");
-  wgrad_blocks_reduce2<<<(unsigned)(n0 + n1), 256, 0, stream>>>(r0, r1, n0);
-  TSGNN_CHECK_LAUNCH();
+  if (dw) return reduce_one(ws, nslab, K_in, N, dw, lddw, oi ? 0 : 1, db, 1, stream);
+  TSGNN_CHECK_LAUNCH();                                   // slabs only: the caller reduces them later (tsgnn_wgrad_reduce_sets_f32)
   return TSGNN_OK;
 }
 

@@ -5,7 +5,7 @@
 //                                      [+ ReLU] [+ L2 normalise] [+ per-graph max / sum readouts of the output in the epilogue]
 //   tsgnn_sage_relu_readout_bwd_f32    du = (dxs + readout gradients) * [h > 0]: the row-wise pass between two layers' backward
 //   tsgnn_sage_readout_decode_f32      packed maxima / fixed-point sums of all layers -> sum_l [gmp || gap] and the arg-max rows
-//   tsgnn_sage_wgrad_reduce_oi_f32     slab partials of all layers -> nn.Linear-layout gradients (lin_l.weight, lin_l.bias, lin_r.weight)
+// (the slab partials of all layers go to nn.Linear-layout gradients through tsgnn_wgrad_reduce_sets_f32, gemm.hip)
 #include <algorithm>
 #include "common.h"
 #include "../../include/tsgnn.h"
@@ -109,66 +109,6 @@ __global__ __launch_bounds__(256) void sage_conv_pack_kernel(PackArgs a) {
     v[c] = ok ? (s.kn ? s.w[(int64_t)k * s.ldw + n] : s.w[(int64_t)n * s.ldw + k]) : 0.f;
   }
   s.out[e] = make_float4(v[0], v[1], v[2], v[3]);
-}
-
-struct OiSet {
-  const float* ws; int nslab, K, N;     // slabs [nslab][K + 1][N] (row K = bias partial); K = 0: rows of partial column sums only
-  float* dw; int64_t lddw;              // dw[n * lddw + k]  (nn.Linear's [out, in]; kn = 1: dw[k * lddw + n], GCNConv's [in, out]);
-                                        // K = 0 (nullable): columns lddw .. lddw + n_db - 1 go to dw[0 .. n_db) (the GraphConv
-                                        // scorer's partial rows [nb][2F + 4]: dw_root from column F + 4)
-  int kn;
-  float* db;                            // nullable [n_db]
-  int n_db;                             // columns of the bias row that go to db (N for a weight set)
-  float* tail;                          // nullable: column n_db of the bias row goes to tail[0] (the SAGPool score layer's
-                                        // partial rows [nb][F + 4]: dw_s in columns 0 .. F-1, db_s in column F)
-  int first_block;
-};
-constexpr int OI_MAX_SETS = 12;
-struct OiArgs { OiSet s[OI_MAX_SETS]; int nsets; float* normparts; float* step_state; };
-
-// block -> 64 consecutive entries (k, n) of one set's [K + 1][N] slab image, n fastest: coalesced slab reads; four wave groups
-// split the slabs (fixed ranges), their partial sums meet in LDS and are added in group order: the same bits every run
-__global__ __launch_bounds__(256) void sage_wgrad_reduce_oi_kernel(OiArgs a) {
-  __shared__ float lds[4][64];
-  int si = 0;
-#pragma unroll
-  for (int t = 1; t < OI_MAX_SETS; ++t)
-    if (t < a.nsets && (int)blockIdx.x >= a.s[t].first_block) si = t;
-  const OiSet& s = a.s[si];
-  const int e_l = threadIdx.x & 63, grp = threadIdx.x >> 6;
-  const int e = ((int)blockIdx.x - s.first_block) * 64 + e_l;
-  const int tot = (s.K + 1) * s.N;
-  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-  if (e < tot) {
-    const int64_t stride = (int64_t)tot;
-    const int per = (s.nslab + 3) / 4;
-    const int s0 = grp * per, s1 = min(s.nslab, s0 + per);
-    int sl = s0;
-    for (; sl + 4 <= s1; sl += 4) {
-      a0 += s.ws[(int64_t)sl * stride + e];
-      a1 += s.ws[(int64_t)(sl + 1) * stride + e];
-      a2 += s.ws[(int64_t)(sl + 2) * stride + e];
-      a3 += s.ws[(int64_t)(sl + 3) * stride + e];
-    }
-    for (; sl < s1; ++sl) a0 += s.ws[(int64_t)sl * stride + e];
-  }
-  lds[grp][e_l] = (a0 + a1) + (a2 + a3);
-  __syncthreads();
-  if (grp != 0) return;
-  float sq = 0.f;
-  if (e < tot) {
-    const float v = (lds[0][e_l] + lds[1][e_l]) + (lds[2][e_l] + lds[3][e_l]);
-    const int k = e / s.N, n = e % s.N;
-    if (k < s.K) { s.dw[s.kn ? (int64_t)k * s.lddw + n : (int64_t)n * s.lddw + k] = v; sq = v * v; }
-    else if (s.db && n < s.n_db) { s.db[n] = v; sq = v * v; }
-    else if (s.tail && n == s.n_db) { s.tail[0] = v; sq = v * v; }
-    else if (s.K == 0 && s.dw && n >= s.lddw && n < s.lddw + s.n_db) { s.dw[n - s.lddw] = v; sq = v * v; }
-  }
-  if (a.normparts) {                                    // this block's share of |grad|^2 (summed in fixed order by the optimiser)
-    sq = wave_sum(sq);
-    if (e_l == 0) a.normparts[blockIdx.x] = sq;
-  }
-  if (a.step_state && blockIdx.x == 0 && e_l == 0) a.step_state[0] += 1.f;   // optimiser step counter, ahead of the update kernel
 }
 
 }  // namespace
@@ -295,45 +235,6 @@ int tsgnn_sage_readout_decode_f32(unsigned long long* packed, unsigned long long
   if (!packed || !sums || !graph_ptr || !read || !arg || B <= 0 || L <= 0 || F <= 0 || ldr < 2 * F) return TSGNN_EINVAL;
   TSGNN_KNAME("sage_readout_decode_kernel");
   sage_readout_decode_kernel<<<(unsigned)B, 128, 0, stream>>>(packed, sums, graph_ptr, B, L, F, read, ldr, arg);
-  TSGNN_CHECK_LAUNCH();
-  return TSGNN_OK;
-}
-
-/* desc (HOST memory): [nsets <= 12, nsets x (ws, nslab, K, N, dw_oi, lddw, db, n_db, tail, kn)] — slab sets in the layout of
- * tsgnn_linear_wgrad_f32 (dw == NULL form), summed in slab order and written transposed: dw_oi[n * lddw + k] (kn = 1: as they lie,
- * dw[k * lddw + n]); db nullable, takes the first n_db columns of the bias row (n_db = N for a weight set).  K = 0: a set of partial ROWS [nslab][N] only whose
- * column sums go to db[0 .. n_db) and, column n_db, to tail[0] when tail != NULL (the SAGPool score layer's per-graph partial rows
- * [nb][F + 4] left by tsgnn_sag_pool_graph_bwd_f32: the work of tsgnn_sag_du_reduce_f32 riding in this launch); dw_oi (nullable) then takes
- * columns [lddw, lddw + n_db) (the GraphConv scorer's rows [nb][2F + 4] of tsgnn_sag_pool_graph_gc_bwd_f32: lddw = F + 4). */
-int tsgnn_sage_wgrad_reduce_oi_blocks(const int64_t* desc) {
-  if (!desc || desc[0] <= 0 || desc[0] > OI_MAX_SETS) return -1;
-  int blocks = 0;
-  for (int t = 0; t < (int)desc[0]; ++t) blocks += (((int)desc[1 + 10 * t + 2] + 1) * (int)desc[1 + 10 * t + 3] + 63) / 64;
-  return blocks;
-}
-
-int tsgnn_sage_wgrad_reduce_oi_f32(const int64_t* desc, float* normparts, float* step_state, tsgnn_stream_t stream) {
-  if (!desc) return TSGNN_EINVAL;
-  const int nsets = (int)desc[0];
-  if (nsets <= 0 || nsets > OI_MAX_SETS) return TSGNN_EINVAL;
-  OiArgs a{};
-  a.nsets = nsets; a.normparts = normparts; a.step_state = step_state;
-  int blocks = 0;
-  const int64_t* d = desc + 1;
-  for (int t = 0; t < nsets; ++t, d += 10) {
-    OiSet& s = a.s[t];
-    s.ws = reinterpret_cast<const float*>(d[0]); s.nslab = (int)d[1]; s.K = (int)d[2]; s.N = (int)d[3];
-    s.dw = reinterpret_cast<float*>(d[4]); s.lddw = d[5]; s.db = reinterpret_cast<float*>(d[6]); s.n_db = (int)d[7];
-    s.tail = reinterpret_cast<float*>(d[8]); s.kn = d[9] ? 1 : 0;
-    if (!s.ws || s.nslab <= 0 || s.K < 0 || s.N <= 0 || s.n_db < 0 || s.n_db > s.N) return TSGNN_EINVAL;
-    if (s.K > 0 && (!s.dw || s.lddw < (s.kn ? s.N : s.K))) return TSGNN_EINVAL;
-    if (s.tail && s.n_db >= s.N) return TSGNN_EINVAL;
-    if (s.K == 0 && s.dw && (s.lddw <= s.n_db || s.lddw + s.n_db > s.N)) return TSGNN_EINVAL;
-    s.first_block = blocks;
-    blocks += ((s.K + 1) * s.N + 63) / 64;
-  }
-  TSGNN_KNAME("sage_wgrad_reduce_oi_kernel");
-  sage_wgrad_reduce_oi_kernel<<<(unsigned)blocks, 256, 0, stream>>>(a);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }

@@ -1470,7 +1470,7 @@ int tsgnn_sag_pool_graph_bwd_f32(const float* y, int64_t ldy, const float* score
 }
 
 /* the GraphConv-scorer form: part gets B rows of 2F + 4 floats [dw_rel (F) | db | 3 unused | dw_root (F)], summed by a partial-row
- * set of tsgnn_sage_wgrad_reduce_oi_f32 (dw = dw_root at column offset F + 4) */
+ * set of tsgnn_wgrad_reduce_sets_f32 (dw = dw_root at column offset F + 4) */
 int tsgnn_sag_pool_graph_gc_bwd_f32(const float* y, int64_t ldy, const float* score, const int* new_id, const int* graph_ptr,
                                     const int* graph_ptr_new, const int* arg, const float* dxp, int64_t lddxp, const float* dread,
                                     int64_t lddr, const int* rowptr, const int* rowend, const int* col, const float* w_rel,

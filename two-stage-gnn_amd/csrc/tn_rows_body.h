@@ -13,7 +13,7 @@ typedef float tn_f32x16 __attribute__((ext_vector_type(16)));
 // The reduction runs over the graph rows (thousands+), the output is tiny, so each workgroup owns a SLAB of
 // rows and produces a full [K_in+1, N] partial (row K_in = bias partial) from coalesced 16-byte row loads;
 // both MFMA operands are natural row-major LDS tiles (lane i reads consecutive floats: conflict-free).
-// Slabs are summed in fixed order by tn_rows_reduce (bitwise reproducible, no float atomics).
+// Slabs are summed in fixed order by slab_sum (gemm.hip; bitwise reproducible, no float atomics).
 constexpr int TN_CH = 32;            // rows per staged chunk
 
 __device__ __forceinline__ int64_t ceil_div_dev(int64_t a, int64_t b) { return (a + b - 1) / b; }

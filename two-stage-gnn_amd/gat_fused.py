@@ -94,7 +94,7 @@ class _PackLayers(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, *dwps):
-        flush_reductions(ctx.pending)                            # the layers' dW' still sit in their slabs: ONE reduction launch for two
+        flush_reductions(ctx.pending)                            # the layers' dW' still sit in their slabs: ONE reduction launch for all
         layers = ctx.layers
         dev = layers[0][4][0].device
         ptrs, res = [], []
@@ -127,27 +127,24 @@ def pack_layers(layers_heads):
 
 
 # A layer's dW' is read only when the parameters are unpacked at the end of the backward pass: the layers leave their slabs pending
-# and _PackLayers.backward reduces them two products per launch (a GAT encoder has two layers: one reduction launch instead of two).
+# and _PackLayers.backward reduces them together (a GAT encoder has two layers: one reduction launch instead of two).
 DEFER_REDUCE = os.environ.get("TSGNN_GAT_DEFER_REDUCE", "1") != "0"
 
 
 def flush_reductions(pending):
-    """reduce the slab sets (ws, nslab, K_in, N, dw) the layers of one forward left pending, two per launch"""
-    while pending:
-        a = pending.pop(0)
-        if pending:
-            b = pending.pop(0)
-            nat.call("wgrad_blocks_reduce2_f32", a[0], a[1], a[2], a[3], a[4], a[4].stride(0), b[0], b[1], b[2], b[3], b[4], b[4].stride(0))
-        else:
-            nat.call("wgrad_blocks_reduce_f32", a[0], a[1], a[2], a[3], a[4], a[4].stride(0))
+    """reduce the slab sets (mp.wgrad_set records) the layers of one forward left pending"""
+    if pending:
+        mp.wgrad_reduce(pending)
+        pending.clear()
 
 
 def _reduce(ws, nslab, K_in, N, dw, defer):
     """defer: the pending list of the pack node that will consume dw (None / False: reduce now)"""
+    st = mp.wgrad_set(ws, nslab, K_in, N, dw, kn=1, blocked=True)
     if defer is not None and defer is not False and DEFER_REDUCE:
-        defer.append((ws, nslab, K_in, N, dw))
+        defer.append(st)
     else:
-        nat.call("wgrad_blocks_reduce_f32", ws, nslab, K_in, N, dw, dw.stride(0))
+        mp.wgrad_reduce([st])
 
 
 def wgrad_blocks(z, K_in, du, defer=None):

@@ -149,27 +149,68 @@ def linear_wgrad_slabs(z, K_in, du, bias_only_rows=0):
     return ws, int(nslab[0])
 
 
+def wgrad_set(ws, nslab, K, N, dw, db=None, n_db=None, tail=None, kn=0, lddw=None, blocked=False):
+    """one record of wgrad_reduce (tsgnn.h, tsgnn_wgrad_reduce_sets_f32): slabs ws [nslab][K + 1][N], row K = the bias partial.
+    Rows k < K go to dw in nn.Linear's layout dw[n, k] (kn = 1: dw[k, n]), the first n_db (default N) columns of row K to db,
+    column n_db to tail[0].  K = 0: partial rows only (the SAGPool score layer's); dw then takes columns lddw .. lddw + n_db - 1.
+    blocked: the slabs of a blocked weight gradient (wgrad_blocks_plan / *_bwd_products), K, N <= 512."""
+    if lddw is None:
+        lddw = dw.stride(0) if dw is not None else 0
+    return (ws, int(nslab), int(K), int(N), dw, int(lddw), db, int(N if n_db is None else n_db), tail, int(kn), int(bool(blocked)))
+
+
+def _desc(sets):
+    words = [len(sets)]
+    for st in sets:
+        words += [0 if v is None else (v.data_ptr() if torch.is_tensor(v) else int(v)) for v in st]
+    return np.asarray(words, dtype=np.int64)
+
+
+def _norm_args(norm_sink, d):
+    """(normparts, step_state) of the reduction launch described by d: one norm-share slot per block the library launches for it,
+    and the optimiser's step counter from the FIRST launch of the step that carries shares.  (A model with several fused nodes —
+    DiffPool's paired stacks and pooled levels — reduces weight gradients more than once per backward; every call used to advance
+    the counter, and Adam's bias correction ran a step ahead: found by tests/test_gpu_fullsize.py.)"""
+    if norm_sink is None:
+        return None, None
+    nblk = int(nat.lib().tsgnn_wgrad_reduce_sets_blocks(d.ctypes.data))
+    if nblk < 0:
+        raise RuntimeError("wgrad_reduce: invalid slab set")
+    parts = norm_sink.norm_slots(nblk)
+    if parts is None or norm_sink.stepped:
+        return parts, None
+    norm_sink.stepped = True
+    return parts, norm_sink.step_state
+
+
+REDUCE_SETS = 12                       # records per tsgnn_wgrad_reduce_sets_f32 call
+
+
+def wgrad_reduce(sets, norm_sink=None):
+    """sum slab sets (wgrad_set records) into their gradients in fixed order, 12 records per call.  norm_sink: a GradSink whose
+    optimiser wants the |grad|^2 shares of these gradients (and its step counter advanced); returns True when the shares were left."""
+    if nat._defer is not None:          # the descriptor is read during the call: it cannot wait in a record
+        raise RuntimeError("wgrad_reduce cannot be recorded under nat.deferred()")
+    normed = norm_sink is not None
+    for i in range(0, len(sets), REDUCE_SETS):
+        d = _desc(sets[i:i + REDUCE_SETS])
+        parts, step = _norm_args(norm_sink, d)
+        normed = normed and parts is not None
+        nat.call("wgrad_reduce_sets_f32", d.ctypes.data, parts, step)
+    return normed
+
+
 def wgrad_reduce_multi(sets, norm_sink=None):
-    """sets: list of (ws, nslab, K, N, dw, db-or-None), at most 4 per launch.  norm_sink: a GradSink whose optimiser wants the
-    |grad|^2 shares of these gradients (and its step counter advanced) from this launch."""
+    """sets: list of (ws, nslab, K, N, dw [K, N], db-or-None), four per launch through the positional entry point (bench.py's
+    per-kernel table reads its arguments; sage_stack.run_paired joins two such launches).  norm_sink as in wgrad_reduce."""
     for i in range(0, len(sets), 4):
+        chunk = list(sets[i:i + 4])
+        parts, step = (_norm_args(norm_sink, _desc([wgrad_set(*st, kn=1, lddw=st[3]) for st in chunk]))
+                       if norm_sink is not None else (None, None))
         args = []
-        nblk = 0
-        for t in range(4):
-            if i + t < len(sets):
-                ws, nslab, K, N, dw, db = sets[i + t]
-                args += [ws, int(nslab), int(K), int(N), dw, db]
-                nblk += ((K + 1) * N + 63) // 64
-            else:
-                args += [None, 0, 0, 0, None, None]
-        parts = norm_sink.norm_slots(nblk) if norm_sink is not None else None
-        # the step counter is advanced ONCE per optimiser step, by the first such launch (a model with several fused nodes —
-        # DiffPool's paired stacks and pooled levels — reduces weight gradients more than once per backward; every call used to
-        # advance it, and Adam's bias correction ran a step ahead: found by tests/test_gpu_fullsize.py)
-        step = norm_sink.step_state if (norm_sink is not None and parts is not None and i == 0 and not norm_sink.stepped) else None
+        for ws, nslab, K, N, dw, db in chunk + [(None, 0, 0, 0, None, None)] * (4 - len(chunk)):
+            args += [ws, int(nslab), int(K), int(N), dw, db]
         nat.call("wgrad_reduce_multi_f32", *args, parts, step)
-        if norm_sink is not None and parts is not None:
-            norm_sink.stepped = norm_sink.stepped or step is not None
 
 
 def linear_wgrad_oi(z, K_in, du, want_db):
@@ -387,7 +428,7 @@ LINEAR_MERGED_BWD = os.environ.get("TSGNN_LINEAR_MERGED_BWD", "1") != "0"   # nn
 
 def linear_bwd_products(x, K_in, dy, w, want_db):
     """(dW[N, K_in], db[N] or None, dx[R, K_in]) of y = x W^T + b in two launches: the blocked weight-gradient slabs beside the
-    input-gradient product (tsgnn_linear_bwd_products_f32) and the slabs' reduction; None when the shape is not taken"""
+    input-gradient product (tsgnn_linear_bwd_products_f32) and the slabs' reduction (wgrad_reduce); None when the shape is not taken"""
     R, N = int(dy.size(0)), int(dy.size(1))
     if not (R >= 256 and K_in <= 512 and N <= 512 and K_in % 4 == 0 and N % 4 == 0 and x.size(1) == K_in and x.stride(0) % 4 == 0
             and dy.stride(0) % 4 == 0 and w.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0
@@ -407,7 +448,7 @@ def linear_bwd_products(x, K_in, dy, w, want_db):
         return None
     dw = _f32(N, int(K_in), device=dy.device)
     db = _f32(N, device=dy.device) if want_db else None
-    nat.call("wgrad_blocks_reduce_oi_f32", ws, int(nslab[0]), int(K_in), N, dw, dw.stride(0), db)
+    wgrad_reduce([wgrad_set(ws, int(nslab[0]), int(K_in), N, dw, db, blocked=True)])
     return dw, db, dx
 
 

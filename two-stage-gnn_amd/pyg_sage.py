@@ -155,37 +155,6 @@ def wgrad_slabs(z, x, K, du):
     return a, b
 
 
-def reduce_oi(sets, norm_sink=None):
-    """sets: list of (ws, nslab, K, N, dw_oi [N, K], db or None) — or (part, nb, 0, F + 4, None, dw_s, F, db_s): the SAGPool score layer's
-    partial rows, column sums to dw_s[0:F] and db_s[0]; a ninth entry kn = 1 writes dw as [K, N] (GCNConv's layout); a tenth overrides
-    lddw (a partial-row set (part, nb, 0, 2F + 4, dw_root, dw_rel, F, db, 0, F + 4): the GraphConv scorer's rows, columns F + 4 ..
-    2F + 3 to dw_root) —: ONE launch for up to 12 sets (tsgnn_sage_wgrad_reduce_oi_f32).
-    norm_sink: a GradSink whose optimiser wants the |grad|^2 shares of these gradients (and its step counter advanced) from this
-    launch; returns True when the shares were left."""
-    normed = norm_sink is not None
-    for i in range(0, len(sets), 12):
-        chunk = sets[i:i + 12]
-        words = [len(chunk)]
-        for st in chunk:
-            ws, nslab, K, N, dw, db = st[:6]
-            n_db, tail = (st[6], st[7]) if len(st) > 6 else (N, None)
-            kn = int(st[8]) if len(st) > 8 else 0
-            lddw = int(st[9]) if len(st) > 9 else (int(dw.stride(0)) if dw is not None else 0)
-            words += [ws.data_ptr(), int(nslab), int(K), int(N), dw.data_ptr() if dw is not None else 0,
-                      lddw, db.data_ptr() if db is not None else 0, int(n_db),
-                      tail.data_ptr() if tail is not None else 0, kn]
-        d = np.asarray(words, dtype=np.int64)
-        parts = step = None
-        if norm_sink is not None:
-            parts = norm_sink.norm_slots(int(nat.lib().tsgnn_sage_wgrad_reduce_oi_blocks(d.ctypes.data)))
-            step = norm_sink.step_state if (parts is not None and not norm_sink.stepped) else None
-        normed = normed and parts is not None
-        nat.call("sage_wgrad_reduce_oi_f32", d.ctypes.data, parts, step)
-        if step is not None:
-            norm_sink.stepped = True
-    return normed
-
-
 class _SageConv(torch.autograd.Function):
     """out = lin_l(aggr_j x_j) + lin_r(x_i) [normalised]: one launch forward; backward = slabs x 2, one reduction, one launch for dx"""
 
@@ -216,7 +185,7 @@ class _SageConv(torch.autograd.Function):
             if sl is not None:
                 dwl, dwr = _f32(N, K, device=du.device), _f32(N, K, device=du.device)
                 dbl = _f32(N, device=du.device) if ctx.has_bias else None
-                reduce_oi([(sl[0][0], sl[0][1], K, N, dwl, dbl), (sl[1][0], sl[1][1], K, N, dwr, None)])
+                mp.wgrad_reduce([mp.wgrad_set(sl[0][0], sl[0][1], K, N, dwl, dbl), mp.wgrad_set(sl[1][0], sl[1][1], K, N, dwr)])
             else:
                 dwl_t, dbl = mp.linear_wgrad(z, K, du, ctx.has_bias)
                 dwr_t, _ = mp.linear_wgrad(x, K, du, False)
@@ -310,8 +279,8 @@ class _SageStack(torch.autograd.Function):
             dwl, s1 = mp._sink_or_new(ctx.params[3 * l], (H, K), dev)
             dwr, s3 = mp._sink_or_new(ctx.params[3 * l + 2], (H, K), dev)
             dbl, s2 = mp._sink_or_new(ctx.params[3 * l + 1], (H,), dev) if ctx.has_bias else (None, False)
-            sets.append((sl[0][0], sl[0][1], K, H, dwl, dbl))
-            sets.append((sl[1][0], sl[1][1], K, H, dwr, None))
+            sets.append(mp.wgrad_set(sl[0][0], sl[0][1], K, H, dwl, dbl))
+            sets.append(mp.wgrad_set(sl[1][0], sl[1][1], K, H, dwr))
             grads[3 * l], grads[3 * l + 1], grads[3 * l + 2] = (None if s1 else dwl), (None if s2 else dbl), (None if s3 else dwr)
             sunk.append(s1 and s3 and (s2 or not ctx.has_bias))
             if l > 0:
@@ -329,7 +298,7 @@ class _SageStack(torch.autograd.Function):
                 dx0 = conv_dx(g, du, dus, ctx.pk_bwd[0][0], ctx.pk_bwd[0][1], K, H, hs[0].size(1))
         sink = mp.GRAD_SINK
         all_sunk = sink is not None and all(sunk)
-        if reduce_oi(sets, norm_sink=sink if all_sunk else None):
+        if mp.wgrad_reduce(sets, norm_sink=sink if all_sunk else None):
             for l in range(L):
                 sink.normed.add(ctx.params[3 * l].data_ptr()); sink.normed.add(ctx.params[3 * l + 2].data_ptr())
                 if ctx.has_bias:

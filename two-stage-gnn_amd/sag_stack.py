@@ -314,8 +314,8 @@ class _SagStack(torch.autograd.Function):
                 db, s2 = mp._sink_or_new(pb, (H,), dev)
                 dws, s3 = mp._sink_or_new(pws, tuple(pws.shape), dev)
                 dbs, s4 = mp._sink_or_new(pbs, (1,), dev)
-                sets.append((slabs[0], slabs[1], Kin, H, dW, db, H, None, 1))
-                sets.append((part, L.B, 0, H + 4, None, dws, H, dbs))
+                sets.append(mp.wgrad_set(slabs[0], slabs[1], Kin, H, dW, db, kn=1))
+                sets.append(mp.wgrad_set(part, L.B, 0, H + 4, None, dws, n_db=H, tail=dbs))
                 set_params += [pW, pb, pws, pbs]
                 sunk.append(s1 and s2 and s3 and s4)
                 grads[4 * l: 4 * l + 4] = [None if s1 else dW, None if s2 else db, None if s3 else dws, None if s4 else dbs]
@@ -340,9 +340,8 @@ class _SagStack(torch.autograd.Function):
                 else:
                     dx = dxin
         if sets:
-            from .pyg_sage import reduce_oi
             sink = mp.GRAD_SINK
-            if reduce_oi(sets, norm_sink=sink if (sink is not None and all(sunk)) else None):
+            if mp.wgrad_reduce(sets, norm_sink=sink if (sink is not None and all(sunk)) else None):
                 for p in set_params:
                     sink.normed.add(p.data_ptr())
         return (dx, None, None, *grads)

@@ -191,16 +191,16 @@ class _SagSageStack(torch.autograd.Function):
             dwr, s3 = mp._sink_or_new(wr, (H, K), dev)
             dws, s4 = mp._sink_or_new(ws, tuple(ws.shape), dev)
             dbs, s5 = mp._sink_or_new(bs, (1,), dev)
-            sets.append((sl[0][0], sl[0][1], K, H, dwl, dbl))
-            sets.append((sl[1][0], sl[1][1], K, H, dwr, None))
+            sets.append(mp.wgrad_set(sl[0][0], sl[0][1], K, H, dwl, dbl))
+            sets.append(mp.wgrad_set(sl[1][0], sl[1][1], K, H, dwr))
             if gc:
                 # partial rows [dw_rel | db | 3 unused | dw_root]: dw_root from column H + 4 of the same set
                 wroot = ctx.params[P * l + 5]
                 dwt, s6 = mp._sink_or_new(wroot, tuple(wroot.shape), dev)
-                sets.append((part, L.B, 0, 2 * H + 4, dwt, dws, H, dbs, 0, H + 4))
+                sets.append(mp.wgrad_set(part, L.B, 0, 2 * H + 4, dwt, dws, n_db=H, tail=dbs, lddw=H + 4))
             else:
                 dwt, s6 = None, True
-                sets.append((part, L.B, 0, H + 4, None, dws, H, dbs))
+                sets.append(mp.wgrad_set(part, L.B, 0, H + 4, None, dws, n_db=H, tail=dbs))
             grads[P * l: P * l + 5] = [None if s1 else dwl, None if s2 else dbl, None if s3 else dwr, None if s4 else dws, None if s5 else dbs]
             if gc:
                 grads[P * l + 5] = None if s6 else dwt
@@ -217,7 +217,7 @@ class _SagSageStack(torch.autograd.Function):
                     dx = dxin[:, :K]
         sink = mp.GRAD_SINK
         all_sunk = sink is not None and all(sunk)
-        if ps.reduce_oi(sets, norm_sink=sink if all_sunk else None):
+        if mp.wgrad_reduce(sets, norm_sink=sink if all_sunk else None):
             for p in ctx.params:
                 sink.normed.add(p.data_ptr())
         return (dx, None, None, None, None, *grads)

@@ -656,18 +656,14 @@ def _pair_slot_post_bwd(a, b):
 
 
 def _pair_reduce(a, b):
-    # 4 x (ws, nslab, K, N, dw, db), normparts, step
-    import numpy as np
+    # 4 x (ws, nslab, K, N, dw, db), normparts, step: the sets of both records in one descriptor
     if a[24] is not None or a[25] is not None or b[24] is not None or b[25] is not None:
         return False
-    sets = [t[6 * k:6 * k + 6] for t in (a, b) for k in range(4) if t[6 * k] is not None]
-    if not sets or len(sets) > 8:
+    sets = [mp.wgrad_set(*t[6 * k:6 * k + 6], kn=1, lddw=t[6 * k + 3]) for t in (a, b) for k in range(4) if t[6 * k] is not None]
+    if not sets:
         return False
-    words = [len(sets)]
-    for st in sets:
-        words += [nat._arg(st[0]), int(st[1]), int(st[2]), int(st[3]), nat._arg(st[4]), nat._arg(st[5]) or 0]
-    d = np.asarray(words, dtype=np.int64)
-    return nat.try_call("wgrad_reduce_sets_f32", d.ctypes.data)
+    d = mp._desc(sets)
+    return nat.try_call("wgrad_reduce_sets_f32", d.ctypes.data, None, None)
 
 
 _PAIRED = {"slot_bn_fwd_f32": _pair_slot_bn, "slot_post_bwd_f32": _pair_slot_post_bwd, "wgrad_reduce_multi_f32": _pair_reduce}
