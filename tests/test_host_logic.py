@@ -77,3 +77,73 @@ def test_workspace_size_helpers():
     assert L.tsgnn_readout_max_ws_words(0, 512, 192) == 0 and L.tsgnn_readout_max_ws_words(1 << 20, 4096, 4096) == -1
     assert L.tsgnn_ragged_tn_direct_supported(64, 512) == 1 and L.tsgnn_ragged_tn_direct_supported(129, 512) == 0
     assert L.tsgnn_ragged_tn_direct_supported(64, 5000) == 0
+
+
+def test_wgrad_sets_closing_reduction_bookkeeping(monkeypatch):
+    """mp.WgradSets, the closing weight-gradient reduction of the fused backward nodes: every slice is taken from the sink once,
+    sunk gradients go back to autograd as None, the shares are asked for only when every gradient went to the sink and the record
+    count allows it, and the parameters are marked normed only when the launcher reports that the shares were left"""
+    from two_stage_gnn_amd import message_passing as mp
+
+    class Sink:
+        def __init__(self, params):
+            self.views = {id(p): torch.zeros(p.shape) for p in params}
+            self.taken = []
+            self.normed = set()
+
+        def take(self, param, shape):
+            self.taken.append(id(param))
+            v = self.views.get(id(param))
+            return v if v is not None and tuple(v.shape) == tuple(shape) else None
+
+    def launcher(flag):
+        def launch(sets, norm_sink=None):
+            launch.calls.append((list(sets), norm_sink))
+            return flag and norm_sink is not None
+        launch.calls = []
+        return launch
+
+    w, b, w2 = torch.ones(3, 2), torch.ones(3), torch.ones(2, 2)
+
+    def run(sink, flag, params, nsets=2, **kw):
+        monkeypatch.setattr(mp, "GRAD_SINK", sink)
+        launch = launcher(flag)
+        red = mp.WgradSets(launch, **kw)
+        bufs = [red.grad(p, tuple(p.shape) if p is not None else (3,)) for p in params]
+        for k in range(nsets):
+            red.add(("set", k))
+        out = [red.autograd_grad(t) for t in bufs]
+        red.close()
+        return bufs, out, launch.calls
+
+    # every gradient from the sink: each slice taken once, None to autograd, shares asked for and the parameters marked normed
+    sink = Sink([w, b, w2])
+    bufs, out, calls = run(sink, True, [w, b, None, w2])
+    assert sorted(sink.taken) == sorted([id(w), id(b), id(w2)])
+    assert [t is sink.views[id(p)] for t, p in zip(bufs, (w, b))] == [True, True] and bufs[2] is None
+    assert out == [None, None, None, None]
+    assert calls == [([("set", 0), ("set", 1)], sink)]
+    assert sink.normed == {w.data_ptr(), b.data_ptr(), w2.data_ptr()}
+    # the launcher did not leave the shares: nothing is marked normed
+    sink = Sink([w, b])
+    _, _, calls = run(sink, False, [w, b])
+    assert calls[0][1] is sink and sink.normed == set()
+    # one gradient the sink does not hold: a new buffer, returned to autograd; no shares
+    sink = Sink([w])
+    bufs, out, calls = run(sink, True, [w, b])
+    assert out[0] is None and out[1] is bufs[1] and bufs[1].shape == (3,) and bufs[1] is not sink.views[id(w)]
+    assert calls[0][1] is None and sink.normed == set()
+    # more records than the shares allow for: no shares, the same single launch
+    sink = Sink([w, b])
+    _, out, calls = run(sink, True, [w, b], nsets=5, max_sets_with_shares=4)
+    assert out == [None, None] and len(calls) == 1 and len(calls[0][0]) == 5 and calls[0][1] is None and sink.normed == set()
+    _, _, calls = run(Sink([w, b]), True, [w, b], nsets=4, max_sets_with_shares=4)
+    assert calls[0][1] is not None
+    # buffers the caller allocated itself (no grad()): the sink is left alone
+    sink = Sink([w])
+    _, _, calls = run(sink, True, [])
+    assert calls[0][1] is None and sink.taken == [] and sink.normed == set()
+    # no sink installed: new buffers, all returned to autograd; nothing recorded -> no launch
+    bufs, out, calls = run(None, True, [w, b])
+    assert out[0] is bufs[0] and out[1] is bufs[1] and calls[0][1] is None
+    assert run(Sink([w]), True, [w], nsets=0)[2] == []

@@ -98,7 +98,7 @@ class _DenseGcnStack(torch.autograd.Function):
         grads = [None] * (2 * L)
         dx_next = None
         first_adj = True
-        slab_sets = []
+        red = mp.WgradSets(mp.wgrad_reduce_multi)        # buffers of its own, not from red.grad(): no flat bucket, no shares
         for l in range(L - 1, -1, -1):
             N = widths[l]
             fin = Fin if l == 0 else widths[l - 1]
@@ -117,7 +117,7 @@ class _DenseGcnStack(torch.autograd.Function):
                 if got is not None:                      # slab partials now, ONE fixed-order reduction for the whole stack below
                     dw = _f32(fin, N, device=dev)
                     db = _f32(N, device=dev) if want_b else None
-                    slab_sets.append((got[0], got[1], fin, N, dw, db))
+                    red.add((got[0], got[1], fin, N, dw, db))
                     grads[2 * l], grads[2 * l + 1] = dw, db
                 else:
                     grads[2 * l], grads[2 * l + 1] = mp.linear_wgrad(aggs[l], fin, du, want_b)
@@ -140,8 +140,7 @@ class _DenseGcnStack(torch.autograd.Function):
                 mp.gemm(adj, 1, K, dagg, fin, 1, dxin, fin, 1, K, fin, K, batch=B, stride_a=K * K, stride_b=K * fin,
                         stride_c=K * fin)
                 dx_next = dxin
-        if slab_sets:
-            mp.wgrad_reduce_multi(slab_sets)
+        red.close()
         dx = dx_next.view(B, K, Fin) if need_x else None
         return (dx, dadj, None, *grads)
 

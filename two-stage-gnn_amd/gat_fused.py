@@ -89,12 +89,12 @@ class _PackLayers(torch.autograd.Function):
         # the slab sets the layers' backward leaves for this node's backward to reduce: a container of THIS forward (not a module
         # global: two models, streams or threads must not see each other's entries, and a backward that never reaches this node
         # leaves nothing behind — the container dies with the graph)
-        ctx.pending = []
+        ctx.pending = mp.WgradSets()
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *dwps):
-        flush_reductions(ctx.pending)                            # the layers' dW' still sit in their slabs: ONE reduction launch for all
+        ctx.pending.close()                                      # the layers' dW' still sit in their slabs: ONE reduction launch for all
         layers = ctx.layers
         dev = layers[0][4][0].device
         ptrs, res = [], []
@@ -131,40 +131,20 @@ def pack_layers(layers_heads):
 DEFER_REDUCE = os.environ.get("TSGNN_GAT_DEFER_REDUCE", "1") != "0"
 
 
-def flush_reductions(pending):
-    """reduce the slab sets (mp.wgrad_set records) the layers of one forward left pending"""
-    if pending:
-        mp.wgrad_reduce(pending)
-        pending.clear()
-
-
-def _reduce(ws, nslab, K_in, N, dw, defer):
-    """defer: the pending list of the pack node that will consume dw (None / False: reduce now)"""
-    st = mp.wgrad_set(ws, nslab, K_in, N, dw, kn=1, blocked=True)
-    if defer is not None and defer is not False and DEFER_REDUCE:
-        defer.append(st)
-    else:
-        mp.wgrad_reduce([st])
-
-
 def wgrad_blocks(z, K_in, du, defer=None):
-    """dW[K_in, N] = z[:, :K_in]^T du (N = du.size(1) <= 512) in two launches; None if the shape is not taken.  defer: only the slab
-    launch now, the reduction with the next flush_reductions() (the returned tensor is filled then)"""
+    """dW[K_in, N] = z[:, :K_in]^T du (N = du.size(1) <= 512) in two launches; None if the shape is not taken.  defer: the pack node's
+    mp.WgradSets — only the slab launch now, the reduction when it closes (the returned tensor is filled then)"""
     R, N = int(du.size(0)), int(du.size(1))
-    nslab = np.zeros(1, dtype=np.int32)
-    rps = np.zeros(1, dtype=np.int64)
-    need = np.zeros(1, dtype=np.int64)
-    nat.call_nostream("wgrad_blocks_plan", R, int(K_in), N, int(z.stride(0)), int(du.stride(0)), nslab.ctypes.data, rps.ctypes.data,
-                      need.ctypes.data)
-    if int(nslab[0]) <= 0 or z.data_ptr() % 16 or du.data_ptr() % 16:
+    nslab, rps, need = mp.wgrad_plan(R, K_in, N, z.stride(0), du.stride(0), blocked=True)
+    if nslab <= 0 or z.data_ptr() % 16 or du.data_ptr() % 16:
         return None
-    ws = _f32(int(need[0]), device=du.device)
+    ws = _f32(need, device=du.device)
     dw = _f32(int(K_in), N, device=du.device)
-    if defer is not None and defer is not False and DEFER_REDUCE:
-        nat.call("wgrad_blocks_slabs_f32", z, z.stride(0), du, du.stride(0), R, int(K_in), N, int(nslab[0]), int(rps[0]), ws)
-        _reduce(ws, int(nslab[0]), int(K_in), N, dw, defer)
+    if defer is not None and DEFER_REDUCE:
+        nat.call("wgrad_blocks_slabs_f32", z, z.stride(0), du, du.stride(0), R, int(K_in), N, nslab, rps, ws)
+        defer.add(mp.wgrad_set(ws, nslab, int(K_in), N, dw, kn=1, blocked=True))
         return dw
-    nat.call("wgrad_blocks_f32", z, z.stride(0), du, du.stride(0), R, int(K_in), N, int(nslab[0]), int(rps[0]), ws, dw, dw.stride(0))
+    nat.call("wgrad_blocks_f32", z, z.stride(0), du, du.stride(0), R, int(K_in), N, nslab, rps, ws, dw, dw.stride(0))
     return dw
 
 
@@ -178,20 +158,20 @@ def bwd_products(x, K_in, du, wp, defer=None):
     if not (128 < K_in <= 512 and N <= 512 and N % 4 == 0 and x.size(1) == K_in and x.stride(0) % 4 == 0 and du.stride(0) % 4 == 0
             and wp.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and du.data_ptr() % 16 == 0 and wp.data_ptr() % 16 == 0 and R > 0):
         return None
-    nslab = np.zeros(1, dtype=np.int32)
-    rps = np.zeros(1, dtype=np.int64)
-    need = np.zeros(1, dtype=np.int64)
-    nat.call_nostream("wgrad_blocks_plan", R, int(K_in), N, int(x.stride(0)), int(du.stride(0)), nslab.ctypes.data, rps.ctypes.data,
-                      need.ctypes.data)
-    if int(nslab[0]) <= 0:
+    nslab, rps, need = mp.wgrad_plan(R, K_in, N, x.stride(0), du.stride(0), blocked=True)
+    if nslab <= 0:
         return None
-    ws = _f32(int(need[0]), device=du.device)
+    ws = _f32(need, device=du.device)
     dw = _f32(int(K_in), N, device=du.device)
     dx = _f32(R, int(K_in), device=du.device)
     if not nat.try_call("gat_bwd_products_f32", x, x.stride(0), du, du.stride(0), R, int(K_in), N, wp, wp.stride(0), dx, dx.stride(0),
-                        int(nslab[0]), int(rps[0]), ws):
+                        nslab, rps, ws):
         return None
-    _reduce(ws, int(nslab[0]), int(K_in), N, dw, defer)
+    st = mp.wgrad_set(ws, nslab, int(K_in), N, dw, kn=1, blocked=True)
+    if defer is not None and DEFER_REDUCE:
+        defer.add(st)
+    else:
+        mp.wgrad_reduce([st])
     return dw, dx
 
 

@@ -122,13 +122,14 @@ def gemm_tn_splitk(Z, K_in, dU, out=None):
     return out
 
 
-def wgrad_plan(rows, K_in, N, ldz, lddu):
-    """(nslab, rows_per_slab, workspace floats) of the weight-gradient slab kernel; nslab = 0: shape unsupported."""
+def wgrad_plan(rows, K_in, N, ldz, lddu, blocked=False):
+    """(nslab, rows_per_slab, workspace floats) of the weight-gradient slab kernel (blocked: of the 128 x 128 block kernels,
+    tsgnn_wgrad_blocks_plan); nslab <= 0: shape unsupported."""
     nslab = np.zeros(1, dtype=np.int32)
     rps = np.zeros(1, dtype=np.int64)
     need = np.zeros(1, dtype=np.int64)
-    nat.call_nostream("linear_wgrad_plan", int(rows), int(K_in), int(N), int(ldz), int(lddu), nslab.ctypes.data, rps.ctypes.data,
-                      need.ctypes.data)
+    nat.call_nostream("wgrad_blocks_plan" if blocked else "linear_wgrad_plan", int(rows), int(K_in), int(N), int(ldz), int(lddu),
+                      nslab.ctypes.data, rps.ctypes.data, need.ctypes.data)
     return int(nslab[0]), int(rps[0]), int(need[0])
 
 
@@ -136,17 +137,12 @@ def linear_wgrad_slabs(z, K_in, du, bias_only_rows=0):
     """slab partials of (dW, db) without the reduction; returns (ws, nslab) or None when the shape is unsupported.
     The last ``bias_only_rows`` rows of du feed db only (ghost rows: their z is zero)."""
     R, N = du.size(0) - int(bias_only_rows), du.size(1)
-    nslab = np.zeros(1, dtype=np.int32)
-    rps = np.zeros(1, dtype=np.int64)
-    need = np.zeros(1, dtype=np.int64)
-    nat.call_nostream("linear_wgrad_plan", int(R), int(K_in), int(N), int(z.stride(0)), int(du.stride(0)), nslab.ctypes.data,
-                      rps.ctypes.data, need.ctypes.data)
-    if int(nslab[0]) <= 0 or z.data_ptr() % 16 or du.data_ptr() % 16:
+    nslab, rps, need = wgrad_plan(R, K_in, N, z.stride(0), du.stride(0))
+    if nslab <= 0 or z.data_ptr() % 16 or du.data_ptr() % 16:
         return None
-    ws = _f32(int(need[0]), device=du.device)
-    nat.call("linear_wgrad_f32", z, z.stride(0), du, du.stride(0), R, int(K_in), int(N), int(nslab[0]), int(rps[0]),
-             int(bias_only_rows), ws, None, None)
-    return ws, int(nslab[0])
+    ws = _f32(need, device=du.device)
+    nat.call("linear_wgrad_f32", z, z.stride(0), du, du.stride(0), R, int(K_in), int(N), nslab, rps, int(bias_only_rows), ws, None, None)
+    return ws, nslab
 
 
 def wgrad_set(ws, nslab, K, N, dw, db=None, n_db=None, tail=None, kn=0, lddw=None, blocked=False):
@@ -202,33 +198,73 @@ def wgrad_reduce(sets, norm_sink=None):
 
 def wgrad_reduce_multi(sets, norm_sink=None):
     """sets: list of (ws, nslab, K, N, dw [K, N], db-or-None), four per launch through the positional entry point (bench.py's
-    per-kernel table reads its arguments; sage_stack.run_paired joins two such launches).  norm_sink as in wgrad_reduce."""
+    per-kernel table reads its arguments; sage_stack.run_paired joins two such launches).  norm_sink and the result as in wgrad_reduce."""
+    normed = norm_sink is not None
     for i in range(0, len(sets), 4):
         chunk = list(sets[i:i + 4])
         parts, step = (_norm_args(norm_sink, _desc([wgrad_set(*st, kn=1, lddw=st[3]) for st in chunk]))
                        if norm_sink is not None else (None, None))
+        normed = normed and parts is not None
         args = []
         for ws, nslab, K, N, dw, db in chunk + [(None, 0, 0, 0, None, None)] * (4 - len(chunk)):
             args += [ws, int(nslab), int(K), int(N), dw, db]
         nat.call("wgrad_reduce_multi_f32", *args, parts, step)
+    return normed
+
+
+class WgradSets:
+    """The closing weight-gradient reduction of a fused backward node: the slab sets it records (add) are summed by ONE call of
+    `launcher` at close().  grad() hands out the gradient buffers: the parameter's slice of the installed GRAD_SINK when it has one,
+    else a new tensor.  close() asks for the |grad|^2 shares (norm_sink) only when every buffer grad() handed out came from the
+    sink and there are at most max_sets_with_shares records, and marks the parameters normed only when the launcher reports that
+    the shares were left.  With no buffer from grad() (gradients the caller allocated itself), nothing goes near the sink."""
+
+    def __init__(self, launcher=wgrad_reduce, max_sets_with_shares=None):
+        self.launcher, self.max_sets = launcher, max_sets_with_shares
+        self.sink = GRAD_SINK
+        self.sets, self.params, self.sunk, self.all_sunk = [], [], [], True
+
+    def grad(self, param, shape):
+        """the buffer the reduction writes param's gradient into; None for a missing parameter (no bias)"""
+        if param is None:
+            return None
+        self.params.append(param)
+        v = self.sink.take(param, shape) if self.sink is not None else None
+        if v is None:
+            self.all_sunk = False
+            return _f32(*shape, device=param.device)
+        self.sunk.append(v)
+        return v
+
+    def autograd_grad(self, buf):
+        """what the node returns to autograd for a buffer of grad(): None when it is the sink's slice"""
+        return None if any(buf is v for v in self.sunk) else buf
+
+    def add(self, record):
+        """a wgrad_set record (the positional 6-tuple of wgrad_reduce_multi when that is the launcher)"""
+        self.sets.append(record)
+
+    def close(self):
+        if not self.sets:
+            return
+        shares = (self.sink is not None and len(self.params) > 0 and self.all_sunk
+                  and (self.max_sets is None or len(self.sets) <= self.max_sets))
+        if self.launcher(self.sets, norm_sink=self.sink if shares else None):
+            self.sink.normed.update(p.data_ptr() for p in self.params)
+        self.sets = []
 
 
 def linear_wgrad_oi(z, K_in, du, want_db):
     """(dW[N, K_in] — torch.nn.Linear's layout —, db[N] or None) = (du^T z[:, :K_in], colsum(du)): 128 x 128 output blocks in one
     launch + one fixed-order reduction (K_in, N <= 512); None when the shape is not taken"""
     R, N = int(du.size(0)), int(du.size(1))
-    nslab = np.zeros(1, dtype=np.int32)
-    rps = np.zeros(1, dtype=np.int64)
-    need = np.zeros(1, dtype=np.int64)
-    nat.call_nostream("wgrad_blocks_plan", R, int(K_in), N, int(z.stride(0)), int(du.stride(0)), nslab.ctypes.data, rps.ctypes.data,
-                      need.ctypes.data)
-    if int(nslab[0]) <= 0 or z.data_ptr() % 16 or du.data_ptr() % 16 or z.stride(0) < (int(K_in) + 3) // 4 * 4:
+    nslab, rps, need = wgrad_plan(R, K_in, N, z.stride(0), du.stride(0), blocked=True)
+    if nslab <= 0 or z.data_ptr() % 16 or du.data_ptr() % 16 or z.stride(0) < (int(K_in) + 3) // 4 * 4:
         return None
-    ws = _f32(int(need[0]), device=du.device)
+    ws = _f32(need, device=du.device)
     dw = _f32(N, int(K_in), device=du.device)
     db = _f32(N, device=du.device) if want_db else None
-    if not nat.try_call("wgrad_blocks_oi_f32", z, z.stride(0), du, du.stride(0), R, int(K_in), N, int(nslab[0]), int(rps[0]), ws, dw,
-                        dw.stride(0), db):
+    if not nat.try_call("wgrad_blocks_oi_f32", z, z.stride(0), du, du.stride(0), R, int(K_in), N, nslab, rps, ws, dw, dw.stride(0), db):
         return None
     return dw, db
 
@@ -238,32 +274,22 @@ def linear_wgrad(z, K_in, du, want_db, du_job=None):
     du_job = (part, nb, F, dws, dbs): the partial rows tsgnn_sag_pool_graph_bwd_f32 left behind (called with dws = dbs = NULL);
     their sum rides in this product's reduction launch when the one-pass slab kernel takes the shape, else it is launched here."""
     R, N = du.size(0), du.size(1)
+    nslab, rps, need = wgrad_plan(R, K_in, N, z.stride(0), du.stride(0))
     if du_job is not None:
         part, nb, F_du, dws, dbs = du_job
-        nslab = np.zeros(1, dtype=np.int32)
-        rps = np.zeros(1, dtype=np.int64)
-        need = np.zeros(1, dtype=np.int64)
-        nat.call_nostream("linear_wgrad_plan", int(R), int(K_in), int(N), int(z.stride(0)), int(du.stride(0)), nslab.ctypes.data,
-                          rps.ctypes.data, need.ctypes.data)
-        if int(nslab[0]) > 0 and nb <= 256 and z.data_ptr() % 16 == 0 and du.data_ptr() % 16 == 0:
-            ws = _f32(int(need[0]), device=du.device)
+        if nslab > 0 and nb <= 256 and z.data_ptr() % 16 == 0 and du.data_ptr() % 16 == 0:
+            ws = _f32(need, device=du.device)
             dw = _f32(K_in, N, device=du.device)
             db = _f32(N, device=du.device) if want_db else None
-            nat.call("linear_wgrad_du_f32", z, z.stride(0), du, du.stride(0), R, int(K_in), int(N), int(nslab[0]), int(rps[0]), ws,
-                     dw, db, part, int(nb), int(F_du), dws, dbs)
+            nat.call("linear_wgrad_du_f32", z, z.stride(0), du, du.stride(0), R, int(K_in), int(N), nslab, rps, ws, dw, db, part, int(nb),
+                     int(F_du), dws, dbs)
             return dw, db
         nat.call("sag_du_reduce_f32", part, int(nb), int(F_du), dws, dbs)
-    nslab = np.zeros(1, dtype=np.int32)
-    rps = np.zeros(1, dtype=np.int64)
-    need = np.zeros(1, dtype=np.int64)
-    nat.call_nostream("linear_wgrad_plan", int(R), int(K_in), int(N), int(z.stride(0)), int(du.stride(0)), nslab.ctypes.data,
-                      rps.ctypes.data, need.ctypes.data)
-    if int(nslab[0]) > 0 and z.data_ptr() % 16 == 0 and du.data_ptr() % 16 == 0:
-        ws = _f32(int(need[0]), device=du.device)
+    if nslab > 0 and z.data_ptr() % 16 == 0 and du.data_ptr() % 16 == 0:
+        ws = _f32(need, device=du.device)
         dw = _f32(K_in, N, device=du.device)
         db = _f32(N, device=du.device) if want_db else None
-        nat.call("linear_wgrad_f32", z, z.stride(0), du, du.stride(0), R, int(K_in), int(N), int(nslab[0]), int(rps[0]), 0, ws,
-                 dw, db)
+        nat.call("linear_wgrad_f32", z, z.stride(0), du, du.stride(0), R, int(K_in), int(N), nslab, rps, 0, ws, dw, db)
         return dw, db
     # wider than one slab pass (<= 128 x 128): the same MFMA slab kernel on 128-wide blocks, ONE fixed-order reduction for all
     # of them — rows of dW when K_in > 128 (GAT layer 2: 256 -> 64), columns when N > 128 through the transposed product
@@ -434,21 +460,17 @@ def linear_bwd_products(x, K_in, dy, w, want_db):
             and dy.stride(0) % 4 == 0 and w.stride(0) % 4 == 0 and x.data_ptr() % 16 == 0 and dy.data_ptr() % 16 == 0
             and w.data_ptr() % 16 == 0):
         return None
-    nslab = np.zeros(1, dtype=np.int32)
-    rps = np.zeros(1, dtype=np.int64)
-    need = np.zeros(1, dtype=np.int64)
-    nat.call_nostream("wgrad_blocks_plan", R, int(K_in), N, int(x.stride(0)), int(dy.stride(0)), nslab.ctypes.data, rps.ctypes.data,
-                      need.ctypes.data)
-    if int(nslab[0]) <= 0:
+    nslab, rps, need = wgrad_plan(R, K_in, N, x.stride(0), dy.stride(0), blocked=True)
+    if nslab <= 0:
         return None
-    ws = _f32(int(need[0]), device=dy.device)
+    ws = _f32(need, device=dy.device)
     dx = _f32(R, int(K_in), device=dy.device)
     if not nat.try_call("linear_bwd_products_f32", x, x.stride(0), dy, dy.stride(0), R, int(K_in), N, w, w.stride(0), dx, dx.stride(0),
-                        int(nslab[0]), int(rps[0]), ws):
+                        nslab, rps, ws):
         return None
     dw = _f32(N, int(K_in), device=dy.device)
     db = _f32(N, device=dy.device) if want_db else None
-    wgrad_reduce([wgrad_set(ws, int(nslab[0]), int(K_in), N, dw, db, blocked=True)])
+    wgrad_reduce([wgrad_set(ws, nslab, int(K_in), N, dw, db, blocked=True)])
     return dw, db, dx
 
 

@@ -63,12 +63,12 @@ class _Pack(torch.autograd.Function):
         d = _desc(layers, [(o, None, None, None) for o in outs])
         nat.call("gatconv_pack_f32", d.ctypes.data)
         ctx.layers = layers
-        ctx.pending = []                      # slab sets the layers' backward leaves for this node to reduce (gat_fused.flush_reductions)
+        ctx.pending = mp.WgradSets()          # slab sets the layers' backward leaves for this node to reduce
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *dwps):
-        gf.flush_reductions(ctx.pending)
+        ctx.pending.close()
         layers = ctx.layers
         dev = layers[0][4].device
         ptrs = []

@@ -257,8 +257,7 @@ class _SageStack(torch.autograd.Function):
         dev = dread.device
         hs, zs = ctx.hs, ctx.zs
         grads = [None] * (3 * L)
-        sets = []
-        sunk = []
+        red = mp.WgradSets()
         dxs = None
         dx0 = None
         du = dus = None
@@ -276,13 +275,12 @@ class _SageStack(torch.autograd.Function):
             sl = wgrad_slabs(zs[l], hs[l], K, du)
             if sl is None:
                 raise RuntimeError("SAGEConv stack: weight-gradient shape %d x %d is not taken by the slab kernel" % (K, H))
-            dwl, s1 = mp._sink_or_new(ctx.params[3 * l], (H, K), dev)
-            dwr, s3 = mp._sink_or_new(ctx.params[3 * l + 2], (H, K), dev)
-            dbl, s2 = mp._sink_or_new(ctx.params[3 * l + 1], (H,), dev) if ctx.has_bias else (None, False)
-            sets.append(mp.wgrad_set(sl[0][0], sl[0][1], K, H, dwl, dbl))
-            sets.append(mp.wgrad_set(sl[1][0], sl[1][1], K, H, dwr))
-            grads[3 * l], grads[3 * l + 1], grads[3 * l + 2] = (None if s1 else dwl), (None if s2 else dbl), (None if s3 else dwr)
-            sunk.append(s1 and s3 and (s2 or not ctx.has_bias))
+            dwl = red.grad(ctx.params[3 * l], (H, K))
+            dwr = red.grad(ctx.params[3 * l + 2], (H, K))
+            dbl = red.grad(ctx.params[3 * l + 1] if ctx.has_bias else None, (H,))
+            red.add(mp.wgrad_set(sl[0][0], sl[0][1], K, H, dwl, dbl))
+            red.add(mp.wgrad_set(sl[1][0], sl[1][1], K, H, dwr))
+            grads[3 * l:3 * l + 3] = [red.autograd_grad(t) for t in (dwl, dbl, dwr)]
             if l > 0:
                 if POST_EPILOGUE:
                     # the input gradient of this layer IS (up to the readout terms and the ReLU mask) the dU of the layer below: its
@@ -296,13 +294,7 @@ class _SageStack(torch.autograd.Function):
                     du = dus = None
             elif ctx.needs_input_grad[0]:
                 dx0 = conv_dx(g, du, dus, ctx.pk_bwd[0][0], ctx.pk_bwd[0][1], K, H, hs[0].size(1))
-        sink = mp.GRAD_SINK
-        all_sunk = sink is not None and all(sunk)
-        if mp.wgrad_reduce(sets, norm_sink=sink if all_sunk else None):
-            for l in range(L):
-                sink.normed.add(ctx.params[3 * l].data_ptr()); sink.normed.add(ctx.params[3 * l + 2].data_ptr())
-                if ctx.has_bias:
-                    sink.normed.add(ctx.params[3 * l + 1].data_ptr())
+        red.close()
         return (dx0, None, None, None) + tuple(grads)
 
 

@@ -267,7 +267,7 @@ class _SagStack(torch.autograd.Function):
         dxp = None
         dx = None
         nxt = None          # (dagg, rowptr, rowend, col, dinv, self_w) of level l + 1 when this level's kernel forms dxp itself
-        sets, set_params, sunk = [], [], []
+        red = mp.WgradSets()
         for l in range(depth - 1, -1, -1):
             L, Ln = plan.levels[l], plan.levels[l + 1]
             N = L.N
@@ -310,15 +310,10 @@ class _SagStack(torch.autograd.Function):
             if slabs is not None:
                 # every level's slabs and score-layer partial rows wait for ONE reduction at the end of the backward, written straight into
                 # the flat gradient bucket (with |grad|^2 shares) when a FlatTrainer is listening
-                dW, s1 = mp._sink_or_new(pW, (Kin, H), dev)
-                db, s2 = mp._sink_or_new(pb, (H,), dev)
-                dws, s3 = mp._sink_or_new(pws, tuple(pws.shape), dev)
-                dbs, s4 = mp._sink_or_new(pbs, (1,), dev)
-                sets.append(mp.wgrad_set(slabs[0], slabs[1], Kin, H, dW, db, kn=1))
-                sets.append(mp.wgrad_set(part, L.B, 0, H + 4, None, dws, n_db=H, tail=dbs))
-                set_params += [pW, pb, pws, pbs]
-                sunk.append(s1 and s2 and s3 and s4)
-                grads[4 * l: 4 * l + 4] = [None if s1 else dW, None if s2 else db, None if s3 else dws, None if s4 else dbs]
+                dW, db, dws, dbs = red.grad(pW, (Kin, H)), red.grad(pb, (H,)), red.grad(pws, tuple(pws.shape)), red.grad(pbs, (1,))
+                red.add(mp.wgrad_set(slabs[0], slabs[1], Kin, H, dW, db, kn=1))
+                red.add(mp.wgrad_set(part, L.B, 0, H + 4, None, dws, n_db=H, tail=dbs))
+                grads[4 * l: 4 * l + 4] = [red.autograd_grad(t) for t in (dW, db, dws, dbs)]
             else:
                 if du_job is not None:
                     dws, dbs = _f32(H, device=dev), _f32(1, device=dev)
@@ -339,11 +334,7 @@ class _SagStack(torch.autograd.Function):
                     dxp = dxin
                 else:
                     dx = dxin
-        if sets:
-            sink = mp.GRAD_SINK
-            if mp.wgrad_reduce(sets, norm_sink=sink if (sink is not None and all(sunk)) else None):
-                for p in set_params:
-                    sink.normed.add(p.data_ptr())
+        red.close()
         return (dx, None, None, *grads)
 
 

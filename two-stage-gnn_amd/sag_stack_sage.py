@@ -164,7 +164,7 @@ class _SagSageStack(torch.autograd.Function):
         dread = dread.contiguous()
         dev = dread.device
         grads = [None] * (P * depth)
-        sets, sunk = [], []
+        red = mp.WgradSets()
         dxp = None
         dx = None
         for l in range(depth - 1, -1, -1):
@@ -186,25 +186,19 @@ class _SagSageStack(torch.autograd.Function):
             sl = ps.wgrad_slabs(cat, cat[:, Kp:], K, dyb)
             if sl is None:
                 raise RuntimeError("SAGPool + SAGEConv stack: weight-gradient shape %d x %d is not taken by the slab kernel" % (K, H))
-            dwl, s1 = mp._sink_or_new(wl, (H, K), dev)
-            dbl, s2 = mp._sink_or_new(bl, (H,), dev)
-            dwr, s3 = mp._sink_or_new(wr, (H, K), dev)
-            dws, s4 = mp._sink_or_new(ws, tuple(ws.shape), dev)
-            dbs, s5 = mp._sink_or_new(bs, (1,), dev)
-            sets.append(mp.wgrad_set(sl[0][0], sl[0][1], K, H, dwl, dbl))
-            sets.append(mp.wgrad_set(sl[1][0], sl[1][1], K, H, dwr))
+            dwl, dbl, dwr = red.grad(wl, (H, K)), red.grad(bl, (H,)), red.grad(wr, (H, K))
+            dws, dbs = red.grad(ws, tuple(ws.shape)), red.grad(bs, (1,))
+            red.add(mp.wgrad_set(sl[0][0], sl[0][1], K, H, dwl, dbl))
+            red.add(mp.wgrad_set(sl[1][0], sl[1][1], K, H, dwr))
             if gc:
                 # partial rows [dw_rel | db | 3 unused | dw_root]: dw_root from column H + 4 of the same set
                 wroot = ctx.params[P * l + 5]
-                dwt, s6 = mp._sink_or_new(wroot, tuple(wroot.shape), dev)
-                sets.append(mp.wgrad_set(part, L.B, 0, 2 * H + 4, dwt, dws, n_db=H, tail=dbs, lddw=H + 4))
+                dwt = red.grad(wroot, tuple(wroot.shape))
+                red.add(mp.wgrad_set(part, L.B, 0, 2 * H + 4, dwt, dws, n_db=H, tail=dbs, lddw=H + 4))
             else:
-                dwt, s6 = None, True
-                sets.append(mp.wgrad_set(part, L.B, 0, H + 4, None, dws, n_db=H, tail=dbs))
-            grads[P * l: P * l + 5] = [None if s1 else dwl, None if s2 else dbl, None if s3 else dwr, None if s4 else dws, None if s5 else dbs]
-            if gc:
-                grads[P * l + 5] = None if s6 else dwt
-            sunk.append(s1 and s2 and s3 and s4 and s5 and s6)
+                dwt = None
+                red.add(mp.wgrad_set(part, L.B, 0, H + 4, None, dws, n_db=H, tail=dbs))
+            grads[P * l: P * l + P] = [red.autograd_grad(t) for t in (dwl, dbl, dwr, dws, dbs, dwt)[:P]]
             if l > 0 or ctx.x_needs_grad:
                 dcat = _f32(N, 2 * Kp, device=dev)
                 nat.call("rowgemm_f32", dyb, dyb.stride(0), wcat, wcat.stride(0), 0, None, dcat, dcat.stride(0), None, N, H, 2 * Kp, 0, 0)
@@ -215,11 +209,7 @@ class _SagSageStack(torch.autograd.Function):
                     dxp = dxin
                 else:
                     dx = dxin[:, :K]
-        sink = mp.GRAD_SINK
-        all_sunk = sink is not None and all(sunk)
-        if mp.wgrad_reduce(sets, norm_sink=sink if all_sunk else None):
-            for p in ctx.params:
-                sink.normed.add(p.data_ptr())
+        red.close()
         return (dx, None, None, None, None, *grads)
 
 

@@ -411,8 +411,7 @@ class _SageStack(torch.autograd.Function):
         dxs = None
         dx0 = None
         keep = []
-        pending = []
-        pend_sunk, pend_layers = [], []
+        red = mp.WgradSets(mp.wgrad_reduce_multi, max_sets_with_shares=4)     # ONE reduction for all layers' slabs, at the end
         for l in range(L - 1, -1, -1):
             z, v, rinv, mean, rstd, lean = ctx.saved[l]
             W = ctx.Ws[l]
@@ -444,11 +443,10 @@ class _SageStack(torch.autograd.Function):
                 nat.call("slot_post_wgrad_f32", g.graph_ptr, g.slot_count, B, sn, g.n_rows, sg, v, v.stride(0), dxs,
                          dxs.stride(0) if dxs is not None else 0, dsl, dout.stride(0) if dsl is not None else 0, argl, N, 1, 1, mean, rstd,
                          rinv, z, z.stride(0), K, ws0, nblk)
-                dw, sw = mp._sink_or_new(ctx.params[0], (K, N), dev)
-                db, sb = mp._sink_or_new(ctx.params[1], (N,), dev) if ctx.has_bias else (None, False)
-                pending.append((ws0, nblk, K, N, dw, db))
-                pend_sunk.append(sw and (sb or not ctx.has_bias)); pend_layers.append(0)
-                grads[0], grads[1] = (None if sw else dw), (None if sb else db)
+                dw = red.grad(ctx.params[0], (K, N))
+                db = red.grad(ctx.params[1] if ctx.has_bias else None, (N,))
+                red.add((ws0, nblk, K, N, dw, db))
+                grads[0], grads[1] = red.autograd_grad(dw), red.autograd_grad(db)
                 continue
             elif ctx.per_graph:
                 # per-graph statistics: readout winners + row layer norm + ReLU + normalise backward, row by row
@@ -476,11 +474,10 @@ class _SageStack(torch.autograd.Function):
                     dxs = torch.empty(R, K, dtype=torch.float32, device=dev)
                     nat.call("sage_layer_bwd_f32", ell, ell_w, tp, tc, du, du.stride(0), W, W.stride(0), dxs, dxs.stride(0), z, z.stride(0),
                              g.n_rows, nslab, rps, bo, ws, int(g.panel_units))
-                    dw, sw = mp._sink_or_new(ctx.params[2 * l], (K, N), dev)
-                    db, sb = mp._sink_or_new(ctx.params[2 * l + 1], (N,), dev) if want_b else (None, False)
-                    pending.append((ws, nslab, K, N, dw, db))
-                    pend_sunk.append(sw and (sb or not want_b)); pend_layers.append(l)
-                    grads[2 * l], grads[2 * l + 1] = (None if sw else dw), (None if sb else db)
+                    dw = red.grad(ctx.params[2 * l], (K, N))
+                    db = red.grad(ctx.params[2 * l + 1] if want_b else None, (N,))
+                    red.add((ws, nslab, K, N, dw, db))
+                    grads[2 * l], grads[2 * l + 1] = red.autograd_grad(dw), red.autograd_grad(db)
                     keep.append(du)
                     merged = True
             if merged:
@@ -490,11 +487,10 @@ class _SageStack(torch.autograd.Function):
                     du[g.n_rows + sg:].zero_()          # rows no slot kernel wrote
                 sl = mp.linear_wgrad_slabs(z, K, du[:g.n_rows + bo] if lean else du, bias_only_rows=bo if lean else 0)
                 if sl is not None:                      # slabs now, ONE reduction for all layers at the end
-                    dw, sw = mp._sink_or_new(ctx.params[2 * l], (K, N), dev)     # straight into the flat bucket if one is installed
-                    db, sb = mp._sink_or_new(ctx.params[2 * l + 1], (N,), dev) if want_b else (None, False)
-                    pending.append((sl[0], sl[1], K, N, dw, db))
-                    pend_sunk.append(sw and (sb or not want_b)); pend_layers.append(l)
-                    dw, db = (None if sw else dw), (None if sb else db)
+                    dw = red.grad(ctx.params[2 * l], (K, N))       # straight into the flat bucket if one is installed
+                    db = red.grad(ctx.params[2 * l + 1] if want_b else None, (N,))
+                    red.add((sl[0], sl[1], K, N, dw, db))
+                    dw, db = red.autograd_grad(dw), red.autograd_grad(db)
                 else:
                     if lean:
                         z[g.n_rows:].zero_()
@@ -528,15 +524,7 @@ class _SageStack(torch.autograd.Function):
                     dxs = _aggregate_raw(g, dz, transposed=True, rows=g.n_rows if (l > 0 and g.n_ghost) else None)
                 if l == 0:
                     dx0 = dxs
-        if pending:
-            sink = mp.GRAD_SINK
-            all_sunk = sink is not None and len(pending) <= 4 and all(pend_sunk)
-            mp.wgrad_reduce_multi(pending, norm_sink=sink if all_sunk else None)
-            if all_sunk and sink.stepped:
-                for l_ in pend_layers:
-                    sink.normed.add(ctx.params[2 * l_].data_ptr())
-                    if ctx.has_bias:
-                        sink.normed.add(ctx.params[2 * l_ + 1].data_ptr())
+        red.close()
         del keep
         return (dx0, None, None, None, None) + tuple(grads) + head_grads
 
