@@ -1138,6 +1138,37 @@ int tsgnn_gatconv_pack_desc_words(void);
 int tsgnn_gatconv_pack_f32(const int64_t* desc, tsgnn_stream_t stream);
 int tsgnn_gatconv_unpack_f32(const int64_t* desc, tsgnn_stream_t stream);
 
+/* ---------------------------------------------------------------- eigen-pooling (eigen_pool.hip; Code/eigengcn/encoders.py:384-417)
+ *
+ * X' = P^T Z for a block-sparse P (every row of Z in at most one cluster), fused with the max readout of the same rows Z.
+ * Z: rows [n_rows0 + nmax (ghost-slot rows), ldz] in the packed layout of graph_ptr0; coef [n_rows0, J] (J <= 5) the rows'
+ * coefficients u_j(v).  Pooled (final_level = 0): graph_ptr1 = the next level's graph_ptr (K_b clusters per graph); the rows grouped
+ * into K_total + B buckets — bucket graph_ptr1[b] + b = graph b's unassigned rows, bucket c + b + 1 = the members of cluster c (of
+ * graph b) —: bptr [K_total + B + 1] / members [n_rows0] (rows ascending inside a bucket; tsgnn_coo_count / tsgnn_coo_fill over the
+ * key of tsgnn_eigen_pool_from_dense_f32).  out [n_rows1 + n_ghost1, ldo] = X' in the next level's packed layout, column block
+ * j = coefficient j, its n_ghost1 ghost rows zeroed.  Final (final_level = 1): one cluster per graph, fsum [B, J * C] = the sums s,
+ * out [B, ldo] = max(s, 0) (the readout of the reference's single-column final pooling).  ro (nullable) [B, ldro] / arg [B, C]: the
+ * max readout of Z (arg = winning row, -1 if none; ties: the lower row); ghost_mode 0: no ghost rows, 1: the ghost rows are zero
+ * (masked embeddings), 2: they are read.  One launch; no atomics. */
+int tsgnn_eigen_pool_fwd_f32(const float* z, int64_t ldz, int C, const int* graph_ptr0, int B, int nmax, int64_t n_rows0,
+                             int ghost_mode, const int* graph_ptr1, const int* bptr, const int* members, const float* coef, int J,
+                             int final_level, float* out, int64_t ldo, int64_t n_rows1, int n_ghost1, float* fsum, float* ro,
+                             int64_t ldro, int* arg, tsgnn_stream_t stream);
+/* dz [rows_total, lddz] (every element written) = sum_j coef[r, j] * dX'[cluster_of[r], j * C + f] (final: dX'[graph, .] where
+ * s >= 0) + the readout gradient dro at the rows arg names.  Ghost rows: 0, or with ghost_mode 2 the readout gradient of the
+ * graphs they won (summed in graph order).  One launch; no atomics. */
+int tsgnn_eigen_pool_bwd_f32(const float* dxp, int64_t lddxp, const float* fsum, const int* cluster_of, const int* row_graph,
+                             const float* coef, int J, int C, const float* dro, int64_t lddro, const int* arg, int B, int nmax,
+                             int64_t n_rows0, int ghost_mode, int final_level, float* dz, int64_t lddz, int64_t rows_total,
+                             tsgnn_stream_t stream);
+/* dense padded pooling matrices P [J, B, nmax, nmax] (the reference's pool_matrices_dic[i]) -> cluster_of [n_rows] (-1: a row whose
+ * J entries are all zero) and coef [n_rows, J] for the packed rows (row_graph / row_slot), and key [n_rows] (nullable) the row's
+ * bucket (see tsgnn_eigen_pool_fwd_f32).  final_level: column 0, cluster = graph.  bad[0] = 1 if a row's column lies outside its
+ * graph's K_b clusters (graph_ptr1). */
+int tsgnn_eigen_pool_from_dense_f32(const float* P, int J, int B, int nmax, const int* row_graph, const int* row_slot,
+                                    const int* graph_ptr1, int64_t n_rows, int final_level, int* cluster_of, float* coef, int64_t* key,
+                                    int* bad, tsgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
