@@ -660,6 +660,27 @@ int tsgnn_mlp3_bwd2_np_f32(const float* x, int64_t ldx, const float* w1, const f
                            int D0, int D1, int D2, int C, float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, float* dx,
                            int64_t lddx, float* ws, float* normparts, tsgnn_stream_t stream);
 
+/* ---- tail of the SAGPool triplet step (Code/sag/tripletnet.py:14-24 on network.py:48-53): the head above on exactly three readout
+ * rows x[3, D0] (anchor, positive, negative) -> embed[3, C] = log_softmax(lin3(relu(lin2(dropout(relu(lin1(x))))))) and
+ * dist = (||e_a - e_p + eps||_2, ||e_a - e_n + eps||_2) (F.pairwise_distance) in ONE launch of one workgroup.  p > 0: dropout with
+ * the mask made inside the launch exactly as tsgnn_mlp3_fwd_drop_f32 makes it for B = 3 (same seed / state / used words: state[0] is
+ * advanced by the launch, tsgnn_mlp3_dropout_mask_f32(p, seed, used[0], 3, D1) regenerates the mask); p == 0: state / used unused.
+ * a1[3, D1], a2[3, D2] (dense rows) are kept for the backward.
+ * backward: from the gradients of the two distances (g_dp[1], g_dn[1]) and of the three embeddings (g_ea, g_ep, g_en [C]; every one
+ * nullable = zero) to dx[3, D0] (nullable) and the six parameter gradients (db1 / db2 / db3 nullable) in ONE launch; a zero distance
+ * contributes a zero gradient (torch's norm backward); keep_scale = 1 / (1 - p).
+ * Taken: D0, D1, D2 multiples of 4 (16-byte weight rows, w1 / w2 / w3 16-byte aligned), D0 <= 2048, D1 <= 1024, D2 <= 512, C <= 512. */
+int tsgnn_mlp3_triplet_supported(int D0, int D1, int D2, int C);
+int tsgnn_mlp3_triplet_fwd_f32(const float* x, int64_t ldx, const float* w1, const float* b1, float p, uint64_t seed,
+                               unsigned long long* state, unsigned long long* used, const float* w2, const float* b2, const float* w3,
+                               const float* b3, int D0, int D1, int D2, int C, float eps, float* a1, float* a2, float* embed, float* dist,
+                               tsgnn_stream_t stream);
+int tsgnn_mlp3_triplet_bwd_f32(const float* x, int64_t ldx, const float* w1, const float* w2, const float* w3, const float* a1,
+                               const float* a2, const float* embed, const float* dist, float eps, float keep_scale, const float* g_dp,
+                               const float* g_dn, const float* g_ea, const float* g_ep, const float* g_en, int D0, int D1, int D2, int C,
+                               float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, float* dx, int64_t lddx,
+                               tsgnn_stream_t stream);
+
 /* ---------------------------------------------------------------- DiffPool link-prediction side loss (linkpred.hip) */
 
 /* encoders.py:416-440 for adj_hop = 1, value and gradient in one pass, no [B,N,N] tensor:

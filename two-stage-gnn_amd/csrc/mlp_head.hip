@@ -659,3 +659,311 @@ int tsgnn_mlp3_bwd2_np_f32(const float* x, int64_t ldx, const float* w1, const f
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- the head on the three rows of a triplet + both distances
+// Code/sag/tripletnet.py:14-24 on Code/sag/network.py:48-53: the head above on exactly three readout rows (anchor, positive,
+// negative), its log_softmax output being the embedding, followed by F.pairwise_distance(e_a, e_p), (e_a, e_n).  A latency kernel:
+// three rows are far too few for MFMA and the weights (~170 KB for nhid 128) are what moves.
+//   forward : ONE workgroup of 8 waves; the three rows sit in LDS, so every weight row is streamed once for all three (a wave
+//             requests eight rows together with 16-byte loads: 24 dot products per pass, wave sums by DPP); log_softmax is one wave
+//             per row, the distances one wave each.  The dropout mask is mlp3_fwd_drop's: the same Philox key (seed + the device
+//             counter) and element coordinates (row, hidden unit) with B = 3, so tsgnn_mlp3_dropout_mask_f32 regenerates it; a single
+//             workgroup advances the counter itself (no ticket).
+//   backward: one launch, a workgroup per 32 input columns.  Every workgroup re-derives the short chain de -> dlogits -> dz2 -> dz1
+//             for the three rows in LDS (36 K multiply-adds, W3 and W2 from L2) and then owns its columns of dx = dz1 W1 and of
+//             dW1 = dz1^T x; dW2, dW3 and the three bias gradients are outer products of vectors every workgroup holds, so they
+//             are dealt out over the whole grid.  No atomics: every output entry has one writer.  (The rows / weights split of
+//             tsgnn_mlp3_bwd2_f32 exists to avoid recomputing the chain for 128 rows per tile; for three rows the chain is cheaper
+//             than a second launch.)
+namespace {
+
+constexpr int MT_WAVES = 8;                   // forward: 512 threads (24 accumulators + eight 16-byte loads per lane spill at the 128 registers of 1,024)
+constexpr int MT_EPW = 8;                  // weight rows a wave requests together
+
+// vs[b][j] = act(W[j,:] . xs[b] + bias[j]) for b < 3, j < E   (W [E, P] row-major, P % 4 == 0; xs [3][P], vs [3][E] in LDS)
+template <bool RELU>
+__device__ __forceinline__ void dense_row3(const float* xs, int P, const float* __restrict__ w, const float* __restrict__ bias, int E,
+                                           float* vs) {
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const int P4 = P >> 2;
+  for (int j0 = wid; j0 < E; j0 += MT_EPW * MT_WAVES) {
+    float s0[MT_EPW], s1[MT_EPW], s2[MT_EPW];
+#pragma unroll
+    for (int u = 0; u < MT_EPW; ++u) { s0[u] = 0.f; s1[u] = 0.f; s2[u] = 0.f; }
+    for (int k4 = lane; k4 < P4; k4 += 64) {
+      float4 wv[MT_EPW];
+#pragma unroll
+      for (int u = 0; u < MT_EPW; ++u) {                                  // rows past E: a mapped row, result dropped
+        const int j = j0 + MT_WAVES * u;
+        wv[u] = ld4(w + (int64_t)(j < E ? j : 0) * P + 4 * k4);
+      }
+      const float4 a = *reinterpret_cast<const float4*>(xs + 4 * k4);
+      const float4 p = *reinterpret_cast<const float4*>(xs + P + 4 * k4);
+      const float4 n = *reinterpret_cast<const float4*>(xs + 2 * P + 4 * k4);
+#pragma unroll
+      for (int u = 0; u < MT_EPW; ++u) {
+        s0[u] += (wv[u].x * a.x + wv[u].y * a.y) + (wv[u].z * a.z + wv[u].w * a.w);
+        s1[u] += (wv[u].x * p.x + wv[u].y * p.y) + (wv[u].z * p.z + wv[u].w * p.w);
+        s2[u] += (wv[u].x * n.x + wv[u].y * n.y) + (wv[u].z * n.z + wv[u].w * n.w);
+      }
+    }
+#pragma unroll
+    for (int u = 0; u < MT_EPW; ++u) {
+      const int j = j0 + MT_WAVES * u;
+      const float t0 = wave_sum(s0[u]), t1 = wave_sum(s1[u]), t2 = wave_sum(s2[u]);
+      if (lane == 0 && j < E) {
+        const float bj = bias ? bias[j] : 0.f;
+        const float v0 = t0 + bj, v1 = t1 + bj, v2 = t2 + bj;
+        vs[j] = RELU ? fmaxf(v0, 0.f) : v0;
+        vs[E + j] = RELU ? fmaxf(v1, 0.f) : v1;
+        vs[2 * E + j] = RELU ? fmaxf(v2, 0.f) : v2;
+      }
+    }
+  }
+}
+
+__global__ __launch_bounds__(64 * MT_WAVES) void mlp3_triplet_fwd_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w1,
+                                                                         const float* __restrict__ b1, float keep_scale,
+                                                                         const float* __restrict__ w2, const float* __restrict__ b2,
+                                                                         const float* __restrict__ w3, const float* __restrict__ b3, int D0,
+                                                                         int D1, int D2, int C, float eps, float* __restrict__ a1,
+                                                                         float* __restrict__ a2, float* __restrict__ embed,
+                                                                         float* __restrict__ dist, Mlp3Drop drop) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  float* xs = smem;                      // [3][D0]
+  float* v1 = xs + 3 * D0;               // [3][D1]
+  float* v2 = v1 + 3 * D1;               // [3][D2]
+  float* lg = v2 + 3 * D2;               // [3][C]
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  unsigned long long ctr = 0ull;
+  if (drop.state) ctr = __hip_atomic_load(drop.state, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  for (int k = tid; k < 3 * D0; k += 64 * MT_WAVES) {
+    const int b = k / D0, i = k - b * D0;
+    xs[k] = x[(int64_t)b * ldx + i];
+  }
+  __syncthreads();
+  dense_row3<true>(xs, D0, w1, b1, D1, v1);
+  __syncthreads();
+  const unsigned klo = drop.seed_lo + (unsigned)(ctr & 0xffffffffull), khi = drop.seed_hi + (unsigned)(ctr >> 32);
+  for (int k = tid; k < 3 * D1; k += 64 * MT_WAVES) {
+    const int b = k / D1, j = k - b * D1;
+    float m = 1.f;                                                                    // dropout after the ReLU (network.py:48-49)
+    if (drop.state) m = mlp3_keep(drop.thresh, klo, khi, (unsigned)b, (unsigned)j) * keep_scale;
+    const float v = v1[k] * m;
+    v1[k] = v;
+    a1[k] = v;
+  }
+  __syncthreads();
+  dense_row3<true>(v1, D1, w2, b2, D2, v2);
+  __syncthreads();
+  for (int k = tid; k < 3 * D2; k += 64 * MT_WAVES) a2[k] = v2[k];
+  dense_row3<false>(v2, D2, w3, b3, C, lg);
+  __syncthreads();
+  if (wid < 3) {                                                                      // log_softmax: one wave per row
+    float* row = lg + wid * C;
+    float m = -INFINITY;
+    for (int c = lane; c < C; c += 64) m = fmaxf(m, row[c]);
+    m = wave_max(m);
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += expf(row[c] - m);
+    s = wave_sum(s);
+    const float lse = m + logf(s);
+    for (int c = lane; c < C; c += 64) {
+      const float e = row[c] - lse;
+      row[c] = e;
+      embed[wid * C + c] = e;
+    }
+  }
+  __syncthreads();
+  if (wid < 2) {                                                                      // ||e_a - e_x + eps||_2, x = positive, negative
+    const float* o = lg + (wid + 1) * C;
+    float q = 0.f;
+    for (int c = lane; c < C; c += 64) {
+      const float d = lg[c] - o[c] + eps;
+      q = fmaf(d, d, q);
+    }
+    q = wave_sum(q);
+    if (lane == 0) dist[wid] = sqrtf(q);
+  }
+  if (drop.state && tid == 0) {
+    drop.used[0] = ctr;
+    asm volatile("" ::"v"((unsigned)ctr));
+    atomicAdd(drop.state, 1ull);                                                      // the only workgroup: the next launch's key
+  }
+}
+
+struct Mlp3TripletBwd {
+  const float* x; int64_t ldx;
+  const float* w1; const float* w2; const float* w3;
+  const float* a1; const float* a2; const float* embed; const float* dist;
+  const float* g_dp; const float* g_dn; const float* g_e[3];
+  float eps, keep_scale;
+  int D0, D1, D2, C;
+  float* dw1; float* db1; float* dw2; float* db2; float* dw3; float* db3; float* dx; int64_t lddx;
+};
+
+constexpr int MTB_T = 256;
+
+// out[b][n] = gate(b, n) * sum_r g[b][r] W[r, n]  for b < 3, n < N   (W [R, N] row-major; g [3][R], out [3][N], part [3][4][64] in LDS;
+// gate = scale where act[b * N + n] > 0, else 0).  64 columns x 4 row lanes per pass: R / 4 independent loads per thread.
+__device__ __forceinline__ void chain3(const float* g, int R, const float* __restrict__ W, int N, const float* act, float scale,
+                                       float* out, float* part) {
+  const int tid = threadIdx.x, j = tid & 63, k = tid >> 6;
+  for (int n0 = 0; n0 < N; n0 += 64) {
+    const int n = n0 + j;
+    const int nc = n < N ? n : 0;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+#pragma unroll 8
+    for (int r = k; r < R; r += 4) {
+      const float wv = W[(int64_t)r * N + nc];
+      s0 = fmaf(g[r], wv, s0); s1 = fmaf(g[R + r], wv, s1); s2 = fmaf(g[2 * R + r], wv, s2);
+    }
+    part[(0 * 4 + k) * 64 + j] = s0; part[(1 * 4 + k) * 64 + j] = s1; part[(2 * 4 + k) * 64 + j] = s2;
+    __syncthreads();
+    if (tid < 192) {
+      const int b = tid >> 6, nn = n0 + j;
+      if (nn < N) {
+        const float s = (part[(b * 4 + 0) * 64 + j] + part[(b * 4 + 1) * 64 + j]) + (part[(b * 4 + 2) * 64 + j] + part[(b * 4 + 3) * 64 + j]);
+        out[b * N + nn] = act[b * N + nn] > 0.f ? s * scale : 0.f;
+      }
+    }
+    __syncthreads();
+  }
+}
+
+__global__ __launch_bounds__(MTB_T) void mlp3_triplet_bwd_kernel(Mlp3TripletBwd p) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
+  const int D0 = p.D0, D1 = p.D1, D2 = p.D2, C = p.C;
+  float* dlg = smem;                     // [3][C]   de, then dlogits
+  float* a2s = dlg + 3 * C;              // [3][D2]
+  float* dz2 = a2s + 3 * D2;             // [3][D2]
+  float* a1s = dz2 + 3 * D2;             // [3][D1]
+  float* dz1 = a1s + 3 * D1;             // [3][D1]
+  float* part = dz1 + 3 * D1;            // [3][4][64] (chain) / [3][8][32] (dx)
+  // the embeddings' gradient: the distance terms (0 at a zero distance, as torch's norm backward) + what reaches them directly
+  const float gp = p.g_dp ? p.g_dp[0] : 0.f, gn = p.g_dn ? p.g_dn[0] : 0.f;
+  const float dpv = p.dist[0], dnv = p.dist[1];
+  const float ip = dpv > 0.f ? gp / dpv : 0.f, in_ = dnv > 0.f ? gn / dnv : 0.f;
+  for (int c = tid; c < C; c += MTB_T) {
+    const float a = p.embed[c], q = p.embed[C + c], n = p.embed[2 * C + c];
+    const float tp = (a - q + p.eps) * ip, tn = (a - n + p.eps) * in_;
+    dlg[c] = tp + tn + (p.g_e[0] ? p.g_e[0][c] : 0.f);
+    dlg[C + c] = -tp + (p.g_e[1] ? p.g_e[1][c] : 0.f);
+    dlg[2 * C + c] = -tn + (p.g_e[2] ? p.g_e[2][c] : 0.f);
+  }
+  for (int k = tid; k < 3 * D2; k += MTB_T) a2s[k] = p.a2[k];
+  for (int k = tid; k < 3 * D1; k += MTB_T) a1s[k] = p.a1[k];
+  __syncthreads();
+  if (wid < 3) {                                                                      // dlogits = de - softmax * sum_c de
+    float* row = dlg + wid * C;
+    float s = 0.f;
+    for (int c = lane; c < C; c += 64) s += row[c];
+    s = wave_sum(s);
+    for (int c = lane; c < C; c += 64) row[c] -= expf(p.embed[wid * C + c]) * s;
+  }
+  __syncthreads();
+  chain3(dlg, C, p.w3, D2, a2s, 1.f, dz2, part);                                      // dz2 = [a2 > 0] dlogits W3
+  chain3(dz2, D2, p.w2, D1, a1s, p.keep_scale, dz1, part);                            // dz1 = keep_scale [a1 > 0] dz2 W2
+  // ---- this workgroup's 32 input columns: dx = dz1 W1, dW1 = dz1^T x; thread (j, k): column j, rows o = k, k + 8, ...
+  {
+    const int j = tid & 31, k = tid >> 5;
+    const int i = 32 * (int)blockIdx.x + j;
+    const bool ok = i < D0;
+    const int ic = ok ? i : 0;
+    const float xa = ok ? p.x[i] : 0.f, xp = ok ? p.x[p.ldx + i] : 0.f, xn = ok ? p.x[2 * p.ldx + i] : 0.f;
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f;
+    for (int o0 = k; o0 < D1; o0 += 64) {                                             // eight rows of W1 per pass, requested together
+      float wv[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) wv[u] = p.w1[(int64_t)min(o0 + 8 * u, D1 - 1) * D0 + ic];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) {
+        const int o = o0 + 8 * u;
+        if (ok && o < D1) {
+          const float g0 = dz1[o], g1 = dz1[D1 + o], g2 = dz1[2 * D1 + o];
+          s0 = fmaf(g0, wv[u], s0); s1 = fmaf(g1, wv[u], s1); s2 = fmaf(g2, wv[u], s2);
+          p.dw1[(int64_t)o * D0 + i] = fmaf(g0, xa, fmaf(g1, xp, g2 * xn));
+        }
+      }
+    }
+    if (p.dx) {
+      part[(0 * 8 + k) * 32 + j] = s0; part[(1 * 8 + k) * 32 + j] = s1; part[(2 * 8 + k) * 32 + j] = s2;
+      __syncthreads();
+      if (tid < 96) {
+        const int b = tid >> 5, jj = tid & 31, ii = 32 * (int)blockIdx.x + jj;
+        float s = 0.f;
+#pragma unroll
+        for (int q = 0; q < 8; ++q) s += part[(b * 8 + q) * 32 + jj];
+        if (ii < D0) p.dx[(int64_t)b * p.lddx + ii] = s;
+      }
+    }
+  }
+  // ---- dW2 = dz2^T a1, dW3 = dlogits^T a2 and the bias gradients: outer products of LDS vectors, dealt out over the grid
+  const int n2 = D2 * D1, n3 = C * D2;
+  const int total = n2 + n3 + D1 + D2 + C;
+  for (int idx = (int)blockIdx.x * MTB_T + tid; idx < total; idx += (int)gridDim.x * MTB_T) {
+    if (idx < n2) {
+      const int k = idx / D1, o = idx - k * D1;
+      p.dw2[idx] = fmaf(dz2[k], a1s[o], fmaf(dz2[D2 + k], a1s[D1 + o], dz2[2 * D2 + k] * a1s[2 * D1 + o]));
+    } else if (idx < n2 + n3) {
+      const int t = idx - n2, c = t / D2, k = t - c * D2;
+      p.dw3[t] = fmaf(dlg[c], a2s[k], fmaf(dlg[C + c], a2s[D2 + k], dlg[2 * C + c] * a2s[2 * D2 + k]));
+    } else if (idx < n2 + n3 + D1) {
+      const int o = idx - n2 - n3;
+      if (p.db1) p.db1[o] = (dz1[o] + dz1[D1 + o]) + dz1[2 * D1 + o];
+    } else if (idx < n2 + n3 + D1 + D2) {
+      const int k = idx - n2 - n3 - D1;
+      if (p.db2) p.db2[k] = (dz2[k] + dz2[D2 + k]) + dz2[2 * D2 + k];
+    } else {
+      const int c = idx - n2 - n3 - D1 - D2;
+      if (p.db3) p.db3[c] = (dlg[c] + dlg[C + c]) + dlg[2 * C + c];
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+/* 1 when the triplet tail accepts the head's widths: 16-byte weight rows in all three layers, bounded LDS */
+int tsgnn_mlp3_triplet_supported(int D0, int D1, int D2, int C) {
+  if (D0 <= 0 || D1 <= 0 || D2 <= 0 || C <= 0 || D0 % 4 || D1 % 4 || D2 % 4) return 0;
+  return (D0 <= 2048 && D1 <= 1024 && D2 <= 512 && C <= 512) ? 1 : 0;
+}
+
+int tsgnn_mlp3_triplet_fwd_f32(const float* x, int64_t ldx, const float* w1, const float* b1, float p, uint64_t seed,
+                               unsigned long long* state, unsigned long long* used, const float* w2, const float* b2, const float* w3,
+                               const float* b3, int D0, int D1, int D2, int C, float eps, float* a1, float* a2, float* embed, float* dist,
+                               tsgnn_stream_t stream) {
+  if (!x || !w1 || !w2 || !w3 || !a1 || !a2 || !embed || !dist || ldx < D0 || !(p >= 0.f) || !(p < 1.f) || (p > 0.f && (!state || !used)))
+    return TSGNN_EINVAL;
+  if (!tsgnn_mlp3_triplet_supported(D0, D1, D2, C) ||
+      ((reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2) | reinterpret_cast<uintptr_t>(w3)) & 15))
+    return TSGNN_EUNSUPPORTED;
+  const size_t lds = sizeof(float) * 3 * ((size_t)D0 + D1 + D2 + C);              // <= 48 KB inside _supported
+  Mlp3Drop d{};
+  if (p > 0.f) d = Mlp3Drop{mlp3_thresh(p), (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), state, used};
+  mlp3_triplet_fwd_kernel<<<1, 64 * MT_WAVES, lds, stream>>>(x, ldx, w1, b1, 1.0f / (1.0f - p), w2, b2, w3, b3, D0, D1, D2, C, eps, a1, a2,
+                                                            embed, dist, d);
+  TSGNN_CHECK_LAUNCH();
+  return TSGNN_OK;
+}
+
+int tsgnn_mlp3_triplet_bwd_f32(const float* x, int64_t ldx, const float* w1, const float* w2, const float* w3, const float* a1,
+                               const float* a2, const float* embed, const float* dist, float eps, float keep_scale, const float* g_dp,
+                               const float* g_dn, const float* g_ea, const float* g_ep, const float* g_en, int D0, int D1, int D2, int C,
+                               float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, float* dx, int64_t lddx,
+                               tsgnn_stream_t stream) {
+  if (!x || !w1 || !w2 || !w3 || !a1 || !a2 || !embed || !dist || !dw1 || !dw2 || !dw3 || ldx < D0 || (dx && lddx < D0))
+    return TSGNN_EINVAL;
+  if (!tsgnn_mlp3_triplet_supported(D0, D1, D2, C)) return TSGNN_EUNSUPPORTED;
+  Mlp3TripletBwd p{x, ldx, w1, w2, w3, a1, a2, embed, dist, g_dp, g_dn, {g_ea, g_ep, g_en}, eps, keep_scale, D0, D1, D2, C,
+                   dw1, db1, dw2, db2, dw3, db3, dx, lddx};
+  const size_t lds = sizeof(float) * (3 * ((size_t)C + 2 * D2 + 2 * D1) + 768);   // <= 28 KB inside _supported
+  mlp3_triplet_bwd_kernel<<<(unsigned)((D0 + 31) / 32), MTB_T, lds, stream>>>(p);
+  TSGNN_CHECK_LAUNCH();
+  return TSGNN_OK;
+}
+
+}  // extern "C"

@@ -71,12 +71,15 @@ class Net(nn.Module):
             return ok and all(c.bias is not None for c in convs)
         return ok and all(c.lin_l.bias is not None and c.root_weight and not c.normalize for c in convs) and self.nhid % 4 == 0
 
-    def _forward_fused(self, data):
+    def _forward_fused(self, data, sizes=None):
+        """sizes (np.int64[B], optional): the graphs of the batch, host-known — per-graph pooling and read-outs whatever ``use_batch``
+        says and without reading ``data.batch`` (sag_triplet.tripletnet: three graphs the reference runs one at a time)"""
         from . import sag_stack
         x = data.x
         g = data.edge_index if isinstance(data.edge_index, pyg.GraphBatch) else pyg.graph_of(data.edge_index, x.size(0), check_symmetry=True)
-        batch = getattr(data, "batch", None) if self.use_batch else None
-        sizes = pyg.segment_sizes(batch, x.size(0))
+        if sizes is None:
+            batch = getattr(data, "batch", None) if self.use_batch else None
+            sizes = pyg.segment_sizes(batch, x.size(0))
         plan = sag_stack.SagPlan.get(sizes, self.pooling_ratio, x.device, depth=3)
         params = []
         if self.conv_kind != "gcn":
