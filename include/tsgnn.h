@@ -412,6 +412,14 @@ int tsgnn_row_post_bwd_f32(const int* row_graph, int B, int64_t n_real, int64_t 
                            int64_t lddxs, const float* dout, int64_t ldo, const int* arg, int F, int relu, int ln, const float* mean,
                            const float* rstd, const float* rinv, float* du, int64_t lddu, tsgnn_stream_t stream);
 
+/* The same pass for a layer whose rows are a block of a NODE-level output (gcn_forward's concatenation, encoders.py:140-167) instead of
+ * feeding a readout: dy = dxs (real rows; nullable) + dnode (the gradient that reaches the layer's block directly; nullable) -> layer-norm
+ * backward (ln) -> ReLU mask (relu) -> du = rinv (dv - v <v, dv>).  Rows [n_real, rows) are ghost rows: nothing aggregates from them, so
+ * only dnode reaches them; ghost_zero != 0 (the output was multiplied by the embedding mask): their du is zero.  F <= 256. */
+int tsgnn_row_post_nodes_bwd_f32(int64_t n_real, int64_t rows, const float* v, int64_t ldv, const float* dxs, int64_t lddxs,
+                                 const float* dnode, int64_t lddn, int ghost_zero, int F, int relu, int ln, const float* mean,
+                                 const float* rstd, const float* rinv, float* du, int64_t lddu, tsgnn_stream_t stream);
+
 /* out[b,f] = max over the nmax node slots of graph b (ghost rows included, trap T5), arg = winning row.
  * Replaces torch.max(x, dim=1) (encoders.py:183,190,197,353,383).  ONE launch.  packed_ws: tsgnn_readout_max_ws_words(B, nmax, F)
  * uint64 words (B * F packed maxima, then the graphs' arrival counters), ALL zero on entry and all zero again on return: a workspace
@@ -1074,6 +1082,21 @@ int tsgnn_triplet_embed_fwd_f32(const float* r, int64_t ldr, const float* w, int
 int tsgnn_triplet_embed_bwd_f32(const float* r, int64_t ldr, const float* w, int64_t ldw, int D, int E, float eps, const float* embed,
                                 const float* dist, const float* d_dp, const float* d_dn, const float* d_ea, const float* d_ep,
                                 const float* d_en, float* d_r, int64_t lddr, float* dw, int64_t lddw, float* db, tsgnn_stream_t stream);
+
+/* ---- tail of the EigenGCN triplet step (csrc/mlp2_triplet.hip; Code/eigengcn/tripletnet.py:58-155 on encoders.py:377):
+ * pred_model = Linear -> ReLU -> Linear on the three readout rows r[3, D] (anchor, positive, negative), nn.Linear's [out, in] layouts
+ * w1[H, D], w2[E, H] (dense), biases nullable:  h[3, H] = relu(W1 r + b1) (kept for the backward), embed[3, E] = W2 h + b2,
+ * dist = (||e_a - e_p + eps||_2, ||e_a - e_n + eps||_2) (F.pairwise_distance) in ONE launch of one workgroup; the backward from the
+ * gradients of the two distances (g_dp[1], g_dn[1]) and of the three embeddings (g_ea, g_ep, g_en [E]; every one nullable = zero) to
+ * dr[3, D] (nullable), dw1[H, D], db1[H] (nullable), dw2[E, H], db2[E] (nullable) in ONE launch (every output element written once).
+ * D % 4 == 0, D <= 2048, H <= 512, E <= 512 (tsgnn_mlp2_triplet_supported), 16-byte aligned r / w1, ldr % 4 == 0. */
+int tsgnn_mlp2_triplet_supported(int D, int H, int E);
+int tsgnn_mlp2_triplet_fwd_f32(const float* r, int64_t ldr, const float* w1, const float* b1, const float* w2, const float* b2, int D,
+                               int H, int E, float eps, float* h, float* embed, float* dist, tsgnn_stream_t stream);
+int tsgnn_mlp2_triplet_bwd_f32(const float* r, int64_t ldr, const float* w1, const float* w2, const float* h, const float* embed,
+                               const float* dist, float eps, const float* g_dp, const float* g_dn, const float* g_ea, const float* g_ep,
+                               const float* g_en, int D, int H, int E, float* dr, int64_t lddr, float* dw1, float* db1, float* dw2,
+                               float* db2, tsgnn_stream_t stream);
 
 /* torch.nn.MarginRankingLoss(margin) of the triplet loop (Code/sage+gat+diffpool/train_triplet.py:235,277) in one launch:
  * loss[0] = mean (mean != 0) or sum over i of max(0, -target[i] (x1[i] - x2[i]) + margin); coef[n] = the gradient coefficients the

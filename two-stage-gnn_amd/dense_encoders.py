@@ -225,16 +225,24 @@ class GcnEncoderGraph(nn.Module):
         """ReLU then (optionally) slot batch-norm: encoders.py:179-181."""
         return mp.bn_slots(v, g, relu=True, bn=self.bn, per_graph=self.per_graph_bn)
 
-    def gcn_forward_rows(self, x, g, conv_first, conv_block, conv_last, mask_ghost=False):
+    def gcn_forward_rows(self, x, g, conv_first, conv_block, conv_last, mask_ghost=False, per_graph_stack=False):
         """gcn_forward (encoders.py:140-167) on rows: per-layer outputs concatenated on the feature axis;
-        ``mask_ghost`` = multiply by the embedding mask (zeroes every ghost row)."""
-        if FUSED_STACK and not self.per_graph_bn and (mask_ghost or not g.n_ghost):
+        ``mask_ghost`` = multiply by the embedding mask (zeroes every ghost row).  ``per_graph_stack``: the caller allows the fused
+        node under per-graph statistics too (masked output on a batch with its full set of ghost-slot rows)."""
+        # the fused node: slot statistics, or — where the caller allows it — the per-graph statistics of the triplet step (masked
+        # output on a batch with its full set of ghost-slot rows: the row-local launches tsgnn_row_ln_fwd_f32 /
+        # tsgnn_row_post_nodes_bwd_f32 in place of the slot ones)
+        per_graph = bool(self.per_graph_bn)
+        allowed = (mask_ghost or not g.n_ghost) if not per_graph else \
+            (per_graph_stack and PER_GRAPH_STACK and mask_ghost and g.row_graph is not None and g.n_ghost == g.nmax)
+        if FUSED_STACK and allowed:
             from . import sage_stack
             convs = [conv_first] + list(conv_block) + [conv_last]
             if (sage_stack.eligible(g, convs, self.bn, x)
                     and bool(mp.nat.lib().tsgnn_slot_fused_supported(g.B, convs[0].output_dim))
                     and bool(mp.nat.lib().tsgnn_slot_fused_supported(g.B, convs[-1].output_dim))):
-                return sage_stack.sage_stack_nodes(x, g, convs, mask_ghost)     # one autograd node, layers write into the cat
+                with sage_stack.per_graph_stats(per_graph):
+                    return sage_stack.sage_stack_nodes(x, g, convs, mask_ghost)     # one autograd node, layers write into the cat
         x = self._post(conv_first.forward_rows(x, g), g)
         x_all = [x]
         for conv in conv_block:

@@ -59,12 +59,14 @@ class WavePoolingGcnEncoder(E.GcnEncoderGraph):
         self._init_convs()
         self.to(E._default_device())
 
-    def _stack(self, x, g, convs, masked):
-        emb = self.gcn_forward_rows(x, g, convs[0], convs[1], convs[2], mask_ghost=masked)
+    def _stack(self, x, g, convs, masked, per_graph_stack=False):
+        emb = self.gcn_forward_rows(x, g, convs[0], convs[1], convs[2], mask_ghost=masked, per_graph_stack=per_graph_stack)
         return emb if self.concat else emb[:, emb.size(1) - self.embedding_dim:]
 
     def forward(self, x, adj, adj_pooled_list=None, batch_num_nodes=None, batch_num_nodes_list=None, pool_matrices_dic=None,
-                **kwargs):
+                readout_only=False, **kwargs):
+        """``readout_only``: return the concatenated readouts, the input of ``pred_model`` (eigen_triplet.tripletnet applies
+        ``pred_model`` itself, together with both distances)"""
         L, J, Jf = len(self.pool_sizes), self.num_pool_matrix, self.num_pool_final_matrix
         if isinstance(adj, ep.EigenBatch):
             eb = adj
@@ -76,7 +78,8 @@ class WavePoolingGcnEncoder(E.GcnEncoderGraph):
         g = eb.g0
         if x.dim() == 3:
             x = mp.pack_rows(x, g, (x.size(2) + 3) // 4 * 4)
-        emb = self._stack(x, g, (self.conv_first, self.conv_block, self.conv_last), True)     # level 0: always masked
+        # level 0: always masked; under per-graph statistics (eigen_triplet) it may still run as the fused node
+        emb = self._stack(x, g, (self.conv_first, self.conv_block, self.conv_last), True, per_graph_stack=True)
         C = emb.size(1)
         head_in = self.pred_model[0].in_features if isinstance(self.pred_model, nn.Sequential) else self.pred_model.in_features
         cols = mp.ReadoutColumns(g.B, head_in, emb.device) if self.concat else None
@@ -110,6 +113,8 @@ class WavePoolingGcnEncoder(E.GcnEncoderGraph):
             output = cols.join(out_all) if cols is not None else torch.cat(out_all, dim=1)
         else:
             output = out_all[-1]
+        if readout_only:
+            return output
         return self.pred_model(output)
 
     def loss(self, pred, label):

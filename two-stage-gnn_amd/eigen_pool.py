@@ -323,6 +323,74 @@ def batch_from_dense(adj, batch_num_nodes, adj_pooled_list, batch_num_nodes_list
     return eb
 
 
+# ----------------------------------------------------------------------------- EigenBatches -> one EigenBatch, on the device
+def _concat_graphs(gs, nmax):
+    """block-diagonal packed GraphBatch of the graphs of several packed GraphBatches (sizes and nnz are host-side numbers: device-side
+    concatenations with a row offset on `col` and an entry offset on `rowptr`, no host synchronisation)"""
+    dev = gs[0].device
+    nnz = int(sum(q.nnz for q in gs))
+    weighted = any(q.val is not None for q in gs)
+    rps, cols, vals, e0, r0 = [], [], [], 0, 0
+    for q in gs:
+        rp = q.rowptr[:q.n_rows]
+        rps.append(rp + e0 if e0 else rp)
+        if q.nnz:
+            c = q.col[:q.nnz]
+            cols.append(c + r0 if r0 else c)
+            if weighted:
+                vals.append(q.val[:q.nnz] if q.val is not None else torch.ones(q.nnz, dtype=torch.float32, device=dev))
+        e0 += q.nnz
+        r0 += q.n_rows
+    rps.append(torch.full((nmax + 1,), nnz, dtype=torch.int32, device=dev))          # the last real row's end + the empty ghost rows
+    col = torch.cat(cols) if nnz else torch.zeros(1, dtype=torch.int32, device=dev)
+    val = (torch.cat(vals) if nnz else torch.zeros(1, dtype=torch.float32, device=dev)) if weighted else None
+    g = GraphBatch.from_csr(torch.cat(rps), col, val, np.concatenate([np.asarray(q.sizes, dtype=np.int64) for q in gs]), nmax,
+                            assume_symmetric=all(q.symmetric for q in gs))
+    g.nnz = nnz
+    return g
+
+
+def concat_batches(batches):
+    """One EigenBatch holding the graphs of several (e.g. cached one-graph batches -> a mini-batch), in order.  Everything is
+    concatenated on the device: rows and clusters of a later batch are offset by the rows before them, and since the bucket order is
+    per graph [unassigned rows, clusters ...] the bucket lists concatenate with a running offset.  The result equals ``collate`` /
+    ``batch_from_dense`` of all the graphs at once.  The batches must share nmax, the number of levels and of pooling matrices."""
+    batches = list(batches)
+    first = batches[0]
+    nmax, L = first.nmax, len(first.levels)
+    for eb in batches:
+        if eb.nmax != nmax or len(eb.levels) != L or (eb.final_coef is None) != (first.final_coef is None) or \
+                any(a.J != b.J for a, b in zip(eb.levels, first.levels)) or \
+                (eb.final_coef is not None and eb.final_coef.size(1) != first.final_coef.size(1)):
+            raise ValueError("concat_batches: the batches must share Nmax, the number of levels and of pooling matrices")
+    prev = [eb.g0 for eb in batches]
+    g0 = _concat_graphs(prev, nmax)
+    dev = g0.device
+    levels = []
+    for i in range(L):
+        lvs = [eb.levels[i] for eb in batches]
+        clus, coef, mem, bp, r0, c0 = [], [], [], [], 0, 0
+        for q, lv in zip(prev, lvs):
+            R, K = q.n_rows, lv.g.n_rows
+            c = lv.cluster_of[:R]
+            clus.append(torch.where(c >= 0, c + c0, c) if c0 else c)
+            coef.append(lv.coef[:R])
+            m = lv.members[:R]
+            mem.append(m + r0 if r0 else m)
+            b = lv.bptr[:K + q.B]                      # (K + B buckets: the closing entry is the next batch's first)
+            bp.append(b + r0 if r0 else b)
+            r0 += R
+            c0 += K
+        bp.append(torch.full((1,), r0, dtype=torch.int32, device=dev))
+        out = EigenLevel()
+        out.g, out.J = _concat_graphs([lv.g for lv in lvs], nmax), lvs[0].J
+        out.cluster_of, out.coef, out.members, out.bptr = torch.cat(clus), torch.cat(coef), torch.cat(mem), torch.cat(bp)
+        levels.append(out)
+        prev = [lv.g for lv in lvs]
+    fc = torch.cat([eb.final_coef[:q.n_rows] for eb, q in zip(batches, prev)]) if first.final_coef is not None else None
+    return EigenBatch(g0, levels, fc, nmax)
+
+
 # ----------------------------------------------------------------------------- the operator
 class _EigenPool(torch.autograd.Function):
     """(pooled rows, [readout of z]) or, final: (max(P^T z, 0) [B, J*C], [readout of z]); see tsgnn_eigen_pool_fwd_f32"""

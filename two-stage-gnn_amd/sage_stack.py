@@ -117,7 +117,9 @@ def _flush_readout(g, B, sn, sg, pending):
 # keeps the batch-norm statistics it would have alone, tripletnet.py:36-38): the slot batch-norm degenerates to a per-row layer norm,
 # so the two slot launches of a hidden layer are replaced by their row-local counterparts (tsgnn_row_ln_fwd_f32 forward,
 # tsgnn_row_post_bwd_f32 backward) and everything else of the stack — aggregation inside the products, the readout partials riding
-# in the next layer's launch, merged weight-gradient / input-gradient launches, one reduction for all layers — stays.  Selected by
+# in the next layer's launch, merged weight-gradient / input-gradient launches, one reduction for all layers — stays.  The node-feature
+# form (`nodes`) runs the same way: the normalised rows go straight into the layer's column block, and the backward is
+# tsgnn_row_post_nodes_bwd_f32 (the block's own gradient in place of the readout pair).  Selected by
 # the caller around the node's forward (`with per_graph_stats(True):`); the statistics without launches of their own (FUSED_BN)
 # are per slot across graphs and are not used in this mode.
 _PER_GRAPH = [False]
@@ -180,8 +182,8 @@ class _SageStack(torch.autograd.Function):
         last_ro_done = False
         bnf = None
         per_graph = ctx.per_graph = bool(_PER_GRAPH[0])
-        if per_graph and (nodes or head is not None):
-            raise NotImplementedError("per-graph statistics: the readout form of the stack only")
+        if per_graph and head is not None:
+            raise NotImplementedError("per-graph statistics: the readout and the node-feature form of the stack only")
         if (FUSED_BN and not per_graph and head is not None and not nodes and L >= 2 and g.n_ghost == g.nmax and sn == sg and sn <= 1024
                 and Fh == 128 and Fl == 128 and Ws[0].size(0) <= 128 and x.size(1) % 4 == 0 and MERGED_FWD and EPILOGUE_READOUT
                 and _gather_ok(g, x) and all(Ws[l].size(0) == 128 and Ws[l].stride(0) % 4 == 0 for l in range(1, L))
@@ -288,11 +290,12 @@ class _SageStack(torch.autograd.Function):
             if l < L - 1 and per_graph:
                 mean = torch.empty(R, dtype=torch.float32, device=dev)      # per ROW
                 rstd = torch.empty(R, dtype=torch.float32, device=dev)
-                y = torch.empty_like(v)
-                if l == 0:
+                y = torch.empty_like(v) if not nodes else cat[:, l * Fh:(l + 1) * Fh]      # (node form: straight into its column block)
+                if l == 0 and not nodes:
                     packed[:total].zero_()                    # (what the first slot_bn_fwd launch does on its way)
                 nat.call("row_ln_fwd_f32", v, v.stride(0), g.n_rows + sg, N, 1, mean, rstd, y, y.stride(0))
-                pending_ro = (y, pk)
+                if not nodes:
+                    pending_ro = (y, pk)
                 keep.append(y)
                 x = y
             elif l < L - 1:
@@ -448,6 +451,11 @@ class _SageStack(torch.autograd.Function):
                 red.add((ws0, nblk, K, N, dw, db))
                 grads[0], grads[1] = red.autograd_grad(dw), red.autograd_grad(db)
                 continue
+            elif ctx.per_graph and ctx.nodes:
+                # per-graph statistics, node output: the block's own gradient + row layer norm + ReLU + normalise backward, row by row
+                nat.call("row_post_nodes_bwd_f32", g.n_rows, g.n_rows + sg, v, v.stride(0), dxs, dxs.stride(0) if dxs is not None else 0,
+                         dnode, dnode.stride(0), 1 if ctx.nodes == 2 else 0, N, 0 if last else 1, 0 if last else 1, mean, rstd, rinv, du,
+                         du.stride(0))
             elif ctx.per_graph:
                 # per-graph statistics: readout winners + row layer norm + ReLU + normalise backward, row by row
                 nat.call("row_post_bwd_f32", g.row_graph, B, g.n_rows, g.n_rows + sg, v, v.stride(0), dxs,
