@@ -326,11 +326,15 @@ int tsgnn_gather_rowgemm_f32(const int* ell, int ell_w, const int* tail_ptr, con
  * associative, so the totals do not depend on the order the panels finish in — bitwise reproducible) and the filler block leaves
  * the ghost row's two numbers in ghost[0..1].  sums [2 * nslots], 16-byte aligned, zero before the launch; row_slot[r] < 0: row r
  * belongs to no graph (padding of a capacity-padded batch).  panel_units: row panels as in tsgnn_panel_blocks.  Consumer:
- * tsgnn_sage_layer_fwd_bn_f32. */
+ * tsgnn_sage_layer_fwd_bn_f32.
+ * pack_desc (nullable; HOST memory, 8-byte aligned, read before the call returns): [nsets <= 8, nsets x (w, ldw, K, N, kn, out)], the
+ * descriptor of tsgnn_sage_conv_pack_f32.  The images are written by extra workgroups at the end of this launch instead of a launch
+ * of their own: the w_img operands of the hidden layers' launches of the same step (tsgnn_sage_layer_fwd_bn_f32: kn = 1,
+ * tsgnn_sage_layer_bwd_f32: kn = 0), packed from the parameters that step uses.  NULL: no such workgroups. */
 int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* x, int64_t ldx, const float* b, int64_t ldb, const float* bias,
                                 float* c, int64_t ldc, float* rinv, float* zout, int64_t ldz, int64_t rows, int K, int N,
                                 int64_t fill_rows, const int* row_slot, unsigned long long* sums, float* ghost, int panel_units,
-                                tsgnn_stream_t stream);
+                                const int64_t* pack_desc, tsgnn_stream_t stream);
 /* tsgnn_sage_layer_fwd[_ro]_f32 for a layer whose INPUT's slot batch-norm has no launch of its own: x = the previous layer's
  * normalised pre-activations v, sums_in / ghost_in = what its statistics epilogue left, slot_count[n] = graphs with more than n
  * nodes.  Every row-panel block turns the sums into (mean, rstd) per slot — exact from the integers, ghost copies by their
@@ -340,14 +344,18 @@ int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, 
  * row_slot != NULL: this layer is followed by a batch-norm as well, its statistics go to sums_out / ghost_out (zero before);
  * packed_out != NULL: last layer, readout epilogue as in tsgnn_sage_layer_fwd_ro_f32 (not both).  ro_map (nullable): see
  * tsgnn_sage_layer_fwd_bn_plan; ignored unless ro_map_ch equals the chunk size the launch uses.  panel_units: row panels as in
- * tsgnn_panel_blocks. */
+ * tsgnn_panel_blocks.
+ * w_img (nullable; 16,384 floats, 16-byte aligned): the fragment-major image of w in the forward orientation (kn = 1 of
+ * tsgnn_sage_conv_pack_f32; in the training step the pack riders of tsgnn_gather_rowgemm_st_f32 write it from the parameters of that
+ * very step).  The row panels then take W from it, 1 KB per wave instruction straight into the matrix cores' operand registers,
+ * instead of staging w through LDS: the same product bit for bit.  NULL: w is staged. */
 int tsgnn_sage_layer_fwd_bn_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias,
                                 float* v, int64_t ldv, float* rinv, float* zout, int64_t ldz, int64_t rows, int K, int64_t fill_rows,
                                 const int* graph_ptr, const int* slot_count, int B, int nslots, int n_ghost, unsigned long long* packed,
                                 unsigned long long* packed_out, const int* row_graph, const unsigned long long* sums_in,
                                 const float* ghost_in, float* mean_out, float* rstd_out, const int* row_slot,
                                 unsigned long long* sums_out, float* ghost_out, const int* ro_map, int ro_map_ch, int panel_units,
-                                tsgnn_stream_t stream);
+                                const float* w_img, tsgnn_stream_t stream);
 /* HOST function: slots per readout block (64 / 128 / 256), row-panel blocks (filler included) and full 32-row panels ahead of the
  * units (0: plain panels) of that launch with the same panel_units — what a caller needs to build ro_map: a permutation of the
  * B * ceil(nslots / ro_ch) readout work items (graph * chunks + chunk) that puts the blocks scanning a graph on the XCD whose row
@@ -373,10 +381,11 @@ int tsgnn_sage_layer_fwd_ro_f32(const int* ell, int ell_w, const int* tail_ptr, 
  * gradient slabs of tsgnn_linear_wgrad_f32 (dw == NULL form: reduce ws later with tsgnn_wgrad_reduce_multi_f32; plan with
  * tsgnn_linear_wgrad_plan(rows, 128, 128, ...)) and dxs = (A du) w^T of tsgnn_gather_rowgemm_f32 (trans_b = 1, symmetric A).
  * A CU hosts one block of each grid, so the two run side by side instead of back to back.  panel_units: row panels as in
- * tsgnn_panel_blocks. */
+ * tsgnn_panel_blocks.  w_img (nullable, as in tsgnn_sage_layer_fwd_bn_f32): the image of w in the input-gradient orientation
+ * (kn = 0 of the pack: w is nn.Linear-like [n][k] for this product); NULL: w is staged through LDS. */
 int tsgnn_sage_layer_bwd_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* du, int64_t lddu, const float* w, int64_t ldw, float* dxs,
                              int64_t lddxs, const float* z, int64_t ldz, int64_t rows, int nslab, int64_t rows_per_slab,
-                             int64_t bias_only_rows, float* ws, int panel_units, tsgnn_stream_t stream);
+                             int64_t bias_only_rows, float* ws, int panel_units, const float* w_img, tsgnn_stream_t stream);
 /* backward of the row normalisation: du = rinv * (dv - v (v.dv)) */
 int tsgnn_l2norm_bwd_f32(const float* v, int64_t ldv, const float* dv, int64_t lddv, const float* rinv, float* du,
                          int64_t lddu, int64_t rows, int F, tsgnn_stream_t stream);

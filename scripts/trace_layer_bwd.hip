@@ -32,7 +32,7 @@ int main(int argc, char** argv) {
   int* ell; hipMalloc(&ell, R * 16 * 4); hipMemcpy(ell, hell.data(), R * 16 * 4, hipMemcpyHostToDevice);
   hipStream_t s; hipStreamCreate(&s);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-  auto run = [&]() { tsgnn_sage_layer_bwd_f32(ell, 16, nullptr, nullptr, du, N, w, N, dxs, K, z, K, R, nslab, rps, 500, ws, 1, s); };
+  auto run = [&]() { tsgnn_sage_layer_bwd_f32(ell, 16, nullptr, nullptr, du, N, w, N, dxs, K, z, K, R, nslab, rps, 500, ws, 1, nullptr, s); };
   for (int it = 0; it < 20; ++it) run();
   hipStreamSynchronize(s);
   hipEventRecord(e0, s);

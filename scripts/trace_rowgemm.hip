@@ -1,9 +1,19 @@
 // Developer harness: per-wave phase timeline of rowgemm_kernel (s_memtime stamps), built as
 //   hipcc --offload-arch=gfx950 -O3 -DTSGNN_TRACE scripts/trace_rowgemm.hip -o gpurun_out/trace_rowgemm
 // (add -DTSGNN_TRACE_WPB=8 for the gather variant: its row panels are 512-thread blocks, waves 4-7 = the second K group)
+//   trace_rowgemm [rows] [gather 0/1] [image 0/1]    image = 1 (with gather): the one-group gather body reading W from a fragment-major
+//   image (rowgemm_body.h BIMG) instead of staging it through LDS; same operands, same stamps
 #include "../two-stage-gnn_amd/csrc/rowgemm.hip"
 #include "trace_util.h"
 thread_local char tsgnn_kname_[160] = "";
+thread_local PullRider tsgnn_pull_rider_{};          // (defined by ingest.hip in the library)
+
+template <bool TRANS_B>
+__global__ __launch_bounds__(256) void trace_img_kernel(RowGemmArgs g) {
+  extern __shared__ __attribute__((aligned(16))) float smem[];
+  rowgemm_body<4, TRANS_B, true, 1, false, false, false, false, true>(g, smem, blockIdx.x);
+}
+__global__ __launch_bounds__(256) void trace_pack_kernel(PackSet s) { sage_conv_pack_body(s, (int)blockIdx.x * 256 + (int)threadIdx.x); }
 #include <cstdio>
 #include <vector>
 #include <algorithm>
@@ -30,11 +40,22 @@ int main(int argc, char** argv) {
   int* ell; hipMalloc(&ell, R * 16 * 4); hipMemcpy(ell, hell.data(), R * 16 * 4, hipMemcpyHostToDevice);
   float* zout; hipMalloc(&zout, R * K * 4);
   const bool gather = argc > 2 && atoi(argv[2]) != 0;
+  const bool image = gather && argc > 3 && atoi(argv[3]) != 0;
+  float4* img[2];                                     // [0]: b as B[K][N] (kn = 1), [1]: b as W[N][K] (kn = 0)
+  for (int t = 0; t < 2; ++t) hipMalloc(&img[t], PACK_SET_ENTRIES * sizeof(float4));
   hipStream_t s; hipStreamCreate(&s);
   hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
   for (int trans = 0; trans < 2; ++trans) {
+    if (image) trace_pack_kernel<<<PACK_SET_ENTRIES / 256, 256, 0, s>>>(PackSet{b, N, K, N, trans ? 0 : 1, img[trans]});
     auto run = [&]() {
-      if (gather) tsgnn_gather_rowgemm_f32(ell, 16, nullptr, nullptr, a, K, b, N, trans, trans ? nullptr : bias, c, N, trans ? nullptr : rinv,
+      if (image) {
+        RowGemmArgs g{a, K, b, N, trans ? nullptr : bias, c, N, trans ? nullptr : rinv, R, K, N, trans ? 0 : 1, 0, ell, 16, trans ? nullptr : zout, K,
+                      nullptr, nullptr};
+        g.b_img = img[trans];
+        const unsigned nblk = (unsigned)((R + 31) / 32);
+        if (trans) trace_img_kernel<true><<<nblk, 256, rowgemm_lds_bytes<4, true, true, 1, false, true>(), s>>>(g);
+        else trace_img_kernel<false><<<nblk, 256, rowgemm_lds_bytes<4, false, true, 1, false, true>(), s>>>(g);
+      } else if (gather) tsgnn_gather_rowgemm_f32(ell, 16, nullptr, nullptr, a, K, b, N, trans, trans ? nullptr : bias, c, N, trans ? nullptr : rinv,
                                            trans ? nullptr : zout, K, R, K, N, trans ? 0 : 1, 0, s);
       else tsgnn_rowgemm_f32(a, K, b, N, trans, trans ? nullptr : bias, c, N, trans ? nullptr : rinv, R, K, N, trans ? 0 : 1, 0, s);
     };

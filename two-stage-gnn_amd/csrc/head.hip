@@ -10,6 +10,8 @@
 namespace {
 
 __device__ __forceinline__ float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+// r[q] for a q that is only known at run time (0 <= q < 4), by selects: indexing the array itself puts it into a private segment
+__device__ __forceinline__ float pick4(const float (&r)[4], int q) { return q == 0 ? r[0] : q == 1 ? r[1] : q == 2 ? r[2] : r[3]; }
 
 // block b: vec[b,:] = W1 out[b,:] + b1 ; y[b,:] = W2 vec[b,:] + b2        (W1 [E,P], W2 [C,E] row-major = nn.Linear.weight)
 constexpr int HW = 16;   // waves per row block (1024 threads): one batch of 8 weight rows per wave covers E = 128
@@ -573,7 +575,7 @@ __device__ __forceinline__ void head2_du_role(const DuArgs& a, float* smem, cons
   // ---- dvt row of graph b, then the segment of dout[b, :]   (expressions and order of the row blocks)
   for (int j = tid; j < E; j += NTH) {
     float acc = j == tid ? dv0 : (dvec ? dvec[(int64_t)b * E + j] : 0.f);
-    for (int q = 0; q < C; ++q) acc = fmaf(dy[(int64_t)b * C + q], (j == tid && q < 4) ? w2r[q] : w2[(int64_t)q * E + j], acc);
+    for (int q = 0; q < C; ++q) acc = fmaf(dy[(int64_t)b * C + q], (j == tid && q < 4) ? pick4(w2r, q) : w2[(int64_t)q * E + j], acc);
     ds[j] = acc;
   }
   __syncthreads();
@@ -738,7 +740,7 @@ __global__ __launch_bounds__(64 * HW) void head2_bwd2_kernel(const float* __rest
     }
     for (int j = tid; j < E; j += NTH) {                 // dvt row (same expression and order as the weight blocks)
       float acc = j == tid ? dv0 : (dvec ? dvec[(int64_t)b * E + j] : 0.f);
-      for (int c = 0; c < C; ++c) acc = fmaf(dy[(int64_t)b * C + c], (j == tid && c < 4) ? w2r[c] : w2[(int64_t)c * E + j], acc);
+      for (int c = 0; c < C; ++c) acc = fmaf(dy[(int64_t)b * C + c], (j == tid && c < 4) ? pick4(w2r, c) : w2[(int64_t)c * E + j], acc);
       ds[j] = acc;
     }
     __syncthreads();
@@ -803,7 +805,7 @@ __global__ __launch_bounds__(64 * HW) void head2_bwd2_kernel(const float* __rest
       float a = 0.f;
       if (jj < E) {
         a = i == tid ? dv0 : (dvec ? dvec[(int64_t)bb * E + jj] : 0.f);
-        for (int c = 0; c < C; ++c) a = fmaf(dy[(int64_t)bb * C + c], (i == tid && c < 4) ? w2r[c] : w2[(int64_t)c * E + jj], a);
+        for (int c = 0; c < C; ++c) a = fmaf(dy[(int64_t)bb * C + c], (i == tid && c < 4) ? pick4(w2r, c) : w2[(int64_t)c * E + jj], a);
       }
       dvs[i] = a;
     }

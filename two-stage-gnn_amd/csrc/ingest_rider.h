@@ -40,13 +40,12 @@ static inline void disarm_pull_rider() { tsgnn_pull_rider_.blocks = 0; }
 // workgroup b of p.blocks: no dependence on the batch's header, so every thread's 16-byte loads are in flight at once
 __device__ __forceinline__ void pull_rider_body(const PullRider& p, unsigned b) {
   const long long gtid = (long long)b * blockDim.x + threadIdx.x, gsize = (long long)p.blocks * blockDim.x;
-  int4 v[4];
+  // four named registers, not an array: the array was given a private segment (80 bytes a lane, three stores and no load), and every
+  // carrier kernel was dispatched with one although the resident step never runs this loop
   long long i = p.lo + gtid;
   for (; i + 3 * gsize < p.n4; i += 4 * gsize) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) v[u] = p.host[i + u * gsize];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) p.mirror[i + u * gsize] = v[u];
+    const int4 v0 = p.host[i], v1 = p.host[i + gsize], v2 = p.host[i + 2 * gsize], v3 = p.host[i + 3 * gsize];
+    p.mirror[i] = v0; p.mirror[i + gsize] = v1; p.mirror[i + 2 * gsize] = v2; p.mirror[i + 3 * gsize] = v3;
   }
   for (; i < p.n4; i += gsize) p.mirror[i] = p.host[i];
 }

@@ -34,13 +34,14 @@ __global__ __launch_bounds__(256) void sage_layer_fwd_kernel(RowGemmArgs ga, Slo
 // The same launch for a layer whose INPUT's slot batch-norm was not materialised (rowgemm_body.h BNIN / STATS, readout_body.h):
 // x = the previous layer's v; the gather and the readout partial form y = BN(relu(v)) on the fly from the previous layer's integer
 // sums.  ST: this layer is followed by a batch-norm too (statistics epilogue); RO: it is the last one (readout epilogue).
-template <bool RO, bool ST, bool UNITS = false>
+// BIMG: W arrives as a fragment-major image (ga.b_img, rowgemm_body.h).
+template <bool RO, bool ST, bool UNITS = false, bool BIMG = false>
 __global__ __launch_bounds__(256, 2) void sage_layer_fwd_bn_kernel(RowGemmArgs ga, SlotArgs sa, BnReadArgs bn, unsigned n_gemm, unsigned ro_gx,
                                                                 int ro_ch, int F4, unsigned long long* __restrict__ packed, unsigned n_main,
                                                                 PullRider pr, const int* __restrict__ ro_map) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if (blockIdx.x < n_gemm) {
-    rowgemm_body<4, false, true, 1, RO, true, ST, UNITS>(ga, smem, blockIdx.x);
+    rowgemm_body<4, false, true, 1, RO, true, ST, UNITS, BIMG>(ga, smem, blockIdx.x);
   } else if (blockIdx.x < n_main) {
     // ro_map (nullable): which (graph, chunk) this block scans — chosen on the host so that the block sits on the XCD whose row
     // panels gather that graph's rows (blocks b, b + 8, ... share an XCD): the rows are in that L2 already instead of being
@@ -79,14 +80,17 @@ int tsgnn_sage_layer_fwd_bn_plan(int64_t rows, int64_t fill_rows, int B, int nsl
  * row_slot != NULL: this layer is followed by a batch-norm as well: its statistics go to sums_out / ghost_out (zero before).
  * packed_out != NULL: last layer, readout epilogue (as tsgnn_sage_layer_fwd_ro_f32).
  * ro_map (nullable, B * ceil(nslots / ro_map_ch) ints, a permutation): readout block r scans work item ro_map[r] = graph * chunks + chunk;
- * tsgnn_sage_layer_fwd_bn_plan tells the chunk size the launch will use. */
+ * tsgnn_sage_layer_fwd_bn_plan tells the chunk size the launch will use.
+ * w_img (nullable, 16-byte aligned, 16,384 floats): the fragment-major image of w in the forward orientation (kn = 1 of tsgnn_sage_conv_pack_f32;
+ * written by the pack riders of tsgnn_gather_rowgemm_st_f32 earlier in the same step).  The row panels then read W from it instead of
+ * staging w through LDS: the same product bit for bit.  NULL: w is staged. */
 int tsgnn_sage_layer_fwd_bn_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* x, int64_t ldx, const float* w, int64_t ldw, const float* bias,
                                 float* v, int64_t ldv, float* rinv, float* zout, int64_t ldz, int64_t rows, int K, int64_t fill_rows,
                                 const int* graph_ptr, const int* slot_count, int B, int nslots, int n_ghost, unsigned long long* packed,
                                 unsigned long long* packed_out, const int* row_graph, const unsigned long long* sums_in,
                                 const float* ghost_in, float* mean_out, float* rstd_out, const int* row_slot,
                                 unsigned long long* sums_out, float* ghost_out, const int* ro_map, int ro_map_ch, int panel_units,
-                                tsgnn_stream_t stream) {
+                                const float* w_img, tsgnn_stream_t stream) {
   if (!ell || !x || !w || !v || !rinv || !graph_ptr || !slot_count || !packed || !sums_in || !ghost_in || !mean_out || !rstd_out ||
       rows <= 0 || fill_rows < 0 || K <= 0 || B <= 0 || nslots <= 0 || (n_ghost != 0 && n_ghost != nslots) || (packed_out && !row_graph) ||
       (row_slot && (!sums_out || !ghost_out)))
@@ -94,7 +98,7 @@ int tsgnn_sage_layer_fwd_bn_f32(const int* ell, int ell_w, const int* tail_ptr, 
   if (ell_w != 4 && ell_w != 8 && ell_w != 16) return TSGNN_EUNSUPPORTED;
   const uintptr_t al = reinterpret_cast<uintptr_t>(ell) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) |
                        reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(zout) | reinterpret_cast<uintptr_t>(bias) |
-                       reinterpret_cast<uintptr_t>(sums_in) | reinterpret_cast<uintptr_t>(sums_out);
+                       reinterpret_cast<uintptr_t>(sums_in) | reinterpret_cast<uintptr_t>(sums_out) | reinterpret_cast<uintptr_t>(w_img);
   if ((al & 15) || K != 128 || (ldx % 4) || (ldw % 4) || (ldv % 4) || (zout && (ldz % 4 || ldz < K)) || ldx < K || ldw < 128 || ldv < 128 ||
       nslots > BN_TAB || rows >= (1 << 20) || n_ghost == 0 || (packed_out && row_slot))
     return TSGNN_EUNSUPPORTED;
@@ -103,6 +107,7 @@ int tsgnn_sage_layer_fwd_bn_f32(const int* ell, int ell_w, const int* tail_ptr, 
   RowGemmArgs ga{x, ldx, w, ldw, bias, v, ldv, rinv, rows, K, 128, 1, fill_rows, ell, ell_w, zout, ldz, tail_ptr, tail_col,
                  packed_out, graph_ptr, row_graph, B, nslots, n_ghost};
   ga.st_row_slot = row_slot; ga.st_sums = sums_out; ga.st_ghost = ghost_out;
+  ga.b_img = reinterpret_cast<const float4*>(w_img);
   ga.bn_sums = sums_in; ga.bn_ghost = ghost_in; ga.bn_slot_count = slot_count; ga.bn_B = B; ga.bn_nslots = nslots; ga.bn_F = K;
   SlotArgs sa{graph_ptr, slot_count, B, nslots, rows, n_ghost};
   BnReadArgs bn{sums_in, ghost_in, K, mean_out, rstd_out};
@@ -114,16 +119,18 @@ int tsgnn_sage_layer_fwd_bn_f32(const int* ell, int ell_w, const int* tail_ptr, 
   while (ro_ch < 256 && n_gemm + (unsigned)((nslots + ro_ch - 1) / ro_ch) * (unsigned)B > 2u * (unsigned)ncu) ro_ch *= 2;
   const unsigned ro_gx = (unsigned)((nslots + ro_ch - 1) / ro_ch);
   if (ro_map && ro_map_ch != ro_ch) ro_map = nullptr;      // (the map was built for another chunk size: plain order)
-  size_t lds = rowgemm_lds_bytes<4, false, true, 1, true>();
+  size_t lds = w_img ? rowgemm_lds_bytes<4, false, true, 1, true, true>() : rowgemm_lds_bytes<4, false, true, 1, true>();
   const size_t lro = 8 * 128 * sizeof(unsigned long long) + 256 * sizeof(float2);
   if (lds < lro) lds = lro;
   const unsigned n_main = n_gemm + ro_gx * (unsigned)B;
   const PullRider pr = take_pull_rider();
   const bool units = ga.unit == 8 || ga.unit == 16;     // (rows beyond one panel per CU as 16- / 8-row units: the UNITS build of the kernels)
-#define TSGNN_FWD_BN(RO_, ST_)                                                                                                              \
-  do {                                                                                                                                      \
-    if (units) sage_layer_fwd_bn_kernel<RO_, ST_, true><<<n_main + pr.blocks, 256, lds, stream>>>(ga, sa, bn, n_gemm, ro_gx, ro_ch, K / 4, packed, n_main, pr, ro_map); \
-    else sage_layer_fwd_bn_kernel<RO_, ST_><<<n_main + pr.blocks, 256, lds, stream>>>(ga, sa, bn, n_gemm, ro_gx, ro_ch, K / 4, packed, n_main, pr, ro_map);             \
+#define TSGNN_FWD_BN_(RO_, ST_, UN_, IM_) \
+  sage_layer_fwd_bn_kernel<RO_, ST_, UN_, IM_><<<n_main + pr.blocks, 256, lds, stream>>>(ga, sa, bn, n_gemm, ro_gx, ro_ch, K / 4, packed, n_main, pr, ro_map)
+#define TSGNN_FWD_BN(RO_, ST_)                                                                  \
+  do {                                                                                          \
+    if (units) { if (w_img) TSGNN_FWD_BN_(RO_, ST_, true, true); else TSGNN_FWD_BN_(RO_, ST_, true, false); }   \
+    else { if (w_img) TSGNN_FWD_BN_(RO_, ST_, false, true); else TSGNN_FWD_BN_(RO_, ST_, false, false); }       \
   } while (0)
   if (packed_out) {
     TSGNN_KNAME("sage_layer_fwd_bn_kernel<true,false,%s>", units ? "true" : "false");
@@ -136,6 +143,7 @@ int tsgnn_sage_layer_fwd_bn_f32(const int* ell, int ell_w, const int* tail_ptr, 
     TSGNN_FWD_BN(false, false);
   }
 #undef TSGNN_FWD_BN
+#undef TSGNN_FWD_BN_
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }

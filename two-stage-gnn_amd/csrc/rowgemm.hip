@@ -20,6 +20,7 @@
 #include <cstdlib>
 #include "rowgemm_body.h"
 #include "ingest_rider.h"
+#include "pack_body.h"
 #include "rowgemm_big_body.h"
 
 namespace {
@@ -48,16 +49,22 @@ __global__ __launch_bounds__(512) void rowgemm_gather_ks2_kernel(RowGemmArgs g) 
 
 // the same two kernels with the statistics epilogue (rowgemm_body.h, STATS): the layer in front of a slot batch-norm that has no
 // launch of its own (tsgnn_gather_rowgemm_st_f32)
+// The launch's LAST workgroups are passengers, two kinds side by side in one grid: [nblk, nblk + pk.blocks) write the fragment-major
+// images of the hidden layers' weights (pack_body.h; the operand of the later launches of the same step), the workgroups behind them
+// carry a share of the NEXT mini-batch's staging buffer -> its mirror (ingest_rider.h).
+__device__ __forceinline__ void st_passengers(const PackRider& pk, const PullRider& pr, unsigned b) {
+  if (b < pk.blocks) pack_rider_body(pk, b);
+  else pull_rider_body(pr, b - pk.blocks);
+}
 template <bool UNITS>
-__global__ __launch_bounds__(256) void rowgemm_gather_st_kernel(RowGemmArgs g, PullRider pr, unsigned nblk) {
+__global__ __launch_bounds__(256) void rowgemm_gather_st_kernel(RowGemmArgs g, PullRider pr, unsigned nblk, PackRider pk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  if (blockIdx.x >= nblk) { pull_rider_body(pr, blockIdx.x - nblk); return; }    // passengers, as below
+  if (blockIdx.x >= nblk) { st_passengers(pk, pr, blockIdx.x - nblk); return; }
   rowgemm_body<4, false, true, 1, false, false, true, UNITS>(g, smem, blockIdx.x);
 }
-// pr: passengers (csrc/ingest_rider.h) — a share of the NEXT mini-batch's staging buffer -> its mirror as the launch's last workgroups
-__global__ __launch_bounds__(512) void rowgemm_gather_ks2_st_kernel(RowGemmArgs g, PullRider pr, unsigned nblk) {
+__global__ __launch_bounds__(512) void rowgemm_gather_ks2_st_kernel(RowGemmArgs g, PullRider pr, unsigned nblk, PackRider pk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  if (blockIdx.x >= nblk) { pull_rider_body(pr, blockIdx.x - nblk); return; }    // (the launch's LAST workgroups)
+  if (blockIdx.x >= nblk) { st_passengers(pk, pr, blockIdx.x - nblk); return; }
   rowgemm_body<4, false, true, 2, false, false, true>(g, smem, blockIdx.x);
 }
 
@@ -254,11 +261,13 @@ int tsgnn_rowgemm_f32(const float* a, int64_t lda, const float* b, int64_t ldb, 
  * (apply_bn, encoders.py:134-138) WITHOUT a launch for it: the epilogue adds every real row's (sum_f relu(v), sum_f relu(v)^2) to
  * sums[2 * row_slot[r]] as 64-bit fixed-point integers (2^-40 units; order-independent, so bitwise reproducible) and the filler
  * block leaves the ghost row's two numbers in ghost[0..1].  sums: zero before the launch.  row_slot[r] < 0: row r belongs to no
- * graph (padding of a capacity-padded batch).  The consumer is tsgnn_sage_layer_fwd_bn_f32. */
+ * graph (padding of a capacity-padded batch).  The consumer is tsgnn_sage_layer_fwd_bn_f32.
+ * pack_desc (nullable, HOST memory, read before the call returns): [nsets <= 8, nsets x (w, ldw, K, N, kn, out)] as tsgnn_sage_conv_pack_f32
+ * takes it: the images are written by extra workgroups of this launch (the hidden layers' w_img operands of the same step). */
 int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* x, int64_t ldx, const float* b, int64_t ldb, const float* bias,
                                 float* c, int64_t ldc, float* rinv, float* zout, int64_t ldz, int64_t rows, int K, int N,
                                 int64_t fill_rows, const int* row_slot, unsigned long long* sums, float* ghost, int panel_units,
-                                tsgnn_stream_t stream) {
+                                const int64_t* pack_desc, tsgnn_stream_t stream) {
   if (!ell || !x || !b || !c || !row_slot || !sums || !ghost || rows <= 0 || fill_rows < 0 || K <= 0 || N <= 0 || ldx < K || ldc < N)
     return TSGNN_EINVAL;
   if (ell_w != 4 && ell_w != 8 && ell_w != 16) return TSGNN_EUNSUPPORTED;
@@ -267,6 +276,17 @@ int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, 
     return TSGNN_EUNSUPPORTED;
   if (zout && ((ldz % 4) || ldz < K || (reinterpret_cast<uintptr_t>(zout) & 15))) return TSGNN_EUNSUPPORTED;
   if ((N % 4) || (ldc % 4) || (reinterpret_cast<uintptr_t>(c) & 15) || (bias && (reinterpret_cast<uintptr_t>(bias) & 15))) return TSGNN_EUNSUPPORTED;
+  PackRider pk{};
+  if (pack_desc) {
+    if (reinterpret_cast<uintptr_t>(pack_desc) & 7) return TSGNN_EINVAL;
+    const int nsets = (int)pack_desc[0];
+    if (nsets <= 0 || nsets > PACK_RIDER_SETS) return TSGNN_EINVAL;
+    for (int t = 0; t < nsets; ++t) {
+      const int rc = pack_set_from_desc(pack_desc + 1 + 6 * t, pk.s[t]);
+      if (rc != TSGNN_OK) return rc;
+    }
+    pk.blocks = (unsigned)nsets;                           // (images; turned into workgroups of the carrier's size below)
+  }
   if ((tail_ptr == nullptr) != (tail_col == nullptr)) return TSGNN_EINVAL;
   RowGemmArgs g{x, ldx, b, ldb, bias, c, ldc, rinv, rows, K, N, 1, fill_rows, ell, ell_w, zout, ldz, tail_ptr, tail_col};
   g.st_row_slot = row_slot; g.st_sums = sums; g.st_ghost = ghost;
@@ -282,13 +302,15 @@ int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, 
       attr = true;
     }
     const PullRider pr = take_pull_rider(512);             // (blocks = 0 unless tsgnn_ingest_arm_pull_rider[_parts] armed one on this thread)
+    pk.blocks *= PACK_SET_ENTRIES / 512;
     TSGNN_KNAME("rowgemm_gather_ks2_st_kernel");
-    rowgemm_gather_ks2_st_kernel<<<nblk + pr.blocks, 512, lds2, stream>>>(g, pr, nblk);
+    rowgemm_gather_ks2_st_kernel<<<nblk + pk.blocks + pr.blocks, 512, lds2, stream>>>(g, pr, nblk, pk);
   } else {
     const PullRider pr = take_pull_rider(256);
+    pk.blocks *= PACK_SET_ENTRIES / 256;
     TSGNN_KNAME("rowgemm_gather_st_kernel<%s>", (g.unit == 8 || g.unit == 16) ? "true" : "false");
-    if (g.unit == 8 || g.unit == 16) rowgemm_gather_st_kernel<true><<<nblk + pr.blocks, 256, rowgemm_lds_bytes<4, false, true>(), stream>>>(g, pr, nblk);
-    else rowgemm_gather_st_kernel<false><<<nblk + pr.blocks, 256, rowgemm_lds_bytes<4, false, true>(), stream>>>(g, pr, nblk);
+    if (g.unit == 8 || g.unit == 16) rowgemm_gather_st_kernel<true><<<nblk + pk.blocks + pr.blocks, 256, rowgemm_lds_bytes<4, false, true>(), stream>>>(g, pr, nblk, pk);
+    else rowgemm_gather_st_kernel<false><<<nblk + pk.blocks + pr.blocks, 256, rowgemm_lds_bytes<4, false, true>(), stream>>>(g, pr, nblk, pk);
   }
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;

@@ -50,6 +50,9 @@ struct RowGemmArgs {
   // (or 8-row) units the busiest CU gathers 40-48 rows instead of 64 (panel_split() below).
   int n_full;
   int unit;                           // rows per unit of the blocks behind the full panels (16 or 8: panel_unit_rows())
+  // BIMG variant: the B operand as a fragment-major image [4 waves][16 steps][64 lanes] of float4 (what sage_conv_pack_body writes:
+  // entry (wv * 16 + u) * 64 + lane = B[k = 8u + 4h .. + 3][n = 32 wv + i], lane = 32 h + i), packed per orientation
+  const float4* b_img;
 };
 
 // blocks of a panel launch of `rows` rows on `ncu` compute units: n_full (0: plain 32-row panels) and the total number of panel blocks
@@ -97,12 +100,18 @@ constexpr int LDA_F = 128;            // row stride of the gathered full-K A pan
 // epilogue), so a CU idles through every memory wait; with two wave groups the gather prologue is shared by twice the
 // lanes (half the rows per lane), each group runs half of the K chunks on its own LDS stages while the other group's
 // waits are covered, and group 1 hands its accumulators to group 0 through LDS before the (unchanged) epilogue.
-template <int NT, bool TRANS_B, bool GATHER, int KS = 1, bool READOUT = false, bool BNIN = false, bool STATS = false, bool UNITS = false>
+// BIMG (GATHER, KS = 1, NT = 4, K = N = 128): B never touches LDS.  Each wave fills the MFMA B operands of its 32 output columns from
+// g.b_img with sixteen 1 KB-contiguous 16-byte loads, asked for AFTER the neighbour rows (a wave's loads return in issue order: W is
+// not needed before the gather has ended); no register staging, no LDS stage, no barrier in the K loop.  The MFMA chain sees the
+// operands of the staged path in the same order, so the product is the same bit for bit.
+template <int NT, bool TRANS_B, bool GATHER, int KS = 1, bool READOUT = false, bool BNIN = false, bool STATS = false, bool UNITS = false,
+          bool BIMG = false>
 __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_all, unsigned bid) {
   static_assert(KS == 1 || (KS == 2 && GATHER && NT <= 4), "the split-K variant is built for the gather kernel, widths <= 128");
   static_assert(!READOUT || (NT <= 4 && KS == 1), "the readout epilogue is built for one column tile per wave");
   static_assert(!BNIN || (GATHER && KS == 1), "batch-norm on the fly lives in the gather prologue of the one-group kernel");
   static_assert(!STATS || NT <= 4, "the statistics epilogue is built for one column tile per wave");
+  static_assert(!BIMG || (GATHER && KS == 1 && NT == 4), "the image variant is built for the one-group gather kernel at K = N = 128");
   constexpr int NP = 32 * NT;
   constexpr int TPW = (NT + 3) / 4;
   constexpr int BV = NT;                               // float4 of B per thread per chunk (KC * NP / 1024)
@@ -117,12 +126,13 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
   const int Kc = KS == 1 ? g.K : ((g.K + 2 * KC - 1) / (2 * KC)) * KC;
   const int kb = grp * Kc;
   const int Kv = KS == 1 ? g.K : min(g.K - kb, Kc);
-  constexpr int GRP = (KS == 2 && 2 * STAGE < 4096 + 256) ? 4096 + 256 : 2 * STAGE;   // LDS floats per wave group
+  // LDS floats per wave group (BIMG: no stages, only what the epilogue and the filler block borrow from them: redq, fred)
+  constexpr int GRP = BIMG ? 256 : (KS == 2 && 2 * STAGE < 4096 + 256) ? 4096 + 256 : 2 * STAGE;
   float* smem = smem_all + grp * GRP;                    // this group's two stages
   // common to the block: the gathered panel, and 256 floats of epilogue scratch (KS = 2: inside group 1's idle stages,
   // after the accumulator exchange buffer)
   float* Apanel = smem_all + KS * GRP + (KS == 2 ? 0 : 256);
-  float* scratch = KS == 2 ? smem_all + GRP + 4096 : smem_all + 2 * STAGE;
+  float* scratch = KS == 2 ? smem_all + GRP + 4096 : smem_all + GRP;
   // XCD-aware panel order: blocks b, b+8, ... share an XCD (and its L2); give each XCD one contiguous run of panels so
   // that the neighbour rows gathered by adjacent panels (same graph) are fetched into one L2 only.  The filler block
   // (last) keeps its index.
@@ -296,6 +306,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
                               : *reinterpret_cast<const float4*>(As + i * lda_s + 8 * u + 4 * h);
       af[4 * u] = v.x; af[4 * u + 1] = v.y; af[4 * u + 2] = v.z; af[4 * u + 3] = v.w;
     }
+    if constexpr (BIMG) return;                         // (the B operands come from the image)
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
       const int tile = wid + 4 * t;
@@ -364,9 +375,20 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
   if constexpr (STATS) {
     if (g.st_sums && wid == 0 && grp == 0 && lane < 32 && (m0 + lane) < rows_hi) st_slot = g.st_row_slot[m0 + lane];
   }
+  if constexpr (!BIMG) {
 #pragma unroll
-  for (int c = 0; c < NS; ++c)
-    if (c == 0 || c * KC < Kc) fetch(st[c], c * KC);
+    for (int c = 0; c < NS; ++c)
+      if (c == 0 || c * KC < Kc) fetch(st[c], c * KC);
+  }
+  float bq[BIMG ? 4 * KC / 2 : 1];                     // BIMG: the wave's B operands of all four chunks (chunk c, step j: bq[16 c + j])
+  auto img_fetch = [&](int u0) {                       // eight steps (two chunks) of the image
+    const float4* img = g.b_img + (wid * 16 + u0) * 64 + lane;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+      const float4 v = img[u * 64];
+      bq[4 * (u0 + u)] = v.x; bq[4 * (u0 + u) + 1] = v.y; bq[4 * (u0 + u) + 2] = v.z; bq[4 * (u0 + u) + 3] = v.w;
+    }
+  };
   if (GATHER) {
     // A panel = aggregated rows.  Row-major like the stand-alone aggregation kernel: 32 lanes per row (one float4 column
     // each), 8 rows per pass, 4 passes; the first GN neighbour rows of all four passes are in flight together
@@ -396,6 +418,11 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
         nbv[p][k] = make_float4(0.f, 0.f, 0.f, 0.f);
         if (colok && ids[p][k] >= 0) nbv[p][k] = ldg4(g.a + (int64_t)(BNIN ? (ids[p][k] & 0xFFFFF) : ids[p][k]) * g.lda + 4 * c4);
       }
+    if constexpr (BIMG) {                              // chunks 0 and 1 behind the rows
+      __builtin_amdgcn_sched_barrier(0);
+      img_fetch(0);
+      __builtin_amdgcn_sched_barrier(0);
+    }
     if constexpr (BNIN) {
       __syncthreads();                                 // the table of (rstd, mean * rstd) is complete
       // y = (relu(v) - mean) rstd = fma(relu(v), rstd, -mean rstd): one max + one fma per element
@@ -462,6 +489,11 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
       }
       if (g.zout && colok && row < rows_hi) st_out(reinterpret_cast<float4*>(g.zout + row * g.ldz + 4 * c4), va);
     }
+    if constexpr (BIMG) {                              // chunks 2 and 3: the neighbour rows' registers are free, and the requests
+      __builtin_amdgcn_sched_barrier(0);               // land under the first two chunks' MFMAs
+      img_fetch(8);
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
   float bias_v[TPW];                                   // fetched now, used in the epilogue
 #pragma unroll
@@ -470,13 +502,28 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
     bias_v[t] = (g.bias && (wid + 4 * t) < NT && cn < g.N) ? g.bias[cn] : 0.f;
   }
   TR(1);
-  commit(st[0], smem);
-  if (KC < Kc) commit(st[1], smem + STAGE);
+  if constexpr (!BIMG) {
+    commit(st[0], smem);
+    if (KC < Kc) commit(st[1], smem + STAGE);
+  }
   __syncthreads();
   TR(2);
   float fa[2][KC / 2], fb[2][TPW][KC / 2];
   frags(smem, 0, fa[0], fb[0]);
-  if (NS == 2) {
+  if constexpr (BIMG) {
+    // K = 128: four chunks, A fragments one chunk ahead out of the gathered panel, B operands in registers; nothing to synchronise
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      if (c < 3) frags(smem, (c + 1) * KC, fa[(c + 1) & 1], fb[0]);
+      __builtin_amdgcn_sched_barrier(0);               // the scheduler would sink the LDS reads to their uses
+#pragma unroll
+      for (int j = 0; j < KC / 2; ++j) acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c & 1][j], bq[16 * c + j], acc[0], 0, 0, 0);
+      __builtin_amdgcn_sched_barrier(0);
+      TR(3 + 2 * c);
+      TR(4 + 2 * c);
+    }
+  }
+  if (NS == 2 && !BIMG) {
     if (2 * KC < Kc) fetch(st[0], 2 * KC);
     if (3 * KC < Kc) fetch(st[1], 3 * KC);
   }
@@ -506,7 +553,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
     if (Kc > 2 * KC) __syncthreads();                  // stage reuse only exists beyond two chunks (both were committed before
     TR(4 + 2 * min(c, 3));                             // the loop): without it the two K groups of a panel run uncoupled
   };
-  for (int c = 0; c * KC < Kc; c += 4) {
+  for (int c = 0; !BIMG && c * KC < Kc; c += 4) {
     body(std::integral_constant<int, 0>{}, c);
     if ((c + 1) * KC < Kc) body(std::integral_constant<int, 1>{}, c + 1);
     if ((c + 2) * KC < Kc) body(std::integral_constant<int, 2>{}, c + 2);
@@ -648,10 +695,10 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
 }
 
 
-template <int NT, bool TRANS_B, bool GATHER, int KS = 1, bool BNIN = false>
+template <int NT, bool TRANS_B, bool GATHER, int KS = 1, bool BNIN = false, bool BIMG = false>
 constexpr size_t rowgemm_lds_bytes() {
   constexpr int NP = 32 * NT;
-  constexpr int STAGE2 = 2 * ((GATHER ? 0 : 32 * LDA_S) + (TRANS_B ? NP * LDA_S : KC * NP));
+  constexpr int STAGE2 = BIMG ? 256 : 2 * ((GATHER ? 0 : 32 * LDA_S) + (TRANS_B ? NP * LDA_S : KC * NP));
   constexpr int GRP = (KS == 2 && STAGE2 < 4096 + 256) ? 4096 + 256 : STAGE2;
   return sizeof(float) * (KS * GRP + (KS == 2 ? 0 : 128 + 4 * 32) + (GATHER ? 32 * LDA_F : 0) + (BNIN ? 2 * BN_TAB : 0));
 }

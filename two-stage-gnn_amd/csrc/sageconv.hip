@@ -10,6 +10,7 @@
 #include "common.h"
 #include "../../include/tsgnn.h"
 #include "sageconv_body.h"
+#include "pack_body.h"
 #include "tn_rows_body.h"
 
 namespace {
@@ -87,28 +88,11 @@ __global__ __launch_bounds__(128) void sage_readout_decode_kernel(unsigned long 
   }
 }
 
-// ---- fragment-major copies of the weights (the B operand of sageconv_body.h)
-struct PackSet {
-  const float* w; int64_t ldw; int K, N; int kn;        // kn = 0: w[n * ldw + k] (nn.Linear's [out, in]); 1: w[k * ldw + n]
-  float4* out;                                          // [4 waves][16 steps][64 lanes]
-};
+// ---- fragment-major copies of the weights (the B operand of sageconv_body.h; the body is pack_body.h)
 struct PackArgs { PackSet s[16]; int nsets; };
 
-// out[(wv * 16 + u) * 64 + lane] = W[k = 8u + 4h + 0..3][n = 32 wv + i]  (lane = 32 h + i), zero beyond K / N
 __global__ __launch_bounds__(256) void sage_conv_pack_kernel(PackArgs a) {
-  const PackSet& s = a.s[blockIdx.y];
-  const int e = (int)blockIdx.x * 256 + (int)threadIdx.x;         // 0 .. 4095
-  const int lane = e & 63, u = (e >> 6) & 15, wv = e >> 10;
-  const int i = lane & 31, h = lane >> 5;
-  const int n = 32 * wv + i, k0 = 8 * u + 4 * h;
-  float v[4];
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const int k = k0 + c;
-    const bool ok = n < s.N && k < s.K;
-    v[c] = ok ? (s.kn ? s.w[(int64_t)k * s.ldw + n] : s.w[(int64_t)n * s.ldw + k]) : 0.f;
-  }
-  s.out[e] = make_float4(v[0], v[1], v[2], v[3]);
+  sage_conv_pack_body(a.s[blockIdx.y], (int)blockIdx.x * 256 + (int)threadIdx.x);     // 0 .. 4095
 }
 
 }  // namespace
@@ -126,11 +110,8 @@ int tsgnn_sage_conv_pack_f32(const int64_t* desc, tsgnn_stream_t stream) {
   a.nsets = nsets;
   const int64_t* d = desc + 1;
   for (int t = 0; t < nsets; ++t, d += 6) {
-    PackSet& s = a.s[t];
-    s.w = reinterpret_cast<const float*>(d[0]); s.ldw = d[1]; s.K = (int)d[2]; s.N = (int)d[3]; s.kn = (int)d[4];
-    s.out = reinterpret_cast<float4*>(d[5]);
-    if (!s.w || !s.out || !tsgnn_sage_conv_supported(s.K, s.N) || s.ldw < (s.kn ? s.N : s.K)) return TSGNN_EINVAL;
-    if (reinterpret_cast<uintptr_t>(s.out) & 15) return TSGNN_EUNSUPPORTED;
+    const int rc = pack_set_from_desc(d, a.s[t]);
+    if (rc != TSGNN_OK) return rc;
   }
   TSGNN_KNAME("sage_conv_pack_kernel");
   sage_conv_pack_kernel<<<dim3(16, (unsigned)nsets), 256, 0, stream>>>(a);

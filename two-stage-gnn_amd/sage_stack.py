@@ -16,6 +16,7 @@ Used when the batch qualifies (slot-BN on, sum aggregation without self term, <=
 configuration runs the operator-by-operator path in dense_encoders.py: same results, more launches.  Every fusion has a switch
 (environment / module attribute) that selects the launch sequence it replaces.
 """
+import numpy as np
 import torch
 
 from . import _native as nat
@@ -124,6 +125,9 @@ def _flush_readout(g, B, sn, sg, pending):
 # are per slot across graphs and are not used in this mode.
 _PER_GRAPH = [False]
 
+_IMG_FLOATS = 16384        # one fragment-major weight image (tsgnn_sage_conv_pack_f32): [4 waves][16 steps][64 lanes] float4
+_IMG_LAYERS = 4            # hidden layers whose two images one launch's pack riders write (8 images)
+
 
 class per_graph_stats:
     def __init__(self, on=True):
@@ -197,6 +201,7 @@ class _SageStack(torch.autograd.Function):
                     bnf["sums"].zero_(); bnf["ghost"].zero_(); bnf["packed"].zero_()
                 bnf["dirty"] = True
                 packed = bnf["packed"]
+        ctx.w_img = ctx.pack_desc = None
         if bnf is not None:
             # ---- slot batch-norm without launches of its own (L launches for the conv stack instead of 2L - 1)
             ell, ell_w, tail = g.ell()
@@ -204,6 +209,20 @@ class _SageStack(torch.autograd.Function):
             ell_s, tc_s = ell_s
             sums, ghost = bnf["sums"], bnf["ghost"]
             ro_map, ro_ch = g.readout_map(sn, gs) if RO_MAP else (None, 0)
+            # fragment-major images of the hidden layers' weights (forward and input-gradient orientation), written by extra workgroups
+            # of layer 0's launch from the parameters THIS call uses: the later launches read W from them instead of staging it through
+            # LDS.  One buffer per call, nothing cached: parameters are also rewritten behind autograd's back (restored snapshots).
+            w_img = pack_desc = None
+            if 1 <= L - 1 <= _IMG_LAYERS:
+                w_img = torch.empty(2 * (L - 1), _IMG_FLOATS, dtype=torch.float32, device=dev)
+                pack_desc = np.empty(1 + 12 * (L - 1), dtype=np.int64)
+                pack_desc[0] = 2 * (L - 1)
+                for l in range(1, L):
+                    for kn in (1, 0):                        # image 2 (l - 1): forward (w[k][n]); 2 (l - 1) + 1: input gradient
+                        t = 2 * (l - 1) + (1 - kn)
+                        pack_desc[1 + 6 * t:7 + 6 * t] = (Ws[l].data_ptr(), Ws[l].stride(0), 128, 128, kn, w_img[t].data_ptr())
+                bnf["pack_desc"] = pack_desc                 # (recorded launches are replayed by address: the last descriptor stays valid)
+            ctx.w_img, ctx.pack_desc = w_img, pack_desc
             for l in range(L):
                 K, N = Ws[l].size(0), Ws[l].size(1)
                 v = torch.empty(R, N, dtype=torch.float32, device=dev)
@@ -213,7 +232,8 @@ class _SageStack(torch.autograd.Function):
                 g_out = ghost[2 * l:2 * l + 2] if l < L - 1 else None
                 if l == 0:
                     nat.call("gather_rowgemm_st_f32", ell, ell_w, tp, tc, x, x.stride(0), Ws[0], Ws[0].stride(0), bs[0], v, v.stride(0), rinv, z,
-                             z.stride(0), g.n_rows, K, N, gs, g.row_slot, s_out, g_out, int(g.panel_units))
+                             z.stride(0), g.n_rows, K, N, gs, g.row_slot, s_out, g_out, int(g.panel_units),
+                             pack_desc.ctypes.data if pack_desc is not None else None)
                     mean = rstd = None
                 else:
                     pm, pr_ = saved[l - 1][3], saved[l - 1][4]
@@ -223,7 +243,8 @@ class _SageStack(torch.autograd.Function):
                              packed[(l - 1) * B * Fh:(l - 1) * B * Fh + B * Fh],
                              packed[l * B * Fh:l * B * Fh + (B + 1) * N] if last else None, g.row_graph,
                              sums[(l - 1) * 2 * sn:l * 2 * sn], ghost[2 * (l - 1):2 * l], pm, pr_,
-                             None if last else g.row_slot, s_out, g_out, ro_map, ro_ch, int(g.panel_units))
+                             None if last else g.row_slot, s_out, g_out, ro_map, ro_ch, int(g.panel_units),
+                             w_img[2 * (l - 1)] if w_img is not None else None)
                 if l < L - 1:
                     mean = torch.empty(g.nmax, dtype=torch.float32, device=dev)     # written by the NEXT launch's readout blocks
                     rstd = torch.empty(g.nmax, dtype=torch.float32, device=dev)
@@ -362,6 +383,7 @@ class _SageStack(torch.autograd.Function):
         g, L = ctx.g, ctx.L
         Fh, Fl = ctx.dims
         R, B = g.total_rows, g.B
+        w_img = ctx.w_img                             # the forward's weight images (input-gradient orientation: rows 2 (l - 1) + 1), or None
         head_grads = ()
         du_last = None                                # the last layer's dU when the head's backward launch produced it
         if ctx.head is None:
@@ -481,7 +503,8 @@ class _SageStack(torch.autograd.Function):
                     ws = torch.empty(need, dtype=torch.float32, device=dev)
                     dxs = torch.empty(R, K, dtype=torch.float32, device=dev)
                     nat.call("sage_layer_bwd_f32", ell, ell_w, tp, tc, du, du.stride(0), W, W.stride(0), dxs, dxs.stride(0), z, z.stride(0),
-                             g.n_rows, nslab, rps, bo, ws, int(g.panel_units))
+                             g.n_rows, nslab, rps, bo, ws, int(g.panel_units),
+                             w_img[2 * (l - 1) + 1] if w_img is not None else None)
                     dw = red.grad(ctx.params[2 * l], (K, N))
                     db = red.grad(ctx.params[2 * l + 1] if want_b else None, (N,))
                     red.add((ws, nslab, K, N, dw, db))
