@@ -1222,6 +1222,20 @@ int tsgnn_eigen_pool_from_dense_f32(const float* P, int J, int B, int nmax, cons
                                     const int* graph_ptr1, int64_t n_rows, int final_level, int* cluster_of, float* coef, int64_t* key,
                                     int* bad, tsgnn_stream_t stream);
 
+/* ---------------------------------------------------------------- stage two: k-nearest-neighbour vote (knn.hip)
+ * What every evaluate() of the reference fits on the host (train_triplet.py:78-94: sklearn KNeighborsClassifier(n_neighbors = k),
+ * uniform weights, Euclidean) as ONE launch: for every query row the k training rows of smallest distance, ascending, equal
+ * distances to the lower training index; a query that is itself a training row finds itself at distance 0.  Distances are
+ * sqrt(sum_d (q_d - x_d)^2) (difference form: the product form cancels in fp32 on embeddings with a common offset).  pred [n_query] =
+ * the most frequent class among the k, a tie to the smallest class; classes are indices 0 .. n_classes - 1 (train_class [n_train]).
+ * query_class + confusion (both nullable): confusion[t, p] += 1 per query (int32 [n_classes, n_classes], atomics: order-independent).
+ * nbr_index / nbr_dist (nullable) [n_query, k].  Rows are 16-byte aligned with strides that are multiples of 4 floats and at least
+ * dim rounded up to 4 (what the padding holds does not matter).  dim <= 1024, k <= 16 (and k <= n_train), n_classes <= 64. */
+int tsgnn_knn_supported(int64_t dim, int k, int n_classes);
+int tsgnn_knn_classify_f32(const float* train, int64_t ld_train, const int* train_class, int64_t n_train, const float* query,
+                           int64_t ld_query, int64_t n_query, int64_t dim, int k, int n_classes, const int* query_class, int* confusion,
+                           int* pred, int* nbr_index, float* nbr_dist, tsgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -104,9 +104,20 @@ class ResidentCache:
         return len(self._entries)
 
 
+_shared_resident = weakref.WeakKeyDictionary()
+
+
+def resident_cache(model):
+    """the ResidentCache of `model`: one per network, shared by every ``tripletnet`` around it and by ``two_stage.embed_dataset``"""
+    c = _shared_resident.get(model)
+    if c is None:
+        c = _shared_resident[model] = ResidentCache()
+    return c
+
+
 class _Triplet:
-    """three graphs as one batch on the device: ``x [N, F]`` (refill it in place between hipGraph replays), the CSR batch ``g``, the
-    host-known ``sizes``, and the pieces the composed path needs (``edge_index`` / ``batch``, built on demand)"""
+    """three graphs (``batch``) or a chunk of a dataset (``batch_of``) as one batch on the device: ``x [N, F]`` (refill it in place
+    between hipGraph replays), the CSR batch ``g``, the host-known ``sizes``, and the pieces the composed path needs (``edge_index`` / ``batch``, built on demand)"""
     __slots__ = ("x", "g", "sizes", "datas", "_ei", "_batch")
 
 
@@ -195,7 +206,7 @@ class tripletnet(nn.Module):
     def __init__(self, model):
         super().__init__()
         self.model = model
-        self.cache = ResidentCache()
+        self.cache = resident_cache(model) if _t.RESIDENT else ResidentCache()
         self._batch_vec = {}
 
     # ------------------------------------------------------------------ graphs
@@ -215,23 +226,35 @@ class tripletnet(nn.Module):
     def batch(self, a, p, n):
         """the three graphs as one block-diagonal batch: cached structure concatenated on the device (no host synchronisation, no
         upload once the three objects have been seen), the feature rows read from ``data.x``"""
-        trip = (a, p, n)
+        return self.batch_of((a, p, n))
+
+    def batch_of(self, datas):
+        """any number of graphs as one block-diagonal batch (``two_stage.embed_dataset``: a chunk of a dataset)"""
+        trip = tuple(datas)
         _check_gpu(trip)
-        dev = a.x.device
+        dev = trip[0].x.device
         parts = [self._graph(d, dev) for d in trip]
-        rps, cols, e0, r0 = [], [], 0, 0
-        for i, q in enumerate(parts):
-            rp = q.rowptr if i == 2 else q.rowptr[:-1]
-            rps.append(rp + e0 if e0 else rp)
-            if q.nnz:
-                cols.append(q.col + r0 if r0 else q.col)
-            e0 += q.nnz
-            r0 += q.n
         g = GraphBatch()
         g.sizes = np.array([q.n for q in parts], dtype=np.int64)
-        g.B, g.nmax, g.n_rows, g.n_ghost, g.layout, g.device = 3, int(g.sizes.max()), r0, 0, "packed", dev
-        g.rowptr = torch.cat(rps)
-        g.col = torch.cat(cols) if cols else torch.zeros(1, dtype=torch.int32, device=dev)
+        if len(parts) > _t._PER_PIECE_MAX:                                       # a chunk of a dataset: one add for all offsets
+            nnzs = np.array([q.nnz for q in parts], dtype=np.int64)
+            e0, r0 = int(nnzs.sum()), int(g.sizes.sum())
+            g.rowptr = torch.cat([_t.offset_cat([q.rowptr[:-1] for q in parts], g.sizes, np.concatenate([[0], np.cumsum(nnzs)[:-1]]), dev),
+                                  torch.full((1,), e0, dtype=torch.int32, device=dev)])
+            g.col = (_t.offset_cat([q.col for q in parts], nnzs, np.concatenate([[0], np.cumsum(g.sizes)[:-1]]), dev) if e0
+                     else torch.zeros(1, dtype=torch.int32, device=dev))
+        else:
+            rps, cols, e0, r0 = [], [], 0, 0
+            for i, q in enumerate(parts):
+                rp = q.rowptr if i == len(parts) - 1 else q.rowptr[:-1]
+                rps.append(rp + e0 if e0 else rp)
+                if q.nnz:
+                    cols.append(q.col + r0 if r0 else q.col)
+                e0 += q.nnz
+                r0 += q.n
+            g.rowptr = torch.cat(rps)
+            g.col = torch.cat(cols) if cols else torch.zeros(1, dtype=torch.int32, device=dev)
+        g.B, g.nmax, g.n_rows, g.n_ghost, g.layout, g.device = len(parts), int(g.sizes.max()), r0, 0, "packed", dev
         g.val, g.nnz, g.symmetric = None, e0, all(q.symmetric for q in parts)
         b = _Triplet()
         x = torch.cat([d.x if d.x.dim() == 2 else d.x.view(d.x.size(0), -1) for d in trip])
@@ -240,7 +263,7 @@ class tripletnet(nn.Module):
         return b
 
     def _composed_inputs(self, b):
-        """edge_index [2, E] and batch [N] of the 3-graph batch for the level-by-level operators (device-side concatenation)"""
+        """edge_index [2, E] and batch [N] of the batch for the level-by-level operators (device-side concatenation)"""
         if b._ei is None:
             off, eis = 0, []
             for d in b.datas:
@@ -252,7 +275,7 @@ class tripletnet(nn.Module):
             if bv is None:
                 if len(self._batch_vec) > 64:
                     self._batch_vec.clear()
-                bv = self._batch_vec[key] = torch.from_numpy(np.repeat(np.arange(3, dtype=np.int64), b.sizes)).to(b.x.device)
+                bv = self._batch_vec[key] = torch.from_numpy(np.repeat(np.arange(len(b.sizes), dtype=np.int64), b.sizes)).to(b.x.device)
                 bv._tsgnn_sizes = (bv._version, b.sizes)
                 self.cache.h2d += 1
             b._batch = bv

@@ -73,6 +73,18 @@ def _resident(obj, dev, cache):
     return e
 
 
+_shared_resident = weakref.WeakKeyDictionary()
+
+
+def resident_cache(model):
+    """the resident graphs of `model`: ONE dictionary per encoder, shared by every ``tripletnet`` around it and by
+    ``two_stage.embed_dataset``, so a graph object uploaded by a training step is not uploaded again by an evaluation (and the reverse)"""
+    c = _shared_resident.get(model)
+    if c is None:
+        c = _shared_resident[model] = {}
+    return c
+
+
 def _ghost_zeros(nmax, ld, dev, cache):
     key = ("z", nmax, ld, dev.index)
     z = cache.get(key)
@@ -81,25 +93,46 @@ def _ghost_zeros(nmax, ld, dev, cache):
     return z
 
 
+def offset_cat(pieces, counts, offsets, dev):
+    """cat(pieces[i] + offsets[i]) with ONE add for all pieces (a chunk of a dataset has hundreds of them: two small uploads of
+    host-known numbers instead of one launch per graph); counts[i] = len(pieces[i])"""
+    off = torch.from_numpy(np.asarray(offsets, dtype=np.int32)).to(dev)
+    cnt = torch.from_numpy(np.asarray(counts, dtype=np.int64)).to(dev)
+    return torch.cat(pieces) + torch.repeat_interleave(off, cnt, output_size=int(np.sum(counts)))
+
+
+_PER_PIECE_MAX = 8          # up to this many graphs (a triplet) every piece gets its own offset launch: nothing is uploaded
+
+
 def _assemble(parts, dev, cache):
-    """three resident graphs -> (GraphBatch, feature rows, assignment rows or None): the block-diagonal batch of packed rows +
-    Nmax empty ghost-slot rows (GraphBatch.from_csr's layout)"""
+    """resident graphs (the three of a triplet, or a chunk of a dataset) -> (GraphBatch, feature rows, assignment rows or None): the
+    block-diagonal batch of packed rows + Nmax empty ghost-slot rows (GraphBatch.from_csr's layout)"""
     nmax = parts[0].nmax
     if any(p.nmax != nmax for p in parts):
-        raise ValueError("the graphs of a triplet must be padded to the same Nmax")
+        raise ValueError("the graphs of a batch must be padded to the same Nmax")
     sizes = np.array([p.n for p in parts], dtype=np.int64)
     nnz = int(sum(p.nnz for p in parts))
-    rps, cols, e0, r0 = [], [], 0, 0
-    for p in parts:
-        rps.append(p.rowptr[:-1] + e0 if e0 else p.rowptr[:-1])
-        cols.append(p.col + r0 if r0 else p.col)
-        e0 += p.nnz
-        r0 += p.n
-    rps.append(torch.full((nmax + 1,), nnz, dtype=torch.int32, device=dev))
+    tail = torch.full((nmax + 1,), nnz, dtype=torch.int32, device=dev)
+    if len(parts) > _PER_PIECE_MAX:
+        e0s = np.concatenate([[0], np.cumsum([p.nnz for p in parts])[:-1]])
+        r0s = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+        rowptr = torch.cat([offset_cat([p.rowptr[:-1] for p in parts], sizes, e0s, dev), tail])
+        col = offset_cat([p.col for p in parts], [p.nnz for p in parts], r0s, dev) if nnz else None
+    else:
+        rps, cols, e0, r0 = [], [], 0, 0
+        for p in parts:
+            rps.append(p.rowptr[:-1] + e0 if e0 else p.rowptr[:-1])
+            cols.append(p.col + r0 if r0 else p.col)
+            e0 += p.nnz
+            r0 += p.n
+        rps.append(tail)
+        rowptr = torch.cat(rps)
+        col = torch.cat(cols) if nnz else None
     weighted = any(p.val is not None for p in parts)
     val = torch.cat([p.val if p.val is not None else torch.ones(p.nnz, device=dev) for p in parts]) if weighted else None
-    col = torch.cat(cols) if nnz else torch.zeros(1, dtype=torch.int32, device=dev)
-    g = GraphBatch.from_csr(torch.cat(rps), col, val, sizes, nmax, assume_symmetric=all(p.symmetric for p in parts))
+    if col is None:
+        col = torch.zeros(1, dtype=torch.int32, device=dev)
+    g = GraphBatch.from_csr(rowptr, col, val, sizes, nmax, assume_symmetric=all(p.symmetric for p in parts))
     g.nnz = nnz
     x = torch.cat([p.feats for p in parts] + [_ghost_zeros(nmax, parts[0].feats.size(1), dev, cache)])
     xa = None
@@ -206,7 +239,7 @@ class tripletnet(nn.Module):
     def __init__(self, model):
         super().__init__()
         self.model = model
-        self._resident = {}
+        self._resident = resident_cache(model) if RESIDENT else {}
 
     def _embed(self, x, g_or_adj, sizes, assign_x):
         """model forward with the per-graph batch-norm statistics of a B = 1 call -> (dist_p, dist_n, embed_a, embed_p, embed_n)"""
