@@ -1,10 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark (BASELINE.json): graphs/sec, forward+backward(+all-reduce+clip+Adam) of the
 3-layer h=128 GraphSage-style encoder (GcnEncoderGraph, `--method=base`) on DD-shaped synthetic batches
-of 32 graphs per GPU, on 1/2/4/8 MI355X, plus the roofline of EVERY kernel the timed step launches, the
-aggregation kernel's batch-size sweep and the reference's dense formulation timed on the host CPU.
+of 32 graphs per GPU, on 1/2/4/8 MI355X.  A plain run does what that figure needs and nothing else: set-up (model, resident
+batch, capture of the step, the settling replays), the W warm-up steps, the K timed steps, --dump-outputs, the JSON line.  With
+--full the same run goes on to everything else the benchmark measures: the roofline of EVERY kernel the timed step launches, the
+aggregation kernel's batch-size sweep, the step at four steps per graph launch and over the batches of seeds 0-7, the
+torch_geometric-named surface, the gradient all-reduce by itself (N > 1) and the reference's dense formulation timed on the host CPU.
 
-  python bench.py --gpus 1 --steps 200 --warmup 20
+  python bench.py --gpus 1 --steps 200 --warmup 20            (the headline figure alone)
+  python bench.py --gpus 1 --steps 200 --warmup 20 --full     (+ every other figure, in the same JSON line)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
   python bench.py --gpus N ...          (WORLD_SIZE unset: starts the N ranks itself as child processes)
@@ -13,7 +17,7 @@ One JSON line on stdout (rank 0).  A "step" = one optimiser step on one batch pe
 backward, gradient bucket (+RCCL all-reduce when N>1), clip_grad_norm(2.0), Adam — exactly the body of the
 reference's loop (train.py:110-131) minus the host->device copies (inputs are resident in HBM).
 
-`roofline` describes the step that was timed:
+`roofline` (--full) describes the step that was timed:
   step_kernels   one row per launch group of the step, in launch order: the device kernel the library dispatched (reported by
                  the library, tsgnn_last_kernel), launches per step, average duration of ONE launch measured with HIP events
                  around a hipGraph burst of that very launch (same arguments, same buffers the step used: layer 0 runs at its
@@ -50,11 +54,16 @@ def parse():
     ap.add_argument("--nmax", type=int, default=1000, help="padded size of the reference (--max_nodes default)")
     ap.add_argument("--hidden", type=int, default=128)
     ap.add_argument("--layers", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure everything that is not the headline figure: the per-kernel roofline table, "
+                         "the aggregation probe and its batch-size sweep, four steps per graph launch, seeds 0-7, the pyg surface, the "
+                         "all-reduce alone (N > 1) and the CPU baseline (each of which --no-kernels / --no-sweep / --no-seeds / --no-pyg / "
+                         "--no-cpu-baseline takes out again).  Off by default: a plain run times its steps and prints its line")
     ap.add_argument("--no-graph", action="store_true", help="launch eagerly instead of replaying a hipGraph")
     ap.add_argument("--steps-per-graph", type=int, default=1,
                     help="N = 1: consecutive optimiser steps captured into one hipGraph launch (GraphedStep.run).  Default 1 = one step per "
-                         "launch, what a training loop with a new batch per step can use (`value`); the 4-steps-per-launch time of the same "
-                         "resident batch is reported beside it as `ms_per_step_four_steps_per_graph`")
+                         "launch, what a training loop with a new batch per step can use (`value`); with --full the 4-steps-per-launch time of the "
+                         "same resident batch is reported beside it as `ms_per_step_four_steps_per_graph`")
     ap.add_argument("--settle-steps", type=int, default=128,
                     help="untimed replays of the captured step right after capture, BEFORE the --warmup steps (the same count on every "
                          "rank): the first ~80 replays of a freshly captured step run 3-4 %% slower than every later one (0.131 -> "
@@ -748,7 +757,9 @@ def main():
     with torch.cuda.stream(stream):
         if use_graph and a.settle_steps > 0:     # part of the set-up (capture + settle), not of the W warm-up steps below
             # the same W + K steps right after capture, BEFORE the settling replays: what the driver's short run measured in the
-            # rounds without them (reported as `ms_per_step_unsettled`; every rank runs the same count)
+            # rounds without them (reported as `ms_per_step_unsettled`; every rank runs the same count).  Not behind --full: these
+            # W + K replays come before the timed ones, so the optimiser state the timed steps start from (and --dump-outputs
+            # writes) counts them, and they are part of what settles the captured step
             gstep.run(a.warmup)
             torch.cuda.synchronize()
             tu = time.perf_counter()
@@ -790,7 +801,7 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
         allreduce = None
-        if multi:
+        if multi and a.full:
             # the gradient all-reduce BY ITSELF (the bucket of the timed step, same communicator and stream), 50 back to back, slowest
             # rank: with TSGNN_AR_BUCKETS = 1 (default) the collective sits between the backward and the optimiser of every step, so
             # this is also what the step exposes of it; every rank issues the same count (collective-safe)
@@ -821,6 +832,7 @@ def main():
             "value": world * a.batch * a.steps / elapsed, "unit": "graphs/s",
             "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": ms_step,
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "full": bool(a.full),
             "config": {"workload": "%s-shaped synthetic graphs (avg %d nodes / %d edges, F_in=%d), batch=%d per GPU, "
                                    "GcnEncoderGraph (GraphSage 'base') %d layers h=%d, Nmax=%d, slot-BN, CE loss, "
                                    "clip 2.0 + Adam; %d step(s) per hipGraph launch, seed = rank, %d untimed settle steps before the warm-up"
@@ -844,6 +856,7 @@ def main():
             out["per_rank"] = per_rank            # every rank's own batch and its own clock around the same K steps
         if allreduce is not None:
             out["allreduce"] = allreduce
+    if rank == 0 and a.full:        # everything below measures something other than `value`
         roofline = {}
         traffic, traffic_src = load_traffic()
         with torch.cuda.stream(stream):
@@ -962,14 +975,14 @@ def main():
                                      "rows": max(vs["per_seed"], key=lambda r: r["ms_per_step"])["rows"],
                                      "vs_headline_batch": vs["worst_ms_per_step"] / ms_step,
                                      "note": "max over seeds 0-7 of the one-GPU step = the pace of an 8-rank step before the all-reduce"}
-    if rank == 0 and world == 1 and use_graph and not a.no_pyg:
+    if rank == 0 and a.full and world == 1 and use_graph and not a.no_pyg:
         out["pyg_surface"] = pyg_surface_run(a, dev, hb, out["ms_per_step"])
     if a.ingest and world == 1:
         out["ingest"] = ingest_run(a, model, trainer, dev, max(a.steps, 100), rank, out["value"])
     if a.triplet and world == 1:
         out["triplet"] = triplet_run(a, dev, not a.no_cpu_baseline)
     if rank == 0:
-        if not a.no_cpu_baseline and world == 1:
+        if a.full and not a.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(hb, a.hidden, a.layers, a.cpu_steps, init_state)
         else:
             out["cpu_baseline"] = None

@@ -7,9 +7,9 @@ R=${TSGNN_ROUND:-r04}; export TSGNN_ROUND=$R
 O=gpurun_out/$R; mkdir -p $O profiles/$R
 for what in "$@"; do
   case $what in
-    bench)   python3 bench.py > $O/bench.json 2> $O/bench.err || exit 1 ;;
+    bench)   python3 bench.py --full > $O/bench.json 2> $O/bench.err || exit 1 ;;
     rocprof) rm -rf $O/rocprof_bench
-             rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_bench -- python3 bench.py --no-cpu-baseline --no-seeds --no-pyg --steps-per-graph 1 > $O/bench_under_rocprof.json 2> $O/rocprof.err || exit 1
+             rocprofv3 --kernel-trace --stats --output-format csv -d $O/rocprof_bench -- python3 bench.py --full --no-cpu-baseline --no-seeds --no-pyg --steps-per-graph 1 > $O/bench_under_rocprof.json 2> $O/rocprof.err || exit 1
              cp $O/rocprof_bench/*/*kernel_stats.csv $O/bench_b32_kernel_stats.csv ;;
     pmc)     bash scripts/pmc_step.sh > $O/pmc_step.log 2>&1 || exit 1
              cp profiles/$R/step_traffic.json $O/step_traffic.json ;;

@@ -749,7 +749,7 @@ def test_bench_two_ranks_end_to_end_gloo():
     env = dict(os.environ, TSGNN_DIST_BACKEND="gloo")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline",
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2", "--full", "--no-cpu-baseline",
                         "--no-sweep", "--no-kernels", "--no-seeds", "--no-pyg", "--settle-steps", "4"],
                        stdout=subprocess.PIPE, stderr=subprocess.PIPE, env=env, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
@@ -764,6 +764,68 @@ def test_bench_two_ranks_end_to_end_gloo():
     assert d["steps_per_graph_launch"] == 1 and d["settle_untimed_steps"] == 4
     ar = d["allreduce"]                                         # the collective by itself, for the scaling analysis of a real N > 1 run
     assert ar["us_alone"] > 0 and ar["bytes"] > 4 * 50000 and ar["backend"] == "gloo" and ar["buckets"] == 1
+
+
+def test_bench_full_is_an_option_and_off_by_default(monkeypatch):
+    """`--full` exists, is off in a plain run, and the options that prune it still parse beside it"""
+    sys.path.insert(0, ROOT)
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert a.full is False and a.steps == 5 and a.warmup == 2
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2", "--full", "--no-sweep", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert a.full is True and a.no_sweep and a.no_cpu_baseline and not a.no_kernels
+
+
+BENCH_EXTRAS = ("roofline", "value_over_seeds", "value_mean_over_seeds", "value_worst_seed", "pyg_surface",
+                "ms_per_step_four_steps_per_graph", "allreduce", "ingest", "triplet")
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_is_lean():
+    """`bench.py --gpus 1 --steps N --warmup W` without `--full`: one JSON line with the headline fields and none of the other
+    measurements, and at most 30 s of the whole process (start to exit, a fresh interpreter) outside its N + W steps."""
+    import json, subprocess, time
+    n, w = 50, 10
+    t0 = time.perf_counter()
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", str(n), "--warmup", str(w)],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    wall = time.perf_counter() - t0
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["metric"] == "graphs/sec fwd+bwd, DD batch=32 SAGE-3L h=128" and d["unit"] == "graphs/s" and d["dtype"] == "f32"
+    assert d["higher_is_better"] is True and d["steps"] == n and d["warmup"] == w and d["full"] is False
+    assert d["value"] > 0 and abs(d["value"] - 32 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert d["steps_per_graph_launch"] == 1 and d["settle_untimed_steps"] == 128 and d["ms_per_step_unsettled"] > 0
+    assert d["cpu_baseline"] is None and not [k for k in BENCH_EXTRAS if k in d]
+    outside = wall - (n + w) * d["ms_per_step"] * 1e-3
+    print("plain bench.py: %.2f s start to exit, %.2f s outside its %d steps" % (wall, outside, n + w))
+    assert outside <= 30.0, outside
+
+
+@pytest.mark.gpu
+def test_bench_full_run_carries_every_other_figure():
+    """`--full` goes on to what a plain run leaves out (a short CPU sample and the two smallest sweep sizes keep it brief): same
+    headline fields, plus the per-kernel roofline, the aggregation sweep, four steps per launch, seeds, the pyg surface, the CPU line."""
+    import json, subprocess
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "50", "--warmup", "10", "--full",
+                        "--cpu-steps", "3", "--sweep-sizes", "32,256", "--seeds", "0,6"],
+                       stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+    assert r.returncode == 0, r.stderr.decode()[-3000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["full"] is True and d["value"] > 0 and abs(d["value"] - 32 / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    rf = d["roofline"]
+    assert rf["step_launches"] == sum(k["launches_per_step"] for k in rf["step_kernels"]) > 0 and 0 < rf["frac"] <= 1
+    assert [s_["graphs"] for s_ in rf["sweep"]] == [32, 256] and rf["aggregation_standalone"]["us_per_launch"] > 0
+    assert d["ms_per_step_four_steps_per_graph"] > 0
+    assert [s_["seed"] for s_ in d["value_over_seeds"]["per_seed"]] == [0, 6] and rf["straggler"]["ms_per_step"] > 0
+    assert d["pyg_surface"]["ms_per_step"] > 0
+    assert d["cpu_baseline"]["value"] > 0 and d["cpu_baseline"]["sparse_variant"]["value"] > 0
 
 
 @pytest.mark.gpu
