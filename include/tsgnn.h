@@ -309,6 +309,29 @@ int tsgnn_rowgemm_f32(const float* a, int64_t lda, const float* b, int64_t ldb, 
  * capacity-padded batches, whose rows beyond one panel per unit are mostly padding.  For callers that size a co-resident role of the
  * same launch (encoders.py:33-40 backward: the weight-gradient slab blocks beside the input-gradient panels). */
 int tsgnn_panel_blocks(int64_t rows, int panel_units);
+/* GATHER SCHEDULE: the `ell` operand of tsgnn_gather_rowgemm_st_f32, tsgnn_sage_layer_fwd_bn_f32 and tsgnn_sage_layer_bwd_f32 in place of
+ * the neighbour table, announced by ell_w = one of the two codes below (= S, the request slots per lane group); tail_ptr / tail_col
+ * are NULL with it.  Built on the host once per batch structure (GraphBatch.gather_schedule): int32 [panels][G][4 + S], 16-byte aligned,
+ * panels = ceil(rows / 32), G lane groups (half-waves of 32 lanes: lane c fetches float4 column c of every row its group asks for).
+ * Record of panel p, group q:
+ *   word 0        first: panel-local index (0..31) of the group's first destination row; the group owns consecutive rows from there
+ *   word 1        start mask: bit s set = slot s opens a destination row
+ *   word 2        end mask:   bit s set = slot s closes one (after it the row's sum is complete and is written)
+ *   word 3        short mask: bit s set (a start slot) = the row has fewer than 8 neighbours
+ *   words 4..4+S  ids: the neighbour row of each slot, -1 = empty; for tsgnn_sage_layer_fwd_bn_f32 slot << 20 | row, as its table
+ * The slots of one destination row are contiguous, in the row's neighbour order, inside one group; a row without neighbours takes one
+ * empty slot, and so does every row of the last panel beyond `rows`: each of a panel's 32 rows is opened and closed exactly once.
+ * Unused groups have all masks 0.  The kernels request all S rows of a lane at once and sum them in slot order: bit for bit the
+ * table path's result (which adds +0.0 for the empty entries among a row's first 8: a short row's sum starts from +0.0, any other from -0.0).
+ * TSGNN_SCHED_8x32: the 256-thread row-panel kernels; TSGNN_SCHED_16x24: the 512-thread kernel of tsgnn_gather_rowgemm_st_f32.
+ * A launch that is cut into 16- / 8-row units (tsgnn_panel_blocks) takes no schedule: TSGNN_EUNSUPPORTED, as is a code that does
+ * not match the kernel the launch dispatches — ask tsgnn_gather_sched_slots. */
+#define TSGNN_SCHED_8x32 32
+#define TSGNN_SCHED_16x24 24
+/* HOST function: the schedule code (S) the launch takes on the current device, or 0 when it is cut into units (neighbour table only).
+ * layer0 != 0: tsgnn_gather_rowgemm_st_f32 with these rows, fill_rows and K; layer0 == 0: tsgnn_sage_layer_fwd_bn_f32 /
+ * tsgnn_sage_layer_bwd_f32 (fill_rows and K ignored). */
+int tsgnn_gather_sched_slots(int64_t rows, int64_t fill_rows, int K, int panel_units, int layer0);
 /* Aggregation fused into the product (GraphConv.forward lines encoders.py:33-40 in one launch; and its input gradient
  * dX = (A dU) W^T for a symmetric A): the A operand of tsgnn_rowgemm_f32 is replaced by
  *   z[r,:] = sum_k x[ell[r*ell_w + k], :K]      (ell = fixed-width neighbour table of tsgnn_csr_to_ell, entries < 0 skipped,

@@ -16,11 +16,12 @@ namespace {
 
 // PANELS_FIRST: the row panels take the low block indices (dispatched first), the slab blocks follow
 // BIMG: W arrives as a fragment-major image (ga.b_img, rowgemm_body.h)
-template <bool PANELS_FIRST, bool UNITS = false, bool BIMG = false>
+// SCHED: ga.ell is the batch's gather schedule, 8 groups x 32 slots (rowgemm_body.h)
+template <bool PANELS_FIRST, bool UNITS = false, bool BIMG = false, int SCHED = 0>
 __global__ __launch_bounds__(256) void sage_layer_bwd_kernel(RowGemmArgs ga, TnArgs gt, unsigned n_tn, unsigned nslab, unsigned n_pan, int slab_delay) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if (PANELS_FIRST) {
-    if (blockIdx.x < n_pan) rowgemm_body<4, true, true, 1, false, false, false, UNITS, BIMG>(ga, smem, blockIdx.x);
+    if (blockIdx.x < n_pan) rowgemm_body<4, true, true, 1, false, false, false, UNITS, BIMG, SCHED>(ga, smem, blockIdx.x);
     else {
       // the slab blocks finish well before the row panels (whose gather prologue is two dependent round trips): let the panels'
       // requests go first instead of competing with the slabs' 64 KB per block for the same first microseconds
@@ -34,7 +35,7 @@ __global__ __launch_bounds__(256) void sage_layer_bwd_kernel(RowGemmArgs ga, TnA
     }
   } else {
     if (blockIdx.x < n_tn) tn_rows_body<4, 4, 2>(gt, smem, blockIdx.x % nslab, blockIdx.x / nslab, nslab);
-    else rowgemm_body<4, true, true, 1, false, false, false, UNITS, BIMG>(ga, smem, blockIdx.x - n_tn);
+    else rowgemm_body<4, true, true, 1, false, false, false, UNITS, BIMG, SCHED>(ga, smem, blockIdx.x - n_tn);
   }
 }
 
@@ -46,7 +47,9 @@ int tsgnn_sage_layer_bwd_f32(const int* ell, int ell_w, const int* tail_ptr, con
                              int64_t lddxs, const float* z, int64_t ldz, int64_t rows, int nslab, int64_t rows_per_slab,
                              int64_t bias_only_rows, float* ws, int panel_units, const float* w_img, tsgnn_stream_t stream) {
   if (!ell || !du || !w || !dxs || !z || !ws || rows <= 0 || nslab <= 0 || rows_per_slab <= 0 || bias_only_rows < 0) return TSGNN_EINVAL;
-  if (ell_w != 4 && ell_w != 8 && ell_w != 16) return TSGNN_EUNSUPPORTED;
+  const bool sched = ell_w == TSGNN_SCHED_8x32;             // ell = the batch's gather schedule
+  if (sched && (tail_ptr || tail_col)) return TSGNN_EINVAL;
+  if (!sched && ell_w != 4 && ell_w != 8 && ell_w != 16) return TSGNN_EUNSUPPORTED;
   const uintptr_t al = reinterpret_cast<uintptr_t>(ell) | reinterpret_cast<uintptr_t>(du) | reinterpret_cast<uintptr_t>(w) |
                        reinterpret_cast<uintptr_t>(dxs) | reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(w_img);
   if ((al & 15) || (lddu % 4) || (ldw % 4) || (lddxs % 4) || (ldz % 4) || lddu < 128 || ldw < 128 || lddxs < 128 || ldz < 128)
@@ -69,16 +72,19 @@ int tsgnn_sage_layer_bwd_f32(const int* ell, int ell_w, const int* tail_ptr, con
   static const int slab_delay_env = [] { const char* e = getenv("TSGNN_SLAB_DELAY"); return e ? atoi(e) : -1; }();
   const int slab_delay = slab_delay_env >= 0 ? slab_delay_env : ((int64_t)n_pan <= (int64_t)ncu ? 2 : 0);
   const bool units = ga.unit == 8 || ga.unit == 16;
+  if (sched && units) return TSGNN_EUNSUPPORTED;        // (a schedule is packed per 32-row panel)
   TSGNN_KNAME("sage_layer_bwd_kernel<%s,%s>", panels_first ? "true" : "false", units ? "true" : "false");   // (the demangled name, without blanks)
-#define TSGNN_BWD_(PF_, UN_) \
+#define TSGNN_BWD_(PF_, UN_, SC_) \
   do {                       \
-    if (w_img) sage_layer_bwd_kernel<PF_, UN_, true><<<n_tn + n_pan, 256, lds, stream>>>(ga, gt, n_tn, (unsigned)nslab, n_pan, slab_delay); \
-    else sage_layer_bwd_kernel<PF_, UN_><<<n_tn + n_pan, 256, lds, stream>>>(ga, gt, n_tn, (unsigned)nslab, n_pan, slab_delay);            \
+    if (w_img) sage_layer_bwd_kernel<PF_, UN_, true, SC_><<<n_tn + n_pan, 256, lds, stream>>>(ga, gt, n_tn, (unsigned)nslab, n_pan, slab_delay); \
+    else sage_layer_bwd_kernel<PF_, UN_, false, SC_><<<n_tn + n_pan, 256, lds, stream>>>(ga, gt, n_tn, (unsigned)nslab, n_pan, slab_delay);       \
   } while (0)
-  if (panels_first && units) TSGNN_BWD_(true, true);
-  else if (panels_first) TSGNN_BWD_(true, false);
-  else if (units) TSGNN_BWD_(false, true);
-  else TSGNN_BWD_(false, false);
+  if (panels_first && units) TSGNN_BWD_(true, true, 0);
+  else if (panels_first && sched) TSGNN_BWD_(true, false, TSGNN_SCHED_8x32);
+  else if (panels_first) TSGNN_BWD_(true, false, 0);
+  else if (units) TSGNN_BWD_(false, true, 0);
+  else if (sched) TSGNN_BWD_(false, false, TSGNN_SCHED_8x32);
+  else TSGNN_BWD_(false, false, 0);
 #undef TSGNN_BWD_
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;

@@ -35,13 +35,14 @@ __global__ __launch_bounds__(256) void sage_layer_fwd_kernel(RowGemmArgs ga, Slo
 // x = the previous layer's v; the gather and the readout partial form y = BN(relu(v)) on the fly from the previous layer's integer
 // sums.  ST: this layer is followed by a batch-norm too (statistics epilogue); RO: it is the last one (readout epilogue).
 // BIMG: W arrives as a fragment-major image (ga.b_img, rowgemm_body.h).
-template <bool RO, bool ST, bool UNITS = false, bool BIMG = false>
+// SCHED: ga.ell is the batch's gather schedule, 8 groups x 32 slots (rowgemm_body.h), ids as slot << 20 | row.
+template <bool RO, bool ST, bool UNITS = false, bool BIMG = false, int SCHED = 0>
 __global__ __launch_bounds__(256, 2) void sage_layer_fwd_bn_kernel(RowGemmArgs ga, SlotArgs sa, BnReadArgs bn, unsigned n_gemm, unsigned ro_gx,
                                                                 int ro_ch, int F4, unsigned long long* __restrict__ packed, unsigned n_main,
                                                                 PullRider pr, const int* __restrict__ ro_map) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if (blockIdx.x < n_gemm) {
-    rowgemm_body<4, false, true, 1, RO, true, ST, UNITS, BIMG>(ga, smem, blockIdx.x);
+    rowgemm_body<4, false, true, 1, RO, true, ST, UNITS, BIMG, SCHED>(ga, smem, blockIdx.x);
   } else if (blockIdx.x < n_main) {
     // ro_map (nullable): which (graph, chunk) this block scans — chosen on the host so that the block sits on the XCD whose row
     // panels gather that graph's rows (blocks b, b + 8, ... share an XCD): the rows are in that L2 already instead of being
@@ -95,7 +96,9 @@ int tsgnn_sage_layer_fwd_bn_f32(const int* ell, int ell_w, const int* tail_ptr, 
       rows <= 0 || fill_rows < 0 || K <= 0 || B <= 0 || nslots <= 0 || (n_ghost != 0 && n_ghost != nslots) || (packed_out && !row_graph) ||
       (row_slot && (!sums_out || !ghost_out)))
     return TSGNN_EINVAL;
-  if (ell_w != 4 && ell_w != 8 && ell_w != 16) return TSGNN_EUNSUPPORTED;
+  const bool sched = ell_w == TSGNN_SCHED_8x32;             // ell = the batch's gather schedule (ids with slots)
+  if (sched && (tail_ptr || tail_col)) return TSGNN_EINVAL;
+  if (!sched && ell_w != 4 && ell_w != 8 && ell_w != 16) return TSGNN_EUNSUPPORTED;
   const uintptr_t al = reinterpret_cast<uintptr_t>(ell) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(w) |
                        reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(zout) | reinterpret_cast<uintptr_t>(bias) |
                        reinterpret_cast<uintptr_t>(sums_in) | reinterpret_cast<uintptr_t>(sums_out) | reinterpret_cast<uintptr_t>(w_img);
@@ -123,14 +126,16 @@ int tsgnn_sage_layer_fwd_bn_f32(const int* ell, int ell_w, const int* tail_ptr, 
   const size_t lro = 8 * 128 * sizeof(unsigned long long) + 256 * sizeof(float2);
   if (lds < lro) lds = lro;
   const unsigned n_main = n_gemm + ro_gx * (unsigned)B;
+  if (sched && ga.n_full > 0) return TSGNN_EUNSUPPORTED;   // (a schedule is packed per 32-row panel: no launch in units)
   const PullRider pr = take_pull_rider();
   const bool units = ga.unit == 8 || ga.unit == 16;     // (rows beyond one panel per CU as 16- / 8-row units: the UNITS build of the kernels)
-#define TSGNN_FWD_BN_(RO_, ST_, UN_, IM_) \
-  sage_layer_fwd_bn_kernel<RO_, ST_, UN_, IM_><<<n_main + pr.blocks, 256, lds, stream>>>(ga, sa, bn, n_gemm, ro_gx, ro_ch, K / 4, packed, n_main, pr, ro_map)
+#define TSGNN_FWD_BN_(RO_, ST_, UN_, IM_, SC_) \
+  sage_layer_fwd_bn_kernel<RO_, ST_, UN_, IM_, SC_><<<n_main + pr.blocks, 256, lds, stream>>>(ga, sa, bn, n_gemm, ro_gx, ro_ch, K / 4, packed, n_main, pr, ro_map)
 #define TSGNN_FWD_BN(RO_, ST_)                                                                  \
   do {                                                                                          \
-    if (units) { if (w_img) TSGNN_FWD_BN_(RO_, ST_, true, true); else TSGNN_FWD_BN_(RO_, ST_, true, false); }   \
-    else { if (w_img) TSGNN_FWD_BN_(RO_, ST_, false, true); else TSGNN_FWD_BN_(RO_, ST_, false, false); }       \
+    if (units) { if (w_img) TSGNN_FWD_BN_(RO_, ST_, true, true, 0); else TSGNN_FWD_BN_(RO_, ST_, true, false, 0); }   \
+    else if (sched) { if (w_img) TSGNN_FWD_BN_(RO_, ST_, false, true, TSGNN_SCHED_8x32); else TSGNN_FWD_BN_(RO_, ST_, false, false, TSGNN_SCHED_8x32); } \
+    else { if (w_img) TSGNN_FWD_BN_(RO_, ST_, false, true, 0); else TSGNN_FWD_BN_(RO_, ST_, false, false, 0); }       \
   } while (0)
   if (packed_out) {
     TSGNN_KNAME("sage_layer_fwd_bn_kernel<true,false,%s>", units ? "true" : "false");

@@ -56,16 +56,18 @@ __device__ __forceinline__ void st_passengers(const PackRider& pk, const PullRid
   if (b < pk.blocks) pack_rider_body(pk, b);
   else pull_rider_body(pr, b - pk.blocks);
 }
-template <bool UNITS>
+// SCHED: g.ell is the batch's gather schedule (rowgemm_body.h): 8 groups x 32 slots for the one-group kernel, 16 x 24 for the two-group one
+template <bool UNITS, int SCHED = 0>
 __global__ __launch_bounds__(256) void rowgemm_gather_st_kernel(RowGemmArgs g, PullRider pr, unsigned nblk, PackRider pk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if (blockIdx.x >= nblk) { st_passengers(pk, pr, blockIdx.x - nblk); return; }
-  rowgemm_body<4, false, true, 1, false, false, true, UNITS>(g, smem, blockIdx.x);
+  rowgemm_body<4, false, true, 1, false, false, true, UNITS, false, SCHED>(g, smem, blockIdx.x);
 }
+template <int SCHED = 0>
 __global__ __launch_bounds__(512) void rowgemm_gather_ks2_st_kernel(RowGemmArgs g, PullRider pr, unsigned nblk, PackRider pk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if (blockIdx.x >= nblk) { st_passengers(pk, pr, blockIdx.x - nblk); return; }
-  rowgemm_body<4, false, true, 2, false, false, true>(g, smem, blockIdx.x);
+  rowgemm_body<4, false, true, 2, false, false, true, false, false, SCHED>(g, smem, blockIdx.x);
 }
 
 // column-split variant for products WITHOUT the row epilogue (no normalise: rows need not be whole): grid.y column blocks of
@@ -270,7 +272,9 @@ int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, 
                                 const int64_t* pack_desc, tsgnn_stream_t stream) {
   if (!ell || !x || !b || !c || !row_slot || !sums || !ghost || rows <= 0 || fill_rows < 0 || K <= 0 || N <= 0 || ldx < K || ldc < N)
     return TSGNN_EINVAL;
-  if (ell_w != 4 && ell_w != 8 && ell_w != 16) return TSGNN_EUNSUPPORTED;
+  const bool sched = ell_w == TSGNN_SCHED_8x32 || ell_w == TSGNN_SCHED_16x24;   // ell = the batch's gather schedule
+  if (sched && (tail_ptr || tail_col)) return TSGNN_EINVAL;
+  if (!sched && ell_w != 4 && ell_w != 8 && ell_w != 16) return TSGNN_EUNSUPPORTED;
   if (!tsgnn_rowgemm_supported(x, ldx, b, ldb, c, ldc, K, N, 0) || N > 128 || N <= 96 || K > 128 || (reinterpret_cast<uintptr_t>(ell) & 15) ||
       (reinterpret_cast<uintptr_t>(sums) & 15))
     return TSGNN_EUNSUPPORTED;
@@ -294,22 +298,27 @@ int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, 
   const bool ks2 = K > KC && nblk <= ks2_max_blocks() && rowgemm_ks2_enabled();
   if (!ks2)                                              // (the one-group kernel: a few more panels than CUs go as 16-row units)
     nblk = panel_split(rows, device_cu_count(), panel_units, &g.n_full, &g.unit) + (fill_rows > 0 ? 1u : 0u);
+  // a schedule is packed for ONE kernel's lane groups: the code must name the kernel this launch takes (tsgnn_gather_sched_slots)
+  if (sched && ell_w != (ks2 ? TSGNN_SCHED_16x24 : (g.unit == 8 || g.unit == 16) ? 0 : TSGNN_SCHED_8x32)) return TSGNN_EUNSUPPORTED;
   if (ks2) {
     constexpr size_t lds2 = rowgemm_lds_bytes<4, false, true, 2>();
     static bool attr = false;
     if (!attr && lds2 > 64 * 1024) {
-      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rowgemm_gather_ks2_st_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rowgemm_gather_ks2_st_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rowgemm_gather_ks2_st_kernel<TSGNN_SCHED_16x24>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2);
       attr = true;
     }
     const PullRider pr = take_pull_rider(512);             // (blocks = 0 unless tsgnn_ingest_arm_pull_rider[_parts] armed one on this thread)
     pk.blocks *= PACK_SET_ENTRIES / 512;
     TSGNN_KNAME("rowgemm_gather_ks2_st_kernel");
-    rowgemm_gather_ks2_st_kernel<<<nblk + pk.blocks + pr.blocks, 512, lds2, stream>>>(g, pr, nblk, pk);
+    if (sched) rowgemm_gather_ks2_st_kernel<TSGNN_SCHED_16x24><<<nblk + pk.blocks + pr.blocks, 512, lds2, stream>>>(g, pr, nblk, pk);
+    else rowgemm_gather_ks2_st_kernel<0><<<nblk + pk.blocks + pr.blocks, 512, lds2, stream>>>(g, pr, nblk, pk);
   } else {
     const PullRider pr = take_pull_rider(256);
     pk.blocks *= PACK_SET_ENTRIES / 256;
     TSGNN_KNAME("rowgemm_gather_st_kernel<%s>", (g.unit == 8 || g.unit == 16) ? "true" : "false");
     if (g.unit == 8 || g.unit == 16) rowgemm_gather_st_kernel<true><<<nblk + pk.blocks + pr.blocks, 256, rowgemm_lds_bytes<4, false, true>(), stream>>>(g, pr, nblk, pk);
+    else if (sched) rowgemm_gather_st_kernel<false, TSGNN_SCHED_8x32><<<nblk + pk.blocks + pr.blocks, 256, rowgemm_lds_bytes<4, false, true>(), stream>>>(g, pr, nblk, pk);
     else rowgemm_gather_st_kernel<false><<<nblk + pk.blocks + pr.blocks, 256, rowgemm_lds_bytes<4, false, true>(), stream>>>(g, pr, nblk, pk);
   }
   TSGNN_CHECK_LAUNCH();
@@ -323,6 +332,21 @@ int tsgnn_panel_blocks(int64_t rows, int panel_units) {
   if (rows <= 0) return 0;
   int nf = 0, un = 16;
   return (int)panel_split(rows, device_cu_count(), panel_units, &nf, &un);
+}
+
+/* slots per lane group of the gather schedule (GraphBatch.gather_schedule) that a row-panel launch of `rows` rows takes on the current
+ * device, or 0: the launch is cut into 16- / 8-row units and keeps the neighbour table.  layer0 != 0: tsgnn_gather_rowgemm_st_f32 at
+ * this K and fill_rows (its two-group kernel: TSGNN_SCHED_16x24); else the one-group kernels of tsgnn_sage_layer_fwd_bn_f32 /
+ * tsgnn_sage_layer_bwd_f32 (TSGNN_SCHED_8x32). */
+int tsgnn_gather_sched_slots(int64_t rows, int64_t fill_rows, int K, int panel_units, int layer0) {
+  if (rows <= 0) return 0;
+  if (layer0) {
+    const unsigned nblk = (unsigned)(ceil_div64(rows, 32) + (fill_rows > 0 ? 1 : 0));
+    if (K > KC && nblk <= ks2_max_blocks() && rowgemm_ks2_enabled()) return TSGNN_SCHED_16x24;
+  }
+  int nf = 0, un = 32;
+  (void)panel_split(rows, device_cu_count(), panel_units, &nf, &un);
+  return nf > 0 ? 0 : TSGNN_SCHED_8x32;
 }
 
 int tsgnn_gather_rowgemm_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* x, int64_t ldx, const float* b, int64_t ldb, int trans_b,

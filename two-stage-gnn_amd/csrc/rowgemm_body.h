@@ -90,6 +90,11 @@ __device__ __forceinline__ unsigned long long rg_pack_max(float val, unsigned r)
 
 __device__ __forceinline__ float4 ldg4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
+// -DTSGNN_EXP_DROP_NB16=1 (scripts/exp_build.sh; timing only, WRONG results on purpose): neighbours 9-16 of a row are not fetched —
+// the price of the gather prologue's second dependent phase (profiles/r08)
+#ifndef TSGNN_EXP_DROP_NB16
+#define TSGNN_EXP_DROP_NB16 0
+#endif
 constexpr int GN = 8;                 // neighbour rows per output row that are gathered in one go (the rest, rare, follow)
 constexpr int LDA_F = 128;            // row stride of the gathered full-K A panel (K <= 128).  No padding: float4 column c of row r
                                       // lives at column c ^ (r & 7), which spreads eight rows over the 32 banks (conflict-free
@@ -104,14 +109,24 @@ constexpr int LDA_F = 128;            // row stride of the gathered full-K A pan
 // g.b_img with sixteen 1 KB-contiguous 16-byte loads, asked for AFTER the neighbour rows (a wave's loads return in issue order: W is
 // not needed before the gather has ended); no register staging, no LDS stage, no barrier in the K loop.  The MFMA chain sees the
 // operands of the staged path in the same order, so the product is the same bit for bit.
+// SCHED = S > 0 (GATHER, plain 32-row panels): g.ell is the batch's GATHER SCHEDULE (include/tsgnn.h; GraphBatch.gather_schedule) instead of
+// the neighbour table.  The table path asks for the first GN neighbours of a lane's 4 / KS rows, waits, and asks rows with more for
+// neighbours 9-16: a second dependent index trip + row trip that nearly every panel pays (13 % of the DD rows have >= 8 neighbours),
+// while its 32 / KS request slots per lane are 60 % used.  The schedule binds the same slots to the panel's edges instead: each of the
+// 8 KS lane groups (half-waves) reads its record [first row, start / end / short masks, S ids] in the trip that fetched table ids, sends
+// ALL S row requests at once, and a fully unrolled walk over the slots sums them in neighbour order, closing a destination row at every
+// end bit.  Bit for bit the table path's sums: the same order, started from +0.0 where the table path added empty entries (rows with
+// fewer than GN neighbours: -0.0 + 0.0 = +0.0) and from -0.0 (x + -0.0 = x for every x) elsewhere.  S = 32 for the 256-thread kernels,
+// 24 for the 512-thread one (KS = 2).
 template <int NT, bool TRANS_B, bool GATHER, int KS = 1, bool READOUT = false, bool BNIN = false, bool STATS = false, bool UNITS = false,
-          bool BIMG = false>
+          bool BIMG = false, int SCHED = 0>
 __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_all, unsigned bid) {
   static_assert(KS == 1 || (KS == 2 && GATHER && NT <= 4), "the split-K variant is built for the gather kernel, widths <= 128");
   static_assert(!READOUT || (NT <= 4 && KS == 1), "the readout epilogue is built for one column tile per wave");
   static_assert(!BNIN || (GATHER && KS == 1), "batch-norm on the fly lives in the gather prologue of the one-group kernel");
   static_assert(!STATS || NT <= 4, "the statistics epilogue is built for one column tile per wave");
   static_assert(!BIMG || (GATHER && KS == 1 && NT == 4), "the image variant is built for the one-group gather kernel at K = N = 128");
+  static_assert(SCHED == 0 || (GATHER && !UNITS && SCHED == (KS == 2 ? 24 : 32)), "gather schedules: 8 x 32 (one group) / 16 x 24 (two groups), plain panels");
   constexpr int NP = 32 * NT;
   constexpr int TPW = (NT + 3) / 4;
   constexpr int BV = NT;                               // float4 of B per thread per chunk (KC * NP / 1024)
@@ -343,7 +358,20 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
   Staged st[NS];
   constexpr int NPASS = 4 / KS;                        // gather passes of 8 * KS rows
   int ids[NPASS][GN];                                  // GATHER: neighbour ids first (head of the dependent chain), the W
-  if (GATHER) {                                        // fetches below fill their latency
+  constexpr int NSL = SCHED ? SCHED : 1;
+  int sid[NSL];                                        // SCHED: the lane group's slot ids, and its record's header
+  int s_first = 0;
+  unsigned s_end = 0u, s_short = 0u;                   // (the walk needs no start mask: a row opens behind every end bit)
+  if constexpr (SCHED != 0) {
+    const int4* rec = reinterpret_cast<const int4*>(g.ell) + ((m0 >> 5) * (8 * KS) + (tid_all >> 5)) * ((4 + SCHED) / 4);
+    const int4 hd = rec[0];
+    s_first = hd.x; s_end = (unsigned)hd.z; s_short = (unsigned)hd.w;
+#pragma unroll
+    for (int q = 0; q < SCHED / 4; ++q) {
+      const int4 v = rec[1 + q];
+      sid[4 * q] = v.x; sid[4 * q + 1] = v.y; sid[4 * q + 2] = v.z; sid[4 * q + 3] = v.w;
+    }
+  } else if (GATHER) {
     const int rsub = tid_all >> 5;
 #pragma unroll
     for (int p = 0; p < NPASS; ++p) {
@@ -410,6 +438,64 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
         }
       }
     }
+    if constexpr (SCHED != 0) {
+      float4 sv[NSL];                                  // every row request of the lane in one go
+#pragma unroll
+      for (int s = 0; s < SCHED; ++s) {
+        sv[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (colok && sid[s] >= 0) sv[s] = ldg4(g.a + (int64_t)(BNIN ? (sid[s] & 0xFFFFF) : sid[s]) * g.lda + 4 * c4);
+      }
+      if constexpr (BIMG) {                            // chunks 0 and 1 behind the rows
+        __builtin_amdgcn_sched_barrier(0);
+        img_fetch(0);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      if constexpr (BNIN) {
+        __syncthreads();                               // the table of (rstd, mean * rstd) is complete
+#pragma unroll
+        for (int s = 0; s < SCHED; ++s) {
+          if (sid[s] >= 0) {
+            const float2 rm = bn_tab[sid[s] >> 20];
+            float4& t = sv[s];
+            t.x = fmaf(fmaxf(t.x, 0.f), rm.x, -rm.y); t.y = fmaf(fmaxf(t.y, 0.f), rm.x, -rm.y);
+            t.z = fmaf(fmaxf(t.z, 0.f), rm.x, -rm.y); t.w = fmaf(fmaxf(t.w, 0.f), rm.x, -rm.y);
+          }
+        }
+      }
+      // The walk: one open sum per lane group, closed at every end bit.  A row starts from +0.0 when it is short (fewer than GN
+      // neighbours: the table path's empty entries) and from -0.0, the exact identity of +, otherwise — the table path's sum, bit for bit.
+      // The two groups of a wave close their rows at different slots: the test of a slot is a scalar one (either group's end bit), so a
+      // slot that closes nothing costs the additions and a scalar branch.
+      const unsigned e_any = (unsigned)__builtin_amdgcn_readlane((int)s_end, 0) | (unsigned)__builtin_amdgcn_readlane((int)s_end, 32);
+      const unsigned nshort = ~s_short;
+      float z0 = __uint_as_float((nshort & 1u) << 31);
+      float4 va = make_float4(z0, z0, z0, z0);
+      float* ap = Apanel + s_first * LDA_F;            // the open row in the panel, and in zout
+      int pr = s_first;
+      const bool zok = g.zout != nullptr && colok;
+      int64_t zoff = (m0 + s_first) * g.ldz + 4 * c4;
+      int zleft = zok ? (int)min(rows_hi - (m0 + s_first), (int64_t)32) : 0;    // rows of this group that exist in the batch
+#pragma unroll
+      for (int s = 0; s < SCHED; ++s) {
+        va.x += sv[s].x; va.y += sv[s].y; va.z += sv[s].z; va.w += sv[s].w;
+        if ((e_any >> s) & 1u) {
+          if ((s_end >> s) & 1u) {
+            *reinterpret_cast<float4*>(ap + 4 * (c4 ^ (pr & 7))) = va;       // swizzled column (see LDA_F)
+            if (zleft > 0) st_out(reinterpret_cast<float4*>(g.zout + zoff), va);
+            ++pr; ap += LDA_F; zoff += g.ldz; --zleft;
+            if (s + 1 < SCHED) {
+              z0 = __uint_as_float(((nshort >> (s + 1)) & 1u) << 31);
+              va = make_float4(z0, z0, z0, z0);
+            }
+          }
+        }
+      }
+      if constexpr (BIMG) {                            // chunks 2 and 3 (as on the table path)
+        __builtin_amdgcn_sched_barrier(0);
+        img_fetch(8);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    } else {
     float4 nbv[NPASS][GN];
 #pragma unroll
     for (int p = 0; p < NPASS; ++p)
@@ -446,7 +532,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
 #pragma unroll
       for (int k = 1; k < GN; ++k) { va.x += nbv[p][k].x; va.y += nbv[p][k].y; va.z += nbv[p][k].z; va.w += nbv[p][k].w; }
       bool table_full = g.ell_w <= GN && ids[p][GN - 1] >= 0;  // only a row whose table is full can continue in the CSR tail
-      if (colok && g.ell_w > GN && ids[p][GN - 1] >= 0) {      // the table fills from the left: maybe more than GN neighbours
+      if (!TSGNN_EXP_DROP_NB16 && colok && g.ell_w > GN && ids[p][GN - 1] >= 0) {      // the table fills from the left: maybe more than GN neighbours
         // the second half of the row's table entries in ONE 32-byte request (same cache line as the first half), then ALL of their
         // rows in one round trip from clamped addresses, added in table order (the same sum, bit for bit, as a loop that fetched
         // entry k, then its row, then entry k + 1 ...: two dependent trips per extra neighbour)
@@ -494,6 +580,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
       img_fetch(8);
       __builtin_amdgcn_sched_barrier(0);
     }
+    }                                                  // (table path)
   }
   float bias_v[TPW];                                   // fetched now, used in the epilogue
 #pragma unroll

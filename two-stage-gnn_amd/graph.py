@@ -38,6 +38,88 @@ def exclusive_scan(counts):
     return out
 
 
+SCHED_SHAPES = ((8, 32), (16, 24))      # (lane groups per 32-row panel, request slots per group): the 256- / 512-thread row-panel kernels
+SCHED_HEADER = 4                         # int32 words in front of a record's slot ids: first row, start / end / short masks
+
+
+def unit_cut(rows, ncu, panel_units=True):
+    """True when a row-panel launch of `rows` rows on `ncu` compute units goes as full panels + 16- / 8-row units (csrc/rowgemm_body.h
+    panel_split gives n_full > 0): such launches keep the neighbour table."""
+    P = -(-int(rows) // 32)
+    return bool(panel_units) and ncu >= 8 and P > ncu and P - ncu <= ncu // 2
+
+
+def pack_gather_schedule(rowptr, col, n_rows, shape, row_slot=None, balance=True):
+    """The per-panel gather schedule of the row-panel kernels (include/tsgnn.h) as int32[panels, G, 4 + S], or None when
+    a row has more than S neighbours or a panel's rows do not fit its G groups.  Host side (numpy) from the CSR of the real rows.
+
+    Record of panel p, lane group q:  [first, start, end, short, id_0 .. id_{S-1}]
+      ids     neighbour rows in the order the group's lanes request them (-1: empty); row_slot given: slot << 20 | row
+      first   panel-local index of the group's first destination row; the group owns consecutive rows from there
+      start   bit s: slot s opens a destination row      end   bit s: slot s closes one (its sum is complete)
+      short   bit s (a start slot): the row has fewer than 8 neighbours (the table path adds +0.0 for their empty entries)
+    Consecutive packing: a row's slots are contiguous, in neighbour order, in one group; a row without neighbours (and every row of
+    the last panel beyond n_rows) takes one empty slot, so each of the 32 panel rows is opened and closed exactly once.
+    balance: a panel's slots are dealt over all G groups in equal shares (every wave of the block issues its part of the requests, and
+    the longest request list of a lane is the panel's mean, not S); a panel that does not fit that way, and balance=False, fill group
+    after group (greedy)."""
+    G, S = shape
+    if (G, S) not in SCHED_SHAPES:
+        raise ValueError("gather schedule shapes: %s" % (SCHED_SHAPES,))
+    n_rows = int(n_rows)
+    rowptr = np.asarray(rowptr, dtype=np.int64)[: n_rows + 1]
+    col = np.asarray(col, dtype=np.int64)
+    deg = np.diff(rowptr)
+    P = -(-n_rows // 32)
+    if n_rows <= 0 or (deg > S).any():
+        return None
+    nnz = int(rowptr[-1])
+    ids = col[:nnz]
+    if nnz and (ids.min() < 0 or ids.max() >= n_rows):
+        return None                                        # (nothing aggregates from a ghost row)
+    if row_slot is not None:
+        ids = (np.asarray(row_slot, dtype=np.int64)[ids] << 20) | ids
+    need = np.ones(32 * P, dtype=np.int64)                 # slots per panel row (at least the one empty slot)
+    need[:n_rows] = np.maximum(deg, 1)
+    degp = np.zeros(32 * P, dtype=np.int64)
+    degp[:n_rows] = deg
+    rec = np.full((P, G, SCHED_HEADER + S), -1, dtype=np.int64)
+    rec[:, :, :SCHED_HEADER] = 0
+    need_l, deg_l, ptr_l = need.tolist(), degp.tolist(), rowptr.tolist()
+    def pack_panel(p, share):
+        """rows of panel p into rec[p]; share: slots per group aimed at (S: greedy).  False: more than G groups needed"""
+        q, used, first, done = 0, 0, 0, 0
+        start = end = short = 0
+        rec[p, :, :SCHED_HEADER] = 0
+        rec[p, :, SCHED_HEADER:] = -1
+        for i in range(32):
+            r = 32 * p + i
+            n = need_l[r]
+            if used and (used + n > S or done + 0.5 * n > (q + 1) * share):     # the row opens the next group
+                rec[p, q, :SCHED_HEADER] = (first, start, end, short)
+                q, used, first = q + 1, 0, i
+                start = end = short = 0
+                if q >= G:
+                    return False
+            d = deg_l[r]
+            if d:
+                rec[p, q, SCHED_HEADER + used:SCHED_HEADER + used + d] = ids[ptr_l[r]:ptr_l[r] + d]
+            start |= 1 << used
+            end |= 1 << (used + n - 1)
+            if d < 8:
+                short |= 1 << used
+            used += n
+            done += n
+        rec[p, q, :SCHED_HEADER] = (first, start, end, short)
+        return True
+
+    for p in range(P):
+        total = sum(need_l[32 * p:32 * p + 32])
+        if not (balance and pack_panel(p, total / G)) and not pack_panel(p, float("inf")):
+            return None
+    return (rec & 0xFFFFFFFF).astype(np.uint32).view(np.int32)      # (bit 31 of a mask: the int32's sign bit)
+
+
 class GraphBatch:
     def __init__(self):
         self.B = 0
@@ -268,6 +350,28 @@ class GraphBatch:
                 tcol = pack(tail[1], int(tail[0][-1].item())) if tail is not None else None
                 self._ell_slots = (table, tcol)
         return self._ell_slots if self._ell_slots is not False else None
+
+    def gather_schedule(self, shape, slots=False, ncu=None):
+        """int32 device tensor [panels, G, 4 + S] (pack_gather_schedule) for the row-panel launches of the fused stack, or None — the
+        neighbour table is used then: weighted graphs, capacity-padded batches (their table is built on the device), a row with more
+        than S neighbours, a panel that does not pack, a launch that is cut into 16- / 8-row units.  slots: ids carry
+        slot << 20 | row (as ell_slots()).  Built once per batch structure, outside the step."""
+        shape = (int(shape[0]), int(shape[1]))
+        if ncu is None:
+            ncu = torch.cuda.get_device_properties(self.device).multi_processor_count
+        cache = self.__dict__.setdefault("_gather_sched", {})
+        key = (shape, bool(slots), int(ncu))
+        if key not in cache:
+            sched = None
+            if (self.val is None and self.sizes is not None and getattr(self, "ghost_slots_fixed", None) is None and self.n_rows > 0
+                    and not unit_cut(self.n_rows, int(ncu), self.panel_units)
+                    and not (slots and (self.total_rows >= (1 << 20) or self.nmax > 1024 or self.row_slot is None))):
+                rec = pack_gather_schedule(self.rowptr.cpu().numpy(), self.col.cpu().numpy(), self.n_rows, shape,
+                                           self.row_slot.cpu().numpy() if slots else None)
+                if rec is not None:
+                    sched = torch.from_numpy(rec).to(self.device)
+            cache[key] = sched
+        return cache[key]
 
     def du_map(self, other_blocks):
         """(du_map int32[n], n, chunk rows) for tsgnn_head2_bwd_du_map_f32, or (None, 0, 64): the non-empty (graph, chunk) pairs of the

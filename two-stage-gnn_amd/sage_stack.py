@@ -67,6 +67,10 @@ SLOT_WGRAD = os.environ.get("TSGNN_SLOT_WGRAD", "0") != "0"
 HEAD_DU = os.environ.get("TSGNN_HEAD_DU", "1") != "0"                     # ... computed by extra workgroups of the head's backward launch
 
 
+# the fused layer launches gather their row panels from the batch's packed neighbour schedule (every neighbour row asked for in ONE round
+# trip, GraphBatch.gather_schedule) instead of the fixed-width table (neighbours 9-16 in a second dependent phase)
+GATHER_SCHED = os.environ.get("TSGNN_GATHER_SCHED", "1") != "0"
+GATHER_SCHED_L0 = os.environ.get("TSGNN_GATHER_SCHED_L0", "1") != "0"    # ... layer 0's launch too (0: only the hidden layers' four)
 DU_MAP = os.environ.get("TSGNN_DU_MAP", "1") != "0"             # exact batches: the head backward's dU workgroups listed by the host
 SLABS_BESIDE = os.environ.get("TSGNN_SLABS_BESIDE", "1") != "0"
 NSLAB_MAX = int(os.environ.get("TSGNN_NSLAB_MAX", "0"))
@@ -106,6 +110,19 @@ def _gather_ok(g, x):
     if not GATHER_FUSED or g.val is not None or not mp.ell_ok(x) or g.total_rows > GATHER_MAX_ROWS:
         return False
     return True
+
+
+def _gather_sched(g, slots=False, layer0_k=0, fill=0):
+    """(schedule, ell_w code) for a fused layer launch on g, or (None, 0): the launch takes the neighbour table.  layer0_k: the launch
+    is tsgnn_gather_rowgemm_st_f32 at this K (fill = its fill_rows); else a hidden layer's forward (slots: ids carry the slot) /
+    backward launch.  The library names the kernel's shape, the batch packs (and caches) the schedule for it."""
+    if not GATHER_SCHED:
+        return None, 0
+    code = int(nat.lib().tsgnn_gather_sched_slots(int(g.n_rows), int(fill), int(layer0_k), int(g.panel_units), 1 if layer0_k else 0))
+    if not code:
+        return None, 0
+    sched = g.gather_schedule((16, 24) if code == 24 else (8, 32), slots=slots)
+    return (sched, code) if sched is not None else (None, 0)
 
 
 def _flush_readout(g, B, sn, sg, pending):
@@ -223,6 +240,8 @@ class _SageStack(torch.autograd.Function):
                         pack_desc[1 + 6 * t:7 + 6 * t] = (Ws[l].data_ptr(), Ws[l].stride(0), 128, 128, kn, w_img[t].data_ptr())
                 bnf["pack_desc"] = pack_desc                 # (recorded launches are replayed by address: the last descriptor stays valid)
             ctx.w_img, ctx.pack_desc = w_img, pack_desc
+            sch0, sch0_w = _gather_sched(g, layer0_k=Ws[0].size(0), fill=gs) if GATHER_SCHED_L0 else (None, 0)
+            schs, schs_w = _gather_sched(g, slots=True)
             for l in range(L):
                 K, N = Ws[l].size(0), Ws[l].size(1)
                 v = torch.empty(R, N, dtype=torch.float32, device=dev)
@@ -231,14 +250,16 @@ class _SageStack(torch.autograd.Function):
                 s_out = sums[l * 2 * sn:(l + 1) * 2 * sn] if l < L - 1 else None
                 g_out = ghost[2 * l:2 * l + 2] if l < L - 1 else None
                 if l == 0:
-                    nat.call("gather_rowgemm_st_f32", ell, ell_w, tp, tc, x, x.stride(0), Ws[0], Ws[0].stride(0), bs[0], v, v.stride(0), rinv, z,
+                    e_, w_, tp_, tc_ = (sch0, sch0_w, None, None) if sch0 is not None else (ell, ell_w, tp, tc)
+                    nat.call("gather_rowgemm_st_f32", e_, w_, tp_, tc_, x, x.stride(0), Ws[0], Ws[0].stride(0), bs[0], v, v.stride(0), rinv, z,
                              z.stride(0), g.n_rows, K, N, gs, g.row_slot, s_out, g_out, int(g.panel_units),
                              pack_desc.ctypes.data if pack_desc is not None else None)
                     mean = rstd = None
                 else:
                     pm, pr_ = saved[l - 1][3], saved[l - 1][4]
                     last = l == L - 1
-                    nat.call("sage_layer_fwd_bn_f32", ell_s, ell_w, tp, tc_s, saved[l - 1][1], saved[l - 1][1].stride(0), Ws[l], Ws[l].stride(0), bs[l],
+                    e_, w_, tp_, tc_ = (schs, schs_w, None, None) if schs is not None else (ell_s, ell_w, tp, tc_s)
+                    nat.call("sage_layer_fwd_bn_f32", e_, w_, tp_, tc_, saved[l - 1][1], saved[l - 1][1].stride(0), Ws[l], Ws[l].stride(0), bs[l],
                              v, v.stride(0), rinv, z, z.stride(0), g.n_rows, K, gs, g.graph_ptr, g.slot_count, B, sn, sg,
                              packed[(l - 1) * B * Fh:(l - 1) * B * Fh + B * Fh],
                              packed[l * B * Fh:l * B * Fh + (B + 1) * N] if last else None, g.row_graph,
@@ -500,6 +521,9 @@ class _SageStack(torch.autograd.Function):
                     # weight-gradient slabs and dX = (A dU) W^T side by side in one launch (both only need dU)
                     ell, ell_w, tail = g.ell()
                     tp, tc = tail if tail is not None else (None, None)
+                    schb, schb_w = _gather_sched(g)
+                    if schb is not None:
+                        ell, ell_w, tp, tc = schb, schb_w, None, None
                     ws = torch.empty(need, dtype=torch.float32, device=dev)
                     dxs = torch.empty(R, K, dtype=torch.float32, device=dev)
                     nat.call("sage_layer_bwd_f32", ell, ell_w, tp, tc, du, du.stride(0), W, W.stride(0), dxs, dxs.stride(0), z, z.stride(0),
