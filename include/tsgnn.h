@@ -1259,6 +1259,34 @@ int tsgnn_knn_classify_f32(const float* train, int64_t ld_train, const int* trai
                            int64_t ld_query, int64_t n_query, int64_t dim, int k, int n_classes, const int* query_class, int* confusion,
                            int* pred, int* nbr_index, float* nbr_dist, tsgnn_stream_t stream);
 
+/* ---------------------------------------------------------------- stage two: the MLP probe (mlp_probe.hip)
+ * The reference's evaluate_mlp() (Code/sage+gat+diffpool/train_triplet.py:105-183): Linear(dim, h1) - LeakyReLU - Linear(h1, h2) -
+ * LeakyReLU - Linear(h2, n_classes), trained with ONE torch.optim.Adam step per training row on the cross-entropy of that row, in row
+ * order.  The six parameter tensors have torch's [out, in] layout.  Sizes: dim <= 1024, h1, h2 <= 64, 2 <= n_classes <= 64
+ * (tsgnn_mlp_probe_supported); anything else is TSGNN_EINVAL.  Rows of x / q are 16-byte aligned with strides that are multiples of
+ * 4 floats and at least dim (what the padding holds does not matter).  Hyper-parameters are doubles, as torch holds them: the bias
+ * corrections 1 - beta^t are formed in double from running products.
+ *
+ * tsgnn_mlp_probe_fit_f32: the n single-sample steps as ONE launch of ONE workgroup; parameters are in/out.  cls [n]: class indices
+ * 0 .. n_classes - 1.  exp_avg / exp_avg_sq (both or neither): Adam's moments, in/out, each one buffer of the six tensors in the
+ * order W1, b1, W2, b2, W3, b3; when NULL the moments start at zero and are discarded (dim <= 512 only: wider first layers keep their
+ * moments in these buffers during the launch, TSGNN_EUNSUPPORTED without them).  step0: steps already taken (step i uses t = step0 +
+ * i + 1).  Per step: m = beta1 m + (1 - beta1) g, v = beta2 v + (1 - beta2) g^2, p -= (lr / (1 - beta1^t)) m / (sqrt(v) / sqrt(1 -
+ * beta2^t) + eps); LeakyReLU's derivative at exactly 0 is negative_slope.  loss (nullable) [n]: the cross-entropy of row i before
+ * its update.  Two runs on the same inputs give the same bits.
+ *
+ * tsgnn_mlp_probe_predict_f32: forward of n_query rows on an ordinary grid.  logits (nullable) [n_query, n_classes]; pred [n_query] =
+ * argmax, a tie to the lowest class; query_class + correct (both or neither): correct[0] += 1 per row with pred == query_class
+ * (atomic: the count accumulates over calls). */
+int tsgnn_mlp_probe_supported(int64_t dim, int h1, int h2, int n_classes);
+int tsgnn_mlp_probe_fit_f32(const float* x, int64_t ld_x, const int* cls, int64_t n, int64_t dim, int h1, int h2, int n_classes, float* w1,
+                            float* b1, float* w2, float* b2, float* w3, float* b3, float* exp_avg, float* exp_avg_sq, int64_t step0,
+                            double lr, double beta1, double beta2, double eps, double negative_slope, float* loss, tsgnn_stream_t stream);
+int tsgnn_mlp_probe_predict_f32(const float* q, int64_t ld_q, int64_t n_query, int64_t dim, int h1, int h2, int n_classes, const float* w1,
+                                const float* b1, const float* w2, const float* b2, const float* w3, const float* b3,
+                                double negative_slope, float* logits, int* pred, const int* query_class, int* correct,
+                                tsgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -17,7 +17,7 @@ HEADER = os.path.join(_ROOT, "include", "tsgnn.h")
 CSRC = os.path.join(_PKG_DIR, "csrc")
 LIB_PATH = os.path.join(_PKG_DIR, "libtsgnn_hip.so")
 
-_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+_SCALARS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float, "double": ctypes.c_double,
             "unsigned": ctypes.c_uint, "unsigned long long": ctypes.c_ulonglong, "uint64_t": ctypes.c_uint64}
 
 

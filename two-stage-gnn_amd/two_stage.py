@@ -6,6 +6,10 @@ Here the graphs go through the encoder in block-diagonal chunks (``embed_dataset
 ``triplet.py`` / ``sag_triplet.py``, per-graph statistics, so row i is the eval-mode B = 1 forward of graph i), the classifier is one
 HIP launch per prediction (csrc/knn.hip: distances, selection, vote and confusion matrix) and ``evaluate`` copies two small confusion
 matrices to the host, once.
+
+The reference's other probe, ``evaluate_mlp()`` (train_triplet.py:105-183: a fresh three-layer MLP trained with one Adam step per
+training embedding, then one forward per validation graph), is ``MLPProbe`` / ``evaluate_mlp`` at the end of this module: the whole
+training loop is ONE launch of one workgroup (csrc/mlp_probe.hip), the predictions and their correct count a second one.
 """
 import contextlib
 
@@ -366,3 +370,241 @@ def evaluate(train_graphs, val_graphs, model, n_neighbors=3, chunk=None):
     total = int(conf[1].sum())
     result["train acc"] = int(np.trace(conf[1])) / total if total else 0.0
     return result
+
+
+# ----------------------------------------------------------------------------- the MLP probe
+def _probe_sizes(E, h1, h2, C):
+    """element counts of W1, b1, W2, b2, W3, b3: the order of the flat parameter and moment buffers (and of the C ABI)"""
+    return [h1 * E, h1, h2 * h1, h2, C * h2, C]
+
+
+def _probe_views(flat, E, h1, h2, C):
+    shapes = [(h1, E), (h1,), (h2, h1), (h2,), (C, h2), (C,)]
+    out, o = [], 0
+    for n, shp in zip(_probe_sizes(E, h1, h2, C), shapes):
+        out.append(flat[o:o + n].view(shp))
+        o += n
+    return out
+
+
+def mlp_probe_torch(X, cls, params, exp_avg, exp_avg_sq, step0, lr, betas, eps, negative_slope):
+    """the fit kernel's semantics as a torch composition (tensors on the CPU, sizes ``tsgnn_mlp_probe_supported`` does not take): the
+    reference's loop itself, one ``torch.optim.Adam`` step per row on that row's cross-entropy.  ``params`` (six tensors) and the
+    moments (six views each, same order) are updated in place, ``step0`` steps lie behind them.  -> per-step losses [n]"""
+    ps = [torch.nn.Parameter(t) for t in params]                       # (a Parameter shares its tensor's storage)
+    opt = torch.optim.Adam(ps, lr=lr, betas=betas, eps=eps)
+    for p, m, v in zip(ps, exp_avg, exp_avg_sq):
+        opt.state[p] = {"step": torch.tensor(float(step0)), "exp_avg": m, "exp_avg_sq": v}
+    losses = []
+    target = cls.long()
+    for i in range(X.size(0)):
+        h = F.leaky_relu(F.linear(X[i], ps[0], ps[1]), negative_slope)
+        h = F.leaky_relu(F.linear(h, ps[2], ps[3]), negative_slope)
+        loss = F.cross_entropy(F.linear(h, ps[4], ps[5]).unsqueeze(0), target[i:i + 1])
+        loss.backward()
+        opt.step()
+        opt.zero_grad()
+        losses.append(loss.detach())
+    return torch.stack(losses) if losses else torch.zeros(0, device=X.device)
+
+
+class MLPProbe:
+    """The classifier of the reference's ``evaluate_mlp()``: ``Linear(E, h1) - LeakyReLU - Linear(h1, h2) - LeakyReLU - Linear(h2, C)``
+    trained by ONE pass over the training rows, in row order, one ``torch.optim.Adam`` step per row on that row's cross-entropy.  On
+    device tensors the pass is one launch of one workgroup (csrc/mlp_probe.hip) and ``fit`` never waits for the device; CPU tensors
+    and sizes outside ``tsgnn_mlp_probe_supported`` take ``mlp_probe_torch``, the same loop written with torch.
+
+    ``C = max(2, len(classes_))`` unless ``n_classes`` asks for more (the reference's last layer has two rows whatever the labels).
+    ``X`` / ``Q``: what ``KNeighborsClassifier`` takes."""
+
+    def __init__(self, hidden=(64, 32), n_classes=None, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, negative_slope=0.01):
+        if len(hidden) != 2 or min(int(h) for h in hidden) < 1:
+            raise ValueError("hidden must be two positive widths")
+        if n_classes is not None and int(n_classes) < 2:
+            raise ValueError("n_classes must be at least 2")
+        self.hidden = (int(hidden[0]), int(hidden[1]))
+        self.n_classes = None if n_classes is None else int(n_classes)
+        self.lr, self.betas, self.eps, self.negative_slope = float(lr), (float(betas[0]), float(betas[1])), float(eps), float(negative_slope)
+
+    # ---- parameters
+    def _initial(self, init, E, C):
+        """six host tensors [out, in]: copies of ``init`` (an ``nn.Sequential`` of the reference's shape or its six tensors), or what the
+        reference's ``nn.Linear(E, h1)``, ``nn.Linear(h1, h2)``, ``nn.Linear(h2, C)`` hold when constructed now, in that order, on the
+        host (train_triplet.py:151-155 builds them there before ``.cuda()``: the same draws from torch's global generator)"""
+        h1, h2 = self.hidden
+        if init is None:
+            lins = [torch.nn.Linear(E, h1), torch.nn.Linear(h1, h2), torch.nn.Linear(h2, C)]
+            ts = [t for m in lins for t in (m.weight, m.bias)]
+        elif isinstance(init, torch.nn.Module):
+            lins = [m for m in init.modules() if isinstance(m, torch.nn.Linear)]
+            if len(lins) != 3:
+                raise ValueError("init must hold three Linear layers")
+            ts = [t for m in lins for t in (m.weight, m.bias)]
+        else:
+            ts = list(init)
+            if len(ts) != 6:
+                raise ValueError("init must be six tensors: W1, b1, W2, b2, W3, b3")
+        ts = [torch.as_tensor(t).detach().to("cpu", torch.float32) for t in ts]
+        want = [(h1, E), (h1,), (h2, h1), (h2,), (C, h2), (C,)]
+        if [tuple(t.shape) for t in ts] != want:
+            raise ValueError("initial parameters have shapes %s, expected %s" % ([tuple(t.shape) for t in ts], want))
+        return ts
+
+    def _dims(self):
+        return (self._E,) + self.hidden + (self._C,)
+
+    def kernel_ok(self):
+        return bool(self._flat.is_cuda and nat.lib().tsgnn_mlp_probe_supported(*self._dims()))
+
+    # ---- training
+    def fit(self, X, y, classes=None, init=None):
+        """one pass over the rows of ``X`` from fresh parameters (``init``, never written; default: the reference's own construction
+        under torch's global generator) and zero moments.  ``y`` / ``classes``: as ``KNeighborsClassifier.fit``"""
+        yh = y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
+        yh = yh.reshape(-1)
+        X = _rows16(_as_matrix(X))
+        if X.size(0) != yh.size:
+            raise ValueError("X has %d rows, y has %d labels" % (X.size(0), yh.size))
+        if X.size(0) < 1 or X.size(1) < 1:
+            raise ValueError("fit needs at least one row and one column")
+        self.classes_ = np.unique(yh) if classes is None else np.asarray(classes)
+        self._y_tensor = isinstance(y, torch.Tensor)
+        self._E = int(X.size(1))
+        self._C = max(2, int(self.classes_.size), self.n_classes or 0)
+        host = torch.cat([t.reshape(-1) for t in self._initial(init, self._E, self._C)])
+        self._flat = _upload(host.numpy(), X.device) if X.is_cuda else host.clone()
+        self._params = _probe_views(self._flat, *self._dims())
+        self._exp_avg, self._exp_avg_sq = torch.zeros_like(self._flat), torch.zeros_like(self._flat)
+        self._step = 0
+        return self._steps(X, yh)
+
+    def partial_fit(self, X, y):
+        """continue with the rows of ``X`` from the kept parameters, moments and step count: ``fit(X[:h])`` then ``partial_fit(X[h:])``
+        is ``fit(X)``, bit for bit.  Labels must be in ``classes_``"""
+        if not hasattr(self, "_flat"):
+            raise RuntimeError("partial_fit continues a fit: call fit first")
+        yh = y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
+        X = _rows16(_as_matrix(X, self._flat.device))
+        if X.size(1) != self._E or X.size(0) != yh.size:
+            raise ValueError("rows of %d columns with %d labels; fitted on %d columns" % (X.size(1), yh.size, self._E))
+        return self._steps(X, yh.reshape(-1))
+
+    def _steps(self, X, yh):
+        n = int(X.size(0))
+        if n == 0:
+            self.losses_ = torch.zeros(0, device=X.device)
+            return self
+        cls = self.class_index(yh)
+        if self.kernel_ok():
+            self.losses_ = torch.empty(n, dtype=torch.float32, device=X.device)
+            E, h1, h2, C = self._dims()
+            nat.call("mlp_probe_fit_f32", X, X.stride(0), cls, n, E, h1, h2, C, *self._params, self._exp_avg, self._exp_avg_sq,
+                     self._step, self.lr, self.betas[0], self.betas[1], self.eps, self.negative_slope, self.losses_)
+        else:
+            dims = self._dims()
+            self.losses_ = mlp_probe_torch(X, cls, self._params, _probe_views(self._exp_avg, *dims), _probe_views(self._exp_avg_sq, *dims),
+                                           self._step, self.lr, self.betas, self.eps, self.negative_slope)
+        self._step += n
+        return self
+
+    def class_index(self, labels, strict=True):
+        """host labels -> int32 tensor (on the parameters' device) of their positions in ``classes_``; a label that is not in
+        ``classes_`` raises, or with ``strict=False`` becomes -1 (a class no prediction equals)"""
+        labels = np.asarray(labels).reshape(-1)
+        pos = np.searchsorted(self.classes_, labels)
+        bad = (pos >= self.classes_.size) | (self.classes_[np.minimum(pos, self.classes_.size - 1)] != labels) if labels.size else np.zeros(0, bool)
+        if strict and bad.any():
+            raise ValueError("a label is not in classes_")
+        return _upload(np.where(bad, -1, pos).astype(np.int32), self._flat.device)
+
+    # ---- prediction
+    def forward(self, Q, query_class=None, correct=None, logits=False):
+        """-> (pred int32 [nq]: positions in ``classes_`` (the argmax of the logits, a tie to the lowest class), logits [nq, C] or None);
+        with ``query_class`` (int32 positions) and ``correct`` (int32 [1] on the device): ``correct[0] += 1`` per row predicted right.
+        ONE launch, nothing copied to the host"""
+        dev = self._flat.device
+        Q = _as_matrix(Q, dev)
+        if Q.size(1) != self._E:
+            raise ValueError("query rows have %d columns, training rows %d" % (Q.size(1), self._E))
+        nq, C = int(Q.size(0)), self._C
+        if nq == 0:
+            return torch.zeros(0, dtype=torch.int32, device=dev), (torch.zeros(0, C, device=dev) if logits else None)
+        if self.kernel_ok():
+            Q = _rows16(Q)
+            pred = torch.empty(nq, dtype=torch.int32, device=dev)
+            out = torch.empty(nq, C, dtype=torch.float32, device=dev) if logits else None
+            count = correct is not None and query_class is not None
+            E, h1, h2, _ = self._dims()
+            nat.call("mlp_probe_predict_f32", Q, Q.stride(0), nq, E, h1, h2, C, *self._params, self.negative_slope, out, pred,
+                     query_class if count else None, correct if count else None)
+            return pred, out
+        p = self._params
+        h = F.leaky_relu(F.linear(Q, p[0], p[1]), self.negative_slope)
+        h = F.leaky_relu(F.linear(h, p[2], p[3]), self.negative_slope)
+        out = F.linear(h, p[4], p[5])
+        pred = (out == out.max(dim=1, keepdim=True).values).int().argmax(dim=1).int()      # (the first maximum: the lowest class)
+        if correct is not None and query_class is not None:
+            correct += (pred == query_class.to(dev)).sum().to(correct.dtype)
+        return pred, (out if logits else None)
+
+    def decision_function(self, Q):
+        """logits [nq, C]: a tensor on Q's device for a tensor, else a numpy array"""
+        out = self.forward(Q, logits=True)[1]
+        return out.to(Q.device) if isinstance(Q, torch.Tensor) else out.cpu().numpy()
+
+    def _label_table(self):
+        """classes_, continued past its end when the last layer has more rows than there are labels (a row nobody was trained
+        towards can still win): those read as max(classes_) + 1, + 2, ..."""
+        extra = self._C - int(self.classes_.size)
+        if extra <= 0:
+            return self.classes_
+        return np.concatenate([self.classes_, (self.classes_.max() + 1 + np.arange(extra)).astype(self.classes_.dtype)])
+
+    def predict(self, Q):
+        """labels of the rows of ``Q`` with the dtype of ``y``: a tensor on Q's device for a tensor, else a numpy array"""
+        pred = self.forward(Q)[0]
+        if isinstance(Q, torch.Tensor):
+            return _upload(self._label_table(), pred.device)[pred.long()].to(Q.device)
+        return self._label_table()[pred.cpu().numpy()]
+
+    def correct_count(self, Q, y, correct=None):
+        """-> int32 [1] on the device: rows of ``Q`` whose prediction is their label in ``y`` (a label outside ``classes_`` counts as
+        wrong), added to ``correct`` when given.  One launch, no copy to the host"""
+        yh = y.detach().cpu().numpy() if isinstance(y, torch.Tensor) else np.asarray(y)
+        if correct is None:
+            correct = torch.zeros(1, dtype=torch.int32, device=self._flat.device)
+        self.forward(Q, self.class_index(yh, strict=False), correct)
+        return correct
+
+    def score(self, Q, y):
+        """accuracy on (Q, y): one launch and ONE copy to the host"""
+        n = len(Q)
+        return int(self.correct_count(Q, y).cpu()) / n if n else 0.0
+
+    def module(self):
+        """an ``nn.Sequential`` of the reference's shape holding (copies of) the trained parameters, on their device"""
+        E, h1, h2, C = self._dims()
+        seq = torch.nn.Sequential(torch.nn.Linear(E, h1), torch.nn.LeakyReLU(self.negative_slope), torch.nn.Linear(h1, h2),
+                                  torch.nn.LeakyReLU(self.negative_slope), torch.nn.Linear(h2, C)).to(self._flat.device)
+        with torch.no_grad():
+            for lin, (w, b) in zip((seq[0], seq[2], seq[4]), zip(self._params[0::2], self._params[1::2])):
+                lin.weight.copy_(w)
+                lin.bias.copy_(b)
+        return seq
+
+
+def evaluate_mlp(train_graphs, val_graphs, model, hidden=(64, 32), n_classes=None, init=None, chunk=None, probe=None):
+    """The reference's ``evaluate_mlp()`` (train_triplet.py:105-183): embed both sets, train the probe on the training embeddings in
+    dataset order (one Adam step per graph), predict the validation set -> ``{'acc': ...}``.  Containers and labels as ``evaluate``.
+    After the embeddings exist: one fit launch, one predict launch, ONE copy to the host (the correct count).
+
+    accuracy count: intent, not the reference's arithmetic.  The reference adds ``pred.eq(torch.Tensor(val_labels[i]))``, and
+    ``torch.Tensor(int)`` is an UNINITIALISED tensor of that length (empty for label 0), so its printed accuracy is not a function of
+    its predictions.  Here a graph counts when its prediction equals its label; a validation label the training set does not have
+    counts as wrong.  Everything up to the predictions is the reference's."""
+    train, val = _flatten(train_graphs), _flatten(val_graphs)
+    y_train, y_val = _labels(train), _labels(val)
+    emb = embed_dataset(model, train + val, chunk)
+    probe = MLPProbe(hidden, n_classes) if probe is None else probe
+    probe.fit(emb[:len(train)], y_train, init=init)
+    return {"acc": probe.score(emb[len(train):], y_val)}
