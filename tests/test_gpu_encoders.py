@@ -1059,15 +1059,18 @@ def test_triplet_batched_equals_three_b1_forwards(kind):
             continue
         err = (p.grad.cpu() - ref).abs().max().item()
         assert err <= 5e-3 * ref.abs().max().item() + 1e-6, (k, err, ref.abs().max().item())
-    # the graphs stay resident after their first use (triplet._resident): a second step builds nothing and gives the same bits;
+    # the graphs stay resident after their first use (resident.ResidentCache): a second step builds nothing and gives the same bits;
     # the per-step upload of the dense adjacencies (the reference's way, TSGNN_TRIPLET_CACHE=0) agrees
     from two_stage_gnn_amd import triplet as T3
-    assert T3.RESIDENT and len(net._resident) >= 3
+    assert T3.RESIDENT and len(net._resident) == 3                     # one entry per graph object, nothing else
     before = {k: id(v) for k, v in net._resident.items()}
+    h2d = net._resident.h2d
+    assert h2d == 3 * 3                                              # rowptr, col, feats of each (unit weights, assign_feats is feats)
     dp2, dn2, ea2 = net(*gs)[:3]
-    assert {k: id(v) for k, v in net._resident.items()} == before
+    assert {k: id(v) for k, v in net._resident.items()} == before and net._resident.h2d == h2d
     assert torch.equal(dp2, dp) and torch.equal(dn2, dn) and torch.equal(ea2, ea)
     dp3, dn3, ea3 = net(gs[1], gs[0], gs[2])[:3]                      # the same objects in another order: assembled from the same pieces
+    assert {k: id(v) for k, v in net._resident.items()} == before and net._resident.h2d == h2d
     torch.testing.assert_close(dn3.cpu(), torch.nn.functional.pairwise_distance(embeds[1], embeds[2], 2).detach(), rtol=1e-4, atol=1e-4)
     T3.RESIDENT = False
     try:

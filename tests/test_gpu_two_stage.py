@@ -170,21 +170,23 @@ def test_embed_dataset_dense_equals_b1_forwards(kind, final_dim):
     cache = T3.resident_cache(m)
     assert net._resident is cache
     before = {k: id(v) for k, v in cache.items()}
+    assert len(before) == 3 and cache.h2d == 3 * 3                         # rowptr, col, feats of each of the step's graphs
     full = TS.embed_dataset(m, graphs)
     assert m.training and m.per_graph_bn is False and full.shape == (n_graphs, 8) and not full.requires_grad
-    assert all(id(cache[k]) == v for k, v in before.items())               # the step's entries were reused, not rebuilt
-    assert len([k for k in cache if k[0] != "z"]) == n_graphs              # one entry per graph object
+    entries = {k: id(v) for k, v in cache.items()}
+    assert all(entries[k] == v for k, v in before.items())                 # the step's entries were reused, not rebuilt
+    assert len(cache) == n_graphs and cache.h2d == 3 * n_graphs            # one entry per graph object, each uploaded once
     err = (full.cpu() - want).abs().max().item()
     print("%s %s: max |embed_dataset - fp64 B=1| = %.3g (scale %.3g)" % (kind, final_dim, err, want.abs().max().item()))
     torch.testing.assert_close(full.cpu(), want, rtol=1e-4, atol=1e-4)
-    entries = {k: id(v) for k, v in cache.items()}
     for chunk in (1, 7, 16, n_graphs):                                     # 44 = 6 * 7 + 2 = 2 * 16 + 12: short last chunks
         got = TS.embed_dataset(m, graphs, chunk=chunk)
         print("  chunk %d: bitwise equal to one chunk: %s" % (chunk, torch.equal(got, full)))
         torch.testing.assert_close(got.cpu(), want, rtol=1e-4, atol=1e-4)
-    assert {k: id(v) for k, v in cache.items()} == entries                 # nothing uploaded again
+    assert {k: id(v) for k, v in cache.items()} == entries and cache.h2d == 3 * n_graphs     # nothing uploaded again
     dp, dn = net(graphs[20], graphs[21], graphs[22])[:2]                   # ... and the reverse: a step on graphs an evaluation made resident
-    assert {k: id(v) for k, v in cache.items()} == entries and torch.isfinite(dp).all() and torch.isfinite(dn).all()
+    assert {k: id(v) for k, v in cache.items()} == entries and cache.h2d == 3 * n_graphs
+    assert torch.isfinite(dp).all() and torch.isfinite(dn).all()
     as_dict = {}
     for g in graphs:
         as_dict.setdefault(g.graph["label"], []).append(g)

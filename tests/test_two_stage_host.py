@@ -212,9 +212,17 @@ def test_chunk_and_neighbour_arguments_are_checked():
 
 
 def test_shared_resident_caches_are_per_model():
-    """a tripletnet and embed_dataset around the same model see one cache (no second upload of a graph); another model has its own"""
-    from two_stage_gnn_amd import sag_triplet as ST, triplet as T
+    """a tripletnet and embed_dataset around the same model see one cache (no second upload of a graph); another model has its own;
+    one registry serves the three families"""
+    import types
+    from two_stage_gnn_amd import eigen_triplet as ET, resident as RS, sag_triplet as ST, triplet as T
     a, b = _Stub(), _Stub()
     assert T.resident_cache(a) is T.resident_cache(a) and T.resident_cache(a) is not T.resident_cache(b)
-    assert T.tripletnet(a)._resident is T.resident_cache(a)
+    assert T.resident_cache is RS.resident_cache and ST.resident_cache is RS.resident_cache and ST.ResidentCache is RS.ResidentCache
+    assert T.tripletnet(a)._resident is T.resident_cache(a) and isinstance(T.tripletnet(a)._resident, RS.ResidentCache)
     assert ST.tripletnet(a).cache is ST.resident_cache(a) and ST.tripletnet(b).cache is not ST.tripletnet(a).cache
+    args = types.SimpleNamespace(pool_sizes="3_2", num_pool_matrix=2, num_pool_final_matrix=1)
+    for m in (a, b):
+        m.pool_sizes, m.num_pool_matrix, m.num_pool_final_matrix = [3, 2], 2, 1
+    assert ET.tripletnet(a, args).cache is ET.tripletnet(a, args).cache and ET.tripletnet(a, args).cache is RS.resident_cache(a)
+    assert ET.tripletnet(b, args).cache is RS.resident_cache(b) and ET.tripletnet(b, args).cache is not ET.tripletnet(a, args).cache

@@ -19,6 +19,7 @@ import torch
 from . import _native as nat
 from . import message_passing as mp
 from .graph import GraphBatch, exclusive_scan
+from .resident import concat_csr
 
 N_POOL = 5          # pooling matrices per level (the reference hard-codes num_nodes_in_largest_clusters = 5)
 N_FINAL = 4         # final matrices (num_nodes_before_final = 4)
@@ -324,28 +325,11 @@ def batch_from_dense(adj, batch_num_nodes, adj_pooled_list, batch_num_nodes_list
 
 
 # ----------------------------------------------------------------------------- EigenBatches -> one EigenBatch, on the device
-def _concat_graphs(gs, nmax):
-    """block-diagonal packed GraphBatch of the graphs of several packed GraphBatches (sizes and nnz are host-side numbers: device-side
-    concatenations with a row offset on `col` and an entry offset on `rowptr`, no host synchronisation)"""
-    dev = gs[0].device
-    nnz = int(sum(q.nnz for q in gs))
-    weighted = any(q.val is not None for q in gs)
-    rps, cols, vals, e0, r0 = [], [], [], 0, 0
-    for q in gs:
-        rp = q.rowptr[:q.n_rows]
-        rps.append(rp + e0 if e0 else rp)
-        if q.nnz:
-            c = q.col[:q.nnz]
-            cols.append(c + r0 if r0 else c)
-            if weighted:
-                vals.append(q.val[:q.nnz] if q.val is not None else torch.ones(q.nnz, dtype=torch.float32, device=dev))
-        e0 += q.nnz
-        r0 += q.n_rows
-    rps.append(torch.full((nmax + 1,), nnz, dtype=torch.int32, device=dev))          # the last real row's end + the empty ghost rows
-    col = torch.cat(cols) if nnz else torch.zeros(1, dtype=torch.int32, device=dev)
-    val = (torch.cat(vals) if nnz else torch.zeros(1, dtype=torch.float32, device=dev)) if weighted else None
-    g = GraphBatch.from_csr(torch.cat(rps), col, val, np.concatenate([np.asarray(q.sizes, dtype=np.int64) for q in gs]), nmax,
-                            assume_symmetric=all(q.symmetric for q in gs))
+def _concat(gs, nmax):
+    """block-diagonal packed GraphBatch of the graphs of several packed GraphBatches (``resident.concat_csr``: device-side
+    concatenations, no host synchronisation)"""
+    rowptr, col, val, nnz, sym = concat_csr([(q.rowptr, q.col, q.val, q.n_rows, q.nnz, q.symmetric) for q in gs], nmax + 1)
+    g = GraphBatch.from_csr(rowptr, col, val, np.concatenate([np.asarray(q.sizes, dtype=np.int64) for q in gs]), nmax, assume_symmetric=sym)
     g.nnz = nnz
     return g
 
@@ -364,7 +348,7 @@ def concat_batches(batches):
                 (eb.final_coef is not None and eb.final_coef.size(1) != first.final_coef.size(1)):
             raise ValueError("concat_batches: the batches must share Nmax, the number of levels and of pooling matrices")
     prev = [eb.g0 for eb in batches]
-    g0 = _concat_graphs(prev, nmax)
+    g0 = _concat(prev, nmax)
     dev = g0.device
     levels = []
     for i in range(L):
@@ -383,7 +367,7 @@ def concat_batches(batches):
             c0 += K
         bp.append(torch.full((1,), r0, dtype=torch.int32, device=dev))
         out = EigenLevel()
-        out.g, out.J = _concat_graphs([lv.g for lv in lvs], nmax), lvs[0].J
+        out.g, out.J = _concat([lv.g for lv in lvs], nmax), lvs[0].J
         out.cluster_of, out.coef, out.members, out.bptr = torch.cat(clus), torch.cat(coef), torch.cat(mem), torch.cat(bp)
         levels.append(out)
         prev = [lv.g for lv in lvs]

@@ -7,8 +7,8 @@ The reference calls ``WavePoolingGcnEncoder`` three times at B = 1 (anchor, posi
   clusters / coefficients / bucket lists, the final coefficients — the compact pieces ``eigen_pool.collate`` builds) and goes to the
   device at the object's first use, together with its feature rows (16-byte row stride).  No ``[Nmax, Nmax]`` array is uploaded.
   ``feats`` are host numpy arrays that cross_val.py builds once and the reference never writes, so they are cached with the structure
-  (as ``triplet._resident`` caches them; ``Code/sag`` keeps device tensors instead, which ``sag_triplet`` reads in place).  The cache is
-  ``sag_triplet.ResidentCache`` keyed by the object's identity; ``TSGNN_TRIPLET_CACHE=0`` (``triplet.RESIDENT``) rebuilds every step;
+  (as ``triplet.resident_graph`` caches them; ``Code/sag`` keeps device tensors instead, which ``sag_triplet`` reads in place).  The
+  cache is the model's ``resident.ResidentCache``, keyed by the object's identity; ``TSGNN_TRIPLET_CACHE=0`` rebuilds every step;
 * a step concatenates three cached graphs into one three-graph ``EigenBatch`` on the device (``eigen_pool.concat_batches``) and runs the
   model ONCE with per-graph statistics (``per_graph_bn``: the fresh ``BatchNorm1d(Nmax)`` at B = 1 is a per-row layer norm) — level 0
   as the fused stack node, pooled levels layer by layer;
@@ -20,18 +20,15 @@ The reference calls ``WavePoolingGcnEncoder`` three times at B = 1 (anchor, posi
 import numpy as np
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import _native as nat
 from . import eigen_pool as ep
 from . import message_passing as mp
+from . import resident as R
 from . import triplet as _t
 from .graph import GraphBatch
-from .sag_triplet import ResidentCache
 
 MarginRankingLoss = _t.MarginRankingLoss        # the documented replacement for the loop's `criterion` (train_triplet.py:292)
-_EPS = 1e-6                                     # F.pairwise_distance's default
-_GPU_ONLY = "two_stage_gnn_amd operators run on the GPU only (no CPU fallback)"
 
 
 # ----------------------------------------------------------------------------- host half: a .graph dict -> compact pieces (pure numpy)
@@ -42,15 +39,6 @@ def _square(d, key, nmax):
     if a.ndim != 2 or a.shape[0] != a.shape[1] or (nmax is not None and a.shape[0] != nmax):
         raise ValueError("%s has shape %s, expected [Nmax, Nmax]%s" % (key, a.shape, "" if nmax is None else " with Nmax = %d" % nmax))
     return a
-
-
-def _csr(a, n):
-    """weighted CSR of a[:n, :n]: columns ascending inside a row (as GraphBatch.from_dense fills them) + is it symmetric"""
-    sub = np.asarray(a[:n, :n], dtype=np.float32)
-    r, c = np.nonzero(sub)
-    rp = np.zeros(n + 1, dtype=np.int32)
-    np.cumsum(np.bincount(r, minlength=n), out=rp[1:])
-    return rp, c.astype(np.int32), np.ascontiguousarray(sub[r, c]), bool(np.array_equal(sub, sub.T))
 
 
 def pack_host(graph, L, J, Jf):
@@ -70,7 +58,7 @@ def pack_host(graph, L, J, Jf):
     n0 = int(graph["num_nodes"])
     if not 1 <= n0 <= nmax:
         raise ValueError("num_nodes must lie in [1, Nmax]")
-    sizes, graphs, levels = [n0], [_csr(_square(graph, "adj", nmax), n0)], []
+    sizes, graphs, levels = [n0], [R.dense_csr_host(_square(graph, "adj", nmax), n0)], []
     for i in range(L):
         n = sizes[-1]
         k = int(graph["num_nodes_%d" % (i + 1)])
@@ -92,7 +80,7 @@ def pack_host(graph, L, J, Jf):
         bptr = np.zeros(k + 2, dtype=np.int32)
         np.cumsum(np.bincount(key, minlength=k + 1), out=bptr[1:])
         levels.append({"cluster_of": clus, "coef": np.ascontiguousarray(coef), "bptr": bptr, "members": members})
-        graphs.append(_csr(_square(graph, "adj_pool_%d" % (i + 1), nmax), k))
+        graphs.append(R.dense_csr_host(_square(graph, "adj_pool_%d" % (i + 1), nmax), k))
         sizes.append(k)
     final = None
     if Jf:
@@ -149,11 +137,7 @@ def to_device(packed, feats, dev):
     if packed["final"] is not None:
         fc = _up(packed["final"], dev)
         copies += 1
-    f = np.asarray(feats, dtype=np.float32)[:sizes[0]]
-    ld = (f.shape[1] + 3) // 4 * 4                                     # 16-byte rows for the float4 gather
-    fp = np.zeros((sizes[0], ld), dtype=np.float32)
-    fp[:, :f.shape[1]] = f
-    return ep.EigenBatch(gs[0], levels, fc, nmax), _up(fp, dev), copies + 1
+    return ep.EigenBatch(gs[0], levels, fc, nmax), R.padded_rows(feats, sizes[0], dev), copies + 1
 
 
 # ----------------------------------------------------------------------------- pred_model + both distances: one launch each way
@@ -168,7 +152,7 @@ class _Mlp2TripletTail(torch.autograd.Function):
         D, H, E = int(w1.size(1)), int(w1.size(0)), int(w2.size(0))
         dev = r.device
         h, embed, dist = mp._f32(3, H, device=dev), mp._f32(3, E, device=dev), mp._f32(2, device=dev)
-        nat.call("mlp2_triplet_fwd_f32", r, r.stride(0), w1, b1, w2, b2, D, H, E, _EPS, h, embed, dist)
+        nat.call("mlp2_triplet_fwd_f32", r, r.stride(0), w1, b1, w2, b2, D, H, E, R.EPS, h, embed, dist)
         ctx.save_for_backward(r, w1, w2, h, embed, dist)
         ctx.params = params
         ctx.set_materialize_grads(False)                  # an unused output's gradient arrives as None, not as a zero-filled tensor
@@ -180,16 +164,12 @@ class _Mlp2TripletTail(torch.autograd.Function):
         D, H, E = int(w1.size(1)), int(w1.size(0)), int(w2.size(0))
         dev = r.device
         c = lambda t: t.contiguous() if t is not None else None
-        pw1, pb1, pw2, pb2 = ctx.params
         # straight into the trainer's flat gradient bucket when one is installed (FlatTrainer): no AccumulateGrad copy, no zeroing
-        dw1, s1 = mp._sink_or_new(pw1, (H, D), dev)
-        dw2, s2 = mp._sink_or_new(pw2, (E, H), dev)
-        db1, t1 = mp._sink_or_new(pb1, (H,), dev) if pb1 is not None else (None, False)
-        db2, t2 = mp._sink_or_new(pb2, (E,), dev) if pb2 is not None else (None, False)
+        (dw1, db1, dw2, db2), grads = mp._sinks_or_new(ctx.params, ((H, D), (H,), (E, H), (E,)), dev)
         dr = mp._f32(3, D, device=dev) if ctx.needs_input_grad[0] else None
-        nat.call("mlp2_triplet_bwd_f32", r, r.stride(0), w1, w2, h, embed, dist, _EPS, c(g_dp), c(g_dn), c(g_a), c(g_p), c(g_n), D, H, E,
+        nat.call("mlp2_triplet_bwd_f32", r, r.stride(0), w1, w2, h, embed, dist, R.EPS, c(g_dp), c(g_dn), c(g_a), c(g_p), c(g_n), D, H, E,
                  dr, D, dw1, db1, dw2, db2)
-        return dr, None if s1 else dw1, None if t1 else db1, None if s2 else dw2, None if t2 else db2
+        return (dr,) + grads
 
 
 def _linears(pred):
@@ -241,13 +221,12 @@ class tripletnet(nn.Module):
             raise ValueError("args.num_pool_final_matrix = %d, the model's is %d"
                              % (args.num_pool_final_matrix, model.num_pool_final_matrix))
         self.L, self.J, self.Jf = len(pool_sizes), int(args.num_pool_matrix), int(args.num_pool_final_matrix)
-        self.cache = ResidentCache()
-        self._zeros = {}                                     # the Nmax zero ghost-slot feature rows, per (Nmax, width, device)
+        self.cache = R.cache_for(model)                      # (the entries depend on (L, J, Jf) only, which equal the model's)
 
     # ------------------------------------------------------------------ graphs
     def _graph(self, obj, dev):
         """the device side of one graph object (built at its first use)"""
-        e = self.cache.lookup(obj, dev.index) if _t.RESIDENT else None
+        e = self.cache.lookup(obj, dev.index) if R.RESIDENT else None
         if e is not None:
             return e
         e = _Graph()
@@ -255,7 +234,7 @@ class tripletnet(nn.Module):
         e.eb, e.feats, copies = to_device(packed, obj.graph["feats"], dev)
         e.n, e.nmax = packed["n"][0], packed["nmax"]
         self.cache.h2d += copies
-        return self.cache.store(obj, e, dev.index) if _t.RESIDENT else e
+        return self.cache.store(obj, e, dev.index) if R.RESIDENT else e
 
     def batch(self, a, p, n):
         """the triplet as one three-graph batch on the device: the cached pieces concatenated there (no host synchronisation, no
@@ -265,7 +244,7 @@ class tripletnet(nn.Module):
         lie outside a step captured on ``embed(batch)``."""
         dev = next(self.model.parameters()).device
         if dev.type != "cuda":
-            raise RuntimeError(_GPU_ONLY)
+            raise RuntimeError(R.GPU_ONLY)
         parts = [self._graph(o, dev) for o in (a, p, n)]
         if any(q.nmax != parts[0].nmax for q in parts):
             raise ValueError("the graphs of a triplet must be padded to the same Nmax")
@@ -273,7 +252,7 @@ class tripletnet(nn.Module):
             raise ValueError("the graphs of a triplet must have the same number of features")
         b = _Triplet()
         b.eb = ep.concat_batches([q.eb for q in parts])
-        b.x = torch.cat([q.feats for q in parts] + [_t._ghost_zeros(parts[0].nmax, parts[0].feats.size(1), dev, self._zeros)])
+        b.x = torch.cat([q.feats for q in parts] + [R.ghost_zeros(parts[0].nmax, parts[0].feats.size(1), dev)])
         b.sizes = b.eb.g0.sizes
         return b
 
@@ -287,19 +266,12 @@ class tripletnet(nn.Module):
             return _Mlp2TripletTail.apply(r, pm[0].weight, pm[0].bias, pm[2].weight, pm[2].bias)
         if kind == "linear":
             return _t._TripletTail.apply(r, pm.weight, pm.bias)
-        e = pm(r)
-        ea, e_p, en = e[0:1], e[1:2], e[2:3]
-        return F.pairwise_distance(ea, e_p, 2), F.pairwise_distance(ea, en, 2), ea, e_p, en
+        return R.torch_distances(pm(r))
 
     def embed(self, b):
         """the step on a batch from ``batch()``: the model once with the per-graph statistics of a B = 1 call, then the tail"""
-        m = self.model
-        prev = getattr(m, "per_graph_bn", False)
-        m.per_graph_bn = True
-        try:
-            r = m(b.x, b.eb, readout_only=True)
-        finally:
-            m.per_graph_bn = prev
+        with R.per_graph_statistics(self.model):
+            r = self.model(b.x, b.eb, readout_only=True)
         return self._tail(r)
 
     def forward(self, a, p, n):

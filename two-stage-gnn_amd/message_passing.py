@@ -1133,6 +1133,17 @@ def _sink_or_new(param, shape, device):
     return _f32(*shape, device=device), False
 
 
+def _sinks_or_new(params, shapes, device):
+    """``_sink_or_new`` for the saved Parameter objects of a backward (None: an absent bias) -> (gradient buffers for the kernel, None
+    for an absent parameter; what ``backward`` returns for them: None where the buffer is the sink's or absent)"""
+    bufs, rets = [], []
+    for p, shape in zip(params, shapes):
+        buf, sunk = _sink_or_new(p, shape, device) if p is not None else (None, True)
+        bufs.append(buf)
+        rets.append(None if sunk else buf)
+    return bufs, tuple(rets)
+
+
 def unit_seed(device):
     """cached scalar 1.0 to seed ``loss.backward(gradient=unit_seed(dev))``: no fill launch, and the fused loss node
     recognises the object and skips the multiply by 1."""

@@ -5,13 +5,11 @@ in ONE batch with per-graph pooling and read-outs are exactly those three calls:
 readout node once (``sag_stack`` / ``sag_stack_sage``), and the head on the three readout rows, its log_softmax and both
 ``F.pairwise_distance`` are one launch each way (csrc/mlp_head.hip, ``tsgnn_mlp3_triplet_fwd_f32 / _bwd_f32``).
 
-A ``Data`` object's graph structure (CSR rows of its edge list, symmetry flag) is built at its first use and stays on the device, keyed
-by the object's identity (``TSGNN_TRIPLET_CACHE=0``: rebuilt every step); a step concatenates three cached graphs on the device.  The
+A ``Data`` object's graph structure (CSR rows of its edge list, symmetry flag) is built at its first use and stays on the device, in
+the model's ``resident.ResidentCache`` (``TSGNN_TRIPLET_CACHE=0``: rebuilt every step); a step concatenates three cached graphs on the device.  The
 feature rows are NOT cached: ``data.x`` already is a device tensor (the loop's ``.to(device)``), one concatenation launch per step reads it
 in place, and a copy kept here would go stale when a caller refills ``data.x``.
 """
-import weakref
-
 import numpy as np
 import torch
 import torch.nn as nn
@@ -19,12 +17,12 @@ import torch.nn.functional as F
 
 from . import _native as nat
 from . import message_passing as mp
+from . import resident as R
 from . import triplet as _t
 from .graph import GraphBatch
+from .resident import ResidentCache, resident_cache       # (importable from here as before)
 
 MarginRankingLoss = _t.MarginRankingLoss        # the documented replacement for the loop's `criterion` (train_triplet.py:196)
-_EPS = 1e-6                                     # F.pairwise_distance's default
-_GPU_ONLY = "two_stage_gnn_amd operators run on the GPU only (no CPU fallback)"
 
 
 # ----------------------------------------------------------------------------- host half: edge lists -> CSR (pure numpy)
@@ -59,60 +57,10 @@ def pack_host(datas):
     return (np.concatenate(rps).astype(np.int32), col, np.repeat(np.arange(sizes.size, dtype=np.int64), sizes), sizes, tuple(sym))
 
 
-# ----------------------------------------------------------------------------- the graphs of the dataset, resident
-_MAX_RESIDENT = 1 << 17
-
-
+# ----------------------------------------------------------------------------- the graphs of the dataset, resident (see resident.py)
 class _Graph:
     """device-side structure of one Data object"""
     __slots__ = ("ref", "n", "nnz", "rowptr", "col", "symmetric")
-
-
-class ResidentCache:
-    """entries keyed by the identity of the object they were built from; an entry only answers for THAT object (a weak reference is
-    compared on every look-up, so a recycled ``id()`` cannot hit a stale entry).  Objects that cannot be weakly referenced are kept
-    alive by their entry instead.  Counters: ``hits`` / ``misses`` of look-ups, ``h2d`` = host-to-device copies of graph structure."""
-
-    def __init__(self):
-        self._entries = {}
-        self.hits = self.misses = self.h2d = 0
-
-    def lookup(self, obj, dev_index=None):
-        hit = self._entries.get((id(obj), dev_index))
-        if hit is not None and hit.ref() is obj:
-            self.hits += 1
-            return hit
-        self.misses += 1
-        return None
-
-    def store(self, obj, entry, dev_index=None):
-        key = (id(obj), dev_index)
-        try:
-            entry.ref = weakref.ref(obj, lambda _r, k=key, e=entry: self._drop(k, e))
-        except TypeError:
-            entry.ref = lambda o=obj: o
-        if len(self._entries) >= _MAX_RESIDENT:
-            self._entries.clear()
-        self._entries[key] = entry
-        return entry
-
-    def _drop(self, key, entry):
-        if self._entries.get(key) is entry:
-            del self._entries[key]
-
-    def __len__(self):
-        return len(self._entries)
-
-
-_shared_resident = weakref.WeakKeyDictionary()
-
-
-def resident_cache(model):
-    """the ResidentCache of `model`: one per network, shared by every ``tripletnet`` around it and by ``two_stage.embed_dataset``"""
-    c = _shared_resident.get(model)
-    if c is None:
-        c = _shared_resident[model] = ResidentCache()
-    return c
 
 
 class _Triplet:
@@ -125,7 +73,7 @@ def _check_gpu(datas):
     for d in datas:
         for t in (d.x, d.edge_index):
             if not (isinstance(t, torch.Tensor) and t.is_cuda):
-                raise RuntimeError(_GPU_ONLY)
+                raise RuntimeError(R.GPU_ONLY)
 
 
 # ----------------------------------------------------------------------------- head + log_softmax + both distances: one launch each way
@@ -142,7 +90,7 @@ class _SagTripletTail(torch.autograd.Function):
         a1, a2 = mp._f32(3, D1, device=dev), mp._f32(3, D2, device=dev)
         embed, dist = mp._f32(3, C, device=dev), mp._f32(2, device=dev)
         p_, seed, state, used = drop if drop is not None else (0.0, 0, None, None)
-        nat.call("mlp3_triplet_fwd_f32", r, r.stride(0), w1, b1, float(p_), int(seed), state, used, w2, b2, w3, b3, D0, D1, D2, C, _EPS,
+        nat.call("mlp3_triplet_fwd_f32", r, r.stride(0), w1, b1, float(p_), int(seed), state, used, w2, b2, w3, b3, D0, D1, D2, C, R.EPS,
                  a1, a2, embed, dist)
         ctx.save_for_backward(r, w1, w2, w3, a1, a2, embed, dist)
         ctx.keep_scale = 1.0 / (1.0 - float(p_))
@@ -156,19 +104,12 @@ class _SagTripletTail(torch.autograd.Function):
         D0, D1, D2, C = int(w1.size(1)), int(w1.size(0)), int(w2.size(0)), int(w3.size(0))
         dev = r.device
         c = lambda t: t.contiguous() if t is not None else None
-        pw1, pb1, pw2, pb2, pw3, pb3 = ctx.params
         # straight into the trainer's flat gradient bucket when one is installed (FlatTrainer): no AccumulateGrad copy, no zeroing
-        dw1, s1 = mp._sink_or_new(pw1, (D1, D0), dev)
-        dw2, s2 = mp._sink_or_new(pw2, (D2, D1), dev)
-        dw3, s3 = mp._sink_or_new(pw3, (C, D2), dev)
-        db1, t1 = mp._sink_or_new(pb1, (D1,), dev) if pb1 is not None else (None, False)
-        db2, t2 = mp._sink_or_new(pb2, (D2,), dev) if pb2 is not None else (None, False)
-        db3, t3 = mp._sink_or_new(pb3, (C,), dev) if pb3 is not None else (None, False)
+        (dw1, db1, dw2, db2, dw3, db3), grads = mp._sinks_or_new(ctx.params, ((D1, D0), (D1,), (D2, D1), (D2,), (C, D2), (C,)), dev)
         dx = mp._f32(3, D0, device=dev) if ctx.needs_input_grad[0] else None
-        nat.call("mlp3_triplet_bwd_f32", r, r.stride(0), w1, w2, w3, a1, a2, embed, dist, _EPS, ctx.keep_scale, c(g_dp), c(g_dn), c(g_a),
+        nat.call("mlp3_triplet_bwd_f32", r, r.stride(0), w1, w2, w3, a1, a2, embed, dist, R.EPS, ctx.keep_scale, c(g_dp), c(g_dn), c(g_a),
                  c(g_p), c(g_n), D0, D1, D2, C, dw1, db1, dw2, db2, dw3, db3, dx, D0)
-        return (dx, None if s1 else dw1, None if t1 else db1, None if s2 else dw2, None if t2 else db2, None if s3 else dw3,
-                None if t3 else db3, None)
+        return (dx,) + grads + (None,)
 
 
 def tail_ok(model, r):
@@ -206,13 +147,13 @@ class tripletnet(nn.Module):
     def __init__(self, model):
         super().__init__()
         self.model = model
-        self.cache = resident_cache(model) if _t.RESIDENT else ResidentCache()
+        self.cache = R.cache_for(model)
         self._batch_vec = {}
 
     # ------------------------------------------------------------------ graphs
     def _graph(self, d, dev):
         """the device-side structure of one Data object (built at its first use)"""
-        e = self.cache.lookup(d, dev.index) if _t.RESIDENT else None
+        e = self.cache.lookup(d, dev.index) if R.RESIDENT else None
         if e is not None:
             return e
         rowptr, col, _, sizes, sym = pack_host([d])
@@ -221,7 +162,7 @@ class tripletnet(nn.Module):
         e.rowptr = torch.from_numpy(rowptr).to(dev)
         e.col = torch.from_numpy(col).to(dev) if col.size else torch.zeros(0, dtype=torch.int32, device=dev)
         self.cache.h2d += 2
-        return self.cache.store(d, e, dev.index) if _t.RESIDENT else e
+        return self.cache.store(d, e, dev.index) if R.RESIDENT else e
 
     def batch(self, a, p, n):
         """the three graphs as one block-diagonal batch: cached structure concatenated on the device (no host synchronisation, no
@@ -234,28 +175,10 @@ class tripletnet(nn.Module):
         _check_gpu(trip)
         dev = trip[0].x.device
         parts = [self._graph(d, dev) for d in trip]
-        g = GraphBatch()
+        g = GraphBatch()                                                         # (filled by hand: no bookkeeping upload, no row_maps launch)
         g.sizes = np.array([q.n for q in parts], dtype=np.int64)
-        if len(parts) > _t._PER_PIECE_MAX:                                       # a chunk of a dataset: one add for all offsets
-            nnzs = np.array([q.nnz for q in parts], dtype=np.int64)
-            e0, r0 = int(nnzs.sum()), int(g.sizes.sum())
-            g.rowptr = torch.cat([_t.offset_cat([q.rowptr[:-1] for q in parts], g.sizes, np.concatenate([[0], np.cumsum(nnzs)[:-1]]), dev),
-                                  torch.full((1,), e0, dtype=torch.int32, device=dev)])
-            g.col = (_t.offset_cat([q.col for q in parts], nnzs, np.concatenate([[0], np.cumsum(g.sizes)[:-1]]), dev) if e0
-                     else torch.zeros(1, dtype=torch.int32, device=dev))
-        else:
-            rps, cols, e0, r0 = [], [], 0, 0
-            for i, q in enumerate(parts):
-                rp = q.rowptr if i == len(parts) - 1 else q.rowptr[:-1]
-                rps.append(rp + e0 if e0 else rp)
-                if q.nnz:
-                    cols.append(q.col + r0 if r0 else q.col)
-                e0 += q.nnz
-                r0 += q.n
-            g.rowptr = torch.cat(rps)
-            g.col = torch.cat(cols) if cols else torch.zeros(1, dtype=torch.int32, device=dev)
-        g.B, g.nmax, g.n_rows, g.n_ghost, g.layout, g.device = len(parts), int(g.sizes.max()), r0, 0, "packed", dev
-        g.val, g.nnz, g.symmetric = None, e0, all(q.symmetric for q in parts)
+        g.rowptr, g.col, g.val, g.nnz, g.symmetric = R.concat_csr([(q.rowptr, q.col, None, q.n, q.nnz, q.symmetric) for q in parts], 1)
+        g.B, g.nmax, g.n_rows, g.n_ghost, g.layout, g.device = len(parts), int(g.sizes.max()), int(g.sizes.sum()), 0, "packed", dev
         b = _Triplet()
         x = torch.cat([d.x if d.x.dim() == 2 else d.x.view(d.x.size(0), -1) for d in trip])
         b.x = x if x.dtype == torch.float32 else x.float()
@@ -282,7 +205,7 @@ class tripletnet(nn.Module):
         return b._ei, b._batch
 
     # ------------------------------------------------------------------ forward
-    def _readout(self, b):
+    def readout(self, b):
         """[3, 2 nhid]: the three levels' [gmp || gap] summed (network.py:33-46), per graph"""
         from . import pyg
         m = self.model
@@ -299,6 +222,8 @@ class tripletnet(nn.Module):
             outs.append(torch.cat([pyg.global_max_pool(x, batch), pyg.global_mean_pool(x, batch)], dim=1))
         return outs[0] + outs[1] + outs[2]
 
+    _readout = readout
+
     def _torch_tail(self, r):
         from . import pyg
         m = self.model
@@ -306,8 +231,7 @@ class tripletnet(nn.Module):
         x = F.dropout(x, p=m.dropout_ratio, training=m.training)
         x = pyg.relu(mp.linear_oi(x, m.lin2.weight, m.lin2.bias))
         e = F.log_softmax(mp.linear_oi(x, m.lin3.weight, m.lin3.bias), dim=-1)
-        ea, ep, en = e[0:1], e[1:2], e[2:3]
-        return F.pairwise_distance(ea, ep, 2), F.pairwise_distance(ea, en, 2), ea, ep, en
+        return R.torch_distances(e)
 
     def _tail(self, r):
         """readout rows [3, 2 nhid] -> (dist_p, dist_n, embed_a, embed_p, embed_n): one launch, or the torch composition for a head
@@ -323,7 +247,7 @@ class tripletnet(nn.Module):
         return self._torch_tail(r)
 
     def embed(self, b):
-        return self._tail(self._readout(b))
+        return self._tail(self.readout(b))
 
     def forward(self, a, p, n):
         """a, p, n: PyG-``Data``-like objects with ``.x [n, F]`` and ``.edge_index [2, E]`` on the GPU (anything else on them is

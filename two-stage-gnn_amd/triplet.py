@@ -6,145 +6,77 @@ block-diagonal GraphBatch and go through the kernels once; ``per_graph_bn`` keep
 would have alone in its batch, so embeddings and gradients equal the three separate B = 1 calls.
 """
 import os
-import weakref
+import sys
+import types
 
 import numpy as np
 import torch
 import torch.nn as nn
-import torch.nn.functional as F
 
 from . import _native as nat
 from . import message_passing as mp
+from . import resident as R
 from .graph import GraphBatch
+from .resident import resident_cache                               # (the documented name of the model's cache)
 
 
-# ----------------------------------------------------------------------------- the graphs of the dataset, resident
-# The reference uploads the three dense [1, Nmax, Nmax] adjacencies of a triplet at every step (tripletnet.py:18-33: 12 MB for DD)
-# although the sampler draws them from a fixed set of graph objects (triplet_sampler.py).  Here a graph object's CSR rows, features
-# and assignment features go to the device ONCE (keyed by its `adj` array; ~100 KB for a DD graph, so the whole dataset stays
-# resident in a corner of the 288 GB) and a step only concatenates three of them into the block-diagonal batch: a handful of small
-# device copies, no PCIe traffic, no scan of 3 Nmax^2 floats, no host synchronisation.  The arrays are taken to be immutable, as the
-# reference treats them (cross_val.py:158-184 builds them once); TSGNN_TRIPLET_CACHE=0 restores the upload per step.
-RESIDENT = os.environ.get("TSGNN_TRIPLET_CACHE", "1") != "0"
-_MAX_RESIDENT = 1 << 17
+class _Module(types.ModuleType):
+    """``triplet.RESIDENT`` (TSGNN_TRIPLET_CACHE) reads and assigns ``resident.RESIDENT``, the one switch every caller reads"""
+    RESIDENT = property(lambda self: R.RESIDENT, lambda self, on: setattr(R, "RESIDENT", bool(on)))
 
 
+sys.modules[__name__].__class__ = _Module
+
+
+# ----------------------------------------------------------------------------- the graphs of the dataset, resident (see resident.py)
 class _Resident:
+    """device pieces of one graph object (~100 KB for a DD graph), keyed by its ``adj`` array"""
     __slots__ = ("ref", "n", "nnz", "nmax", "rowptr", "col", "val", "feats", "assign", "symmetric")
 
 
-def _resident(obj, dev, cache):
-    """the device-side pieces of one graph object (built at its first use)"""
+def resident_graph(obj, dev, cache):
+    """the device-side pieces of one graph object (built at its first use): CSR rows of ``adj[:n, :n]`` (no ``val`` when every weight
+    is 1.0), feature rows and, when they differ from those, assignment feature rows"""
     adj = obj.graph["adj"]
-    key = (id(adj), dev.index)
-    hit = cache.get(key)
-    if hit is not None and hit.ref() is adj:
-        return hit
-    a = np.asarray(adj, dtype=np.float32)
+    e = cache.lookup(adj, dev.index)
+    if e is not None:
+        return e
+    a = np.asarray(adj)
     n = int(obj.graph["num_nodes"])
     if a.ndim != 2 or a.shape[0] != a.shape[1] or not 0 <= n <= a.shape[0]:
         raise ValueError("adj must be [Nmax, Nmax] with num_nodes <= Nmax")
-    sub = a[:n, :n]
-    r, c = np.nonzero(sub)                                              # row-major: columns ascending inside a row, as from_dense fills them
-    rp = np.zeros(n + 1, dtype=np.int32)
-    np.cumsum(np.bincount(r, minlength=n), out=rp[1:])
-    v = sub[r, c]
+    rp, c, v, sym = R.dense_csr_host(a, n)
     e = _Resident()
-    e.ref = weakref.ref(adj) if isinstance(adj, np.ndarray) else (lambda: adj)
-    e.n, e.nnz, e.nmax = n, int(r.size), int(a.shape[0])
-    e.symmetric = bool(np.array_equal(sub, sub.T))
-    e.rowptr = torch.from_numpy(rp).to(dev)
-    e.col = torch.from_numpy(c.astype(np.int32)).to(dev)
-    e.val = None if bool((v == 1.0).all()) else torch.from_numpy(np.ascontiguousarray(v)).to(dev)
-
-    def rows(key_):
-        f = np.asarray(obj.graph[key_], dtype=np.float32)[:n]
-        ld = (f.shape[1] + 3) // 4 * 4                                  # 16-byte rows for the float4 gather
-        out = torch.zeros(n, ld, dtype=torch.float32, device=dev)
-        out[:, :f.shape[1]] = torch.from_numpy(np.ascontiguousarray(f)).to(dev)
-        return out
-
-    e.feats = rows("feats")
+    e.n, e.nnz, e.nmax, e.symmetric = n, int(c.size), int(a.shape[0]), sym
+    e.rowptr, e.col = torch.from_numpy(rp).to(dev), torch.from_numpy(c).to(dev)
+    e.val = None if bool((v == 1.0).all()) else torch.from_numpy(v).to(dev)
+    e.feats = R.padded_rows(obj.graph["feats"], n, dev)
     fa, ff = np.asarray(obj.graph["assign_feats"]), np.asarray(obj.graph["feats"])
-    e.assign = None if (fa.shape == ff.shape and np.array_equal(fa, ff)) else rows("assign_feats")
-    if len(cache) >= _MAX_RESIDENT:
-        cache.clear()
-    cache[key] = e
-    return e
+    e.assign = None if (fa.shape == ff.shape and np.array_equal(fa, ff)) else R.padded_rows(fa, n, dev)
+    cache.h2d += 3 + (e.val is not None) + (e.assign is not None)
+    return cache.store(adj, e, dev.index)
 
 
-_shared_resident = weakref.WeakKeyDictionary()
-
-
-def resident_cache(model):
-    """the resident graphs of `model`: ONE dictionary per encoder, shared by every ``tripletnet`` around it and by
-    ``two_stage.embed_dataset``, so a graph object uploaded by a training step is not uploaded again by an evaluation (and the reverse)"""
-    c = _shared_resident.get(model)
-    if c is None:
-        c = _shared_resident[model] = {}
-    return c
-
-
-def _ghost_zeros(nmax, ld, dev, cache):
-    key = ("z", nmax, ld, dev.index)
-    z = cache.get(key)
-    if z is None:
-        z = cache[key] = torch.zeros(nmax, ld, dtype=torch.float32, device=dev)
-    return z
-
-
-def offset_cat(pieces, counts, offsets, dev):
-    """cat(pieces[i] + offsets[i]) with ONE add for all pieces (a chunk of a dataset has hundreds of them: two small uploads of
-    host-known numbers instead of one launch per graph); counts[i] = len(pieces[i])"""
-    off = torch.from_numpy(np.asarray(offsets, dtype=np.int32)).to(dev)
-    cnt = torch.from_numpy(np.asarray(counts, dtype=np.int64)).to(dev)
-    return torch.cat(pieces) + torch.repeat_interleave(off, cnt, output_size=int(np.sum(counts)))
-
-
-_PER_PIECE_MAX = 8          # up to this many graphs (a triplet) every piece gets its own offset launch: nothing is uploaded
-
-
-def _assemble(parts, dev, cache):
-    """resident graphs (the three of a triplet, or a chunk of a dataset) -> (GraphBatch, feature rows, assignment rows or None): the
-    block-diagonal batch of packed rows + Nmax empty ghost-slot rows (GraphBatch.from_csr's layout)"""
+def assemble(parts, dev):
+    """resident graphs (the three of a triplet, or a chunk of a dataset) -> (GraphBatch, feature rows, assignment rows or None, sizes):
+    the block-diagonal batch of packed rows + Nmax empty ghost-slot rows (GraphBatch.from_csr's layout)"""
     nmax = parts[0].nmax
     if any(p.nmax != nmax for p in parts):
         raise ValueError("the graphs of a batch must be padded to the same Nmax")
     sizes = np.array([p.n for p in parts], dtype=np.int64)
-    nnz = int(sum(p.nnz for p in parts))
-    tail = torch.full((nmax + 1,), nnz, dtype=torch.int32, device=dev)
-    if len(parts) > _PER_PIECE_MAX:
-        e0s = np.concatenate([[0], np.cumsum([p.nnz for p in parts])[:-1]])
-        r0s = np.concatenate([[0], np.cumsum(sizes)[:-1]])
-        rowptr = torch.cat([offset_cat([p.rowptr[:-1] for p in parts], sizes, e0s, dev), tail])
-        col = offset_cat([p.col for p in parts], [p.nnz for p in parts], r0s, dev) if nnz else None
-    else:
-        rps, cols, e0, r0 = [], [], 0, 0
-        for p in parts:
-            rps.append(p.rowptr[:-1] + e0 if e0 else p.rowptr[:-1])
-            cols.append(p.col + r0 if r0 else p.col)
-            e0 += p.nnz
-            r0 += p.n
-        rps.append(tail)
-        rowptr = torch.cat(rps)
-        col = torch.cat(cols) if nnz else None
-    weighted = any(p.val is not None for p in parts)
-    val = torch.cat([p.val if p.val is not None else torch.ones(p.nnz, device=dev) for p in parts]) if weighted else None
-    if col is None:
-        col = torch.zeros(1, dtype=torch.int32, device=dev)
-    g = GraphBatch.from_csr(rowptr, col, val, sizes, nmax, assume_symmetric=all(p.symmetric for p in parts))
+    rowptr, col, val, nnz, sym = R.concat_csr([(p.rowptr, p.col, p.val, p.n, p.nnz, p.symmetric) for p in parts], nmax + 1)
+    g = GraphBatch.from_csr(rowptr, col, val, sizes, nmax, assume_symmetric=sym)
     g.nnz = nnz
-    x = torch.cat([p.feats for p in parts] + [_ghost_zeros(nmax, parts[0].feats.size(1), dev, cache)])
+    x = torch.cat([p.feats for p in parts] + [R.ghost_zeros(nmax, parts[0].feats.size(1), dev)])
     xa = None
     if any(p.assign is not None for p in parts):
         pa = [p.assign if p.assign is not None else p.feats for p in parts]
-        xa = torch.cat(pa + [_ghost_zeros(nmax, pa[0].size(1), dev, cache)])
+        xa = torch.cat(pa + [R.ghost_zeros(nmax, pa[0].size(1), dev)])
     return g, x, xa, sizes
 
 
 # ----------------------------------------------------------------------------- embeddings + distances: one launch each way
 FUSED_TAIL = os.environ.get("TSGNN_TRIPLET_TAIL", "1") != "0"
-_EPS = 1e-6                      # F.pairwise_distance's default
 
 
 class _TripletTail(torch.autograd.Function):
@@ -159,9 +91,8 @@ class _TripletTail(torch.autograd.Function):
         D, E = int(w.size(1)), int(w.size(0))
         embed = torch.empty(3, E, dtype=torch.float32, device=r.device)
         dist = torch.empty(2, dtype=torch.float32, device=r.device)
-        nat.call("triplet_embed_fwd_f32", r, r.stride(0), w, w.stride(0), b, D, E, _EPS, embed, dist)
+        nat.call("triplet_embed_fwd_f32", r, r.stride(0), w, w.stride(0), b, D, E, R.EPS, embed, dist)
         ctx.save_for_backward(r, w, embed, dist)
-        ctx.has_bias = b is not None
         ctx.params = (w0, b)                              # (the Parameter objects: their slices of a trainer's flat gradient bucket)
         ctx.set_materialize_grads(False)                  # an unused output's gradient arrives as None, not as a zero-filled tensor
         outs = (dist[0:1], dist[1:2], embed[0:1], embed[1:2], embed[2:3])
@@ -175,11 +106,10 @@ class _TripletTail(torch.autograd.Function):
         c = lambda t: t.contiguous() if t is not None else None
         d_r = torch.empty(3, D, dtype=torch.float32, device=dev)
         # straight into the trainer's flat gradient bucket when one is installed (FlatTrainer): no AccumulateGrad copy, no zeroing
-        dw, sw = mp._sink_or_new(ctx.params[0], (E, D), dev)
-        db, sb = mp._sink_or_new(ctx.params[1], (E,), dev) if ctx.has_bias else (None, False)
-        nat.call("triplet_embed_bwd_f32", r, r.stride(0), w, w.stride(0), D, E, _EPS, embed, dist, c(g_dp), c(g_dn), c(g_a), c(g_p), c(g_n), d_r,
+        (dw, db), grads = mp._sinks_or_new(ctx.params, ((E, D), (E,)), dev)
+        nat.call("triplet_embed_bwd_f32", r, r.stride(0), w, w.stride(0), D, E, R.EPS, embed, dist, c(g_dp), c(g_dn), c(g_a), c(g_p), c(g_n), d_r,
                  d_r.stride(0), dw, dw.stride(0), db)
-        return d_r, (None if sw else dw), (None if sb else db)
+        return (d_r,) + grads
 
 
 class _MarginRank(torch.autograd.Function):
@@ -239,28 +169,25 @@ class tripletnet(nn.Module):
     def __init__(self, model):
         super().__init__()
         self.model = model
-        self._resident = resident_cache(model) if RESIDENT else {}
+        self._resident = R.cache_for(model)
 
     def _embed(self, x, g_or_adj, sizes, assign_x):
         """model forward with the per-graph batch-norm statistics of a B = 1 call -> (dist_p, dist_n, embed_a, embed_p, embed_n)"""
         m = self.model
-        prev = getattr(m, "per_graph_bn", False)
         fuse = (FUSED_TAIL and isinstance(m, _rows_models()) and getattr(m, "final_dim", None) in ("output_dim", "pretrain")
                 and isinstance(getattr(m, "map_model", None), nn.Linear))       # (encoders whose _heads honours _defer_map)
-        m.per_graph_bn = True
         m._defer_map = fuse
         try:
-            out, embed = m(x, g_or_adj, sizes, assign_x=assign_x)
+            with R.per_graph_statistics(m):
+                out, embed = m(x, g_or_adj, sizes, assign_x=assign_x)
         finally:
-            m.per_graph_bn = prev
             m._defer_map = False
         if fuse:
             r = out if m.final_dim == "output_dim" else embed      # the concatenated readouts (encoders.py:201-205)
             if tail_ok(m, r):
                 return _TripletTail.apply(r, m.map_model.weight, m.map_model.bias)
             embed = m.map_model(r)
-        embed_a, embed_p, embed_n = embed[0:1], embed[1:2], embed[2:3]
-        return (F.pairwise_distance(embed_a, embed_p, 2), F.pairwise_distance(embed_a, embed_n, 2), embed_a, embed_p, embed_n)
+        return R.torch_distances(embed)
 
     @staticmethod
     def _stack(graphs, key, device):
@@ -271,8 +198,8 @@ class tripletnet(nn.Module):
         prepares them (cross_val.py:158-184)."""
         dev = next(self.model.parameters()).device
         trip = (a, p, n)
-        if RESIDENT and dev.type == "cuda" and isinstance(self.model, _rows_models()):
-            g, x, xa, sizes = _assemble([_resident(t, dev, self._resident) for t in trip], dev, self._resident)
+        if R.RESIDENT and dev.type == "cuda" and isinstance(self.model, _rows_models()):
+            g, x, xa, sizes = assemble([resident_graph(t, dev, self._resident) for t in trip], dev)
             return self._embed(x, g, sizes, x if xa is None else xa)
         adj = self._stack(trip, "adj", dev)
         h0 = self._stack(trip, "feats", dev)

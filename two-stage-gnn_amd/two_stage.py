@@ -3,7 +3,7 @@ embeddings — the reference's ``evaluate()`` (Code/sage+gat+diffpool/train_trip
 runs one B = 1 forward per graph, copies every embedding to the host and fits sklearn's ``KNeighborsClassifier`` there.
 
 Here the graphs go through the encoder in block-diagonal chunks (``embed_dataset``: the resident per-graph device pieces of
-``triplet.py`` / ``sag_triplet.py``, per-graph statistics, so row i is the eval-mode B = 1 forward of graph i), the classifier is one
+``resident.py``, per-graph statistics, so row i is the eval-mode B = 1 forward of graph i), the classifier is one
 HIP launch per prediction (csrc/knn.hip: distances, selection, vote and confusion matrix) and ``evaluate`` copies two small confusion
 matrices to the host, once.
 
@@ -19,6 +19,7 @@ import torch.nn.functional as F
 
 from . import _native as nat
 from . import message_passing as mp
+from . import resident as R
 
 
 # ----------------------------------------------------------------------------- containers
@@ -56,18 +57,12 @@ def _eval_mode(model):
     """eval mode (dropout off), per-graph batch-norm statistics (trap T2: the slot batch-norm uses fresh statistics in eval mode too,
     so a chunk must give every graph the statistics it has alone), no autograd; everything restored on exit, also on an exception"""
     training = model.training
-    has_pg = hasattr(model, "per_graph_bn")
-    per_graph = getattr(model, "per_graph_bn", None)
     try:
         model.eval()
-        if has_pg:
-            model.per_graph_bn = True
-        with torch.no_grad():
+        with R.per_graph_statistics(model), torch.no_grad():
             yield
     finally:
         model.train(training)
-        if has_pg:
-            model.per_graph_bn = per_graph
 
 
 def _device_of(model):
@@ -96,7 +91,7 @@ def dense_chunk_limit(model):
 
 def _embed_dense_chunk(model, graphs, dev, cache):
     from . import triplet as T
-    g, x, xa, sizes = T._assemble([T._resident(o, dev, cache) for o in graphs], dev, cache)
+    g, x, xa, sizes = T.assemble([T.resident_graph(o, dev, cache) for o in graphs], dev)
     _, feat = model(x, g, sizes, assign_x=x if xa is None else xa)
     return feat
 
@@ -106,7 +101,7 @@ def _embed_net_chunk(tnet, graphs):
     all rows of the chunk at once"""
     from . import pyg
     m = tnet.model
-    r = tnet._readout(tnet.batch_of(graphs))
+    r = tnet.readout(tnet.batch_of(graphs))
     if mp.mlp3_ok(r, m.lin1, m.lin2, m.lin3):
         return mp.mlp3_log_softmax(r, m.lin1, m.lin2, m.lin3, m.dropout_ratio, False)
     h = pyg.relu(mp.linear_oi(r, m.lin1.weight, m.lin1.bias))
@@ -152,9 +147,9 @@ def embed_dataset(model, graphs, chunk=None):
     with _eval_mode(model):
         if not graphs:
             return torch.zeros(0, 0, dtype=torch.float32, device=dev)
-        if isinstance(model, E.GcnEncoderGraph) and dev.type == "cuda" and T.RESIDENT and _is_dense(graphs[0]):
+        if isinstance(model, E.GcnEncoderGraph) and dev.type == "cuda" and R.RESIDENT and _is_dense(graphs[0]):
             step = int(chunk) if chunk is not None else dense_chunk_limit(model)
-            cache = T.resident_cache(model)
+            cache = R.resident_cache(model)
             for i in range(0, len(graphs), step):
                 rows.append(_embed_dense_chunk(model, graphs[i:i + step], dev, cache))
         elif isinstance(model, S.Net) and dev.type == "cuda" and not _is_dense(graphs[0]):
