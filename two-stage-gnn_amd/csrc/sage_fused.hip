@@ -567,7 +567,9 @@ static inline bool slot_wide16() {
 #define TSGNN_SLOT_DISPATCH(KERNEL, GRID, LDS, ...)                                                                     \
   do {                                                                                                                   \
     const int F4_ = F / 4;                                                                                               \
-    TSGNN_KNAME("%s<8,%d,%d>", #KERNEL, F4_ <= 8 ? 1 : (F4_ <= 16 ? 2 : 4), B <= 32 ? 256 : (B <= 64 ? 512 : 1024));     \
+    const bool w16_ = F4_ > 8 && F4_ <= 16 && B <= 16 && slot_wide16();                                                  \
+    TSGNN_KNAME("%s<%d,%d,%d>", #KERNEL, w16_ ? 16 : 8, F4_ <= 8 || w16_ ? 1 : (F4_ <= 16 ? 2 : 4),                      \
+                B <= 32 ? 256 : (B <= 64 ? 512 : 1024));                                                                 \
     if (B <= 32) {                                                                                                       \
       if (F4_ <= 8) KERNEL<8, 1, 256><<<GRID, 256, LDS, stream>>> __VA_ARGS__;                                            \
       else if (F4_ <= 16 && B <= 16 && slot_wide16()) KERNEL<16, 1, 256><<<GRID, 256, LDS, stream>>> __VA_ARGS__;         \
@@ -613,6 +615,28 @@ int tsgnn_slot_bn_fwd_pair_f32(const int* graph_ptr, const int* slot_count, int 
   return TSGNN_OK;
 }
 
+// 128-wide rows of up to 32 graphs: 16 threads per row (two float4 each) in 512-thread workgroups rather than the dispatch table's
+// 8 x four float4 in 256 — half the dependent chain per thread, twice the requests in flight per slot: the headline step 0.1284 ->
+// 0.1275 ms (two launches; A/B on one box).  32 threads x one float4 in 1,024-thread workgroups: 0.1324 (slower).
+// Up to 64 graphs (1,024-thread workgroups) the same: PROTEINS b64 116.6 -> 115.4 us.
+// One launcher for the single and the paired entry point (grid.y = 2): a paired half runs the very instantiation a launch of its own
+// would, so its dU is the same bit for bit whether sage_stack.run_paired found a partner for it or not.
+// (The timings above are of the single launch; the paired launch at this shape has not been timed against the table's entry.)
+static void slot_post_bwd_wide128(const SlotArgs& s, dim3 grid, const float* v, int64_t ldv, const float* dxs, int64_t lddxs, const float* dxs2,
+                                  int64_t lddxs2, const float* dout, int64_t ldo, const int* arg, int relu, int bn, const float* mean,
+                                  const float* rstd, const float* rinv, float* du, int64_t lddu, SlotBwdAlt alt, tsgnn_stream_t stream) {
+  constexpr int F = 128;
+  const int nww = s.B <= 32 ? 8 : 16;
+  const size_t ldsw = sizeof(float) * ((s.n_ghost ? (size_t)nww * F : 0) + 2 * nww + 4);
+  if (s.B <= 32) {
+    TSGNN_KNAME("slot_post_bwd<16,2,512>");
+    slot_post_bwd<16, 2, 512><<<grid, 512, ldsw, stream>>>(s, v, ldv, dxs, lddxs, dxs2, lddxs2, dout, ldo, arg, F / 4, relu, bn, mean, rstd, rinv, du, lddu, alt);
+  } else {
+    TSGNN_KNAME("slot_post_bwd<16,2,1024>");
+    slot_post_bwd<16, 2, 1024><<<grid, 1024, ldsw, stream>>>(s, v, ldv, dxs, lddxs, dxs2, lddxs2, dout, ldo, arg, F / 4, relu, bn, mean, rstd, rinv, du, lddu, alt);
+  }
+}
+
 int tsgnn_slot_post_bwd_f32(const int* graph_ptr, const int* slot_count, int B, int nmax, int64_t n_real, int n_ghost,
                             const float* v, int64_t ldv, const float* dxs, int64_t lddxs, const float* dxs2, int64_t lddxs2,
                             const float* dout, int64_t ldo, const int* arg, int F, int relu, int bn, const float* mean,
@@ -623,20 +647,9 @@ int tsgnn_slot_post_bwd_f32(const int* graph_ptr, const int* slot_count, int B, 
     return TSGNN_EINVAL;
   if (!tsgnn_slot_fused_supported(B, F)) return TSGNN_EUNSUPPORTED;
   SlotArgs s{graph_ptr, slot_count, B, nmax, n_real, n_ghost};
-  // 128-wide rows of up to 32 graphs: 16 threads per row (two float4 each) in 512-thread workgroups rather than the dispatch table's
-  // 8 x four float4 in 256 — half the dependent chain per thread, twice the requests in flight per slot: the headline step 0.1284 ->
-  // 0.1275 ms (two launches; A/B on one box).  32 threads x one float4 in 1,024-thread workgroups: 0.1324 (slower).
-  // Up to 64 graphs (1,024-thread workgroups) the same: PROTEINS b64 116.6 -> 115.4 us.
   if (F == 128 && B <= 64) {
-    const int nww = B <= 32 ? 8 : 16;
-    const size_t ldsw = sizeof(float) * ((n_ghost ? (size_t)nww * F : 0) + 2 * nww + 4);
-    if (B <= 32) {
-      TSGNN_KNAME("slot_post_bwd<16,2,512>");
-      slot_post_bwd<16, 2, 512><<<nmax, 512, ldsw, stream>>>(s, v, ldv, dxs, lddxs, dxs2, lddxs2, dout, ldo, arg, F / 4, relu, bn, mean, rstd, rinv, du, lddu, SlotBwdAlt{});
-    } else {
-      TSGNN_KNAME("slot_post_bwd<16,2,1024>");
-      slot_post_bwd<16, 2, 1024><<<nmax, 1024, ldsw, stream>>>(s, v, ldv, dxs, lddxs, dxs2, lddxs2, dout, ldo, arg, F / 4, relu, bn, mean, rstd, rinv, du, lddu, SlotBwdAlt{});
-    }
+    slot_post_bwd_wide128(s, dim3((unsigned)nmax), v, ldv, dxs, lddxs, dxs2, lddxs2, dout, ldo, arg, relu, bn, mean, rstd, rinv, du, lddu, SlotBwdAlt{},
+                          stream);
     TSGNN_CHECK_LAUNCH();
     return TSGNN_OK;
   }
@@ -689,10 +702,16 @@ int tsgnn_slot_post_bwd_pair_f32(const int* graph_ptr, const int* slot_count, in
     return TSGNN_EINVAL;
   if (!tsgnn_slot_fused_supported(B, F)) return TSGNN_EUNSUPPORTED;
   SlotArgs s{graph_ptr, slot_count, B, nmax, n_real, n_ghost};
-  const int nw = B <= 32 ? 4 : (B <= 64 ? 8 : 16);
-  const size_t lds = sizeof(float) * ((n_ghost ? (size_t)nw * F : 0) + 2 * nw + 4);
   const float* nof = nullptr;
   const int* noi = nullptr;
+  if (F == 128 && B <= 64) {                                 // as tsgnn_slot_post_bwd_f32 does
+    slot_post_bwd_wide128(s, dim3((unsigned)nmax, 2), v0, ldv, dxs0, lddxs, dxs2_0, lddxs2, nof, 0, noi, relu, bn, mean0, rstd0, rinv0, du0, lddu,
+                          SlotBwdAlt{v1, dxs1, dxs2_1, mean1, rstd1, rinv1, du1}, stream);
+    TSGNN_CHECK_LAUNCH();
+    return TSGNN_OK;
+  }
+  const int nw = B <= 32 ? 4 : (B <= 64 ? 8 : 16);
+  const size_t lds = sizeof(float) * ((n_ghost ? (size_t)nw * F : 0) + 2 * nw + 4);
   TSGNN_SLOT_DISPATCH(slot_post_bwd, dim3((unsigned)nmax, 2), lds,
                       (s, v0, ldv, dxs0, lddxs, dxs2_0, lddxs2, nof, 0, noi, F / 4, relu, bn, mean0, rstd0, rinv0, du0, lddu,
                        SlotBwdAlt{v1, dxs1, dxs2_1, mean1, rstd1, rinv1, du1}));
