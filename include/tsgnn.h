@@ -648,6 +648,27 @@ int tsgnn_gat_score_rowsum_f32(const int* rowptr, const int* col, const int* epe
 int tsgnn_gat_pack_desc_words(void);
 int tsgnn_gat_pack_f32(const int64_t* desc, tsgnn_stream_t stream);
 int tsgnn_gat_unpack_f32(const int64_t* desc, tsgnn_stream_t stream);
+/* Resident one-graph pieces of the GAT encoder's packed batch (n real rows + one ghost representative when n < Nmax) -> every array
+ * the fused GAT launches read for the concatenated batch, in ONE launch for up to tsgnn_gat_assemble_max_pieces() (8) pieces; more
+ * pieces take further calls that write disjoint slices of the same arrays.  No atomics: every output element has one writer.
+ * A piece is one int32 device buffer (16-byte aligned) with piece-local indices, its sections starting at the word offsets
+ * tsgnn_gat_assemble_layout(nr, nnz, k, ldf, off[10]) returns: rowptr [nr + 1] | rowptr_t [nr + 1] | col [nnz] | col_t [nnz] |
+ * src_e_t [nnz] | its inverse [nnz] | edge-less rows [k] | their weights [k] (float bits) | feature rows [nr, ldf] (float bits);
+ * off[9] = the buffer's length.
+ * desc lives in HOST memory (8-byte aligned, read before the call returns):
+ *   header (tsgnn_gat_assemble_header_words() words): K, R, E, I (rows, entries, listed edge-less columns of the WHOLE batch), B (graphs
+ *     of the whole batch), ldf (floats per feature row, a multiple of 4), nH, H_0..H_3 (head counts whose indicator is written), then the
+ *     outputs (each 16-byte aligned): rowptr [R + 1], col [E], rowptr_t [R + 1], col_t [E], src_e_t [E], inv [E], row_mult [R],
+ *     graph_ptr [B + 1], row_graph [R], row_slot [R], iso_idx [I], iso_w [I], iso_ptr [B + 1], x [R, ldf], iso_cols_0..3 [R, H_v];
+ *   per piece (tsgnn_gat_assemble_piece_words() words): buffer, n, nr, nnz, k, Nmax - n, first row, first entry, first listed column,
+ *     graph number, last (1: the piece closes the batch and writes the arrays' closing entries).
+ * TSGNN_EINVAL without a launch: K outside 1..8, a negative size, a piece that leaves [0, R) x [0, E) x [0, I) (all below 2^31), a
+ * missing or misaligned pointer. */
+int tsgnn_gat_assemble_header_words(void);
+int tsgnn_gat_assemble_piece_words(void);
+int tsgnn_gat_assemble_max_pieces(void);
+int tsgnn_gat_assemble_layout(int64_t nr, int64_t nnz, int64_t k, int64_t ldf, int64_t* off);
+int tsgnn_gat_assemble_f32(const int64_t* desc, tsgnn_stream_t stream);
 /* ELU (encoders_GAT.py:47) / mean over heads then ELU (:78-83) */
 int tsgnn_elu_heads_fwd_f32(const float* x, int64_t rows, int H, int Fh, int mean_heads, int apply_elu, float* y, tsgnn_stream_t stream);
 int tsgnn_elu_heads_bwd_f32(const float* x, const float* dy, int64_t rows, int H, int Fh, int mean_heads, int apply_elu, float* dx,

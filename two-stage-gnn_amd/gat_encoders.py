@@ -316,9 +316,13 @@ class DGATEncoderGraph(nn.Module):
             if x.dim() == 3:
                 x = x.reshape(g.B * g.nmax, x.size(2))
             x = mp.readout_max(x, g)                                                        # max over ALL padded rows (:189)
+        return x, self.head(x)
+
+    def head(self, x):
+        """readouts [B, E] -> the second output of forward (encoders_GAT.py:191-198)"""
         lin1 = self.pred_model if self.final_dim != "output_dim" else self.map_model
         if mp.head2_ok(x, lin1, self.map2_model):
-            return x, mp.head2(x, lin1, self.map2_model)[1]                                # both nn.Linear: one launch each way
+            return mp.head2(x, lin1, self.map2_model)[1]                                # both nn.Linear: one launch each way
         if FUSED_HEAD and isinstance(self.map2_model, torch.nn.Identity) and isinstance(lin1, nn.Linear) and x.is_cuda \
                 and x.size(1) % 4 == 0 and x.size(0) <= 1024 and lin1.out_features <= 256 and lin1.weight.data_ptr() % 16 == 0:
             # map2_model is Identity (:117): the two-Linear head kernels with W2 = I (1 * v + 0 * u is exact) — one launch each way,
@@ -329,8 +333,8 @@ class DGATEncoderGraph(nn.Module):
                 eye = _eye_cache[(C, x.device)] = torch.eye(C, dtype=torch.float32, device=x.device)
             y = mp._Head2.apply(x, lin1.weight, lin1.bias, eye, None)[1]
             y._tsgnn_defer_ce = True          # (under FlatTrainer(defer_loss=True) / mp.deferred_loss(): mp._SoftmaxCE)
-            return x, y
-        return x, self.map2_model(lin1(x))
+            return y
+        return self.map2_model(lin1(x))
 
     def loss(self, pred, label, type="softmax"):
         if type == "softmax":

@@ -134,10 +134,14 @@ def embed_dataset(model, graphs, chunk=None):
     ``dense_encoders.GcnEncoderGraph`` / ``SoftPoolingGcnEncoder`` and ``sag_layers.Net`` run in block-diagonal chunks of ``chunk``
     graphs (default: the most the fused per-graph launches take) on the graphs' resident device pieces — the caches of
     ``triplet.tripletnet`` / ``sag_triplet.tripletnet`` around the same model, so a graph a training step has used is not uploaded
-    again, and the reverse.  ANY OTHER model (the GAT encoder, EigenGCN, a module of your own) gets a plain loop of B = 1 forwards
-    with the rows kept on the device: correct, and not fast.  ``model`` may also be a ``tripletnet`` (its ``.model`` is used)."""
-    from . import dense_encoders as E, sag_layers as S, sag_triplet as ST, triplet as T
-    if isinstance(model, (T.tripletnet, ST.tripletnet)):
+    again, and the reverse.  A ``gat_triplet.tripletnet`` (or a bare ``gat_encoders.DGATEncoderGraph`` when ``chunk`` is given) runs its
+    GAT encoder on packed chunks with one ghost representative per graph, assembled from the same cache (default
+    ``gat_triplet.DEFAULT_CHUNK`` graphs, at most the 1024 rows the encoder's fused head takes).  ANY OTHER model (a bare GAT encoder
+    without ``chunk``, EigenGCN, a module of your own) gets a plain loop of B = 1 forwards with the rows kept on the device: correct,
+    and not fast.  ``model`` may also be a ``tripletnet`` (its ``.model`` is used)."""
+    from . import dense_encoders as E, gat_encoders as GE, gat_triplet as GT, sag_layers as S, sag_triplet as ST, triplet as T
+    gat_chunks = isinstance(model, GT.tripletnet)             # (a bare GAT encoder takes the chunked path only when chunk= is given)
+    if isinstance(model, (T.tripletnet, ST.tripletnet, GT.tripletnet)):
         model = model.model
     graphs = _flatten(graphs)
     dev = _device_of(model)
@@ -152,6 +156,12 @@ def embed_dataset(model, graphs, chunk=None):
             cache = R.resident_cache(model)
             for i in range(0, len(graphs), step):
                 rows.append(_embed_dense_chunk(model, graphs[i:i + step], dev, cache))
+        elif isinstance(model, GE.DGATEncoderGraph) and (gat_chunks or chunk is not None) and dev.type == "cuda" and R.RESIDENT \
+                and _is_dense(graphs[0]):
+            step = min(int(chunk) if chunk is not None else GT.DEFAULT_CHUNK, GT.HEAD_ROWS_MAX)
+            cache = R.resident_cache(model)
+            for i in range(0, len(graphs), step):
+                rows.append(GT.embed_chunk(model, graphs[i:i + step], dev, cache))
         elif isinstance(model, S.Net) and dev.type == "cuda" and not _is_dense(graphs[0]):
             step = int(chunk) if chunk is not None else _NET_CHUNK
             tnet = ST.tripletnet(model)
