@@ -669,6 +669,35 @@ int tsgnn_gat_assemble_piece_words(void);
 int tsgnn_gat_assemble_max_pieces(void);
 int tsgnn_gat_assemble_layout(int64_t nr, int64_t nnz, int64_t k, int64_t ldf, int64_t* off);
 int tsgnn_gat_assemble_f32(const int64_t* desc, tsgnn_stream_t stream);
+/* Resident one-graph pieces of the EigenGCN encoder -> the complete EigenBatch of a chunk (eigen_pool.concat_batches of the same
+ * one-graph batches, word for word): per level graph i = 0..L rowptr [R_i + Nmax + 1] (the Nmax ghost-slot rows empty), col, val,
+ * graph_ptr [B + 1], row_graph, row_slot, slot_count [Nmax]; per pooling level i < L cluster_of [R_i] (-1 kept), coef [R_i, J],
+ * bptr [R_{i+1} + B + 1], members [R_i]; final [R_L, Jf]; x [R_0 + Nmax, ldf] with the ghost rows zero.  No atomics: every output word
+ * has one writer (slot_count: one per call, continued in stream order by the next).
+ * A piece is one int32 device buffer (16-byte aligned) with piece-local indices; tsgnn_eigen_assemble_layout(nlev = L + 1, J, Jf, ldf,
+ * n[nlev], nnz[nlev], off[7 nlev - 1]) returns its sections' word offsets, each a multiple of 4: per level graph rowptr [n_i + 1] |
+ * col [nnz_i] | val [nnz_i] (float bits), then per pooling level cluster_of [n_i] | coef [n_i, J] | bptr [n_{i+1} + 2] | members [n_i],
+ * then final [n_L, Jf] | feature rows [n_0, ldf]; the last offset is the buffer's length.  The layout takes ANY nlev >= 1
+ * (a piece of more than 4 level graphs is only read through views of its sections); the launch takes nlev <= 4.
+ * desc lives in HOST memory (8-byte aligned, read before the call returns):
+ *   header (tsgnn_eigen_assemble_header_words() words): [0] K pieces of this call, [1] B graphs of the whole batch, [2] nlev (1..4),
+ *     [3] J (1..5), [4] Jf (0..4), [5] ldf (a multiple of 4), [6] Nmax, [7] first (1: this call starts the slot counts),
+ *     [9] x, [10] final, [12 + 2 i] R_i, [13 + 2 i] E_i (rows and entries of the WHOLE batch), [20 + 7 i ..] rowptr, col, val,
+ *     graph_ptr, row_graph, row_slot, slot_count of level graph i, [48 + 4 i ..] cluster_of, coef, bptr, members of pooling level i
+ *     (every output 16-byte aligned);
+ *   per piece (tsgnn_eigen_assemble_piece_words() words): buffer, graph number, last (1: the piece closes the batch and writes the
+ *     arrays' closing entries and the ghost rows), then per level graph n_i, nnz_i, first row, first entry (the first cluster of
+ *     pooling level i is the first row of level i + 1).
+ *   The pieces' records travel in the kernel arguments: K <= tsgnn_eigen_assemble_max_pieces() (32) per call, more pieces take further
+ *     calls that write disjoint slices of the same arrays.
+ * TSGNN_EINVAL without a launch: a count outside its range, a negative size, a piece that leaves its level's [0, R_i) x [0, E_i) (all
+ * below 2^31), a closing piece that does not end there, a missing or misaligned pointer. */
+int tsgnn_eigen_assemble_header_words(void);
+int tsgnn_eigen_assemble_piece_words(void);
+int tsgnn_eigen_assemble_max_pieces(void);
+int tsgnn_eigen_assemble_max_levels(void);
+int tsgnn_eigen_assemble_layout(int nlev, int J, int Jf, int64_t ldf, const int64_t* n, const int64_t* nnz, int64_t* off);
+int tsgnn_eigen_assemble_f32(const int64_t* desc, tsgnn_stream_t stream);
 /* ELU (encoders_GAT.py:47) / mean over heads then ELU (:78-83) */
 int tsgnn_elu_heads_fwd_f32(const float* x, int64_t rows, int H, int Fh, int mean_heads, int apply_elu, float* y, tsgnn_stream_t stream);
 int tsgnn_elu_heads_bwd_f32(const float* x, const float* dy, int64_t rows, int H, int Fh, int mean_heads, int apply_elu, float* dx,

@@ -16,6 +16,14 @@ The reference calls ``WavePoolingGcnEncoder`` three times at B = 1 (anchor, posi
   Linear-ReLU-Linear, csrc/triplet.hip for a single Linear); any other head runs through torch.
 
 ``batch(a, p, n)`` / ``embed(batch)`` split the call for a step replayed from a hipGraph on a resident triplet (refill ``batch.x`` in place).
+
+Stage two (``two_stage.embed_dataset``: the reference's ``evaluate()`` / ``evaluate_mlp()``, train_triplet.py:30-268) embeds hundreds of
+graphs per call.  What is resident per graph object is therefore ONE int32 device buffer, the piece (``piece_buffer``: every level's
+CSR, every pooling level's clusters / coefficients / bucket lists, the final coefficients and the feature rows, piece-local indices,
+sections on 16 bytes at ``tsgnn_eigen_assemble_layout``'s offsets), uploaded in one copy.  The triplet step's one-graph ``EigenBatch``
+is made of views of that buffer at its first use; ``assemble`` writes the complete ``EigenBatch`` of a chunk from the pieces
+(csrc/eigen_assemble.hip), and ``embed_chunk`` runs the model once on it.  Either side finds the other's entries in the model's
+``resident.ResidentCache``, so a graph is uploaded once whoever sees it first.
 """
 import numpy as np
 import torch
@@ -29,6 +37,8 @@ from . import triplet as _t
 from .graph import GraphBatch
 
 MarginRankingLoss = _t.MarginRankingLoss        # the documented replacement for the loop's `criterion` (train_triplet.py:292)
+DEFAULT_CHUNK = 256                             # graphs per chunk of stage two: the fastest of 32 / 64 / 128 / 256 (profiles/r10/eigen_two_stage.txt)
+GUARD = 0x5A5A5A5A                              # assemble(guard=...): the word tests look for behind the arrays
 
 
 # ----------------------------------------------------------------------------- host half: a .graph dict -> compact pieces (pure numpy)
@@ -96,9 +106,153 @@ def pack_host(graph, L, J, Jf):
 
 
 # ----------------------------------------------------------------------------- the graphs of the dataset, resident
+def graph_dict(obj):
+    """the ``.graph`` dict of a graph object, or the dict itself (``GraphSampler.__getitem__`` hands out bare dicts)"""
+    return obj if isinstance(obj, dict) else obj.graph
+
+
+def check_dict(d, L, J, Jf):
+    """ValueError for a dict that was prepared for another number of levels or pooling matrices than the model's (the sampler writes
+    exactly ``num_pool_matrix`` matrices per level and ``num_pool_final_matrix`` final ones): a key the model needs is missing, or a
+    level / matrix beyond the model's is present"""
+    need = ["adj", "feats", "num_nodes"] + [k % (i + 1) for i in range(L) for k in ("adj_pool_%d", "num_nodes_%d")] + \
+        ["pool_adj_%d_%d" % (i, j) for i in range(L) for j in range(J)] + ["pool_adj_%d_%d" % (L, j) for j in range(Jf)]
+    over = ["adj_pool_%d" % (L + 1), "num_nodes_%d" % (L + 1), "pool_adj_%d_%d" % (L, Jf)] + ["pool_adj_%d_%d" % (i, J) for i in range(L)]
+    for k in need:
+        if k not in d:
+            raise ValueError("the graph dict has no '%s': the model has %d pooling levels, %d pooling and %d final matrices" % (k, L, J, Jf))
+    for k in over:
+        if k in d:
+            raise ValueError("the graph dict has '%s': the model has %d pooling levels, %d pooling and %d final matrices" % (k, L, J, Jf))
+
+
+def padded_rows_host(f, n):
+    """``resident.padded_rows`` on the host: the first n rows, zero-padded to a row stride that is a multiple of 4 floats"""
+    f = np.asarray(f, dtype=np.float32)
+    if f.ndim != 2 or f.shape[0] < n:
+        raise ValueError("feats must be [Nmax, F]")
+    out = np.zeros((n, max(4, (f.shape[1] + 3) // 4 * 4)), dtype=np.float32)
+    out[:, :f.shape[1]] = f[:n]
+    return out
+
+
+def piece_layout(n, nnz, J, Jf, ldf):
+    """word offsets of a piece buffer's sections (``tsgnn_eigen_assemble_layout``; the last entry is the buffer's length): per level
+    graph rowptr | col | val, per pooling level cluster_of | coef | bptr | members, then final | feature rows"""
+    nlev = len(n)
+    off = np.zeros(7 * nlev - 1, dtype=np.int64)
+    nn, zz = np.asarray(n, dtype=np.int64), np.asarray(nnz, dtype=np.int64)
+    nat.call_nostream("eigen_assemble_layout", nlev, max(int(J), 1), int(Jf), int(ldf), nn.ctypes.data, zz.ctypes.data, off.ctypes.data)
+    return off
+
+
+def piece_buffer(packed, feats, J):
+    """pack_host's result + the feature rows (``padded_rows_host``) as the ONE int32 buffer the assembler reads -> (buffer, offsets)"""
+    n, L = packed["n"], len(packed["levels"])
+    nnz = [int(c[1].size) for c in packed["graphs"]]
+    Jf = 0 if packed["final"] is None else int(packed["final"].shape[1])
+    off = piece_layout(n, nnz, J, Jf, feats.shape[1])
+    buf = np.zeros(int(off[-1]), dtype=np.int32)
+    parts = []
+    for rp, col, val, _ in packed["graphs"]:
+        parts += [rp, col, val.view(np.int32)]
+    for lv in packed["levels"]:
+        parts += [lv["cluster_of"], lv["coef"].reshape(-1).view(np.int32), lv["bptr"], lv["members"]]
+    parts += [(packed["final"].reshape(-1).view(np.int32) if Jf else np.zeros(0, np.int32)), feats.reshape(-1).view(np.int32)]
+    for o, part in zip(off[:-1], parts):
+        buf[int(o):int(o) + part.size] = part
+    return buf, off
+
+
+def unpack_piece(buf, n, nnz, J, Jf, ldf):
+    """the sections of a piece buffer back as arrays (host or device, views): ``graphs`` [(rowptr, col, val)], ``levels`` [dicts as
+    pack_host's], ``final`` [n_L, Jf] or None, ``feats`` [n_0, ldf]"""
+    off = piece_layout(n, nnz, J, Jf, ldf)
+    f32 = (lambda a: a.view(np.float32)) if isinstance(buf, np.ndarray) else (lambda a: a.view(torch.float32))
+    sec = lambda s, count: buf[int(off[s]):int(off[s]) + int(count)]
+    nlev, L = len(n), len(n) - 1
+    graphs = [(sec(3 * i, n[i] + 1), sec(3 * i + 1, nnz[i]), f32(sec(3 * i + 2, nnz[i]))) for i in range(nlev)]
+    levels = []
+    for i in range(L):
+        s = 3 * nlev + 4 * i
+        levels.append({"cluster_of": sec(s, n[i]), "coef": f32(sec(s + 1, n[i] * J)).reshape(n[i], J), "bptr": sec(s + 2, n[i + 1] + 2),
+                       "members": sec(s + 3, n[i])})
+    s = 3 * nlev + 4 * L
+    final = f32(sec(s, n[L] * Jf)).reshape(n[L], Jf) if Jf else None
+    return {"graphs": graphs, "levels": levels, "final": final, "feats": f32(sec(s + 1, n[0] * ldf)).reshape(n[0], ldf)}
+
+
 class _Graph:
-    """device side of one graph object: a one-graph EigenBatch and its feature rows [n, ld]"""
-    __slots__ = ("ref", "eb", "feats", "n", "nmax")
+    """device side of one graph object: the piece buffer ``buf``, the host numbers the assembler's description needs, and — built from
+    views of the buffer when the triplet step first asks — the one-graph EigenBatch ``eb`` and the feature rows ``feats`` [n, ld]"""
+    __slots__ = ("ref", "buf", "ptr", "sizes", "nnz", "sym", "n", "nmax", "ldf", "fin", "L", "J", "Jf", "_eb", "_feats")
+
+    @property
+    def eb(self):
+        if self._eb is None:
+            self._eb, self._feats = _views(self)
+        return self._eb
+
+    @property
+    def feats(self):
+        if self._feats is None:
+            self._eb, self._feats = _views(self)
+        return self._feats
+
+
+def _views(e):
+    """the one-graph EigenBatch and feature rows of a resident piece, on the device: views of its buffer (only ``rowptr`` is a new
+    tensor: the piece's n + 1 entries and the Nmax closing entries of the empty ghost-slot rows).  No graph data is uploaded, which
+    is what ``cache.h2d`` counts; like ``tripletnet.batch``, every ``GraphBatch.from_csr`` here still uploads its ``graph_ptr`` and
+    ``slot_count`` (a few dozen bytes from host-known sizes) and launches ``row_maps``, once per object"""
+    dev, nmax = e.buf.device, e.nmax
+    u = unpack_piece(e.buf, e.sizes, e.nnz, e.J, e.Jf, e.ldf)
+    gs = []
+    for (rp, col, val), n, z, sym in zip(u["graphs"], e.sizes, e.nnz, e.sym):
+        rowptr = torch.cat([rp, rp[n:n + 1].expand(nmax)])
+        if not z:
+            col, val = torch.zeros(1, dtype=torch.int32, device=dev), torch.zeros(1, dtype=torch.float32, device=dev)
+        g = GraphBatch.from_csr(rowptr, col, val, np.array([n], dtype=np.int64), nmax, assume_symmetric=sym)
+        g.nnz = int(z)
+        gs.append(g)
+    levels = []
+    for i, h in enumerate(u["levels"]):
+        lv = ep.EigenLevel()
+        lv.g, lv.J = gs[i + 1], e.J
+        lv.cluster_of, lv.coef, lv.bptr, lv.members = h["cluster_of"], h["coef"], h["bptr"], h["members"]
+        levels.append(lv)
+    return ep.EigenBatch(gs[0], levels, u["final"], nmax), u["feats"]
+
+
+def device_piece(packed, feats, J, dev):
+    """pack_host's result + the graph's ``feats`` -> the resident entry: ONE host-to-device copy"""
+    rows = padded_rows_host(feats, packed["n"][0])
+    buf, _ = piece_buffer(packed, rows, J)
+    e = _Graph()
+    e.buf = torch.from_numpy(buf).to(dev)
+    e.ptr = int(e.buf.data_ptr())
+    e.sizes, e.nnz = [int(v) for v in packed["n"]], [int(c[1].size) for c in packed["graphs"]]
+    e.sym = [bool(c[3]) for c in packed["graphs"]]
+    e.n, e.nmax, e.ldf, e.fin = e.sizes[0], int(packed["nmax"]), int(rows.shape[1]), int(np.asarray(feats).shape[1])
+    e.L, e.J, e.Jf = len(packed["levels"]), int(J), 0 if packed["final"] is None else int(packed["final"].shape[1])
+    e._eb = e._feats = None
+    return e
+
+
+def resident_graph(obj, dev, cache, L, J, Jf, check=False):
+    """the resident piece of one graph object (packed and uploaded — one copy — at its first use), keyed by the object; a bare dict is
+    packed at every call (the sampler makes a new one per access: there is nothing to key on).  ``check``: ``check_dict`` before
+    packing"""
+    keyed = R.RESIDENT and not isinstance(obj, dict)
+    e = cache.lookup(obj, dev.index) if keyed else None
+    if e is not None:
+        return e
+    d = graph_dict(obj)
+    if check:
+        check_dict(d, L, J, Jf)
+    e = device_piece(pack_host(d, L, J, Jf), d["feats"], J, dev)
+    cache.h2d += 1
+    return cache.store(obj, e, dev.index) if keyed else e
 
 
 class _Triplet:
@@ -107,37 +261,151 @@ class _Triplet:
     __slots__ = ("eb", "x", "sizes")
 
 
-def _up(a, dev):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def _device_graph(csr, n, nmax, dev):
-    rp, col, val, sym = csr
-    rowptr = np.concatenate([rp, np.full(nmax, rp[-1], dtype=np.int32)])
-    g = GraphBatch.from_csr(_up(rowptr, dev), _up(col if col.size else np.zeros(1, np.int32), dev),
-                            _up(val if val.size else np.zeros(1, np.float32), dev), np.array([n], dtype=np.int64), nmax,
-                            assume_symmetric=sym)
-    g.nnz = int(col.size)
-    return g
-
-
 def to_device(packed, feats, dev):
-    """pack_host's result + the feature rows -> (one-graph EigenBatch, feats [n, ld] with a 16-byte row stride, host-to-device copies)"""
-    nmax, sizes = packed["nmax"], packed["n"]
-    gs = [_device_graph(c, n, nmax, dev) for c, n in zip(packed["graphs"], sizes)]
-    copies = 3 * len(gs)
+    """pack_host's result + the feature rows -> (one-graph EigenBatch, feats [n, ld] with a 16-byte row stride, host-to-device copies):
+    the piece buffer in ONE copy, both results views of it"""
+    J = int(packed["levels"][0]["coef"].shape[1]) if packed["levels"] else 1
+    e = device_piece(packed, feats, J, dev)
+    return e.eb, e.feats, 1
+
+
+# ----------------------------------------------------------------------------- resident pieces -> the EigenBatch of a chunk
+def _a4(v):
+    return (int(v) + 3) // 4 * 4
+
+
+def chunk_shape(parts):
+    """(Nmax, ldf, L, J, Jf) shared by the pieces of a chunk; ValueError when they differ"""
+    f = parts[0]
+    if any(p.nmax != f.nmax for p in parts):
+        raise ValueError("the graphs of a chunk must be padded to the same Nmax")
+    if any(p.ldf != f.ldf or p.fin != f.fin for p in parts):
+        raise ValueError("the graphs of a chunk must have the same number of features")
+    if any((p.L, p.J, p.Jf) != (f.L, f.J, f.Jf) for p in parts):
+        raise ValueError("the graphs of a chunk must share the number of levels and of pooling matrices")
+    return f.nmax, f.ldf, f.L, f.J, f.Jf
+
+
+def max_levels():
+    """pooling levels the assembler takes (``tsgnn_eigen_assemble_max_levels``)"""
+    return int(nat.lib().tsgnn_eigen_assemble_max_levels())
+
+
+def assemble(parts, dev, guard=0):
+    """resident pieces (a chunk of a dataset) -> (feature rows [R_0 + Nmax, ldf] with the ghost rows zero, EigenBatch): every array of
+    ``eigen_pool.concat_batches`` of the same one-graph batches, word for word, with the row bookkeeping ``GraphBatch.from_csr`` would
+    launch and upload (``graph_ptr``, ``row_graph``, ``row_slot``, ``slot_count``) written by the same kernel.  Two allocations (the
+    integer and the float arrays, every array on 16 bytes), all sizes host numbers: ceil(len(parts) / 32) launches with the pieces'
+    records in the kernel arguments, no upload, no host synchronisation.  ``guard`` (tests): that many words of ``GUARD`` behind every array; ``eb._raw`` = (both buffers, the arrays' offsets and
+    lengths in them)."""
+    lib = nat.lib()
+    kmax, hw, pw = (int(f()) for f in (lib.tsgnn_eigen_assemble_max_pieces, lib.tsgnn_eigen_assemble_header_words,
+                                       lib.tsgnn_eigen_assemble_piece_words))
+    nmax, ldf, L, J, Jf = chunk_shape(parts)
+    if L > max_levels():
+        raise ValueError("the assembler takes up to %d pooling levels" % max_levels())
+    B, nlev = len(parts), L + 1
+    n = np.array([p.sizes for p in parts], dtype=np.int64).reshape(B, nlev)
+    z = np.array([p.nnz for p in parts], dtype=np.int64).reshape(B, nlev)
+    row0, e0 = np.zeros((B + 1, nlev), dtype=np.int64), np.zeros((B + 1, nlev), dtype=np.int64)
+    np.cumsum(n, axis=0, out=row0[1:])
+    np.cumsum(z, axis=0, out=e0[1:])
+    Rr, E = [int(v) for v in row0[-1]], [int(v) for v in e0[-1]]
+    isz, fsz = [], []
+    for i in range(nlev):                                    # rowptr, col, graph_ptr, row_graph, row_slot, slot_count | val
+        isz += [Rr[i] + nmax + 1, max(E[i], 1), B + 1, Rr[i], Rr[i], nmax]
+        fsz.append(max(E[i], 1))
+    for i in range(L):                                       # cluster_of, bptr, members | coef
+        isz += [Rr[i], Rr[i + 1] + B + 1, Rr[i]]
+        fsz.append(Rr[i] * J)
+    fsz += [Rr[L] * Jf, (Rr[0] + nmax) * ldf]
+    ioff = np.concatenate([[0], np.cumsum([_a4(s + guard) for s in isz])])
+    foff = np.concatenate([[0], np.cumsum([_a4(s + guard) for s in fsz])])
+    ibuf = torch.empty(int(ioff[-1]), dtype=torch.int32, device=dev)
+    fbuf = torch.empty(int(foff[-1]), dtype=torch.float32, device=dev)
+    if guard:
+        ibuf.fill_(GUARD)
+        fbuf.view(torch.int32).fill_(GUARD)
+    iv = [ibuf[int(o):int(o) + s] for o, s in zip(ioff, isz)]
+    fv = [fbuf[int(o):int(o) + s] for o, s in zip(foff, fsz)]
+    head = np.zeros(hw, dtype=np.int64)
+    head[1:8] = (B, nlev, J, Jf, ldf, nmax, 1)
+    head[9], head[10] = fv[-1].data_ptr(), fv[-2].data_ptr() if Jf else 0
+    for i in range(nlev):
+        head[12 + 2 * i], head[13 + 2 * i] = Rr[i], E[i]
+        g = iv[6 * i:6 * i + 6]
+        head[20 + 7 * i:27 + 7 * i] = [g[0].data_ptr(), g[1].data_ptr(), fv[i].data_ptr()] + [t.data_ptr() for t in g[2:]]
+        if E[i] == 0:                                        # (one unread word each; kept defined, as concat_csr's zeros(1))
+            g[1].zero_()
+            fv[i].zero_()
+    for i in range(L):
+        lv = iv[6 * nlev + 3 * i:6 * nlev + 3 * i + 3]
+        head[48 + 4 * i:52 + 4 * i] = (lv[0].data_ptr(), fv[nlev + i].data_ptr(), lv[1].data_ptr(), lv[2].data_ptr())
+    rec = np.zeros((B, pw), dtype=np.int64)
+    rec[:, 0] = [p.ptr for p in parts]
+    rec[:, 1] = np.arange(B)
+    rec[B - 1, 2] = 1
+    for i in range(nlev):
+        rec[:, 3 + 4 * i], rec[:, 4 + 4 * i], rec[:, 5 + 4 * i], rec[:, 6 + 4 * i] = n[:, i], z[:, i], row0[:B, i], e0[:B, i]
+    for s in range(0, B, kmax):
+        d = np.concatenate([head, rec[s:s + kmax].reshape(-1)])
+        d[0], d[7] = min(kmax, B - s), int(s == 0)             # (the first launch starts the slot counts, the others continue them)
+        nat.call("eigen_assemble_f32", d.ctypes.data)
+    gs = []
+    for i in range(nlev):
+        g = GraphBatch()
+        g.layout, g.B, g.nmax, g.device = "packed", B, nmax, dev
+        g.sizes, g.n_rows, g.n_ghost = n[:, i].copy(), Rr[i], nmax
+        g.rowptr, g.col, g.graph_ptr, g.row_graph, g.row_slot, g.slot_count = iv[6 * i:6 * i + 6]
+        g.val, g.nnz, g.symmetric = fv[i], E[i], all(p.sym[i] for p in parts)
+        gs.append(g)
     levels = []
-    for i, h in enumerate(packed["levels"]):
+    for i in range(L):
         lv = ep.EigenLevel()
-        lv.g, lv.J = gs[i + 1], int(h["coef"].shape[1])
-        lv.cluster_of, lv.coef, lv.bptr, lv.members = (_up(h[k], dev) for k in ("cluster_of", "coef", "bptr", "members"))
+        lv.g, lv.J = gs[i + 1], J
+        lv.cluster_of, lv.bptr, lv.members = iv[6 * nlev + 3 * i:6 * nlev + 3 * i + 3]
+        lv.coef = fv[nlev + i].view(Rr[i], J)
         levels.append(lv)
-        copies += 4
-    fc = None
-    if packed["final"] is not None:
-        fc = _up(packed["final"], dev)
-        copies += 1
-    return ep.EigenBatch(gs[0], levels, fc, nmax), R.padded_rows(feats, sizes[0], dev), copies + 1
+    eb = ep.EigenBatch(gs[0], levels, fv[-2].view(Rr[L], Jf) if Jf else None, nmax)
+    eb._raw = (ibuf, fbuf, ioff, isz, foff, fsz)
+    eb._pieces = parts                                     # (a recorded launch replays by address: the buffers outlive the batch's use)
+    return fv[-1].view(Rr[0] + nmax, ldf), eb
+
+
+# ----------------------------------------------------------------------------- stage two: the embeddings of a chunk of graphs
+def model_shape(model):
+    """(L, J, Jf) of a ``WavePoolingGcnEncoder``"""
+    return len(model.pool_sizes), int(model.num_pool_matrix), int(model.num_pool_final_matrix)
+
+
+def embed_one(model, obj, dev):
+    """the embedding [1, E] of one graph object or bare ``.graph`` dict by a call of its own: a one-graph ``EigenBatch`` from
+    ``pack_host`` / ``to_device`` through the model call of ``embed_chunk`` (``TSGNN_TRIPLET_CACHE=0``, a chunk the assembler does not
+    take).  Nothing is cached.  The caller holds eval mode / no_grad."""
+    if dev.type != "cuda":
+        raise RuntimeError(R.GPU_ONLY)
+    L, J, Jf = model_shape(model)
+    d = graph_dict(obj)
+    check_dict(d, L, J, Jf)
+    eb, feats, _ = to_device(pack_host(d, L, J, Jf), d["feats"], dev)
+    x = torch.cat([feats, R.ghost_zeros(eb.nmax, feats.size(1), dev)])
+    with R.per_graph_statistics(model):
+        return model.pred_model(model(x, eb, readout_only=True))
+
+
+def embed_chunk(model, graphs, dev, cache):
+    """embeddings [len(graphs), E] of a chunk of graph objects (or bare ``.graph`` dicts): the chunk's ``EigenBatch`` assembled from
+    the resident pieces, the model ONCE under per-graph statistics, ``pred_model`` on all rows — row i is ``feat[0]`` of the
+    reference's eval-mode B = 1 call for graph i (train_triplet.py:77-78).  The caller holds eval mode / no_grad
+    (``two_stage.embed_dataset``).  ValueError for mixed Nmax, mixed feature widths, a dict prepared for another L / J / Jf than the
+    model's."""
+    L, J, Jf = model_shape(model)
+    if L > max_levels():
+        return torch.cat([embed_one(model, o, dev) for o in graphs])
+    parts = [resident_graph(o, dev, cache, L, J, Jf, check=True) for o in graphs]
+    x, eb = assemble(parts, dev)
+    with R.per_graph_statistics(model):
+        return model.pred_model(model(x, eb, readout_only=True))
 
 
 # ----------------------------------------------------------------------------- pred_model + both distances: one launch each way
@@ -226,15 +494,7 @@ class tripletnet(nn.Module):
     # ------------------------------------------------------------------ graphs
     def _graph(self, obj, dev):
         """the device side of one graph object (built at its first use)"""
-        e = self.cache.lookup(obj, dev.index) if R.RESIDENT else None
-        if e is not None:
-            return e
-        e = _Graph()
-        packed = pack_host(obj.graph, self.L, self.J, self.Jf)
-        e.eb, e.feats, copies = to_device(packed, obj.graph["feats"], dev)
-        e.n, e.nmax = packed["n"][0], packed["nmax"]
-        self.cache.h2d += copies
-        return self.cache.store(obj, e, dev.index) if R.RESIDENT else e
+        return resident_graph(obj, dev, self.cache, self.L, self.J, self.Jf)
 
     def batch(self, a, p, n):
         """the triplet as one three-graph batch on the device: the cached pieces concatenated there (no host synchronisation, no

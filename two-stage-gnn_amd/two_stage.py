@@ -35,12 +35,17 @@ def _is_dense(g):
     return isinstance(getattr(g, "graph", None), dict)
 
 
+def _is_eigen_dict(g):
+    """a bare ``.graph`` dict (what ``GraphSampler.__getitem__`` returns): only the EigenGCN route takes these"""
+    return isinstance(g, dict) and "adj" in g
+
+
 def _labels(graphs):
     """host labels of the graphs: ``graph.graph['label']`` or ``data.y`` (labels that live on the device come back in ONE copy)"""
     if not graphs:
         return np.zeros(0, dtype=np.int64)
-    if _is_dense(graphs[0]):
-        return np.asarray([np.asarray(g.graph["label"]).reshape(-1)[0] for g in graphs])
+    if _is_dense(graphs[0]) or _is_eigen_dict(graphs[0]):
+        return np.asarray([np.asarray((g if isinstance(g, dict) else g.graph)["label"]).reshape(-1)[0] for g in graphs])
     ys = [g.y for g in graphs]
     if any(isinstance(y, torch.Tensor) and y.is_cuda for y in ys):
         return torch.cat([torch.as_tensor(y).reshape(-1)[:1].to(ys[0].device) for y in ys]).cpu().numpy()
@@ -110,7 +115,11 @@ def _embed_net_chunk(tnet, graphs):
 
 
 def _embed_one(model, g, dev):
-    """the reference's own call for one graph (train_triplet.py:52-59; Code/sag/train_triplet.py:45-47)"""
+    """the reference's own call for one graph (train_triplet.py:52-59; Code/sag/train_triplet.py:45-47; an EigenGCN encoder:
+    ``eigen_triplet.embed_one``, Code/eigengcn/train_triplet.py:42-78)"""
+    from . import eigen_encoders as EE, eigen_triplet as ET
+    if isinstance(model, EE.WavePoolingGcnEncoder):
+        return ET.embed_one(model, g, dev)[0]
     if _is_dense(g):
         d = g.graph
         adj = torch.as_tensor(np.asarray(d["adj"], dtype=np.float32)[None], device=dev)
@@ -136,12 +145,25 @@ def embed_dataset(model, graphs, chunk=None):
     ``triplet.tripletnet`` / ``sag_triplet.tripletnet`` around the same model, so a graph a training step has used is not uploaded
     again, and the reverse.  A ``gat_triplet.tripletnet`` (or a bare ``gat_encoders.DGATEncoderGraph`` when ``chunk`` is given) runs its
     GAT encoder on packed chunks with one ghost representative per graph, assembled from the same cache (default
-    ``gat_triplet.DEFAULT_CHUNK`` graphs, at most the 1024 rows the encoder's fused head takes).  ANY OTHER model (a bare GAT encoder
-    without ``chunk``, EigenGCN, a module of your own) gets a plain loop of B = 1 forwards with the rows kept on the device: correct,
-    and not fast.  ``model`` may also be a ``tripletnet`` (its ``.model`` is used)."""
+    ``gat_triplet.DEFAULT_CHUNK`` graphs, at most the 1024 rows the encoder's fused head takes).
+
+    An ``eigen_triplet.tripletnet`` or a bare ``eigen_encoders.WavePoolingGcnEncoder`` (its ``pool_sizes``, ``num_pool_matrix`` and
+    ``num_pool_final_matrix`` say what the dicts must hold) runs in chunks of ``eigen_triplet.DEFAULT_CHUNK`` graphs: the chunk's
+    ``EigenBatch`` is written from the graphs' resident pieces by one launch per 32 graphs (``eigen_triplet.assemble``, csrc/eigen_assemble.hip), the
+    model runs once on it, row i is ``feat[0]`` of Code/eigengcn/train_triplet.py:77-78 for graph i.  Pass the LIST of graph objects
+    (``.graph`` = {'adj', 'feats', 'num_nodes', 'adj_pool_i', 'num_nodes_i', 'pool_adj_i_j', 'label'}, what ``GraphSampler`` fills and
+    ``TripletSampler`` hands out), not the reference's shuffled batch-1 ``DataLoader``: rows come back in the list's order, and the
+    objects key the cache shared with the triplet step.  Bare ``.graph`` dicts are taken too and packed at every call (the sampler
+    makes a new dict per access).  ValueError for mixed Nmax, mixed feature widths, a dict prepared for other L / J / Jf than the
+    model's.  With ``TSGNN_TRIPLET_CACHE=0``, or more pooling levels than the assembler takes, every graph gets a call of its own
+    on a one-graph ``EigenBatch`` (``eigen_triplet.embed_one``).
+
+    ANY OTHER model (a bare GAT encoder without ``chunk``, a module of your own) gets a plain loop of B = 1 forwards with the rows
+    kept on the device: correct, and not fast.  ``model`` may also be a ``tripletnet`` (its ``.model`` is used)."""
     from . import dense_encoders as E, gat_encoders as GE, gat_triplet as GT, sag_layers as S, sag_triplet as ST, triplet as T
+    from . import eigen_encoders as EE, eigen_triplet as ET
     gat_chunks = isinstance(model, GT.tripletnet)             # (a bare GAT encoder takes the chunked path only when chunk= is given)
-    if isinstance(model, (T.tripletnet, ST.tripletnet, GT.tripletnet)):
+    if isinstance(model, (T.tripletnet, ST.tripletnet, GT.tripletnet, ET.tripletnet)):
         model = model.model
     graphs = _flatten(graphs)
     dev = _device_of(model)
@@ -151,7 +173,15 @@ def embed_dataset(model, graphs, chunk=None):
     with _eval_mode(model):
         if not graphs:
             return torch.zeros(0, 0, dtype=torch.float32, device=dev)
-        if isinstance(model, E.GcnEncoderGraph) and dev.type == "cuda" and R.RESIDENT and _is_dense(graphs[0]):
+        if isinstance(model, EE.WavePoolingGcnEncoder):       # (a GcnEncoderGraph by inheritance: asked first)
+            if dev.type == "cuda" and R.RESIDENT and len(model.pool_sizes) <= ET.max_levels():
+                step = int(chunk) if chunk is not None else ET.DEFAULT_CHUNK
+                cache = R.resident_cache(model)
+                for i in range(0, len(graphs), step):
+                    rows.append(ET.embed_chunk(model, graphs[i:i + step], dev, cache))
+            else:
+                rows = [_embed_one(model, g, dev).reshape(1, -1) for g in graphs]
+        elif isinstance(model, E.GcnEncoderGraph) and dev.type == "cuda" and R.RESIDENT and _is_dense(graphs[0]):
             step = int(chunk) if chunk is not None else dense_chunk_limit(model)
             cache = R.resident_cache(model)
             for i in range(0, len(graphs), step):
