@@ -29,11 +29,10 @@ import pytest
 import torch
 
 import slot_ref as S
+from fp32_yardstick import EPS32, K_DEFAULT, _check, _ratio
 
 pytestmark = pytest.mark.gpu
 
-EPS32 = 2.0 ** -23
-K_DEFAULT = 8.0
 NAN = float("nan")
 NMAX = 11
 GRID_B = [1, 16, 17, 32, 33, 64, 65, 128]
@@ -46,27 +45,7 @@ def _nat():
     return nat
 
 
-# ----------------------------------------------------------------------------- tolerance
-def _ratio(hip, ref64, cpu32):
-    ref64 = ref64.double()
-    yard = max((cpu32.double() - ref64).abs().max().item(), EPS32 * ref64.abs().max().item()) if ref64.numel() else 0.0
-    err = (hip.double() - ref64).abs().max().item() if ref64.numel() else 0.0
-    if err != err:
-        return float("inf")
-    if yard == 0.0:
-        return 0.0 if err == 0.0 else float("inf")
-    return err / yard
-
-
-def _check(what, hip, ref64, cpu32, K=K_DEFAULT):
-    hip = hip.detach().cpu()
-    assert hip.shape == ref64.shape, (what, hip.shape, ref64.shape)
-    assert not torch.isnan(hip).any().item(), "%s: %d elements were never written" % (what, int(torch.isnan(hip).sum()))
-    r = _ratio(hip, ref64, cpu32)
-    print("%s: max|hip - ref64| / yardstick = %.3f" % (what, r))
-    assert r <= K, "%s: %.3f x the fp32 yardstick (bound %g)" % (what, r, K)
-
-
+# ----------------------------------------------------------------------------- tolerance (_ratio, _check: fp32_yardstick.py)
 def _check_rows(what, hip, ref64, cpu32, special_rows, K=K_DEFAULT):
     """the rows of a clamped norm carry gradients 1e12 times the others': they are held to their own scale"""
     hip = hip.detach().cpu()
