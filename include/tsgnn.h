@@ -358,6 +358,19 @@ int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, 
                                 float* c, int64_t ldc, float* rinv, float* zout, int64_t ldz, int64_t rows, int K, int N,
                                 int64_t fill_rows, const int* row_slot, unsigned long long* sums, float* ghost, int panel_units,
                                 const int64_t* pack_desc, tsgnn_stream_t stream);
+/* tsgnn_gather_rowgemm_st_f32 with the path of its B operand (w) named.  b_mode:
+ *   0  the library's choice: direct wherever it applies (this is tsgnn_gather_rowgemm_st_f32)
+ *   1  staged: w travels global -> registers -> LDS stage -> operand registers, chunk by chunk
+ *   2  direct: every wave loads the operands of its own 32 output columns straight from w (four coalesced dword loads per MFMA
+ *      group of four steps, requested behind the neighbour rows), no LDS stage and no barrier inside the K loop; the second wave
+ *      group of the two-group kernel runs only the chunks that hold a k < K.  Applies to 96 < N <= 128, K <= 128 — everything the
+ *      entry point takes; TSGNN_EUNSUPPORTED otherwise.
+ * The kernel shape (two-group / one-group / units), the schedule code and the order of every sum are the same in all modes: all
+ * outputs are the same bit for bit.  b_mode outside 0..2: TSGNN_EINVAL. */
+int tsgnn_gather_rowgemm_st_mode_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* x, int64_t ldx, const float* b, int64_t ldb,
+                                     const float* bias, float* c, int64_t ldc, float* rinv, float* zout, int64_t ldz, int64_t rows, int K, int N,
+                                     int64_t fill_rows, const int* row_slot, unsigned long long* sums, float* ghost, int panel_units,
+                                     const int64_t* pack_desc, int b_mode, tsgnn_stream_t stream);
 /* tsgnn_sage_layer_fwd[_ro]_f32 for a layer whose INPUT's slot batch-norm has no launch of its own: x = the previous layer's
  * normalised pre-activations v, sums_in / ghost_in = what its statistics epilogue left, slot_count[n] = graphs with more than n
  * nodes.  Every row-panel block turns the sums into (mean, rstd) per slot — exact from the integers, ghost copies by their

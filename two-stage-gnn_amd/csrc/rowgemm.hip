@@ -57,17 +57,18 @@ __device__ __forceinline__ void st_passengers(const PackRider& pk, const PullRid
   else pull_rider_body(pr, b - pk.blocks);
 }
 // SCHED: g.ell is the batch's gather schedule (rowgemm_body.h): 8 groups x 32 slots for the one-group kernel, 16 x 24 for the two-group one
-template <bool UNITS, int SCHED = 0>
+// BDIR: the B operands straight from W into registers (rowgemm_body.h), no LDS stage; false: W staged through LDS (b_mode = 1)
+template <bool UNITS, int SCHED = 0, bool BDIR = false>
 __global__ __launch_bounds__(256) void rowgemm_gather_st_kernel(RowGemmArgs g, PullRider pr, unsigned nblk, PackRider pk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if (blockIdx.x >= nblk) { st_passengers(pk, pr, blockIdx.x - nblk); return; }
-  rowgemm_body<4, false, true, 1, false, false, true, UNITS, false, SCHED>(g, smem, blockIdx.x);
+  rowgemm_body<4, false, true, 1, false, false, true, UNITS, false, SCHED, BDIR>(g, smem, blockIdx.x);
 }
-template <int SCHED = 0>
+template <int SCHED = 0, bool BDIR = false>
 __global__ __launch_bounds__(512) void rowgemm_gather_ks2_st_kernel(RowGemmArgs g, PullRider pr, unsigned nblk, PackRider pk) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   if (blockIdx.x >= nblk) { st_passengers(pk, pr, blockIdx.x - nblk); return; }
-  rowgemm_body<4, false, true, 2, false, false, true, false, false, SCHED>(g, smem, blockIdx.x);
+  rowgemm_body<4, false, true, 2, false, false, true, false, false, SCHED, BDIR>(g, smem, blockIdx.x);
 }
 
 // column-split variant for products WITHOUT the row epilogue (no normalise: rows need not be whole): grid.y column blocks of
@@ -270,6 +271,18 @@ int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, 
                                 float* c, int64_t ldc, float* rinv, float* zout, int64_t ldz, int64_t rows, int K, int N,
                                 int64_t fill_rows, const int* row_slot, unsigned long long* sums, float* ghost, int panel_units,
                                 const int64_t* pack_desc, tsgnn_stream_t stream) {
+  return tsgnn_gather_rowgemm_st_mode_f32(ell, ell_w, tail_ptr, tail_col, x, ldx, b, ldb, bias, c, ldc, rinv, zout, ldz, rows, K, N, fill_rows, row_slot, sums,
+                                          ghost, panel_units, pack_desc, 0, stream);
+}
+
+/* the same launch with the path of its B operand named: b_mode 0 = the library's choice (direct), 1 = W staged through LDS, 2 = W
+ * straight into the matrix cores' operand registers (rowgemm_body.h BDIR).  The same kernel shape, schedule code and summation order
+ * either way: every output is the same bit for bit. */
+int tsgnn_gather_rowgemm_st_mode_f32(const int* ell, int ell_w, const int* tail_ptr, const int* tail_col, const float* x, int64_t ldx, const float* b, int64_t ldb,
+                                     const float* bias, float* c, int64_t ldc, float* rinv, float* zout, int64_t ldz, int64_t rows, int K, int N,
+                                     int64_t fill_rows, const int* row_slot, unsigned long long* sums, float* ghost, int panel_units,
+                                     const int64_t* pack_desc, int b_mode, tsgnn_stream_t stream) {
+  if (b_mode < 0 || b_mode > 2) return TSGNN_EINVAL;
   if (!ell || !x || !b || !c || !row_slot || !sums || !ghost || rows <= 0 || fill_rows < 0 || K <= 0 || N <= 0 || ldx < K || ldc < N)
     return TSGNN_EINVAL;
   const bool sched = ell_w == TSGNN_SCHED_8x32 || ell_w == TSGNN_SCHED_16x24;   // ell = the batch's gather schedule
@@ -295,6 +308,7 @@ int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, 
   RowGemmArgs g{x, ldx, b, ldb, bias, c, ldc, rinv, rows, K, N, 1, fill_rows, ell, ell_w, zout, ldz, tail_ptr, tail_col};
   g.st_row_slot = row_slot; g.st_sums = sums; g.st_ghost = ghost;
   unsigned nblk = (unsigned)(ceil_div64(rows, 32) + (fill_rows > 0 ? 1 : 0));
+  const bool direct = b_mode != 1;                       // (the direct path takes everything this entry point takes: 96 < N <= 128, K <= 128)
   const bool ks2 = K > KC && nblk <= ks2_max_blocks() && rowgemm_ks2_enabled();
   if (!ks2)                                              // (the one-group kernel: a few more panels than CUs go as 16-row units)
     nblk = panel_split(rows, device_cu_count(), panel_units, &g.n_full, &g.unit) + (fill_rows > 0 ? 1u : 0u);
@@ -311,15 +325,28 @@ int tsgnn_gather_rowgemm_st_f32(const int* ell, int ell_w, const int* tail_ptr, 
     const PullRider pr = take_pull_rider(512);             // (blocks = 0 unless tsgnn_ingest_arm_pull_rider[_parts] armed one on this thread)
     pk.blocks *= PACK_SET_ENTRIES / 512;
     TSGNN_KNAME("rowgemm_gather_ks2_st_kernel");
-    if (sched) rowgemm_gather_ks2_st_kernel<TSGNN_SCHED_16x24><<<nblk + pk.blocks + pr.blocks, 512, lds2, stream>>>(g, pr, nblk, pk);
-    else rowgemm_gather_ks2_st_kernel<0><<<nblk + pk.blocks + pr.blocks, 512, lds2, stream>>>(g, pr, nblk, pk);
+    const unsigned grid = nblk + pk.blocks + pr.blocks;
+    constexpr size_t ldsd = rowgemm_lds_bytes<4, false, true, 2, false, true>();    // (direct: the exchange buffer and the panel, 50 KiB)
+    if (direct && sched) rowgemm_gather_ks2_st_kernel<TSGNN_SCHED_16x24, true><<<grid, 512, ldsd, stream>>>(g, pr, nblk, pk);
+    else if (direct) rowgemm_gather_ks2_st_kernel<0, true><<<grid, 512, ldsd, stream>>>(g, pr, nblk, pk);
+    else if (sched) rowgemm_gather_ks2_st_kernel<TSGNN_SCHED_16x24><<<grid, 512, lds2, stream>>>(g, pr, nblk, pk);
+    else rowgemm_gather_ks2_st_kernel<0><<<grid, 512, lds2, stream>>>(g, pr, nblk, pk);
   } else {
     const PullRider pr = take_pull_rider(256);
     pk.blocks *= PACK_SET_ENTRIES / 256;
     TSGNN_KNAME("rowgemm_gather_st_kernel<%s>", (g.unit == 8 || g.unit == 16) ? "true" : "false");
-    if (g.unit == 8 || g.unit == 16) rowgemm_gather_st_kernel<true><<<nblk + pk.blocks + pr.blocks, 256, rowgemm_lds_bytes<4, false, true>(), stream>>>(g, pr, nblk, pk);
-    else if (sched) rowgemm_gather_st_kernel<false, TSGNN_SCHED_8x32><<<nblk + pk.blocks + pr.blocks, 256, rowgemm_lds_bytes<4, false, true>(), stream>>>(g, pr, nblk, pk);
-    else rowgemm_gather_st_kernel<false><<<nblk + pk.blocks + pr.blocks, 256, rowgemm_lds_bytes<4, false, true>(), stream>>>(g, pr, nblk, pk);
+    const unsigned grid = nblk + pk.blocks + pr.blocks;
+    constexpr size_t lds = rowgemm_lds_bytes<4, false, true>(), ldsd = rowgemm_lds_bytes<4, false, true, 1, false, true>();
+    const bool units = g.unit == 8 || g.unit == 16;
+    if (direct) {
+      if (units) rowgemm_gather_st_kernel<true, 0, true><<<grid, 256, ldsd, stream>>>(g, pr, nblk, pk);
+      else if (sched) rowgemm_gather_st_kernel<false, TSGNN_SCHED_8x32, true><<<grid, 256, ldsd, stream>>>(g, pr, nblk, pk);
+      else rowgemm_gather_st_kernel<false, 0, true><<<grid, 256, ldsd, stream>>>(g, pr, nblk, pk);
+    } else {
+      if (units) rowgemm_gather_st_kernel<true><<<grid, 256, lds, stream>>>(g, pr, nblk, pk);
+      else if (sched) rowgemm_gather_st_kernel<false, TSGNN_SCHED_8x32><<<grid, 256, lds, stream>>>(g, pr, nblk, pk);
+      else rowgemm_gather_st_kernel<false><<<grid, 256, lds, stream>>>(g, pr, nblk, pk);
+    }
   }
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;

@@ -109,6 +109,13 @@ constexpr int LDA_F = 128;            // row stride of the gathered full-K A pan
 // g.b_img with sixteen 1 KB-contiguous 16-byte loads, asked for AFTER the neighbour rows (a wave's loads return in issue order: W is
 // not needed before the gather has ended); no register staging, no LDS stage, no barrier in the K loop.  The MFMA chain sees the
 // operands of the staged path in the same order, so the product is the same bit for bit.
+// BDIR (GATHER, NT = 4, K <= 128, B = W row-major; KS = 1 or 2): the image path without an image.  The fragment a lane wants,
+// B[k = 8u + 4h .. + 3][n = 32 wave + i], is four dword loads out of W itself, each coalesced over i into one 128-byte line (W is hot
+// in L2 in every block): every wave fills the operands of its group's chunks (bq[], the image path's layout) with unconditional loads
+// from clamped addresses, asked for AFTER the neighbour rows, and masks k >= K and n >= N to 0.f once they are in — what the staged
+// path writes into its LDS stage.  No register staging, no stage, no barrier between a group's first and last MFMA; the chain sees
+// the staged path's operands in the same order (the zero rows of a partial last chunk included).  KS = 2: group 1 runs only the
+// chunks that hold a k < K (at K = 92 its second chunk, k in [96, 128), multiplies zeros by zeros: +0.0 added to every accumulator).
 // SCHED = S > 0 (GATHER, plain 32-row panels): g.ell is the batch's GATHER SCHEDULE (include/tsgnn.h; GraphBatch.gather_schedule) instead of
 // the neighbour table.  The table path asks for the first GN neighbours of a lane's 4 / KS rows, waits, and asks rows with more for
 // neighbours 9-16: a second dependent index trip + row trip that nearly every panel pays (13 % of the DD rows have >= 8 neighbours),
@@ -119,13 +126,14 @@ constexpr int LDA_F = 128;            // row stride of the gathered full-K A pan
 // fewer than GN neighbours: -0.0 + 0.0 = +0.0) and from -0.0 (x + -0.0 = x for every x) elsewhere.  S = 32 for the 256-thread kernels,
 // 24 for the 512-thread one (KS = 2).
 template <int NT, bool TRANS_B, bool GATHER, int KS = 1, bool READOUT = false, bool BNIN = false, bool STATS = false, bool UNITS = false,
-          bool BIMG = false, int SCHED = 0>
+          bool BIMG = false, int SCHED = 0, bool BDIR = false>
 __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_all, unsigned bid) {
   static_assert(KS == 1 || (KS == 2 && GATHER && NT <= 4), "the split-K variant is built for the gather kernel, widths <= 128");
   static_assert(!READOUT || (NT <= 4 && KS == 1), "the readout epilogue is built for one column tile per wave");
   static_assert(!BNIN || (GATHER && KS == 1), "batch-norm on the fly lives in the gather prologue of the one-group kernel");
   static_assert(!STATS || NT <= 4, "the statistics epilogue is built for one column tile per wave");
   static_assert(!BIMG || (GATHER && KS == 1 && NT == 4), "the image variant is built for the one-group gather kernel at K = N = 128");
+  static_assert(!BDIR || (GATHER && NT == 4 && !TRANS_B && !BIMG && !BNIN), "direct B operands: the layer-0 gather kernels, widths 97..128");
   static_assert(SCHED == 0 || (GATHER && !UNITS && SCHED == (KS == 2 ? 24 : 32)), "gather schedules: 8 x 32 (one group) / 16 x 24 (two groups), plain panels");
   constexpr int NP = 32 * NT;
   constexpr int TPW = (NT + 3) / 4;
@@ -142,7 +150,8 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
   const int kb = grp * Kc;
   const int Kv = KS == 1 ? g.K : min(g.K - kb, Kc);
   // LDS floats per wave group (BIMG: no stages, only what the epilogue and the filler block borrow from them: redq, fred)
-  constexpr int GRP = BIMG ? 256 : (KS == 2 && 2 * STAGE < 4096 + 256) ? 4096 + 256 : 2 * STAGE;
+  constexpr bool BREG = BIMG || BDIR;                    // B operands in registers: no stages
+  constexpr int GRP = BREG ? (KS == 2 ? 4096 + 256 : 256) : (KS == 2 && 2 * STAGE < 4096 + 256) ? 4096 + 256 : 2 * STAGE;
   float* smem = smem_all + grp * GRP;                    // this group's two stages
   // common to the block: the gathered panel, and 256 floats of epilogue scratch (KS = 2: inside group 1's idle stages,
   // after the accumulator exchange buffer)
@@ -321,7 +330,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
                               : *reinterpret_cast<const float4*>(As + i * lda_s + 8 * u + 4 * h);
       af[4 * u] = v.x; af[4 * u + 1] = v.y; af[4 * u + 2] = v.z; af[4 * u + 3] = v.w;
     }
-    if constexpr (BIMG) return;                         // (the B operands come from the image)
+    if constexpr (BREG) return;                         // (the B operands come from the image / from W itself)
 #pragma unroll
     for (int t = 0; t < TPW; ++t) {
       const int tile = wid + 4 * t;
@@ -403,12 +412,8 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
   if constexpr (STATS) {
     if (g.st_sums && wid == 0 && grp == 0 && lane < 32 && (m0 + lane) < rows_hi) st_slot = g.st_row_slot[m0 + lane];
   }
-  if constexpr (!BIMG) {
-#pragma unroll
-    for (int c = 0; c < NS; ++c)
-      if (c == 0 || c * KC < Kc) fetch(st[c], c * KC);
-  }
-  float bq[BIMG ? 4 * KC / 2 : 1];                     // BIMG: the wave's B operands of all four chunks (chunk c, step j: bq[16 c + j])
+  constexpr int NCH = 4 / KS;                          // chunks of a group at K = 128
+  float bq[BREG ? NCH * KC / 2 : 1];                   // BIMG / BDIR: the wave's B operands of all its chunks (chunk c, step j: bq[16 c + j])
   auto img_fetch = [&](int u0) {                       // eight steps (two chunks) of the image
     const float4* img = g.b_img + (wid * 16 + u0) * 64 + lane;
 #pragma unroll
@@ -417,6 +422,47 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
       bq[4 * (u0 + u)] = v.x; bq[4 * (u0 + u) + 1] = v.y; bq[4 * (u0 + u) + 2] = v.z; bq[4 * (u0 + u) + 3] = v.w;
     }
   };
+  // BDIR: the K range the group's loop covers (group 1 stops behind its last chunk that holds a k < K), the lane's column, and
+  // chunk c of W -> bq: whole chunks from W + (scalar row offset), a partial one from clamped rows; dir_mask zeroes what is not there
+  const int Kl = (BDIR && KS == 2) ? Kv : Kc;
+  const int dn = wid * 32 + i;
+  const float* dbp = g.b + min(dn, g.N - 1);
+  auto dir_fetch = [&](int c) {
+    if (c * KC >= Kl) return;
+    const int kc0 = kb + c * KC;
+    if (kc0 + KC <= g.K) {
+      const float* p = dbp + (int64_t)(kc0 + 4 * h) * g.ldb;
+#pragma unroll
+      for (int u = 0; u < KC / 8; ++u)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bq[16 * c + 4 * u + q] = p[(int64_t)(8 * u + q) * g.ldb];
+    } else {
+#pragma unroll
+      for (int u = 0; u < KC / 8; ++u)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) bq[16 * c + 4 * u + q] = dbp[(int64_t)min(kc0 + 8 * u + 4 * h + q, g.K - 1) * g.ldb];
+    }
+  };
+  auto dir_mask = [&](int c) {
+    const int kc0 = kb + c * KC;
+    if (c * KC >= Kl || (kc0 + KC <= g.K && g.N == NP)) return;
+#pragma unroll
+    for (int u = 0; u < KC / 8; ++u)
+#pragma unroll
+      for (int q = 0; q < 4; ++q)
+        if (kc0 + 8 * u + 4 * h + q >= g.K || dn >= g.N) bq[16 * c + 4 * u + q] = 0.f;
+  };
+  auto dir_fetch2 = [&](int c0) {                      // two chunks, in this place of the wave's load queue
+    __builtin_amdgcn_sched_barrier(0);
+    if (c0 < NCH) dir_fetch(c0);
+    if (c0 + 1 < NCH) dir_fetch(c0 + 1);
+    __builtin_amdgcn_sched_barrier(0);
+  };
+  if constexpr (!BREG) {
+#pragma unroll
+    for (int c = 0; c < NS; ++c)
+      if (c == 0 || c * KC < Kc) fetch(st[c], c * KC);
+  }
   if (GATHER) {
     // A panel = aggregated rows.  Row-major like the stand-alone aggregation kernel: 32 lanes per row (one float4 column
     // each), 8 rows per pass, 4 passes; the first GN neighbour rows of all four passes are in flight together
@@ -450,6 +496,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
         img_fetch(0);
         __builtin_amdgcn_sched_barrier(0);
       }
+      if constexpr (BDIR) dir_fetch2(0);
       if constexpr (BNIN) {
         __syncthreads();                               // the table of (rstd, mean * rstd) is complete
 #pragma unroll
@@ -495,6 +542,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
         img_fetch(8);
         __builtin_amdgcn_sched_barrier(0);
       }
+      if constexpr (BDIR && NCH > 2) dir_fetch2(2);
     } else {
     float4 nbv[NPASS][GN];
 #pragma unroll
@@ -509,6 +557,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
       img_fetch(0);
       __builtin_amdgcn_sched_barrier(0);
     }
+    if constexpr (BDIR) dir_fetch2(0);
     if constexpr (BNIN) {
       __syncthreads();                                 // the table of (rstd, mean * rstd) is complete
       // y = (relu(v) - mean) rstd = fma(relu(v), rstd, -mean rstd): one max + one fma per element
@@ -580,6 +629,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
       img_fetch(8);
       __builtin_amdgcn_sched_barrier(0);
     }
+    if constexpr (BDIR && NCH > 2) dir_fetch2(2);
     }                                                  // (table path)
   }
   float bias_v[TPW];                                   // fetched now, used in the epilogue
@@ -589,7 +639,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
     bias_v[t] = (g.bias && (wid + 4 * t) < NT && cn < g.N) ? g.bias[cn] : 0.f;
   }
   TR(1);
-  if constexpr (!BIMG) {
+  if constexpr (!BREG) {
     commit(st[0], smem);
     if (KC < Kc) commit(st[1], smem + STAGE);
   }
@@ -610,7 +660,23 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
       TR(4 + 2 * c);
     }
   }
-  if (NS == 2 && !BIMG) {
+  if constexpr (BDIR) {
+    // up to NCH chunks, A fragments one chunk ahead out of the gathered panel, B operands in registers; nothing to synchronise
+#pragma unroll
+    for (int c = 0; c < NCH; ++c) {
+      if (c * KC < Kl) {
+        if (c + 1 < NCH && (c + 1) * KC < Kl) frags(smem, (c + 1) * KC, fa[(c + 1) & 1], fb[0]);
+        dir_mask(c);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int j = 0; j < KC / 2; ++j) acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[c & 1][j], bq[16 * c + j], acc[0], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);
+        TR(3 + 2 * c);
+        TR(4 + 2 * c);
+      }
+    }
+  }
+  if (NS == 2 && !BREG) {
     if (2 * KC < Kc) fetch(st[0], 2 * KC);
     if (3 * KC < Kc) fetch(st[1], 3 * KC);
   }
@@ -640,7 +706,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
     if (Kc > 2 * KC) __syncthreads();                  // stage reuse only exists beyond two chunks (both were committed before
     TR(4 + 2 * min(c, 3));                             // the loop): without it the two K groups of a panel run uncoupled
   };
-  for (int c = 0; !BIMG && c * KC < Kc; c += 4) {
+  for (int c = 0; !BREG && c * KC < Kc; c += 4) {
     body(std::integral_constant<int, 0>{}, c);
     if ((c + 1) * KC < Kc) body(std::integral_constant<int, 1>{}, c + 1);
     if ((c + 2) * KC < Kc) body(std::integral_constant<int, 2>{}, c + 2);
@@ -694,7 +760,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
       float* red = scratch;                            // [32 rows][4 waves]
       float* inv = red + 128 + wid * 32;               // per wave [32 rows]
       float* redq = smem_all;                          // [2][32 rows][4 waves]: the K loop's stages are idle once every wave has left it
-      if constexpr (STATS) { if (Kc <= 2 * KC) __syncthreads(); }      // (the loop only synchronises beyond two chunks)
+      if constexpr (STATS && !BDIR) { if (Kc <= 2 * KC) __syncthreads(); }      // (the loop only synchronises beyond two chunks; BDIR: no stages)
       float tot = row16_sum_transpose(ss);
       tot += __shfl_xor(tot, 16, 64);
       float t1 = 0.f, t2 = 0.f;

@@ -71,6 +71,9 @@ HEAD_DU = os.environ.get("TSGNN_HEAD_DU", "1") != "0"                     # ... 
 # trip, GraphBatch.gather_schedule) instead of the fixed-width table (neighbours 9-16 in a second dependent phase)
 GATHER_SCHED = os.environ.get("TSGNN_GATHER_SCHED", "1") != "0"
 GATHER_SCHED_L0 = os.environ.get("TSGNN_GATHER_SCHED_L0", "1") != "0"    # ... layer 0's launch too (0: only the hidden layers' four)
+# layer 0's launch takes its weight operands straight from W (no LDS stage; csrc/rowgemm_body.h BDIR).  0: W staged through LDS
+# (tsgnn_gather_rowgemm_st_mode_f32 at b_mode = 1): the same result bit for bit, for A/B measurements and the tests
+L0_DIRECT_B = os.environ.get("TSGNN_L0_DIRECT_B", "1") != "0"
 DU_MAP = os.environ.get("TSGNN_DU_MAP", "1") != "0"             # exact batches: the head backward's dU workgroups listed by the host
 SLABS_BESIDE = os.environ.get("TSGNN_SLABS_BESIDE", "1") != "0"
 NSLAB_MAX = int(os.environ.get("TSGNN_NSLAB_MAX", "0"))
@@ -251,9 +254,13 @@ class _SageStack(torch.autograd.Function):
                 g_out = ghost[2 * l:2 * l + 2] if l < L - 1 else None
                 if l == 0:
                     e_, w_, tp_, tc_ = (sch0, sch0_w, None, None) if sch0 is not None else (ell, ell_w, tp, tc)
-                    nat.call("gather_rowgemm_st_f32", e_, w_, tp_, tc_, x, x.stride(0), Ws[0], Ws[0].stride(0), bs[0], v, v.stride(0), rinv, z,
-                             z.stride(0), g.n_rows, K, N, gs, g.row_slot, s_out, g_out, int(g.panel_units),
-                             pack_desc.ctypes.data if pack_desc is not None else None)
+                    a0 = (e_, w_, tp_, tc_, x, x.stride(0), Ws[0], Ws[0].stride(0), bs[0], v, v.stride(0), rinv, z,
+                          z.stride(0), g.n_rows, K, N, gs, g.row_slot, s_out, g_out, int(g.panel_units),
+                          pack_desc.ctypes.data if pack_desc is not None else None)
+                    if L0_DIRECT_B:
+                        nat.call("gather_rowgemm_st_f32", *a0)
+                    else:
+                        nat.call("gather_rowgemm_st_mode_f32", *a0, 1)
                     mean = rstd = None
                 else:
                     pm, pr_ = saved[l - 1][3], saved[l - 1][4]
