@@ -238,9 +238,7 @@ class GcnEncoderGraph(nn.Module):
         if FUSED_STACK and allowed:
             from . import sage_stack
             convs = [conv_first] + list(conv_block) + [conv_last]
-            if (sage_stack.eligible(g, convs, self.bn, x)
-                    and bool(mp.nat.lib().tsgnn_slot_fused_supported(g.B, convs[0].output_dim))
-                    and bool(mp.nat.lib().tsgnn_slot_fused_supported(g.B, convs[-1].output_dim))):
+            if sage_stack.eligible(g, convs, self.bn, x):
                 with sage_stack.per_graph_stats(per_graph):
                     return sage_stack.sage_stack_nodes(x, g, convs, mask_ghost)     # one autograd node, layers write into the cat
         x = self._post(conv_first.forward_rows(x, g), g)
@@ -259,8 +257,6 @@ class GcnEncoderGraph(nn.Module):
         from . import sage_stack
         convs = [self.conv_first] + list(self.conv_block) + [self.conv_last]
         if self.concat and FUSED_STACK and sage_stack.eligible(g, convs, self.bn, x) and \
-                bool(mp.nat.lib().tsgnn_slot_fused_supported(g.B, convs[0].output_dim)) and \
-                bool(mp.nat.lib().tsgnn_slot_fused_supported(g.B, convs[-1].output_dim)) and \
                 (not self.per_graph_bn or (PER_GRAPH_STACK and g.row_graph is not None and g.n_ghost == g.nmax
                                            and convs[0].output_dim <= 256)):
             # (per-graph statistics, the triplet step: the same node with the row-local batch-norm launches, sage_stack.per_graph_stats)
@@ -310,9 +306,7 @@ class GcnEncoderGraph(nn.Module):
     def _stack_fusable(self, x, g):
         from . import sage_stack
         convs = [self.conv_first] + list(self.conv_block) + [self.conv_last]
-        ok = (self.concat and FUSED_STACK and not self.per_graph_bn and sage_stack.eligible(g, convs, self.bn, x)
-              and bool(mp.nat.lib().tsgnn_slot_fused_supported(g.B, convs[0].output_dim))
-              and bool(mp.nat.lib().tsgnn_slot_fused_supported(g.B, convs[-1].output_dim)))
+        ok = self.concat and FUSED_STACK and not self.per_graph_bn and sage_stack.eligible(g, convs, self.bn, x)
         return ok, convs
 
     def forward(self, x, adj, batch_num_nodes=None, **kwargs):
@@ -423,13 +417,10 @@ class SoftPoolingGcnEncoder(GcnEncoderGraph):
         from . import sage_stack
         if not (FUSED_STACK and sage_stack.PAIR_LAUNCHES and not self.per_graph_bn and (masked or not g.n_ghost)):
             return False
-        lib = mp.nat.lib()
         for xx, convs in ((x, [self.conv_first] + list(self.conv_block) + [self.conv_last]),
                           (x_a, [self.assign_conv_first_modules[0]] + list(self.assign_conv_block_modules[0])
                            + [self.assign_conv_last_modules[0]])):
-            if not (torch.is_tensor(xx) and xx.dim() == 2 and sage_stack.eligible(g, convs, self.bn, xx)
-                    and bool(lib.tsgnn_slot_fused_supported(g.B, convs[0].output_dim))
-                    and bool(lib.tsgnn_slot_fused_supported(g.B, convs[-1].output_dim))):
+            if not (torch.is_tensor(xx) and xx.dim() == 2 and sage_stack.eligible(g, convs, self.bn, xx)):
                 return False
         return True
 

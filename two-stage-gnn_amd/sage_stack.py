@@ -9,6 +9,11 @@ sequence (the b = 32 shape is bound by launch boundaries and per-
                        sage_layer_bwd (dW/db slabs || dX = (A dU) W^T) for hidden layers / linear_wgrad slabs for layer 0,
                        ONE slab reduction for all layers (straight into the trainer's flat gradient bucket when installed)
 
+The node's forward and backward are drivers over these stages (DESIGN.md has the map from stage to launch group):
+
+  forward  : _Fwd (set-up) -> _fused_bn_workspace ? _forward_fused_bn : _forward_layers (_layer_product, _layer_post) -> _forward_tail
+  backward : _head_backward -> per layer _layer_du, then _spend_du (merged launch, else slabs and the dX product) -> one WgradSets.close()
+
 Ghost rows (DESIGN.md): they aggregate nothing, so the products skip them and a filler block writes their constant output;
 only the ghost slots up to the largest graph can influence anything, so the slot kernels run on those.
 
@@ -16,6 +21,10 @@ Used when the batch qualifies (slot-BN on, sum aggregation without self term, <=
 configuration runs the operator-by-operator path in dense_encoders.py: same results, more launches.  Every fusion has a switch
 (environment / module attribute) that selects the launch sequence it replaces.
 """
+import contextlib
+import os
+from collections import namedtuple
+
 import numpy as np
 import torch
 
@@ -24,6 +33,7 @@ from . import message_passing as mp
 
 
 def eligible(g, convs, bn, x):
+    """may this stack run as the fused node?  (the whole answer: shapes, layout, and the library's word on the slot kernels)"""
     if not bn or g.B > 128 or len(convs) < 2:
         return False
     hid = convs[0].output_dim
@@ -34,7 +44,10 @@ def eligible(g, convs, bn, x):
             return False
         if i < len(convs) - 1 and c.output_dim != hid:
             return False
-    return x.dim() == 2 and x.size(1) % 4 == 0 and x.is_cuda and x.stride(0) % 4 == 0
+    if not (x.dim() == 2 and x.size(1) % 4 == 0 and x.is_cuda and x.stride(0) % 4 == 0):
+        return False
+    # (host-only query: the slot kernels take B graphs at the first and the last layer's width)
+    return all(bool(nat.lib().tsgnn_slot_fused_supported(g.B, c.output_dim)) for c in (convs[0], convs[-1]))
 
 
 def _aggregate_raw(g, x, transposed=False, rows=None):
@@ -46,8 +59,6 @@ def _aggregate_raw(g, x, transposed=False, rows=None):
     rp, col, val = g.transposed() if transposed else (g.rowptr, g.col, g.val)
     return mp.spmm_raw(rp, col, val, x, n)
 
-
-import os
 
 FUSED_TAIL = os.environ.get("TSGNN_FUSED_TAIL", "1") != "0"        # last readout + decode + the two Linear layers in one launch
 MERGED_FWD = os.environ.get("TSGNN_MERGED_FWD", "1") != "0"        # a layer's product + the readout partial of its input in one launch
@@ -81,10 +92,9 @@ _ncu = {}
 
 
 def _cu_count(dev):
-    n = _ncu.get(dev)
-    if n is None:
-        n = _ncu[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
-    return n
+    if dev not in _ncu:
+        _ncu[dev] = torch.cuda.get_device_properties(dev).multi_processor_count
+    return _ncu[dev]
 
 
 def _slabs_beside_panels(nslab, rps, need, rows, K, N, dev, panel_units):
@@ -110,9 +120,7 @@ def _slabs_beside_panels(nslab, rps, need, rows, K, N, dev, panel_units):
 
 
 def _gather_ok(g, x):
-    if not GATHER_FUSED or g.val is not None or not mp.ell_ok(x) or g.total_rows > GATHER_MAX_ROWS:
-        return False
-    return True
+    return bool(GATHER_FUSED and g.val is None and mp.ell_ok(x) and g.total_rows <= GATHER_MAX_ROWS)
 
 
 def _gather_sched(g, slots=False, layer0_k=0, fill=0):
@@ -128,12 +136,6 @@ def _gather_sched(g, slots=False, layer0_k=0, fill=0):
     return (sched, code) if sched is not None else (None, 0)
 
 
-def _flush_readout(g, B, sn, sg, pending):
-    if pending is not None:
-        y, pk = pending
-        nat.call("readout_partial_f32", g.graph_ptr, B, sn, g.n_rows, sg, y, y.stride(0), y.size(1), pk)
-
-
 # Per-graph statistics (B = 1 semantics: the 2stg triplet step runs anchor / positive / negative as one batch in which every graph
 # keeps the batch-norm statistics it would have alone, tripletnet.py:36-38): the slot batch-norm degenerates to a per-row layer norm,
 # so the two slot launches of a hidden layer are replaced by their row-local counterparts (tsgnn_row_ln_fwd_f32 forward,
@@ -144,22 +146,401 @@ def _flush_readout(g, B, sn, sg, pending):
 # the caller around the node's forward (`with per_graph_stats(True):`); the statistics without launches of their own (FUSED_BN)
 # are per slot across graphs and are not used in this mode.
 _PER_GRAPH = [False]
-
 _IMG_FLOATS = 16384        # one fragment-major weight image (tsgnn_sage_conv_pack_f32): [4 waves][16 steps][64 lanes] float4
 _IMG_LAYERS = 4            # hidden layers whose two images one launch's pack riders write (8 images)
+_Saved = namedtuple("_Saved", "z v rinv mean rstd lean")      # what a layer leaves for the backward (lean: z has the real rows only)
 
 
-class per_graph_stats:
-    def __init__(self, on=True):
-        self.on = bool(on)
+@contextlib.contextmanager
+def per_graph_stats(on=True):
+    prev, _PER_GRAPH[0] = _PER_GRAPH[0], bool(on)
+    try:
+        yield
+    finally:
+        _PER_GRAPH[0] = prev
 
-    def __enter__(self):
-        self.prev = _PER_GRAPH[0]
-        _PER_GRAPH[0] = self.on
 
-    def __exit__(self, *exc):
-        _PER_GRAPH[0] = self.prev
-        return False
+def _neighbours(g, sched=None, width=0, table=None):
+    """(table, width, tail_ptr, tail_col): the neighbour operands of a gather launch on g.  sched / width: a packed schedule
+    (_gather_sched) goes in the table's place, without a tail; table: (table, tail_col) of g.ell_slots() in place of the plain ids."""
+    ell, ell_w, tail = g.ell()
+    if sched is not None:
+        return sched, width, None, None
+    tp, tc = tail if tail is not None else (None, None)
+    return (ell, ell_w, tp, tc) if table is None else (table[0], ell_w, tp, table[1])
+
+
+class _Fwd:
+    """one forward's set-up (operands, ghost slots, output buffers) and the state its layers hand on: pending_ro = (y, packed
+    segment) of a readout that rides in the next layer's launch, off = the layer's offset in `packed`, last_ro_done"""
+
+    def __init__(s, x0, g, has_bias, nodes, params):
+        s.g, s.nodes, L = g, nodes, len(params) // 2
+        Ws = s.Ws = [params[2 * l].contiguous() for l in range(L)]
+        bs = s.bs = [params[2 * l + 1] if has_bias else None for l in range(L)]
+        R, B, dev = g.total_rows, g.B, x0.device
+        Fh, Fl = Ws[0].size(1), Ws[-1].size(1)
+        s.L, s.Fh, s.Fl, s.dev = L, Fh, Fl, dev
+        s.total = B * ((L - 1) * Fh + Fl)
+        # cleared by the first slot_bn_fwd launch; Fl spare words behind the last layer's segment take the readout of the dummy
+        # graph that the padding rows of a capacity-padded batch (ingest.py) belong to: never cleared, never read
+        s.packed = torch.empty(s.total + Fl, dtype=torch.int64, device=dev) if not nodes else None
+        s.cat = torch.empty(R, (L - 1) * Fh + Fl, dtype=torch.float32, device=dev) if nodes else None
+        x = s.x = mp._check(x0, R)
+        # Ghost slots actually needed.  Every graph's padded rows at slots >= the largest graph are bitwise identical in
+        # every layer (same bias row, same statistics), the max readout breaks ties towards the smallest row, and nothing
+        # aggregates from a ghost row: only slots [0, max_size] can influence an output or a gradient.  The slot kernels,
+        # the filler and the bias gradient therefore run on  gs = min(nmax, max_size + 1)  ghost rows (half of nmax on DD).
+        # (nodes = 1, the unmasked node output: every ghost row is part of the result)
+        gs = g.n_ghost
+        if nodes != 1 and g.n_ghost > 0 and x.stride(0) % 4 == 0 and all(
+                Ws[l].size(1) % 4 == 0 and Ws[l].data_ptr() % 16 == 0 and (bs[l] is None or bs[l].data_ptr() % 16 == 0) for l in range(L)):
+            # (capacity-padded batches keep one shape for every batch: a fixed bound instead of this batch's largest graph)
+            fixed = getattr(g, "ghost_slots_fixed", None)
+            gs = min(g.nmax, (int(fixed) if fixed is not None else int(g.sizes.max()) + 1))
+        s.gs, (s.sn, s.sg) = gs, ((gs, gs) if g.n_ghost else (g.nmax, 0))      # (slots, ghost rows) handed to the slot kernels
+        s.keep, s.pending_ro, s.off, s.last_ro_done = [], None, 0, False
+
+
+def _fused_bn_workspace(s, head, per_graph):
+    """the batch's workspace (GraphBatch.bn_workspace, cleared if an earlier forward left it dirty) when the stack runs with slot
+    batch-norm inside its products (_forward_fused_bn), else None"""
+    g, x, Ws, bs, L, Fh, Fl, sn = s.g, s.x, s.Ws, s.bs, s.L, s.Fh, s.Fl, s.sn
+    if not (FUSED_BN and not per_graph and head is not None and not s.nodes and L >= 2 and g.n_ghost == g.nmax and sn == s.sg and sn <= 1024
+            and Fh == 128 and Fl == 128 and Ws[0].size(0) <= 128 and x.size(1) % 4 == 0 and MERGED_FWD and EPILOGUE_READOUT
+            and _gather_ok(g, x) and all(Ws[l].size(0) == 128 and Ws[l].stride(0) % 4 == 0 for l in range(1, L))
+            and all(Ws[l].data_ptr() % 16 == 0 and (bs[l] is None or bs[l].data_ptr() % 16 == 0) for l in range(L))
+            and mp.rowgemm_ok(x, x.stride(0), Ws[0], Ws[0].stride(0), Ws[0].size(0), Fh, False)
+            and head[0].size(0) <= 128 and (L - 1) * Fh + Fl <= 2048 and g.row_graph is not None) or g.ell_slots() is None:
+        return None
+    bnf = g.bn_workspace(g.B, L, Fh, Fl, sn)
+    if bnf["dirty"]:
+        bnf["sums"].zero_(); bnf["ghost"].zero_(); bnf["packed"].zero_()
+    bnf["dirty"] = True
+    return bnf
+
+
+def _forward_fused_bn(s, bnf):
+    """slot batch-norm without launches of its own (L launches for the conv stack instead of 2L - 1): gather_rowgemm_st, then one
+    sage_layer_fwd_bn per hidden / last layer.  -> (saved, w_img, pack_desc)"""
+    g, x, Ws, bs, L, Fh, dev, gs, sn, packed = s.g, s.x, s.Ws, s.bs, s.L, s.Fh, s.dev, s.gs, s.sn, s.packed
+    R, B, sums, ghost = g.total_rows, g.B, bnf["sums"], bnf["ghost"]
+    ro_map, ro_ch = g.readout_map(sn, gs) if RO_MAP else (None, 0)
+    # fragment-major images of the hidden layers' weights (forward and input-gradient orientation), written by extra workgroups
+    # of layer 0's launch from the parameters THIS call uses: the later launches read W from them instead of staging it through
+    # LDS.  One buffer per call, nothing cached: parameters are also rewritten behind autograd's back (restored snapshots).
+    w_img = pack_desc = None
+    if 1 <= L - 1 <= _IMG_LAYERS:
+        w_img = torch.empty(2 * (L - 1), _IMG_FLOATS, dtype=torch.float32, device=dev)
+        pack_desc = np.empty(1 + 12 * (L - 1), dtype=np.int64)
+        pack_desc[0] = 2 * (L - 1)
+        for l in range(1, L):
+            for kn in (1, 0):                        # image 2 (l - 1): forward (w[k][n]); 2 (l - 1) + 1: input gradient
+                t = 2 * (l - 1) + (1 - kn)
+                pack_desc[1 + 6 * t:7 + 6 * t] = (Ws[l].data_ptr(), Ws[l].stride(0), 128, 128, kn, w_img[t].data_ptr())
+        bnf["pack_desc"] = pack_desc                 # (recorded launches are replayed by address: the last descriptor stays valid)
+    sch0, sch0_w = _gather_sched(g, layer0_k=Ws[0].size(0), fill=gs) if GATHER_SCHED_L0 else (None, 0)
+    schs, schs_w = _gather_sched(g, slots=True)
+    saved = []
+    for l in range(L):
+        K, N = Ws[l].size(0), Ws[l].size(1)
+        v = torch.empty(R, N, dtype=torch.float32, device=dev)
+        rinv = torch.empty(R, dtype=torch.float32, device=dev)
+        z = torch.empty(R, x.size(1) if l == 0 else Fh, dtype=torch.float32, device=dev)
+        s_out, g_out = (sums[l * 2 * sn:(l + 1) * 2 * sn], ghost[2 * l:2 * l + 2]) if l < L - 1 else (None, None)
+        if l == 0:
+            a0 = (*_neighbours(g, sch0, sch0_w), x, x.stride(0), Ws[0], Ws[0].stride(0), bs[0], v, v.stride(0), rinv, z, z.stride(0), g.n_rows,
+                  K, N, gs, g.row_slot, s_out, g_out, int(g.panel_units), pack_desc.ctypes.data if pack_desc is not None else None)
+            name, mode = ("gather_rowgemm_st_f32", ()) if L0_DIRECT_B else ("gather_rowgemm_st_mode_f32", (1,))     # (b_mode 1: W through LDS)
+            nat.call(name, *a0, *mode)
+        else:
+            p, last = saved[l - 1], l == L - 1
+            nat.call("sage_layer_fwd_bn_f32", *_neighbours(g, schs, schs_w, table=g.ell_slots()), p.v, p.v.stride(0), Ws[l], Ws[l].stride(0),
+                     bs[l], v, v.stride(0), rinv, z, z.stride(0), g.n_rows, K, gs, g.graph_ptr, g.slot_count, B, sn, s.sg,
+                     packed[(l - 1) * B * Fh:(l - 1) * B * Fh + B * Fh], packed[l * B * Fh:l * B * Fh + (B + 1) * N] if last else None,
+                     g.row_graph, sums[(l - 1) * 2 * sn:l * 2 * sn], ghost[2 * (l - 1):2 * l], p.mean, p.rstd, None if last else g.row_slot,
+                     s_out, g_out, ro_map, ro_ch, int(g.panel_units), w_img[2 * (l - 1)] if w_img is not None else None)
+        mean = torch.empty(g.nmax, dtype=torch.float32, device=dev) if l < L - 1 else None     # written by the NEXT launch's readout blocks
+        rstd = torch.empty(g.nmax, dtype=torch.float32, device=dev) if l < L - 1 else None
+        saved.append(_Saved(z, v, rinv, mean, rstd, True))
+    s.last_ro_done = True
+    return saved, w_img, pack_desc
+
+
+def _layer_product(s, l, x, v, rinv):
+    """layer l's aggregation + `.W` + bias + L2 normalise into (v, rinv), by the first of five launch forms that takes it -> (z, lean)"""
+    g, W, b, gs, sn, sg = s.g, s.Ws[l], s.bs[l], s.gs, s.sn, s.sg
+    R, B, K, N = g.total_rows, g.B, W.size(0), W.size(1)
+    # Ghost rows aggregate nothing (z = 0): their output is the normalised bias, written by a filler block, and
+    # their z is neither produced nor read (255 row panels + 1 filler = one block per CU on the DD batch).
+    lean = (g.n_ghost > 0 and x.stride(0) % 4 == 0 and N % 4 == 0 and W.data_ptr() % 16 == 0 and (b is None or b.data_ptr() % 16 == 0))
+    fused = lean and N <= 128 and _gather_ok(g, x) and mp.rowgemm_ok(x, x.stride(0), W, W.stride(0), K, N, False)
+    if fused and MERGED_FWD and s.pending_ro is not None and K == 128 and N == 128 and x.size(1) == 128 and W.stride(0) % 4 == 0:
+        # (1) this layer's product and the max-readout partial of its input (the previous layer's output) in one launch
+        z = torch.empty(R, x.size(1), dtype=torch.float32, device=s.dev)
+        a = (*_neighbours(g), x, x.stride(0), W, W.stride(0), b, v, v.stride(0), rinv, z, z.stride(0), g.n_rows, K, gs, g.graph_ptr, B, sn, sg,
+             s.pending_ro[1])
+        if EPILOGUE_READOUT and l == s.L - 1 and not s.nodes and l > 0 and (not g.n_ghost or gs > 0):
+            # last layer: no slot batch-norm follows, so its own max readout is folded into the product's epilogue
+            # (packed was cleared by layer 0's slot_bn_fwd launch): no pass over v for it
+            nat.call("sage_layer_fwd_ro_f32", *a, s.packed[s.off:s.off + (B + 1) * N], g.row_graph)
+            s.last_ro_done = True
+        else:
+            nat.call("sage_layer_fwd_f32", *a)
+        s.pending_ro = None
+        return z, lean
+    if s.pending_ro is not None:                        # the input's readout partial rides with nobody: a launch of its own
+        y, pk = s.pending_ro
+        nat.call("readout_partial_f32", g.graph_ptr, B, sn, g.n_rows, sg, y, y.stride(0), y.size(1), pk)
+    s.pending_ro = None
+    if fused:
+        # (2) aggregation fused into the product: the neighbour rows are summed while the A panel is staged
+        nb = _neighbours(g)
+        z = torch.empty(R, x.size(1), dtype=torch.float32, device=s.dev)
+        nat.call("gather_rowgemm_f32", *nb, x, x.stride(0), W, W.stride(0), 0, b, v, v.stride(0), rinv, z, z.stride(0), g.n_rows, K, N, 1, gs)
+        return z, lean
+    z = _aggregate_raw(g, x, rows=g.n_rows if lean else None)
+    ok = mp.rowgemm_ok(z, z.stride(0), W, W.stride(0), K, N, False)
+    if lean and ok:                                     # (3) row-panel product of the real rows + the ghost rows' filler
+        nat.call("rowgemm_f32", z, z.stride(0), W, W.stride(0), 0, b, v, v.stride(0), rinv, g.n_rows, K, N, 1, gs)
+        return z, True
+    if lean:
+        z[g.n_rows:].zero_()
+    if ok:                                              # (4) row-panel product of every row
+        nat.call("rowgemm_f32", z, z.stride(0), W, W.stride(0), 0, b, v, v.stride(0), rinv, R, K, N, 1, 0)
+    else:                                               # (5) any shape
+        nat.call("linear_l2norm_f32", z, z.stride(0), W, W.stride(0), b, v, v.stride(0), rinv, R, K, N, 1)
+    return z, False
+
+
+def _layer_post(s, l, v, per_graph, head):
+    """what follows layer l's product: ReLU + the row layer norm (per-graph statistics) or the slot batch-norm for l < L - 1 — their
+    readout rides in the next layer's launch —, the readout partial for the last layer.  -> (mean, rstd, y: the next layer's input)"""
+    g, R, B, N, L, Fh, nodes, sn, sg, dev = s.g, s.g.total_rows, s.g.B, v.size(1), s.L, s.Fh, s.nodes, s.sn, s.sg, s.dev
+    pk = s.packed[s.off:s.off + B * N] if not nodes else None
+    if l == L - 1:
+        if head is None and not nodes and not s.last_ro_done:
+            nat.call("readout_partial_f32", g.graph_ptr, B, sn, g.n_rows, sg, v, v.stride(0), N, pk)
+        return None, None, None
+    mean = torch.empty(R if per_graph else g.nmax, dtype=torch.float32, device=dev)      # per ROW / per slot
+    rstd = torch.empty(R if per_graph else g.nmax, dtype=torch.float32, device=dev)
+    y = torch.empty_like(v) if not nodes else s.cat[:, l * Fh:(l + 1) * Fh]      # (node form: straight into its column block)
+    if per_graph:
+        if l == 0 and not nodes:
+            s.packed[:s.total].zero_()                    # (what the first slot_bn_fwd launch does on its way)
+        nat.call("row_ln_fwd_f32", v, v.stride(0), g.n_rows + sg, N, 1, mean, rstd, y, y.stride(0))
+    else:
+        nat.call("slot_bn_fwd_f32", g.graph_ptr, g.slot_count, B, sn, g.n_rows, sg, v, v.stride(0), N, 1, mean, rstd, y, y.stride(0),
+                 s.packed if (l == 0 and not nodes) else None, s.total)
+    if not nodes:
+        s.pending_ro = (y, pk)                    # rides along with the next layer's product (or is flushed before it)
+    s.keep.append(y)
+    return mean, rstd, y
+
+
+def _forward_layers(s, head, per_graph):
+    """the generic route: per layer one product launch (_layer_product) and its post step (_layer_post).  -> saved"""
+    g, L, x, saved = s.g, s.L, s.x, []
+    for l in range(L):
+        N = s.Ws[l].size(1)
+        # (node form: the last layer's output IS its block of the concatenation)
+        v = s.cat[:, (L - 1) * s.Fh:] if (s.nodes and l == L - 1) else torch.empty(g.total_rows, N, dtype=torch.float32, device=s.dev)
+        rinv = torch.empty(g.total_rows, dtype=torch.float32, device=s.dev)
+        z, lean = _layer_product(s, l, x, v, rinv)
+        mean, rstd, y = _layer_post(s, l, v, per_graph, head)
+        saved.append(_Saved(z, v, rinv, mean, rstd, lean))
+        s.off += g.B * N
+        x = y
+    return saved
+
+
+def _forward_tail(s, head, bnf, saved):
+    """the node's result: the node features, or readout_decode_layers, or the decode + both nn.Linear in one of three head launches.
+    -> (result, arg, ctx.head)"""
+    g, B, L, Fh, Fl, dev, packed, sn, sg = s.g, s.g.B, s.L, s.Fh, s.Fl, s.dev, s.packed, s.sn, s.sg
+    if s.nodes:
+        if s.nodes == 2 and g.n_ghost:
+            nat.defer_zero(s.cat[g.n_rows:])               # embedding mask: ghost rows of the node output are zero
+        return s.cat, None, None
+    out = torch.empty(B, (L - 1) * Fh + Fl, dtype=torch.float32, device=dev)
+    arg = torch.empty(s.total, dtype=torch.int32, device=dev)
+    if head is None:
+        nat.call("readout_decode_layers_f32", packed, B, L, Fh, Fl, out, out.stride(0), arg)
+        return out, arg, None
+    # last layer's readout (straight from its rows) + decode of the earlier layers + both Linear layers: one launch
+    w1, b1, w2, b2 = head
+    w1c, w2c = w1.contiguous(), w2.contiguous()
+    E, C = w1c.size(0), w2c.size(0)
+    vec = torch.empty(B, E, dtype=torch.float32, device=dev)
+    y = torch.empty(B, C, dtype=torch.float32, device=dev)
+    if bnf is not None:
+        # decode + both Linear layers + the step's housekeeping (packed and the integer sums zeroed for the next step)
+        nat.call("packed_head_fwd_z_f32", packed, B, L, Fh, Fl, out, out.stride(0), arg, w1c, b1, w2c, b2, E, C, vec, y, bnf["sums"],
+                 (L - 1) * 2 * sn)
+        bnf["dirty"] = False
+    elif s.last_ro_done and E <= 128 and out.size(1) <= 2048:
+        # every layer's maxima are in `packed`: decode + both Linear layers, one memory round trip per block
+        nat.call("packed_head_fwd_f32", packed, B, L, Fh, Fl, out, out.stride(0), arg, w1c, b1, w2c, b2, E, C, vec, y)
+    else:
+        nat.call("readout_head_fwd_f32", packed, B, L, Fh, Fl, saved[-1].v, saved[-1].v.stride(0), g.graph_ptr, g.n_rows, sn, sg, out,
+                 out.stride(0), arg, w1c, b1, w2c, b2, E, C, vec, y)
+    return (vec, y), arg, (out, vec, w1c, w2c, head)
+
+
+def _head_backward(ctx, gouts, keep):
+    """the head's backward launch; the last layer's dU rides in it where it can (head2_bwd_du_map).
+    -> (dout, du_last or None, head_grads), or None: no gradient arrived"""
+    g, L, (Fh, Fl), (dvec, dy), (sn, sg) = ctx.g, ctx.L, ctx.dims, gouts, ctx.slots
+    out, vec, w1c, w2c, (pw1, pb1, pw2, pb2) = ctx.head
+    R, B, dev, last = g.total_rows, g.B, out.device, ctx.saved[L - 1]
+    P, E, C = out.size(1), w1c.size(0), w2c.size(0)
+    if dy is None and dvec is None:
+        return None
+    ce = mp.take_deferred_ce(dy) if dy is not None else None      # deferred cross-entropy: this backward rebuilds dy
+    if ce is None:
+        dy = dy.contiguous() if dy is not None else torch.zeros(B, C, device=dev)
+    dvec = dvec.contiguous() if dvec is not None else None
+    dout = torch.empty(B, P, dtype=torch.float32, device=dev)
+    dw1, s1 = mp._sink_or_new(pw1, (E, P), dev)
+    dw2, s2 = mp._sink_or_new(pw2, (C, E), dev)
+    db1, s3 = mp._sink_or_new(pb1, (E,), dev) if pb1 is not None else (None, False)
+    db2, s4 = mp._sink_or_new(pb2, (C,), dev) if pb2 is not None else (None, False)
+    parts = mp.head_norm_slots((s1, s2, s3, s4), (pb1 is not None, pb2 is not None), (pw1, pb1, pw2, pb2), E)
+    keep.append((ce, dy, dvec, dw1, dw2, db1, db2, parts))
+    du_last = None
+    if (HEAD_DU and LAST_LAYER_ROWS and not ctx.nodes and L > 1 and last.lean and Fl % 4 == 0 and Fl <= 128 and g.n_ghost == g.nmax
+            and sn == sg and g.n_ghost >= B and ctx.needs_input_grad[5 + 2 * (L - 1)] and last.v.stride(0) % 4 == 0):
+        # the last layer's dU (a row-wise function of the readout gradient: it has no batch-norm) rides in this launch
+        du_l = torch.empty(R, Fl, dtype=torch.float32, device=dev)
+        keep.append(du_l)
+        argl = ctx.arg[(L - 1) * B * Fh:(L - 1) * B * Fh + B * Fl]
+        # (the non-empty (graph, chunk) pairs listed by the host for an exact batch: no workgroup that only returns)
+        dmap, ndmap, dchunk = g.du_map(B + (E + 3) // 4 + 1) if DU_MAP else (None, 0, 64)
+        if nat.try_call("head2_bwd_du_map_f32", out, out.stride(0), vec, ce[0] if ce is not None else None,
+                        ce[1] if ce is not None else None, ce[2] if ce is not None else None, None if ce is not None else dy, dvec,
+                        w1c, w2c, B, P, E, C, dout, dout.stride(0), dw1, db1, dw2, db2, parts, g.graph_ptr, g.n_rows, sg, sn,
+                        last.v, last.v.stride(0), last.rinv, argl, (L - 1) * Fh, Fl, du_l, du_l.stride(0), dmap, ndmap, dchunk):
+            du_last = du_l
+    if du_last is None and ce is not None:
+        nat.call("head2_bwd_ce_f32", out, out.stride(0), vec, ce[0], ce[1], ce[2], dvec, w1c, w2c, B, P, E, C, dout, dout.stride(0),
+                 dw1, db1, dw2, db2, parts)
+    elif du_last is None:
+        nat.call("head2_bwd_f32", out, out.stride(0), vec, dy, dvec, w1c, w2c, B, P, E, C, dout, dout.stride(0), dw1, db1, dw2, db2, parts)
+    if mp.GRAD_SINK is not None and s1 and s2 and (s3 or pb1 is None) and (s4 or pb2 is None):
+        mp.GRAD_SINK.ready((pw1, pb1, pw2, pb2))       # final already: their all-reduce may overlap the conv backward
+    return dout, du_last, (None if s1 else dw1, None if s3 else db1, None if s2 else dw2, None if s4 else db2)
+
+
+def _layer_du(ctx, l, dout, dxs, du_last, red, grads, keep):
+    """layer l's dU = gradient of its product's output, from the readout (or node-block) gradient `dout` and the next layer's input
+    gradient `dxs`, by one of five launch forms.  -> (du, bo: rows behind the real ones that feed the bias gradient only), or
+    (None, 0) where the launch took the layer's weight gradient along (slot_post_wgrad: nothing is left to spend)"""
+    g, L, nodes, Fh, (sn, sg), dev = ctx.g, ctx.L, ctx.nodes, ctx.dims[0], ctx.slots, dout.device
+    z, v, rinv, mean, rstd, lean = ctx.saved[l]
+    R, B, K, N = g.total_rows, g.B, ctx.Ws[l].size(0), ctx.Ws[l].size(1)
+    last = l == L - 1
+    if last and du_last is not None:
+        return du_last, B                         # B ghost CONTRIBUTION rows stand for the sg ghost rows (tsgnn_head2_bwd_du_f32)
+    du = torch.empty(R, N, dtype=torch.float32, device=dev)
+    dsl = dout[:, l * Fh:l * Fh + N] if not nodes else None      # this layer's readout gradient and its winners' rows ...
+    argl = ctx.arg[l * B * Fh:l * B * Fh + B * N] if not nodes else None
+    dnode = dout[:, l * Fh:l * Fh + N] if nodes else None        # ... or the gradient of this layer's block of the node output
+    lddxs, post = dxs.stride(0) if dxs is not None else 0, 0 if last else 1      # (post: ReLU and batch-norm follow the layer)
+    if (LAST_LAYER_ROWS and last and not nodes and dxs is None and N % 4 == 0 and N <= 128 and g.n_ghost == g.nmax
+            and sn == sg and dout.stride(0) % 4 == 0 and dsl.data_ptr() % 16 == 0 and g.row_graph is not None):
+        # the last layer has no batch-norm: its dU is a row-wise function of the readout gradient (no slot structure)
+        nat.call("readout_l2_bwd_f32", g.graph_ptr, g.row_graph, B, g.n_rows, sg, v, v.stride(0), dsl, dout.stride(0), argl, N, rinv, du,
+                 du.stride(0))
+    elif (SLOT_WGRAD and l == 0 and L > 1 and not nodes and not ctx.needs_input_grad[0] and lean and B <= 32 and N == 128
+          and K <= 128 and sn == sg and g.n_ghost == g.nmax and ctx.needs_input_grad[5] and z.stride(0) % 4 == 0
+          and z.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0 and (not ctx.has_bias or ctx.needs_input_grad[6])):
+        # layer 0's dU has ONE consumer, its own weight / bias gradient: both in one launch, the rows of dU stay in LDS
+        per = int(os.environ.get("TSGNN_SLOT_WGRAD_PER", "2"))      # slots per workgroup (each slot is a full latency chain)
+        nblk = max(1, -(-sn // per))
+        ws0 = torch.empty(nblk * (K + 1) * N, dtype=torch.float32, device=dev)
+        nat.call("slot_post_wgrad_f32", g.graph_ptr, g.slot_count, B, sn, g.n_rows, sg, v, v.stride(0), dxs, lddxs, dsl,
+                 dout.stride(0) if dsl is not None else 0, argl, N, 1, 1, mean, rstd, rinv, z, z.stride(0), K, ws0, nblk)
+        dw = red.grad(ctx.params[0], (K, N))
+        db = red.grad(ctx.params[1] if ctx.has_bias else None, (N,))
+        red.add((ws0, nblk, K, N, dw, db))
+        grads[0], grads[1] = red.autograd_grad(dw), red.autograd_grad(db)
+        keep.append(du)
+        return None, 0
+    elif ctx.per_graph and nodes:
+        # per-graph statistics, node output: the block's own gradient + row layer norm + ReLU + normalise backward, row by row
+        nat.call("row_post_nodes_bwd_f32", g.n_rows, g.n_rows + sg, v, v.stride(0), dxs, lddxs, dnode, dnode.stride(0),
+                 1 if nodes == 2 else 0, N, post, post, mean, rstd, rinv, du, du.stride(0))
+    elif ctx.per_graph:
+        # per-graph statistics: readout winners + row layer norm + ReLU + normalise backward, row by row
+        nat.call("row_post_bwd_f32", g.row_graph, B, g.n_rows, g.n_rows + sg, v, v.stride(0), dxs, lddxs, dsl, dout.stride(0), argl, N,
+                 post, post, mean, rstd, rinv, du, du.stride(0))
+    else:
+        nat.call("slot_post_bwd_f32", g.graph_ptr, g.slot_count, B, sn, g.n_rows, sg, v, v.stride(0), dxs, lddxs, dnode,
+                 dnode.stride(0) if dnode is not None else 0, dsl, dout.stride(0) if dsl is not None else 0, argl, N, post, post,
+                 mean, rstd, rinv, du, du.stride(0))
+    return du, sg
+
+
+def _spend_du(ctx, l, du, bo, red, grads, keep):
+    """layer l's gradients from its dU: weight-gradient slabs beside dX in the merged launch, else slabs / linear_wgrad / the bias
+    column sum, and then the input gradient by the fused gather product or the transposed aggregation.  -> dX, or None when nobody asks"""
+    g, W, sg = ctx.g, ctx.Ws[l], ctx.slots[1]
+    z, lean, K, N = ctx.saved[l].z, ctx.saved[l].lean, W.size(0), W.size(1)
+    want_w = ctx.needs_input_grad[5 + 2 * l]
+    want_b = ctx.has_bias and ctx.needs_input_grad[6 + 2 * l]
+    keep.append(du)
+    dxs = sl = None
+    if (MERGED_BWD and want_w and lean and l > 0 and K == 128 and N == 128 and g.symmetric and z.size(1) == K
+            and _gather_ok(g, du) and z.data_ptr() % 16 == 0 and du.data_ptr() % 16 == 0 and W.data_ptr() % 16 == 0
+            and W.stride(0) % 4 == 0):
+        nslab, rps, need = mp.wgrad_plan(g.n_rows, K, N, z.stride(0), du.stride(0))
+        nslab, rps, need = _slabs_beside_panels(nslab, rps, need, g.n_rows, K, N, du.device, g.panel_units)
+        if 0 < nslab < 512:
+            # weight-gradient slabs and dX = (A dU) W^T side by side in one launch (both only need dU); the forward's weight
+            # image in input-gradient orientation (rows 2 (l - 1) + 1) stands in for W when there is one
+            nb = _neighbours(g, *_gather_sched(g))
+            ws = torch.empty(need, dtype=torch.float32, device=du.device)
+            dxs = torch.empty(g.total_rows, K, dtype=torch.float32, device=du.device)
+            nat.call("sage_layer_bwd_f32", *nb, du, du.stride(0), W, W.stride(0), dxs, dxs.stride(0), z, z.stride(0), g.n_rows, nslab, rps,
+                     bo, ws, int(g.panel_units), ctx.w_img[2 * (l - 1) + 1] if ctx.w_img is not None else None)
+            sl = (ws, nslab)
+    if want_w and sl is None:
+        if not lean and sg < g.n_ghost:
+            du[g.n_rows + sg:].zero_()          # rows no slot kernel wrote
+        sl = mp.linear_wgrad_slabs(z, K, du[:g.n_rows + bo] if lean else du, bias_only_rows=bo if lean else 0)
+        if sl is None:
+            if lean:
+                z[g.n_rows:].zero_()
+                du[g.n_rows + sg:].zero_()
+            grads[2 * l], grads[2 * l + 1] = mp.linear_wgrad(z, K, du, want_b)
+    elif want_b and not want_w:
+        if sg < g.n_ghost:
+            du[g.n_rows + sg:].zero_()
+        grads[2 * l + 1] = mp.colsum(du)
+    if sl is not None:                          # slabs now, ONE reduction for all layers at the end
+        dw = red.grad(ctx.params[2 * l], (K, N))       # straight into the flat bucket if one is installed
+        db = red.grad(ctx.params[2 * l + 1] if want_b else None, (N,))
+        red.add((sl[0], sl[1], K, N, dw, db))
+        grads[2 * l], grads[2 * l + 1] = red.autograd_grad(dw), red.autograd_grad(db)
+    if dxs is not None or not (l > 0 or ctx.needs_input_grad[0]):
+        return dxs
+    R, ldz, dev = g.total_rows, z.size(1), du.device
+    if (l > 0 and g.n_ghost > 0 and g.symmetric and ldz == K and K <= 128 and _gather_ok(g, du)
+            and mp.rowgemm_ok(du, du.stride(0), W, W.stride(0), N, K, True)):
+        # dX = A^T (dU W^T) = (A dU) W^T for a symmetric A: the same fused gather + product; only real rows
+        nb = _neighbours(g)
+        dxs = torch.empty(R, ldz, dtype=torch.float32, device=dev)
+        nat.call("gather_rowgemm_f32", *nb, du, du.stride(0), W, W.stride(0), 1, None, dxs, dxs.stride(0), None, None, 0, g.n_rows, N, K, 0, 0)
+        return dxs
+    dz = torch.zeros(R, ldz, dtype=torch.float32, device=dev) if ldz > K else torch.empty(R, ldz, dtype=torch.float32, device=dev)
+    keep.append(dz)
+    if mp.rowgemm_ok(du, du.stride(0), W, W.stride(0), N, K, True):
+        # ghost rows have no edges: their dz is never gathered, so only the real rows go through the product
+        nat.call("rowgemm_f32", du, du.stride(0), W, W.stride(0), 1, None, dz, dz.stride(0), None, g.n_rows, N, K, 0, 0)
+    else:
+        mp.gemm(du, du.stride(0), 1, W, 1, W.stride(0), dz, dz.stride(0), 1, R, K, N)
+    # ... and nothing reads the ghost rows of the aggregated gradient (slot_post_bwd takes 0 for them)
+    return _aggregate_raw(g, dz, transposed=True, rows=g.n_rows if (l > 0 and g.n_ghost) else None)
 
 
 class _SageStack(torch.autograd.Function):
@@ -173,441 +554,68 @@ class _SageStack(torch.autograd.Function):
     def forward(ctx, x0, g, has_bias, n_head, nodes, *params):
         head = params[len(params) - n_head:] if n_head else None
         params = params[:len(params) - n_head] if n_head else params
-        L = len(params) // 2
-        Ws = [params[2 * l].contiguous() for l in range(L)]
-        bs = [params[2 * l + 1] if has_bias else None for l in range(L)]
-        dev = x0.device
-        R, B = g.total_rows, g.B
-        Fh, Fl = Ws[0].size(1), Ws[-1].size(1)
-        total = B * ((L - 1) * Fh + Fl)
-        # cleared by the first slot_bn_fwd launch; Fl spare words behind the last layer's segment take the readout of the dummy
-        # graph that the padding rows of a capacity-padded batch (ingest.py) belong to: never cleared, never read
-        packed = torch.empty(total + Fl, dtype=torch.int64, device=dev) if not nodes else None
-        cat = torch.empty(R, (L - 1) * Fh + Fl, dtype=torch.float32, device=dev) if nodes else None
-        x = mp._check(x0, R)
-        # Ghost slots actually needed.  Every graph's padded rows at slots >= the largest graph are bitwise identical in
-        # every layer (same bias row, same statistics), the max readout breaks ties towards the smallest row, and nothing
-        # aggregates from a ghost row: only slots [0, max_size] can influence an output or a gradient.  The slot kernels,
-        # the filler and the bias gradient therefore run on  gs = min(nmax, max_size + 1)  ghost rows (half of nmax on DD).
-        gs = g.n_ghost
-        if g.n_ghost > 0 and x.stride(0) % 4 == 0 and all(
-                Ws[l].size(1) % 4 == 0 and Ws[l].data_ptr() % 16 == 0 and (bs[l] is None or bs[l].data_ptr() % 16 == 0)
-                for l in range(L)):
-            # (capacity-padded batches keep one shape for every batch: a fixed bound instead of this batch's largest graph)
-            fixed = getattr(g, "ghost_slots_fixed", None)
-            gs = min(g.nmax, (int(fixed) if fixed is not None else int(g.sizes.max()) + 1))
-        if nodes == 1:
-            gs = g.n_ghost                                   # unmasked node output: every ghost row is part of the result
-        sn, sg = (gs, gs) if g.n_ghost else (g.nmax, 0)      # (slots, ghost rows) handed to the slot kernels
-        saved = []
-        off = 0
-        pending_ro = None
-        keep = []
-        last_ro_done = False
-        bnf = None
+        s = _Fwd(x0, g, has_bias, nodes, params)
         per_graph = ctx.per_graph = bool(_PER_GRAPH[0])
         if per_graph and head is not None:
             raise NotImplementedError("per-graph statistics: the readout and the node-feature form of the stack only")
-        if (FUSED_BN and not per_graph and head is not None and not nodes and L >= 2 and g.n_ghost == g.nmax and sn == sg and sn <= 1024
-                and Fh == 128 and Fl == 128 and Ws[0].size(0) <= 128 and x.size(1) % 4 == 0 and MERGED_FWD and EPILOGUE_READOUT
-                and _gather_ok(g, x) and all(Ws[l].size(0) == 128 and Ws[l].stride(0) % 4 == 0 for l in range(1, L))
-                and all(Ws[l].data_ptr() % 16 == 0 and (bs[l] is None or bs[l].data_ptr() % 16 == 0) for l in range(L))
-                and mp.rowgemm_ok(x, x.stride(0), Ws[0], Ws[0].stride(0), Ws[0].size(0), Fh, False)
-                and head[0].size(0) <= 128 and (L - 1) * Fh + Fl <= 2048 and g.row_graph is not None):
-            ell_s = g.ell_slots()
-            if ell_s is not None:
-                bnf = g.bn_workspace(B, L, Fh, Fl, sn)
-                if bnf["dirty"]:
-                    bnf["sums"].zero_(); bnf["ghost"].zero_(); bnf["packed"].zero_()
-                bnf["dirty"] = True
-                packed = bnf["packed"]
         ctx.w_img = ctx.pack_desc = None
+        bnf = _fused_bn_workspace(s, head, per_graph)
         if bnf is not None:
-            # ---- slot batch-norm without launches of its own (L launches for the conv stack instead of 2L - 1)
-            ell, ell_w, tail = g.ell()
-            tp, tc = tail if tail is not None else (None, None)
-            ell_s, tc_s = ell_s
-            sums, ghost = bnf["sums"], bnf["ghost"]
-            ro_map, ro_ch = g.readout_map(sn, gs) if RO_MAP else (None, 0)
-            # fragment-major images of the hidden layers' weights (forward and input-gradient orientation), written by extra workgroups
-            # of layer 0's launch from the parameters THIS call uses: the later launches read W from them instead of staging it through
-            # LDS.  One buffer per call, nothing cached: parameters are also rewritten behind autograd's back (restored snapshots).
-            w_img = pack_desc = None
-            if 1 <= L - 1 <= _IMG_LAYERS:
-                w_img = torch.empty(2 * (L - 1), _IMG_FLOATS, dtype=torch.float32, device=dev)
-                pack_desc = np.empty(1 + 12 * (L - 1), dtype=np.int64)
-                pack_desc[0] = 2 * (L - 1)
-                for l in range(1, L):
-                    for kn in (1, 0):                        # image 2 (l - 1): forward (w[k][n]); 2 (l - 1) + 1: input gradient
-                        t = 2 * (l - 1) + (1 - kn)
-                        pack_desc[1 + 6 * t:7 + 6 * t] = (Ws[l].data_ptr(), Ws[l].stride(0), 128, 128, kn, w_img[t].data_ptr())
-                bnf["pack_desc"] = pack_desc                 # (recorded launches are replayed by address: the last descriptor stays valid)
-            ctx.w_img, ctx.pack_desc = w_img, pack_desc
-            sch0, sch0_w = _gather_sched(g, layer0_k=Ws[0].size(0), fill=gs) if GATHER_SCHED_L0 else (None, 0)
-            schs, schs_w = _gather_sched(g, slots=True)
-            for l in range(L):
-                K, N = Ws[l].size(0), Ws[l].size(1)
-                v = torch.empty(R, N, dtype=torch.float32, device=dev)
-                rinv = torch.empty(R, dtype=torch.float32, device=dev)
-                z = torch.empty(R, x.size(1) if l == 0 else Fh, dtype=torch.float32, device=dev)
-                s_out = sums[l * 2 * sn:(l + 1) * 2 * sn] if l < L - 1 else None
-                g_out = ghost[2 * l:2 * l + 2] if l < L - 1 else None
-                if l == 0:
-                    e_, w_, tp_, tc_ = (sch0, sch0_w, None, None) if sch0 is not None else (ell, ell_w, tp, tc)
-                    a0 = (e_, w_, tp_, tc_, x, x.stride(0), Ws[0], Ws[0].stride(0), bs[0], v, v.stride(0), rinv, z,
-                          z.stride(0), g.n_rows, K, N, gs, g.row_slot, s_out, g_out, int(g.panel_units),
-                          pack_desc.ctypes.data if pack_desc is not None else None)
-                    if L0_DIRECT_B:
-                        nat.call("gather_rowgemm_st_f32", *a0)
-                    else:
-                        nat.call("gather_rowgemm_st_mode_f32", *a0, 1)
-                    mean = rstd = None
-                else:
-                    pm, pr_ = saved[l - 1][3], saved[l - 1][4]
-                    last = l == L - 1
-                    e_, w_, tp_, tc_ = (schs, schs_w, None, None) if schs is not None else (ell_s, ell_w, tp, tc_s)
-                    nat.call("sage_layer_fwd_bn_f32", e_, w_, tp_, tc_, saved[l - 1][1], saved[l - 1][1].stride(0), Ws[l], Ws[l].stride(0), bs[l],
-                             v, v.stride(0), rinv, z, z.stride(0), g.n_rows, K, gs, g.graph_ptr, g.slot_count, B, sn, sg,
-                             packed[(l - 1) * B * Fh:(l - 1) * B * Fh + B * Fh],
-                             packed[l * B * Fh:l * B * Fh + (B + 1) * N] if last else None, g.row_graph,
-                             sums[(l - 1) * 2 * sn:l * 2 * sn], ghost[2 * (l - 1):2 * l], pm, pr_,
-                             None if last else g.row_slot, s_out, g_out, ro_map, ro_ch, int(g.panel_units),
-                             w_img[2 * (l - 1)] if w_img is not None else None)
-                if l < L - 1:
-                    mean = torch.empty(g.nmax, dtype=torch.float32, device=dev)     # written by the NEXT launch's readout blocks
-                    rstd = torch.empty(g.nmax, dtype=torch.float32, device=dev)
-                else:
-                    mean = rstd = None
-                saved.append((z, v, rinv, mean, rstd, True))
-            last_ro_done = True
-        for l in (range(L) if bnf is None else ()):
-            K, N = Ws[l].size(0), Ws[l].size(1)
-            if nodes and l == L - 1:
-                v = cat[:, (L - 1) * Fh:]                    # the last layer's output IS its block of the concatenation
-            else:
-                v = torch.empty(R, N, dtype=torch.float32, device=dev)
-            rinv = torch.empty(R, dtype=torch.float32, device=dev)
-            # Ghost rows aggregate nothing (z = 0): their output is the normalised bias, written by a filler block, and
-            # their z is neither produced nor read (255 row panels + 1 filler = one block per CU on the DD batch).
-            lean = (g.n_ghost > 0 and x.stride(0) % 4 == 0 and N % 4 == 0 and Ws[l].data_ptr() % 16 == 0
-                    and (bs[l] is None or bs[l].data_ptr() % 16 == 0))
-            fused = lean and N <= 128 and _gather_ok(g, x) and mp.rowgemm_ok(x, x.stride(0), Ws[l], Ws[l].stride(0), K, N, False)
-            if (fused and MERGED_FWD and pending_ro is not None and K == 128 and N == 128 and x.size(1) == 128
-                    and Ws[l].stride(0) % 4 == 0):
-                # this layer's product and the max-readout partial of its input (the previous layer's output) in one launch
-                ell, ell_w, tail = g.ell()
-                tp, tc = tail if tail is not None else (None, None)
-                z = torch.empty(R, x.size(1), dtype=torch.float32, device=dev)
-                if EPILOGUE_READOUT and l == L - 1 and not nodes and l > 0 and (not g.n_ghost or gs > 0):
-                    # last layer: no slot batch-norm follows, so its own max readout is folded into the product's epilogue
-                    # (packed was cleared by layer 0's slot_bn_fwd launch): no pass over v for it
-                    nat.call("sage_layer_fwd_ro_f32", ell, ell_w, tp, tc, x, x.stride(0), Ws[l], Ws[l].stride(0), bs[l], v, v.stride(0),
-                             rinv, z, z.stride(0), g.n_rows, K, gs, g.graph_ptr, B, sn, sg, pending_ro[1],
-                             packed[off:off + (B + 1) * N], g.row_graph)
-                    last_ro_done = True
-                else:
-                    nat.call("sage_layer_fwd_f32", ell, ell_w, tp, tc, x, x.stride(0), Ws[l], Ws[l].stride(0), bs[l], v, v.stride(0), rinv,
-                             z, z.stride(0), g.n_rows, K, gs, g.graph_ptr, B, sn, sg, pending_ro[1])
-                pending_ro = None
-            elif fused:
-                _flush_readout(g, B, sn, sg, pending_ro)
-                pending_ro = None
-                # aggregation fused into the product: the neighbour rows are summed while the A panel is staged
-                ell, ell_w, tail = g.ell()
-                tp, tc = tail if tail is not None else (None, None)
-                z = torch.empty(R, x.size(1), dtype=torch.float32, device=dev)
-                nat.call("gather_rowgemm_f32", ell, ell_w, tp, tc, x, x.stride(0), Ws[l], Ws[l].stride(0), 0, bs[l], v, v.stride(0), rinv,
-                         z, z.stride(0), g.n_rows, K, N, 1, gs)
-            else:
-                _flush_readout(g, B, sn, sg, pending_ro)
-                pending_ro = None
-                z = _aggregate_raw(g, x, rows=g.n_rows if lean else None)
-                if lean and mp.rowgemm_ok(z, z.stride(0), Ws[l], Ws[l].stride(0), K, N, False):
-                    nat.call("rowgemm_f32", z, z.stride(0), Ws[l], Ws[l].stride(0), 0, bs[l], v, v.stride(0), rinv, g.n_rows, K, N, 1,
-                             gs)
-                elif mp.rowgemm_ok(z, z.stride(0), Ws[l], Ws[l].stride(0), K, N, False):
-                    if lean:
-                        z[g.n_rows:].zero_()
-                        lean = False
-                    nat.call("rowgemm_f32", z, z.stride(0), Ws[l], Ws[l].stride(0), 0, bs[l], v, v.stride(0), rinv, R, K, N, 1, 0)
-                else:
-                    if lean:
-                        z[g.n_rows:].zero_()
-                        lean = False
-                    nat.call("linear_l2norm_f32", z, z.stride(0), Ws[l], Ws[l].stride(0), bs[l], v, v.stride(0), rinv, R, K, N, 1)
-            pk = packed[off:off + B * N] if not nodes else None
-            if l < L - 1 and per_graph:
-                mean = torch.empty(R, dtype=torch.float32, device=dev)      # per ROW
-                rstd = torch.empty(R, dtype=torch.float32, device=dev)
-                y = torch.empty_like(v) if not nodes else cat[:, l * Fh:(l + 1) * Fh]      # (node form: straight into its column block)
-                if l == 0 and not nodes:
-                    packed[:total].zero_()                    # (what the first slot_bn_fwd launch does on its way)
-                nat.call("row_ln_fwd_f32", v, v.stride(0), g.n_rows + sg, N, 1, mean, rstd, y, y.stride(0))
-                if not nodes:
-                    pending_ro = (y, pk)
-                keep.append(y)
-                x = y
-            elif l < L - 1:
-                mean = torch.empty(g.nmax, dtype=torch.float32, device=dev)
-                rstd = torch.empty(g.nmax, dtype=torch.float32, device=dev)
-                y = torch.empty_like(v) if not nodes else cat[:, l * Fh:(l + 1) * Fh]
-                nat.call("slot_bn_fwd_f32", g.graph_ptr, g.slot_count, B, sn, g.n_rows, sg, v, v.stride(0), N, 1,
-                         mean, rstd, y, y.stride(0), packed if (l == 0 and not nodes) else None, total)
-                if not nodes:
-                    pending_ro = (y, pk)                    # rides along with the next layer's product (or is flushed before it)
-                keep.append(y)
-                x = y
-            else:
-                mean = rstd = None
-                if head is None and not nodes and not last_ro_done:
-                    nat.call("readout_partial_f32", g.graph_ptr, B, sn, g.n_rows, sg, v, v.stride(0), N, pk)
-            saved.append((z, v, rinv, mean, rstd, lean))
-            off += B * N
-        ctx.nodes = nodes
-        if nodes:
-            if nodes == 2 and g.n_ghost:
-                nat.defer_zero(cat[g.n_rows:])               # embedding mask: ghost rows of the node output are zero
-            ctx.g, ctx.L, ctx.has_bias, ctx.dims = g, L, has_bias, (Fh, Fl)
-            ctx.slots = (sn, sg)
-            ctx.Ws, ctx.saved, ctx.arg = Ws, saved, None
-            ctx.params = params
-            ctx.head = None
-            return cat
-        out = torch.empty(B, (L - 1) * Fh + Fl, dtype=torch.float32, device=dev)
-        arg = torch.empty(total, dtype=torch.int32, device=dev)
-        ctx.g, ctx.L, ctx.has_bias, ctx.dims = g, L, has_bias, (Fh, Fl)
-        ctx.slots = (sn, sg)
-        ctx.Ws, ctx.saved, ctx.arg = Ws, saved, arg
-        ctx.params = params
-        ctx.x0_ld = x.size(1) if L == 0 else x0.size(1)
-        ctx.head = None
-        if head is None:
-            nat.call("readout_decode_layers_f32", packed, B, L, Fh, Fl, out, out.stride(0), arg)
-            return out
-        # last layer's readout (straight from its rows) + decode of the earlier layers + both Linear layers: one launch
-        w1, b1, w2, b2 = head
-        w1c, w2c = w1.contiguous(), w2.contiguous()
-        E, C = w1c.size(0), w2c.size(0)
-        vec = torch.empty(B, E, dtype=torch.float32, device=dev)
-        y = torch.empty(B, C, dtype=torch.float32, device=dev)
-        v_last = saved[-1][1]
-        if bnf is not None:
-            # decode + both Linear layers + the step's housekeeping (packed and the integer sums zeroed for the next step)
-            nat.call("packed_head_fwd_z_f32", packed, B, L, Fh, Fl, out, out.stride(0), arg, w1c, b1, w2c, b2, E, C, vec, y,
-                     bnf["sums"], (L - 1) * 2 * sn)
-            bnf["dirty"] = False
-        elif last_ro_done and E <= 128 and out.size(1) <= 2048:
-            # every layer's maxima are in `packed`: decode + both Linear layers, one memory round trip per block
-            nat.call("packed_head_fwd_f32", packed, B, L, Fh, Fl, out, out.stride(0), arg, w1c, b1, w2c, b2, E, C, vec, y)
+            s.packed = bnf["packed"]
+            saved, ctx.w_img, ctx.pack_desc = _forward_fused_bn(s, bnf)
         else:
-            nat.call("readout_head_fwd_f32", packed, B, L, Fh, Fl, v_last, v_last.stride(0), g.graph_ptr, g.n_rows, sn, sg, out,
-                     out.stride(0), arg, w1c, b1, w2c, b2, E, C, vec, y)
-        ctx.head = (out, vec, w1c, w2c, head)
-        ctx.set_materialize_grads(False)
-        return vec, y
+            saved = _forward_layers(s, head, per_graph)
+        ctx.g, ctx.L, ctx.has_bias, ctx.dims = g, s.L, has_bias, (s.Fh, s.Fl)
+        ctx.slots, ctx.nodes = (s.sn, s.sg), nodes
+        ctx.Ws, ctx.saved, ctx.params = s.Ws, saved, params
+        result, ctx.arg, ctx.head = _forward_tail(s, head, bnf, saved)
+        if ctx.head is not None:
+            ctx.set_materialize_grads(False)
+        return result
 
     @staticmethod
     def backward(ctx, *gouts):
-        g, L = ctx.g, ctx.L
-        Fh, Fl = ctx.dims
-        R, B = g.total_rows, g.B
-        w_img = ctx.w_img                             # the forward's weight images (input-gradient orientation: rows 2 (l - 1) + 1), or None
-        head_grads = ()
-        du_last = None                                # the last layer's dU when the head's backward launch produced it
-        if ctx.head is None:
-            dout = gouts[0].contiguous()
-            dev = dout.device
-        else:
-            out, vec, w1c, w2c, (pw1, pb1, pw2, pb2) = ctx.head
-            dvec, dy = gouts
-            dev = out.device
-            P, E, C = out.size(1), w1c.size(0), w2c.size(0)
-            if dy is None and dvec is None:
-                return (None,) * (5 + 2 * L + 4)
-            ce = mp.take_deferred_ce(dy) if dy is not None else None      # deferred cross-entropy: this backward rebuilds dy
-            if ce is None:
-                dy = dy.contiguous() if dy is not None else torch.zeros(B, C, device=dev)
-            dvec = dvec.contiguous() if dvec is not None else None
-            dout = torch.empty(B, P, dtype=torch.float32, device=dev)
-            dw1, s1 = mp._sink_or_new(pw1, (E, P), dev)
-            dw2, s2 = mp._sink_or_new(pw2, (C, E), dev)
-            db1, s3 = mp._sink_or_new(pb1, (E,), dev) if pb1 is not None else (None, False)
-            db2, s4 = mp._sink_or_new(pb2, (C,), dev) if pb2 is not None else (None, False)
-            parts = mp.head_norm_slots((s1, s2, s3, s4), (pb1 is not None, pb2 is not None), (pw1, pb1, pw2, pb2), E)
-            sn_, sg_ = ctx.slots
-            v_l, rinv_l, lean_l = ctx.saved[L - 1][1], ctx.saved[L - 1][2], ctx.saved[L - 1][5]
-            if (HEAD_DU and LAST_LAYER_ROWS and not ctx.nodes and L > 1 and lean_l and Fl % 4 == 0 and Fl <= 128 and g.n_ghost == g.nmax
-                    and sn_ == sg_ and g.n_ghost >= B and ctx.needs_input_grad[5 + 2 * (L - 1)] and v_l.stride(0) % 4 == 0):
-                # the last layer's dU (a row-wise function of the readout gradient: it has no batch-norm) rides in this launch
-                du_l = torch.empty(R, Fl, dtype=torch.float32, device=dev)
-                argl = ctx.arg[(L - 1) * B * Fh:(L - 1) * B * Fh + B * Fl]
-                # (the non-empty (graph, chunk) pairs listed by the host for an exact batch: no workgroup that only returns)
-                dmap, ndmap, dchunk = g.du_map(B + (E + 3) // 4 + 1) if DU_MAP else (None, 0, 64)
-                if nat.try_call("head2_bwd_du_map_f32", out, out.stride(0), vec, ce[0] if ce is not None else None,
-                                ce[1] if ce is not None else None, ce[2] if ce is not None else None, None if ce is not None else dy, dvec,
-                                w1c, w2c, B, P, E, C, dout, dout.stride(0), dw1, db1, dw2, db2, parts, g.graph_ptr, g.n_rows, sg_,
-                                sn_, v_l, v_l.stride(0), rinv_l, argl, (L - 1) * Fh, Fl, du_l, du_l.stride(0), dmap, ndmap, dchunk):
-                    du_last = du_l
-            if du_last is not None:
-                pass
-            elif ce is not None:
-                nat.call("head2_bwd_ce_f32", out, out.stride(0), vec, ce[0], ce[1], ce[2], dvec, w1c, w2c, B, P, E, C, dout,
-                         dout.stride(0), dw1, db1, dw2, db2, parts)
-            else:
-                nat.call("head2_bwd_f32", out, out.stride(0), vec, dy, dvec, w1c, w2c, B, P, E, C, dout, dout.stride(0), dw1, db1, dw2,
-                         db2, parts)
-            head_grads = (None if s1 else dw1, None if s3 else db1, None if s2 else dw2, None if s4 else db2)
-            if mp.GRAD_SINK is not None and s1 and s2 and (s3 or pb1 is None) and (s4 or pb2 is None):
-                mp.GRAD_SINK.ready((pw1, pb1, pw2, pb2))       # final already: their all-reduce may overlap the conv backward
-        sn, sg = ctx.slots
-        grads = [None] * (2 * L)
-        dxs = None
-        dx0 = None
+        L = ctx.L
         keep = []
+        if ctx.head is None:
+            dout, du_last, head_grads = gouts[0].contiguous(), None, ()
+        else:
+            h = _head_backward(ctx, gouts, keep)
+            if h is None:
+                return (None,) * (5 + 2 * L + 4)
+            dout, du_last, head_grads = h       # du_last: the last layer's dU when the head's backward launch produced it
+        grads = [None] * (2 * L)
+        dxs = dx0 = None
         red = mp.WgradSets(mp.wgrad_reduce_multi, max_sets_with_shares=4)     # ONE reduction for all layers' slabs, at the end
         for l in range(L - 1, -1, -1):
-            z, v, rinv, mean, rstd, lean = ctx.saved[l]
-            W = ctx.Ws[l]
-            K, N = W.size(0), W.size(1)
-            last = l == L - 1
-            du = du_last if (last and du_last is not None) else torch.empty(R, N, dtype=torch.float32, device=dev)
-            bo = sg                                   # rows behind the real ones that feed the bias gradient only
-            if ctx.nodes:
-                dsl = argl = None
-                dnode = dout[:, l * Fh:l * Fh + N]           # gradient of this layer's block of the node output
-            else:
-                dsl = dout[:, l * Fh:l * Fh + N]
-                argl = ctx.arg[l * B * Fh:l * B * Fh + B * N]
-                dnode = None
-            if last and du_last is not None:
-                bo = B                                # B ghost CONTRIBUTION rows stand for the sg ghost rows (tsgnn_head2_bwd_du_f32)
-            elif (LAST_LAYER_ROWS and last and not ctx.nodes and dxs is None and N % 4 == 0 and N <= 128 and g.n_ghost == g.nmax
-                    and sn == sg and dout.stride(0) % 4 == 0 and dsl.data_ptr() % 16 == 0 and g.row_graph is not None):
-                # the last layer has no batch-norm: its dU is a row-wise function of the readout gradient (no slot structure)
-                nat.call("readout_l2_bwd_f32", g.graph_ptr, g.row_graph, B, g.n_rows, sg, v, v.stride(0), dsl, dout.stride(0), argl, N, rinv,
-                         du, du.stride(0))
-            elif (SLOT_WGRAD and l == 0 and L > 1 and not ctx.nodes and not ctx.needs_input_grad[0] and lean and B <= 32 and N == 128
-                  and K <= 128 and sn == sg and g.n_ghost == g.nmax and ctx.needs_input_grad[5] and z.stride(0) % 4 == 0
-                  and z.data_ptr() % 16 == 0 and v.data_ptr() % 16 == 0 and (not ctx.has_bias or ctx.needs_input_grad[6])):
-                # layer 0's dU has ONE consumer, its own weight / bias gradient: both in one launch, the rows of dU stay in LDS
-                per = int(os.environ.get("TSGNN_SLOT_WGRAD_PER", "2"))      # slots per workgroup (each slot is a full latency chain)
-                nblk = max(1, -(-sn // per))
-                ws0 = torch.empty(nblk * (K + 1) * N, dtype=torch.float32, device=dev)
-                nat.call("slot_post_wgrad_f32", g.graph_ptr, g.slot_count, B, sn, g.n_rows, sg, v, v.stride(0), dxs,
-                         dxs.stride(0) if dxs is not None else 0, dsl, dout.stride(0) if dsl is not None else 0, argl, N, 1, 1, mean, rstd,
-                         rinv, z, z.stride(0), K, ws0, nblk)
-                dw = red.grad(ctx.params[0], (K, N))
-                db = red.grad(ctx.params[1] if ctx.has_bias else None, (N,))
-                red.add((ws0, nblk, K, N, dw, db))
-                grads[0], grads[1] = red.autograd_grad(dw), red.autograd_grad(db)
+            du, bo = _layer_du(ctx, l, dout, dxs, du_last, red, grads, keep)
+            if du is None:
                 continue
-            elif ctx.per_graph and ctx.nodes:
-                # per-graph statistics, node output: the block's own gradient + row layer norm + ReLU + normalise backward, row by row
-                nat.call("row_post_nodes_bwd_f32", g.n_rows, g.n_rows + sg, v, v.stride(0), dxs, dxs.stride(0) if dxs is not None else 0,
-                         dnode, dnode.stride(0), 1 if ctx.nodes == 2 else 0, N, 0 if last else 1, 0 if last else 1, mean, rstd, rinv, du,
-                         du.stride(0))
-            elif ctx.per_graph:
-                # per-graph statistics: readout winners + row layer norm + ReLU + normalise backward, row by row
-                nat.call("row_post_bwd_f32", g.row_graph, B, g.n_rows, g.n_rows + sg, v, v.stride(0), dxs,
-                         dxs.stride(0) if dxs is not None else 0, dsl, dout.stride(0), argl, N, 0 if last else 1, 0 if last else 1, mean,
-                         rstd, rinv, du, du.stride(0))
-            else:
-                nat.call("slot_post_bwd_f32", g.graph_ptr, g.slot_count, B, sn, g.n_rows, sg, v, v.stride(0), dxs,
-                         dxs.stride(0) if dxs is not None else 0, dnode, dnode.stride(0) if dnode is not None else 0, dsl,
-                         dout.stride(0) if dsl is not None else 0, argl, N, 0 if last else 1, 0 if last else 1, mean, rstd, rinv, du,
-                         du.stride(0))
-            want_w = ctx.needs_input_grad[5 + 2 * l]
-            want_b = ctx.has_bias and ctx.needs_input_grad[6 + 2 * l]
-            merged = False
-            if (MERGED_BWD and want_w and lean and l > 0 and K == 128 and N == 128 and g.symmetric and z.size(1) == K
-                    and _gather_ok(g, du) and z.data_ptr() % 16 == 0 and du.data_ptr() % 16 == 0 and W.data_ptr() % 16 == 0
-                    and W.stride(0) % 4 == 0):
-                nslab, rps, need = mp.wgrad_plan(g.n_rows, K, N, z.stride(0), du.stride(0))
-                nslab, rps, need = _slabs_beside_panels(nslab, rps, need, g.n_rows, K, N, dev, g.panel_units)
-                if 0 < nslab < 512:
-                    # weight-gradient slabs and dX = (A dU) W^T side by side in one launch (both only need dU)
-                    ell, ell_w, tail = g.ell()
-                    tp, tc = tail if tail is not None else (None, None)
-                    schb, schb_w = _gather_sched(g)
-                    if schb is not None:
-                        ell, ell_w, tp, tc = schb, schb_w, None, None
-                    ws = torch.empty(need, dtype=torch.float32, device=dev)
-                    dxs = torch.empty(R, K, dtype=torch.float32, device=dev)
-                    nat.call("sage_layer_bwd_f32", ell, ell_w, tp, tc, du, du.stride(0), W, W.stride(0), dxs, dxs.stride(0), z, z.stride(0),
-                             g.n_rows, nslab, rps, bo, ws, int(g.panel_units),
-                             w_img[2 * (l - 1) + 1] if w_img is not None else None)
-                    dw = red.grad(ctx.params[2 * l], (K, N))
-                    db = red.grad(ctx.params[2 * l + 1] if want_b else None, (N,))
-                    red.add((ws, nslab, K, N, dw, db))
-                    grads[2 * l], grads[2 * l + 1] = red.autograd_grad(dw), red.autograd_grad(db)
-                    keep.append(du)
-                    merged = True
-            if merged:
-                continue
-            if want_w:
-                if not lean and sg < g.n_ghost:
-                    du[g.n_rows + sg:].zero_()          # rows no slot kernel wrote
-                sl = mp.linear_wgrad_slabs(z, K, du[:g.n_rows + bo] if lean else du, bias_only_rows=bo if lean else 0)
-                if sl is not None:                      # slabs now, ONE reduction for all layers at the end
-                    dw = red.grad(ctx.params[2 * l], (K, N))       # straight into the flat bucket if one is installed
-                    db = red.grad(ctx.params[2 * l + 1] if want_b else None, (N,))
-                    red.add((sl[0], sl[1], K, N, dw, db))
-                    dw, db = red.autograd_grad(dw), red.autograd_grad(db)
-                else:
-                    if lean:
-                        z[g.n_rows:].zero_()
-                        du[g.n_rows + sg:].zero_()
-                    dw, db = mp.linear_wgrad(z, K, du, want_b)
-                grads[2 * l], grads[2 * l + 1] = dw, db
-            elif want_b:
-                if sg < g.n_ghost:
-                    du[g.n_rows + sg:].zero_()
-                grads[2 * l + 1] = mp.colsum(du)
-            keep.append(du)
-            need_dx = l > 0 or ctx.needs_input_grad[0]
-            if need_dx:
-                ldz = z.size(1)
-                if (l > 0 and g.n_ghost > 0 and g.symmetric and ldz == K and K <= 128 and _gather_ok(g, du)
-                        and mp.rowgemm_ok(du, du.stride(0), W, W.stride(0), N, K, True)):
-                    # dX = A^T (dU W^T) = (A dU) W^T for a symmetric A: the same fused gather + product; only real rows
-                    ell, ell_w, tail = g.ell()
-                    tp, tc = tail if tail is not None else (None, None)
-                    dxs = torch.empty(R, ldz, dtype=torch.float32, device=dev)
-                    nat.call("gather_rowgemm_f32", ell, ell_w, tp, tc, du, du.stride(0), W, W.stride(0), 1, None, dxs, dxs.stride(0), None,
-                             None, 0, g.n_rows, N, K, 0, 0)
-                else:
-                    dz = torch.zeros(R, ldz, dtype=torch.float32, device=dev) if ldz > K else torch.empty(R, ldz, dtype=torch.float32, device=dev)
-                    if mp.rowgemm_ok(du, du.stride(0), W, W.stride(0), N, K, True):
-                        # ghost rows have no edges: their dz is never gathered, so only the real rows go through the product
-                        nat.call("rowgemm_f32", du, du.stride(0), W, W.stride(0), 1, None, dz, dz.stride(0), None, g.n_rows, N, K, 0, 0)
-                    else:
-                        mp.gemm(du, du.stride(0), 1, W, 1, W.stride(0), dz, dz.stride(0), 1, R, K, N)
-                    # ... and nothing reads the ghost rows of the aggregated gradient (slot_post_bwd takes 0 for them)
-                    dxs = _aggregate_raw(g, dz, transposed=True, rows=g.n_rows if (l > 0 and g.n_ghost) else None)
+            dx = _spend_du(ctx, l, du, bo, red, grads, keep)
+            if dx is not None:
+                dxs = dx
                 if l == 0:
-                    dx0 = dxs
+                    dx0 = dx
         red.close()
         del keep
         return (dx0, None, None, None, None) + tuple(grads) + head_grads
 
 
+def _conv_params(convs):
+    """(has_bias, [w0, b0, w1, b1, ...]): the node's parameter list; a one-element dummy in each bias's place when there is none"""
+    has_bias = convs[0].bias is not None
+    return has_bias, [p for c in convs for p in (c.weight, c.bias if has_bias else c.weight.new_zeros(1))]
+
+
 def sage_stack_readouts(x, g, convs):
     """concatenated max readouts [B, hidden*(L-1)+embedding] of the conv stack (encoders.py:177-203)."""
-    has_bias = convs[0].bias is not None
-    params = []
-    for c in convs:
-        params.append(c.weight)
-        params.append(c.bias if has_bias else c.weight.new_zeros(1))
+    has_bias, params = _conv_params(convs)
     return _SageStack.apply(x, g, has_bias, 0, 0, *params)
 
 
 def sage_stack_nodes(x, g, convs, mask_ghost):
     """per-layer node features concatenated on the feature axis [R, sum F] (gcn_forward, encoders.py:140-167)."""
-    has_bias = convs[0].bias is not None
-    params = []
-    for c in convs:
-        params.append(c.weight)
-        params.append(c.bias if has_bias else c.weight.new_zeros(1))
+    has_bias, params = _conv_params(convs)
     return _SageStack.apply(x, g, has_bias, 0, 2 if (mask_ghost and g.n_ghost) else 1, *params)
 
 
@@ -620,7 +628,6 @@ def _multi(tn, gs, zero=None):
     """one launch for the recorded argument tuples of <= 2 tsgnn_linear_wgrad_f32 (slab form) and <= 2 tsgnn_gather_rowgemm_f32
     calls; False when the entry point does not take the combination (csrc/multi.hip).  zero: two contiguous tensors that the
     products' filler blocks clear after their own rows (the deferred `_zero` records that follow the products)."""
-    import numpy as np
     words = [len(tn), len(gs)]
     for a in tn:
         words += [nat._arg(v) or 0 for v in a[:11]]
@@ -760,10 +767,7 @@ def sage_stack_nodes_pair(xa, xb, g, convs_a, convs_b, mask_ghost):
     has_bias = convs_a[0].bias is not None
     if (convs_b[0].bias is not None) != has_bias:
         return sage_stack_nodes(xa, g, convs_a, mask_ghost), sage_stack_nodes(xb, g, convs_b, mask_ghost)
-    params = []
-    for c in list(convs_a) + list(convs_b):
-        params.append(c.weight)
-        params.append(c.bias if has_bias else c.weight.new_zeros(1))
+    params = _conv_params(list(convs_a) + list(convs_b))[1]
     nodes = 2 if (mask_ghost and g.n_ghost) else 1
     # lazily built structures of the batch are built NOW: a build launch recorded inside one stack's launch record shifts it
     # against the other's, and the first step on a batch would run every launch singly (a different — split-K — product
@@ -786,11 +790,7 @@ def head_ok(g, convs, lin1, lin2):
 
 def sage_stack_head(x, g, convs, lin1, lin2):
     """(lin1(readout), lin2(lin1(readout))) with the readout tail and the head fused into the stack node."""
-    has_bias = convs[0].bias is not None
-    params = []
-    for c in convs:
-        params.append(c.weight)
-        params.append(c.bias if has_bias else c.weight.new_zeros(1))
+    has_bias, params = _conv_params(convs)
     vec, y = _SageStack.apply(x, g, has_bias, 4, 0, *params, lin1.weight, lin1.bias, lin2.weight, lin2.bias)
     y._tsgnn_defer_ce = True          # a cross-entropy on these logits may be folded into this node's backward (mp._SoftmaxCE)
     return vec, y
