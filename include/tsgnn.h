@@ -158,6 +158,34 @@ int tsgnn_collate_pool_submit_ack(tsgnn_collate_pool* pool, const int64_t* ds_gr
 int tsgnn_collate_pool_wait(tsgnn_collate_pool* pool, int64_t ticket);
 int tsgnn_collate_pool_destroy(tsgnn_collate_pool* pool);
 
+/* Triplet stream (triplet_stream.hip; train_triplet.py:247-287, one new triplet per optimiser step): ONE launch that writes the
+ * capacity-padded batch of schedule entry `state[0] % state[1]` from a dataset that is resident on the device, and advances the cursor —
+ * the work of tsgnn_host_collate_compact + the pull + the expansion without a host in the loop, graph-capturable.
+ *   records [n_graphs][8] int32: n, nnz, ntail, first row, first entry, first tail entry, the graph's index, 0
+ *   arena   int32 words, four sections at the word offsets off_* (each on 16 bytes): graph-local row pointers (graph g's n + 1 at
+ *           first row + g), graph-local columns, graph-local tail pointers (same indexing) and tail columns (the entries beyond the
+ *           first ell_w of a row)
+ *   feats   [total nodes][ldf] float32, ldf % 4 == 0
+ *   sched   int32 [T][B] indices into records (validated by whoever uploads them: the kernel trusts them), T <= sched_cap;
+ *           state int64[2] = {cursor, T} on 16 bytes; ticket unsigned[1] (zero between launches); all on the device, so one captured
+ *           launch serves every schedule that is loaded into these buffers
+ * Outputs, every word rewritten by every launch: graph_ptr[B + 2] (graph B = the dummy graph [n, row_cap)), slot_count[nmax],
+ * row_graph / row_slot [row_cap] (B / -1 on padding rows), ell [(row_cap + nmax) * ell_w] (batch rows, -1 beyond a row's degree and
+ * on padding and ghost rows), tail_ptr[row_cap + nmax + 1], tail_col[: tail entries], ell_slots / tail_slots (both or neither; entry
+ * = slot << 20 | row), x [(row_cap + nmax)][ldx], ldx == ldf (the feature rows, zero on padding and ghost rows), ids_out[B].
+ * The workgroup that draws the last ticket stores cursor + 1; the cursor is taken modulo T (T clamped to 1..sched_cap), so a replay
+ * past the end wraps and never reads outside sched.
+ * TSGNN_EINVAL without a launch: a null pointer, B outside 1..8, sched_cap <= 0, ell_w outside {4, 8, 16}, row_cap < need_rows or
+ * tail_cap < need_tail (the arena's exact bounds: B times its largest n / ntail), section offsets out of order;
+ * TSGNN_EUNSUPPORTED without a launch: a buffer or a section off 16 bytes, a stride that is no multiple of 4, ldx != ldf (every word of x is rewritten), sizes past
+ * 2^31, slot-annotated copies with 2^20 rows or more. */
+int tsgnn_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t off_rowptr, int64_t off_col,
+                             int64_t off_tail_ptr, int64_t off_tail_col, int64_t arena_words, const float* feats, int64_t ldf,
+                             int64_t need_rows, int64_t need_tail, const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket,
+                             int B, int nmax, int64_t row_cap, int64_t tail_cap, int ell_w, int32_t* graph_ptr, int32_t* slot_count,
+                             int32_t* row_graph, int32_t* row_slot, int32_t* ell, int32_t* tail_ptr, int32_t* tail_col,
+                             int32_t* ell_slots, int32_t* tail_slots, float* x, int64_t ldx, int32_t* ids_out, tsgnn_stream_t stream);
+
 /* CSR transpose (A^T for dX = A^T dY); rows of the result sorted by column; src_e[p] = source entry */
 int tsgnn_csr_transpose(const int* rowptr, const int* col, const float* val, int64_t n_rows, int64_t n_cols,
                         int64_t nnz, int* rowptr_t, int* col_t, float* val_t, int* src_e, int* cnt_ws,

@@ -208,7 +208,11 @@ __global__ __launch_bounds__(256) void row_post_bwd(const int* __restrict__ row_
   const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
   if (r >= rows) return;
   const bool ghost = r >= n_real;
-  const int b0 = ghost ? 0 : row_graph[r], b1 = ghost ? B : b0 + 1;
+  const int b0 = ghost ? 0 : row_graph[r];
+  // a padding row of a capacity-padded batch (row_graph = B, the dummy graph: csrc/ingest.hip) wins no readout and takes nothing
+  // from the next layer: arg / dout have B rows, and its dU is zero
+  const bool pad = !ghost && b0 >= B;
+  const int b1 = ghost ? B : (pad ? b0 : b0 + 1);
   const float mu = ln ? mean[r] : 0.f, rs = ln ? rstd[r] : 1.f;
   const float ri = rinv[r];
   float x[4], dy[4];
@@ -219,7 +223,7 @@ __global__ __launch_bounds__(256) void row_post_bwd(const int* __restrict__ row_
     x[q] = 0.f; dy[q] = 0.f;
     if (f < F) {
       x[q] = v[r * ldv + f];
-      float d = (dxs && !ghost) ? dxs[r * lddxs + f] : 0.f;
+      float d = (dxs && !ghost && !pad) ? dxs[r * lddxs + f] : 0.f;
       if (arg)
         for (int b = b0; b < b1; ++b)
           if ((int64_t)arg[(int64_t)b * F + f] == r) d += dout[(int64_t)b * ldo + f];

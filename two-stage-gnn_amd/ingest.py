@@ -135,7 +135,7 @@ class CapacityBatch:
 
     # ------------------------------------------------------------------ host side
     def _check(self):
-        if self.largest + 1 > self.g.ghost_slots_fixed:
+        if min(self.largest + 1, self.nmax) > self.g.ghost_slots_fixed:      # (a graph that fills every slot has no ghost slot)
             raise ValueError("a graph of %d nodes exceeds the slot's fixed ghost-slot bound %d" % (self.largest, self.g.ghost_slots_fixed))
 
     def _wait_pulled(self):

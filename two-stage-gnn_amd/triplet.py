@@ -18,6 +18,7 @@ from . import message_passing as mp
 from . import resident as R
 from .graph import GraphBatch
 from .resident import resident_cache                               # (the documented name of the model's cache)
+from .triplet_stream import TripletStream, pack_arena, schedule_of  # a new triplet per replay of one hipGraph (triplet_stream.py)
 
 
 class _Module(types.ModuleType):
