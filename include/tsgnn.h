@@ -1378,6 +1378,31 @@ int tsgnn_mlp_probe_predict_f32(const float* q, int64_t ld_q, int64_t n_query, i
                                 double negative_slope, float* logits, int* pred, const int* query_class, int* correct,
                                 tsgnn_stream_t stream);
 
+/* ---------------------------------------------------------------- head of the 2stg+ post-training step (posttrain_head.hip)
+ * Code/sage+gat+diffpool/train_triplet_pre_train.py:196-270 on the readout rows r [R, P] (ldr >= P, ldr % 4 == 0, 16-byte aligned;
+ * what the padding holds does not matter): out [R, E] = r W0^T + b0 (map_model), z1 [R, h1] = out W1^T + b1, z2 [R, h2] =
+ * leaky(z1) W2^T + b2, z [R, C] = leaky(z2) W3^T + b3 (the replacement map2_model: z is the reference's `pred`), p = softmax(z),
+ * loss[1] = mean_i (logsumexp(p_i) - p_i[labels[ids[i]]]): F.cross_entropy(F.softmax(pred), label), the soft-max applied twice as
+ * the reference has it.  Weights in torch's [out, in] layout, dense.  ids [R] (what tsgnn_triplet_gather_f32 wrote to ids_out) index
+ * the label table labels [n_labels] of class indices 0 .. C - 1; both are read on the device (and clamped into their ranges).
+ * z1 / z2 are the PRE-activations: LeakyReLU's derivative at exactly 0 is negative_slope.
+ *
+ * _fwd: ONE launch of one workgroup; writes out, z1, z2, z, p, loss.  _bwd: ONE launch; g_loss (nullable = 1): the upstream gradient
+ * of loss, a device float.  dr [R, P] (nullable, lddr >= P) and the eight parameter gradients (dense, shaped like the parameters) are
+ * written once each, every reduction in a fixed order, no atomics: two runs give the same bits.
+ * P % 4 == 0, P <= 2048, E <= 512, h1, h2 <= 64, 2 <= C <= 64, 1 <= R <= 8 (tsgnn_posttrain_head_supported).  TSGNN_EINVAL /
+ * TSGNN_EUNSUPPORTED without a launch. */
+int tsgnn_posttrain_head_supported(int P, int E, int h1, int h2, int C, int R);
+int tsgnn_posttrain_head_fwd_f32(const float* r, int64_t ldr, int R, int P, const float* w0, const float* b0, int E, const float* w1,
+                                 const float* b1, int h1, const float* w2, const float* b2, int h2, const float* w3, const float* b3, int C,
+                                 float negative_slope, const int32_t* ids, const int32_t* labels, int64_t n_labels, float* out, float* z1,
+                                 float* z2, float* z, float* p, float* loss, tsgnn_stream_t stream);
+int tsgnn_posttrain_head_bwd_f32(const float* r, int64_t ldr, int R, int P, const float* w0, int E, const float* w1, int h1, const float* w2,
+                                 int h2, const float* w3, int C, float negative_slope, const int32_t* ids, const int32_t* labels,
+                                 int64_t n_labels, const float* out, const float* z1, const float* z2, const float* p, const float* g_loss,
+                                 float* dr, int64_t lddr, float* dw0, float* db0, float* dw1, float* db1, float* dw2, float* db2, float* dw3,
+                                 float* db3, tsgnn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

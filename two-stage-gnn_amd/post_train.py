@@ -1,0 +1,259 @@
+"""Post-training phase of the 2stg+ setting (Code/sage+gat+diffpool/train_triplet_pre_train.py:196-270): after the triplet
+pre-training the reference replaces ``model.map2_model`` by Linear(output_dim, 64) - LeakyReLU - Linear(64, 32) - LeakyReLU -
+Linear(32, 2) and runs one Adam step per ANCHOR graph at B = 1 on ``F.cross_entropy(F.softmax(pred), label)`` (the soft-max applied
+twice, kept literally), thousands of times per epoch, without gradient clipping (``FlatTrainer(clip=0)``).
+
+    head = post_train.install_head(model)                    # :201-210, BEFORE the FlatTrainer is built (its bucket holds the new weights)
+    loss, pred, out = post_train.post_train_step(model, g)   # :240-256 on one graph object, eager
+    st = post_train.PostTrainStream(model, graphs)           # or: the whole epoch replayed from ONE hipGraph
+    gs = GraphedStep(FlatTrainer(model, lr=1e-3, clip=0), st.step_loss()); st.load(anchors); gs.step() ...
+
+``map_model``, the three layers, both soft-maxes and the loss are one launch forward and one backward (csrc/posttrain_head.hip) on the
+readout rows of the conv stack; the label of a streamed step is read on the device from the index the gather launch wrote
+(``ids_out``), so a replayed step needs no host word.  ``two_stage.evaluate_pred`` is the phase's ``evaluate()`` (:36-72).
+"""
+import numpy as np
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from . import _native as nat
+from . import message_passing as mp
+from . import resident as R
+from .triplet_stream import ArenaStream, _graph_dict, check_schedule
+
+EAGER = "; use the eager drop-in, post_train.post_train_step(model, graph)"
+
+
+# ----------------------------------------------------------------------------- the replacement head
+def make_head(output_dim, hidden=(64, 32), n_classes=2, device=None):
+    """the reference's ``pred_model`` (:201-208).  The three ``nn.Linear`` are constructed on the host, in the reference's order, under
+    torch's global generator (the reference builds each on the host before its ``.cuda()``: the same draws), then moved to ``device``
+    (default: the current GPU when there is one)"""
+    if len(hidden) != 2 or min(int(h) for h in hidden) < 1 or int(n_classes) < 2:
+        raise ValueError("hidden must be two positive widths and n_classes at least 2")
+    h1, h2 = int(hidden[0]), int(hidden[1])
+    lin1 = nn.Linear(int(output_dim), h1)
+    lin2 = nn.Linear(h1, h2)
+    lin3 = nn.Linear(h2, int(n_classes))
+    seq = nn.Sequential(lin1, nn.LeakyReLU(), lin2, nn.LeakyReLU(), lin3)
+    if device is None:
+        from .dense_encoders import _default_device
+        device = _default_device()
+    return seq.to(device)
+
+
+def install_head(model, head=None):
+    """``model.map2_model = pred_model`` (:210) on the model's device; returns the head.  Call it before a ``FlatTrainer`` is built, so
+    the new parameters lie in its bucket"""
+    dev = next(model.parameters()).device
+    if head is None:
+        head = make_head(model.map_model.out_features, device=dev)
+    model.map2_model = head.to(dev)
+    return model.map2_model
+
+
+def head_layers(model):
+    """(map_model, lin1, lin2, lin3, negative_slope) when ``map_model`` is a Linear and ``map2_model`` is Linear - LeakyReLU - Linear -
+    LeakyReLU - Linear with biases and matching widths, else None"""
+    lin0, seq = getattr(model, "map_model", None), getattr(model, "map2_model", None)
+    if not isinstance(lin0, nn.Linear) or not isinstance(seq, nn.Sequential) or len(seq) != 5:
+        return None
+    l1, a1, l2, a2, l3 = seq
+    if not all(isinstance(m, nn.Linear) for m in (l1, l2, l3)) or not all(isinstance(m, nn.LeakyReLU) for m in (a1, a2)):
+        return None
+    if a1.negative_slope != a2.negative_slope or any(m.bias is None for m in (lin0, l1, l2, l3)):
+        return None
+    if l1.in_features != lin0.out_features or l2.in_features != l1.out_features or l3.in_features != l2.out_features:
+        return None
+    return lin0, l1, l2, l3, float(a1.negative_slope)
+
+
+def _layers_fit(layers, rows, dev):
+    """the library takes these layers on ``rows`` readout rows: fp32, contiguous, 16-byte aligned tensors on ``dev``, supported widths"""
+    if layers is None or dev.type != "cuda":
+        return False
+    lin0, l1, l2, l3, _ = layers
+    for m in (lin0, l1, l2, l3):
+        for t in (m.weight, m.bias):
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.data_ptr() % 16 or t.device != dev:
+                return False
+    return bool(nat.lib().tsgnn_posttrain_head_supported(lin0.in_features, lin0.out_features, l1.out_features, l2.out_features,
+                                                         l3.out_features, int(rows)))
+
+
+def head_ok(model, r):
+    """the fused head applies to the readout rows ``r`` of ``model``; otherwise the torch composition of the same expression is used"""
+    layers = head_layers(model)
+    return (layers is not None and r is not None and r.is_cuda and r.dim() == 2 and r.dtype == torch.float32 and r.stride(1) == 1
+            and r.stride(0) % 4 == 0 and r.stride(0) >= r.size(1) and r.data_ptr() % 16 == 0 and r.size(1) == layers[0].in_features
+            and _layers_fit(layers, r.size(0), r.device))
+
+
+class _PostTrainHead(torch.autograd.Function):
+    """(readout rows r [R, P], ids [R] int32, label table int32, slope, the eight head parameters) -> (loss, logits [R, C], out [R, E]):
+    tsgnn_posttrain_head_fwd_f32 / _bwd_f32.  ``logits`` and ``out`` are not differentiable (the reference's step reads them only)."""
+
+    @staticmethod
+    def forward(ctx, r, ids, labels, slope, w0, b0, w1, b1, w2, b2, w3, b3):
+        R_, P = int(r.size(0)), int(r.size(1))
+        E, h1, h2, C = int(w0.size(0)), int(w1.size(0)), int(w2.size(0)), int(w3.size(0))
+        dev = r.device
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        out, z1, z2, z, p, loss = new(R_, E), new(R_, h1), new(R_, h2), new(R_, C), new(R_, C), new(1)
+        nat.call("posttrain_head_fwd_f32", r, r.stride(0), R_, P, w0, b0, E, w1, b1, h1, w2, b2, h2, w3, b3, C, float(slope), ids, labels,
+                 int(labels.numel()), out, z1, z2, z, p, loss)
+        ctx.save_for_backward(r, w0, w1, w2, w3, out, z1, z2, p, ids, labels)
+        ctx.params = (w0, b0, w1, b1, w2, b2, w3, b3)         # (the Parameter objects: their slices of a trainer's flat gradient bucket)
+        ctx.slope = float(slope)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(z, out)
+        return loss.view(()), z, out
+
+    @staticmethod
+    def backward(ctx, g, _gz, _gout):
+        if g is None:
+            return (None,) * 12
+        r, w0, w1, w2, w3, out, z1, z2, p, ids, labels = ctx.saved_tensors
+        R_, P = int(r.size(0)), int(r.size(1))
+        E, h1, h2, C = int(w0.size(0)), int(w1.size(0)), int(w2.size(0)), int(w3.size(0))
+        dev = r.device
+        g = g.contiguous().float()                                # the upstream gradient stays on the device
+        d_r = torch.empty(R_, P, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        # straight into the trainer's flat gradient bucket when one is installed (FlatTrainer): no AccumulateGrad copy, no zeroing
+        bufs, grads = mp._sinks_or_new(ctx.params, ((E, P), (E,), (h1, E), (h1,), (h2, h1), (h2,), (C, h2), (C,)), dev)
+        nat.call("posttrain_head_bwd_f32", r, r.stride(0), R_, P, w0, E, w1, h1, w2, h2, w3, C, ctx.slope, ids, labels, int(labels.numel()),
+                 out, z1, z2, p, g, d_r, P, *bufs)
+        return (d_r, None, None, None) + grads
+
+
+def head_torch(model, r, label):
+    """the same expression as torch modules (:249-256 after the readout): -> (loss, pred, out)"""
+    out = model.map_model(r)
+    pred = model.map2_model(out)
+    return F.cross_entropy(F.softmax(pred, dim=1), label), pred, out
+
+
+def apply_head(model, r, ids, labels):
+    """readout rows -> (loss, pred, out): the fused head where ``head_ok``, else ``head_torch`` on ``labels[ids]``"""
+    if head_ok(model, r):
+        lin0, l1, l2, l3, slope = head_layers(model)
+        return _PostTrainHead.apply(r, ids, labels, slope, lin0.weight, lin0.bias, l1.weight, l1.bias, l2.weight, l2.bias, l3.weight, l3.bias)
+    return head_torch(model, r, labels[ids.long()].long())
+
+
+def _readout(model, x, g, sizes, assign_x):
+    """the model up to its concatenated readout rows under the statistics of a B = 1 call (``_heads`` honours ``_defer_map`` for
+    "pretrain"); the flag is put back on every exit path"""
+    prev = getattr(model, "_defer_map", False)
+    model._defer_map = True
+    try:
+        with R.per_graph_statistics(model):
+            return model(x, g, sizes, assign_x=assign_x)[1]
+    finally:
+        model._defer_map = prev
+
+
+# ----------------------------------------------------------------------------- the eager step
+_consts = {}
+
+
+def _const_i32(dev, value):
+    """a cached one-element int32 device tensor (row 0's index, a label): uploaded once per value, not per step"""
+    key = (dev.type, dev.index, int(value))
+    t = _consts.get(key)
+    if t is None:
+        t = _consts[key] = torch.tensor([int(value)], dtype=torch.int32, device=dev)
+    return t
+
+
+def _label_of(d, what="graph"):
+    if "label" not in d:
+        raise ValueError("%s carries no 'label'" % what)
+    a = np.asarray(d["label"])
+    if a.size != 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("%s: 'label' must be one integer; got %r" % (what, d["label"]))
+    return int(a.reshape(-1)[0])
+
+
+def post_train_step(model, graph):
+    """forward of the reference's post-training step (:240-256) on one graph object (``.graph`` = {'adj', 'feats', 'num_nodes',
+    'assign_feats', 'label'}) -> (loss, pred, out); the caller runs ``backward`` and the optimiser.  A plain ``GcnEncoderGraph`` with
+    final_dim "pretrain" takes the graph's resident pieces from the model's ``ResidentCache`` and applies the fused head to its readout
+    row; any other model gets the module call on the dense arrays and the torch expression."""
+    from . import triplet as T
+    from .dense_encoders import GcnEncoderGraph
+    dev = next(model.parameters()).device
+    d = graph.graph
+    label = _label_of(d)
+    if (R.RESIDENT and dev.type == "cuda" and type(model) is GcnEncoderGraph and model.final_dim == "pretrain"
+            and isinstance(getattr(model, "map_model", None), nn.Linear)):
+        g, x, xa, sizes = T.assemble([T.resident_graph(graph, dev, R.resident_cache(model))], dev)
+        r = _readout(model, x, g, sizes, x if xa is None else xa)
+        return apply_head(model, r, _const_i32(dev, 0), _const_i32(dev, label))
+    adj = torch.as_tensor(np.asarray(d["adj"], dtype=np.float32)[None], device=dev)
+    h0 = torch.as_tensor(np.asarray(d["feats"], dtype=np.float32)[None], device=dev)
+    assign = torch.as_tensor(np.asarray(d["assign_feats"], dtype=np.float32), device=dev) if "assign_feats" in d else h0
+    pred, out = model(h0, adj, np.array([int(d["num_nodes"])]), assign_x=assign)
+    return F.cross_entropy(F.softmax(pred, dim=1), torch.tensor([label], device=dev)), pred, out
+
+
+# ----------------------------------------------------------------------------- the streamed step
+def label_table(graphs, n_classes):
+    """int32 [G] of ``graph['label']``; ValueError, naming the graph's index, for a label that is no integer in [0, n_classes)"""
+    out = np.zeros(len(graphs), dtype=np.int32)
+    for i, obj in enumerate(graphs):
+        y = _label_of(_graph_dict(obj), "graph %d" % i)
+        if not 0 <= y < int(n_classes):
+            raise ValueError("graph %d: label %d lies outside [0, %d)" % (i, y, int(n_classes)))
+        out[i] = y
+    return out
+
+
+def check_anchors(anchors, n_graphs):
+    """[T] or [T, 1] integer indices into the dataset -> contiguous int32 [T, 1] (``triplet_stream.check_schedule``'s refusals)"""
+    s = np.asarray(anchors)
+    if s.ndim == 1:
+        s = s.reshape(-1, 1)
+    return check_schedule(s, n_graphs, 1)
+
+
+class PostTrainStream(ArenaStream):
+    """An epoch of post-training steps from ONE hipGraph: the arena of ``triplet_stream.pack_arena(..., batch=1)``, a device label
+    table, and per replay the gather launch (the anchor of "schedule entry number cursor"), the fused per-graph conv stack on the
+    gathered capacity-padded batch and the fused head, whose label is ``labels[ids_out[0]]`` read on the device.
+
+    ``model``: what ``TripletStream`` takes (a plain ``GcnEncoderGraph`` with concat and bn whose stack runs as the fused node on the
+    gathered batch) with final_dim "pretrain" and the installed head of ``head_ok``'s shape; anything else is a TypeError pointing to
+    ``post_train_step``.  ``load(anchors)``: [T] or [T, 1] indices into ``graphs`` (``schedule_of(sampler, graphs)[:, :1]`` is the
+    reference's epoch).  ``step_loss()`` is the callable for ``GraphedStep``.  ``max_steps``: as ``TripletStream``."""
+
+    def __init__(self, model, graphs, nmax=None, max_steps=None):
+        graphs = list(graphs)
+        super().__init__(model, graphs, 1, nmax, max_steps, name="PostTrainStream",
+                         takes="takes a GcnEncoderGraph with concat and bn", eager=EAGER)
+        if model.final_dim != "pretrain":
+            raise TypeError("PostTrainStream takes a model with final_dim = 'pretrain'" + EAGER)
+        layers = head_layers(model)
+        if not _layers_fit(layers, 1, self.device) or layers[0].in_features != model.pred_input_dim or model.pred_input_dim % 4:
+            raise TypeError("PostTrainStream: map_model / map2_model are not the head the fused launches take (post_train.install_head)" + EAGER)
+        self.n_classes = int(layers[3].out_features)
+        self.labels = torch.from_numpy(label_table(graphs, self.n_classes)).to(self.device)
+        self._warm_up_schedule()
+
+    def _checked(self, anchors):
+        return check_anchors(anchors, self.arena.n_graphs)
+
+    def step(self):
+        """gather launch + the stack's readout row + the head -> (loss, pred, out) of the cursor's entry"""
+        self.gather()
+        r = _readout(self.model, self.x, self.g, None, self.x)
+        if not head_ok(self.model, r):
+            raise RuntimeError("PostTrainStream: the fused head does not take this model's readout rows" + EAGER)
+        return apply_head(self.model, r, self.ids_out, self.labels)
+
+    def step_loss(self):
+        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
+        def step():
+            return self.step()[0]
+        return step

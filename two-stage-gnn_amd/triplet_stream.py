@@ -10,6 +10,9 @@ replayed T times, trains the epoch with no host work per step beyond the replay.
 
 For the GraphSage-family step (``triplet.tripletnet`` over a ``GcnEncoderGraph`` whose conv stack runs as the fused node under
 per-graph statistics); the GAT and EigenGCN families have assemblers of their own.
+
+``ArenaStream`` holds what does not depend on the number of graphs a schedule entry names; ``TripletStream`` (three) and
+``post_train.PostTrainStream`` (one: the anchor of the 2stg+ post-training step) are its users.
 """
 import numpy as np
 import torch
@@ -138,29 +141,27 @@ def schedule_of(sampler, graphs):
     return np.asarray(rows, dtype=np.int32).reshape(-1, 3)
 
 
-class TripletStream:
-    """``net``: a ``triplet.tripletnet`` over a ``GcnEncoderGraph``; ``graphs``: the dataset's graph objects.  Packs and uploads the
-    arena once.  ``load(schedule)`` uploads an epoch's triplets ([T, 3] indices into ``graphs``) and sets the cursor to 0;
-    ``loss(criterion, target)`` is the step for ``GraphedStep``: every call (every replay) consumes the next entry.  The schedule
-    buffer is sized by ``max_steps`` (default: the first schedule loaded): a captured step holds its address.  With ``max_steps`` the
-    stream starts on the one-entry schedule [0, 0, 0], so a ``GraphedStep`` can be built (its warm-up steps run) before the first epoch's
-    schedule exists."""
+class ArenaStream:
+    """What the streams over a packed dataset share, whatever the number ``batch`` of graphs a schedule entry names (3: a triplet,
+    ``TripletStream``; 1: the anchor of the 2stg+ post-training step, ``post_train.PostTrainStream``): the eligibility checks, the arena
+    upload, the capacity-padded batch the gather launch writes, the schedule buffer with cursor and ticket counter, ``load``,
+    ``gather`` and ``position``.  ``model``: a plain ``GcnEncoderGraph`` with concat and bn whose conv stack runs as the fused
+    per-graph node on the gathered batch; anything else is a TypeError that ends in ``eager`` (where the caller's eager drop-in is)."""
 
-    def __init__(self, net, graphs, nmax=None, max_steps=None):
+    def __init__(self, model, graphs, batch, nmax=None, max_steps=None, name="ArenaStream", takes="takes a GcnEncoderGraph with concat and bn",
+                 eager=""):
         from . import sage_stack
         from .dense_encoders import GcnEncoderGraph
         from .ingest import CapacityBatch, ELL_W
-        model = getattr(net, "model", None)
-        eager = "; use the eager drop-in, tripletnet.forward(a, p, n)"
         if type(model) is not GcnEncoderGraph or not model.concat or not model.bn:
-            raise TypeError("TripletStream takes a tripletnet over a GcnEncoderGraph with concat and bn" + eager)
+            raise TypeError("%s %s%s" % (name, takes, eager))
         dev = next(model.parameters()).device
         if dev.type != "cuda":
-            raise TypeError("TripletStream runs on the GPU only" + eager)
+            raise TypeError("%s runs on the GPU only%s" % (name, eager))
         graphs = list(graphs)
         if nmax is None:
             nmax = int(np.asarray(_graph_dict(graphs[0])["adj"]).shape[0])
-        self.net, self.model, self.device, self.B = net, model, dev, 3
+        self.model, self.device, self.B = model, dev, int(batch)
         ar = self.arena = pack_arena(graphs, nmax, ELL_W, batch=self.B)
         rows, _, tail = ar.caps
         self.row_cap = (rows + 31) // 32 * 32
@@ -171,7 +172,7 @@ class TripletStream:
         self.g, self.x = self.batch.g, self.batch.x
         convs = [model.conv_first] + list(model.conv_block) + [model.conv_last]
         if not sage_stack.eligible(self.g, convs, model.bn, self.x) or convs[0].output_dim > 256 or model.conv_first.input_dim != ar.fin:
-            raise TypeError("TripletStream: the model's conv stack does not run as the fused per-graph node on this dataset" + eager)
+            raise TypeError("%s: the model's conv stack does not run as the fused per-graph node on this dataset%s" % (name, eager))
         self.records = torch.from_numpy(ar.records).to(dev)
         self.buf = torch.from_numpy(ar.buf).to(dev)
         self.feats = torch.from_numpy(ar.feats).to(dev)
@@ -180,6 +181,9 @@ class TripletStream:
         # int32 [HEAD + max_steps * B]: {cursor, T} as two int64, the ticket counter (+ 3 spare words), then the schedule
         self._sched = self._host = None
         self.T = 0
+
+    def _warm_up_schedule(self):
+        """with ``max_steps``: the one-entry schedule of graph 0, so that a ``GraphedStep`` can be built before the first epoch's exists"""
         if self.max_steps is not None:
             if self.max_steps < 1:
                 raise ValueError("max_steps must be at least 1")
@@ -188,11 +192,14 @@ class TripletStream:
     def __len__(self):
         return self.T
 
+    def _checked(self, schedule):
+        return check_schedule(schedule, self.arena.n_graphs, self.B)
+
     def load(self, schedule):
         """validate on the host, ONE host-to-device copy ({cursor = 0, T, ticket counter = 0, schedule}), returns T.  An epoch
         boundary: it waits for the steps already enqueued (they read the buffer it overwrites).  The ticket counter goes up with it, so
         a launch that was ever cut short cannot leave the cursor stuck for the next epoch."""
-        s = check_schedule(schedule, self.arena.n_graphs, self.B)
+        s = self._checked(schedule)
         T = int(s.shape[0])
         if self._sched is None:
             if self.max_steps is None:
@@ -201,7 +208,7 @@ class TripletStream:
             self._host = torch.zeros(words, dtype=torch.int32).pin_memory()
             self._sched = torch.zeros(words, dtype=torch.int32, device=self.device)
         if T > self.max_steps:
-            raise ValueError("a schedule of %d triplets exceeds this stream's buffer of %d (max_steps: captured steps hold its address)"
+            raise ValueError("a schedule of %d entries exceeds this stream's buffer of %d (max_steps: captured steps hold its address)"
                              % (T, self.max_steps))
         torch.cuda.synchronize(self.device)
         h = self._host.numpy()
@@ -216,13 +223,37 @@ class TripletStream:
     def gather(self):
         """enqueue (current stream; capturable) the launch that writes the batch of the cursor's entry and advances the cursor"""
         if self._sched is None:
-            raise RuntimeError("TripletStream: load(schedule) before the first step")
+            raise RuntimeError("%s: load(schedule) before the first step" % type(self).__name__)
         ar, g, b = self.arena, self.g, self.batch
         ell, ell_w, (tail_ptr, tail_col) = g._ell
         nat.call("triplet_gather_f32", self.records, ar.n_graphs, self.buf, ar.off["rowptr"], ar.off["col"], ar.off["tail_ptr"],
                  ar.off["tail_col"], ar.words, self.feats, ar.ld, ar.caps[0], ar.caps[2], self._sched[HEAD:], self.max_steps, self._sched,
                  self._sched[4:HEAD], self.B, ar.nmax, self.row_cap, self.tail_cap, ell_w, g.graph_ptr, g.slot_count, g.row_graph, g.row_slot,
                  ell, tail_ptr, tail_col, b.ell_slots, b.tail_slots, self.x, self.x.stride(0), self.ids_out)
+
+    def position(self):
+        """the cursor: entries consumed since ``load``.  Waits for everything enqueued on the device, whichever stream the steps
+        were replayed on (a ``GraphedStep`` has a stream of its own); for tests and epoch boundaries"""
+        if self._sched is None:
+            return 0
+        torch.cuda.synchronize(self.device)
+        return int(self._sched[:2].cpu().numpy().view(np.int64)[0])
+
+
+class TripletStream(ArenaStream):
+    """``net``: a ``triplet.tripletnet`` over a ``GcnEncoderGraph``; ``graphs``: the dataset's graph objects.  Packs and uploads the
+    arena once.  ``load(schedule)`` uploads an epoch's triplets ([T, 3] indices into ``graphs``) and sets the cursor to 0;
+    ``loss(criterion, target)`` is the step for ``GraphedStep``: every call (every replay) consumes the next entry.  The schedule
+    buffer is sized by ``max_steps`` (default: the first schedule loaded): a captured step holds its address.  With ``max_steps`` the
+    stream starts on the one-entry schedule [0, 0, 0], so a ``GraphedStep`` can be built (its warm-up steps run) before the first epoch's
+    schedule exists."""
+
+    def __init__(self, net, graphs, nmax=None, max_steps=None):
+        super().__init__(getattr(net, "model", None), graphs, 3, nmax, max_steps, name="TripletStream",
+                         takes="takes a tripletnet over a GcnEncoderGraph with concat and bn",
+                         eager="; use the eager drop-in, tripletnet.forward(a, p, n)")
+        self.net = net
+        self._warm_up_schedule()
 
     def embed(self):
         """gather + the model on the gathered batch -> (dist_p, dist_n, embed_a, embed_p, embed_n), as ``tripletnet.forward`` returns"""
@@ -235,11 +266,3 @@ class TripletStream:
             out = self.embed()
             return criterion(out[0], out[1], target)
         return step
-
-    def position(self):
-        """the cursor: entries consumed since ``load``.  Waits for everything enqueued on the device, whichever stream the steps
-        were replayed on (a ``GraphedStep`` has a stream of its own); for tests and epoch boundaries"""
-        if self._sched is None:
-            return 0
-        torch.cuda.synchronize(self.device)
-        return int(self._sched[:2].cpu().numpy().view(np.int64)[0])

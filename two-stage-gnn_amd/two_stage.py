@@ -407,6 +407,44 @@ def evaluate(train_graphs, val_graphs, model, n_neighbors=3, chunk=None):
     return result
 
 
+def predict_dataset(graphs, model, chunk=None):
+    """class index per graph, int32 on the model's device: the argmax (a tie to the lowest class) of ``model.map2_model`` on the
+    graph's ``embed_dataset`` row.  For a final_dim "pretrain" encoder that row is ``out`` and the result the argmax of the reference's
+    ``pred`` (train_triplet_pre_train.py:59-63).  A head of the MLP probe's shape (``post_train.make_head``) is ONE launch of
+    ``tsgnn_mlp_probe_predict_f32``; any other ``map2_model`` is applied as torch modules"""
+    from . import post_train as PT
+    net = model.model if (hasattr(model, "model") and not hasattr(model, "map2_model")) else model
+    emb = embed_dataset(model, graphs, chunk)
+    n = int(emb.size(0))
+    if n == 0:
+        return torch.zeros(0, dtype=torch.int32, device=emb.device)
+    layers = PT.head_layers(net)
+    if layers is not None and emb.is_cuda:
+        _, l1, l2, l3, slope = layers
+        E, h1, h2, C = int(l1.in_features), int(l1.out_features), int(l2.out_features), int(l3.out_features)
+        ps = [t.detach() for m in (l1, l2, l3) for t in (m.weight, m.bias)]
+        if (E == emb.size(1) and nat.lib().tsgnn_mlp_probe_supported(E, h1, h2, C)
+                and all(t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda for t in ps)):
+            pred = torch.empty(n, dtype=torch.int32, device=emb.device)
+            nat.call("mlp_probe_predict_f32", emb, emb.stride(0), n, E, h1, h2, C, *ps, slope, None, pred, None, None)
+            return pred
+    with _eval_mode(net):
+        z = net.map2_model(emb)
+    return (z == z.max(dim=1, keepdim=True).values).int().argmax(dim=1).int()      # (the first maximum: the lowest class)
+
+
+def evaluate_pred(graphs, model, chunk=None):
+    """The ``evaluate()`` of the 2stg+ post-training phase (train_triplet_pre_train.py:36-72): the argmax of ``pred`` per graph against
+    ``graph.graph['label']`` -> {'prec' (macro), 'recall' (macro), 'acc', 'F1' (micro)}.  ``graphs``: a ``{class: [graphs]}`` dictionary
+    (iteration order kept) or a sequence.  After the embeddings exist: one predict launch and ONE copy of the predictions to the
+    host; the metrics are numpy on the confusion matrix."""
+    graphs = _flatten(graphs)
+    y = _labels(graphs).reshape(-1)
+    pred = predict_dataset(graphs, model, chunk).cpu().numpy().astype(np.int64)
+    labels = np.unique(np.concatenate([y.astype(np.int64), pred]))
+    return metrics_from_confusion(confusion_matrix(y, pred, labels))
+
+
 # ----------------------------------------------------------------------------- the MLP probe
 def _probe_sizes(E, h1, h2, C):
     """element counts of W1, b1, W2, b2, W3, b3: the order of the flat parameter and moment buffers (and of the C ABI)"""
