@@ -54,25 +54,45 @@ inline int device_cu_count() {
   return n;
 }
 
-// store of a value that THIS kernel will not read again (results handed to a later launch): -DTSGNN_NT_STORES=1 marks them
-// non-temporal.  Measured (round 3, A/B of two builds through TSGNN_LIB_PATH): the producers' own burst times drop (row panels
-// 10.0 -> 9.4 / 14.5 -> 13.8 / 13.1 -> 12.1 us: less to write back at the kernel boundary) and the replayed STEP does not move at all
-// (0.1295 ms both ways): what a producer saves its consumer pays on the read.  Off.
-#ifndef TSGNN_NT_STORES
-#define TSGNN_NT_STORES 0
+// Result stores: a value that THIS launch will not read again and a LATER launch reads (v / dX rows, z, weight-gradient slabs, dU
+// rows).  They are WRITE-THROUGH (sc1): the bytes leave the XCD's L2 while the kernel still runs, so nothing is left dirty for the
+// write-back at the launch boundary, and the consumer finds them where that write-back would have put them.  Rule for a call site:
+// no block of the same launch reads the buffer back (sc1 drops the line from this XCD's L2), and the buffer is not one that atomics
+// write (packed, the integer sums, error words).  The stored values and addresses are those of a plain store.
+// Measured (profiles/r12; alternating A/B builds through TSGNN_LIB_PATH, one job, us per step of the headline batch, four rounds):
+//   plain 118.88 | every call site write-through as it stands (dword and float4) 113.67 | the float4 sites only 116.78 |
+//   non-temporal (round 3's -DTSGNN_NT_STORES=1, never sc1-less nt on a hand-off) 119.49 | no result stores at all (ceiling) 111.83
+//   | float4 sites write-through + the dword epilogues restaged through LDS into float4 115.69 | restaged, plain 120.04.
+// The dword epilogues straight out of the MFMA accumulator layout win as they are (32 lanes of a store cover one 128-byte line):
+// passing the tiles through LDS to leave as 16 bytes per lane costs 1.2 us of the step and is not in the tree.
+// TSGNN_ST_WT: bit mask by store width in bytes (4 | 8 | 16) of the forms that are write-through; -DTSGNN_ST_WT=0 (scripts/exp_build.sh)
+// builds the plain-store library for A/B runs.
+#ifndef TSGNN_ST_WT
+#define TSGNN_ST_WT 28
 #endif
 typedef float tsgnn_f32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ void st_out(float* p, float v) {
-#if TSGNN_NT_STORES
-  __builtin_nontemporal_store(v, p);
+#if TSGNN_ST_WT & 4
+  __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                  // global_store_dword ... sc1
+#else
+  *p = v;
+#endif
+}
+__device__ __forceinline__ void st_out(float2* p, float2 v) {
+#if TSGNN_ST_WT & 8
+  __hip_atomic_store(reinterpret_cast<unsigned long long*>(p), __builtin_bit_cast(unsigned long long, v), __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_AGENT);                                          // global_store_dwordx2 ... sc1
 #else
   *p = v;
 #endif
 }
 __device__ __forceinline__ void st_out(float4* p, float4 v) {
-#if TSGNN_NT_STORES
-  tsgnn_f32x4 t = {v.x, v.y, v.z, v.w};
-  __builtin_nontemporal_store(t, reinterpret_cast<tsgnn_f32x4*>(p));
+#if TSGNN_ST_WT & 16
+  // (no builtin stores 16 bytes write-through through a per-lane pointer.  The compiler does not count this store: that is safe for
+  // a value nothing in the kernel reads back — its own waits only get longer —, and s_nop 1 keeps the next instruction from
+  // overwriting the four data registers before the store has read them)
+  const tsgnn_f32x4 t = {v.x, v.y, v.z, v.w};
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" : : "v"(p), "v"(t) : "memory");
 #else
   *p = v;
 #endif

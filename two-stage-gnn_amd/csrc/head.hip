@@ -535,7 +535,7 @@ __device__ __forceinline__ void head2_du_role(const DuArgs& a, float* smem, cons
   if (pad_k >= 0) {                                              // padding rows of a capacity-padded batch: zeros
     const int64_t lo = a.graph_ptr[B];
     for (int64_t r = lo + (int64_t)pad_k * 32 + rg; r < a.n_real; r += (int64_t)max(pad_n, 1) * 32)
-      if (lig < F4) *reinterpret_cast<float4*>(a.du + r * a.lddu + 4 * lig) = z4;
+      if (lig < F4) st_out(reinterpret_cast<float4*>(a.du + r * a.lddu + 4 * lig), z4);
     return;
   }
   const int g0 = a.graph_ptr[b], sz = a.graph_ptr[b + 1] - g0;
@@ -645,9 +645,9 @@ __device__ __forceinline__ void head2_du_role(const DuArgs& a, float* smem, cons
     dot = group_sum<32>(dot);
     if (rows[u] >= 0 && lig < F4) {
       if (ri[u] >= 0.999e12f) dot = 0.f;
-      *reinterpret_cast<float4*>(a.du + (size_t)((unsigned)rows[u] * lddu + col)) =
-          make_float4(ri[u] * (dyv.x - vv[u].x * dot), ri[u] * (dyv.y - vv[u].y * dot), ri[u] * (dyv.z - vv[u].z * dot),
-                      ri[u] * (dyv.w - vv[u].w * dot));
+      st_out(reinterpret_cast<float4*>(a.du + (size_t)((unsigned)rows[u] * lddu + col)),
+             make_float4(ri[u] * (dyv.x - vv[u].x * dot), ri[u] * (dyv.y - vv[u].y * dot), ri[u] * (dyv.z - vv[u].z * dot),
+                         ri[u] * (dyv.w - vv[u].w * dot)));
     }
   }
   if (ghost_job && rg == 0) {                                    // (one whole half-wave: the cross-lane sum below is complete)
@@ -665,8 +665,8 @@ __device__ __forceinline__ void head2_du_role(const DuArgs& a, float* smem, cons
     dot = group_sum<32>(dot);
     if (gri >= 0.999e12f) dot = 0.f;
     if (lig < F4)
-      *reinterpret_cast<float4*>(a.du + (size_t)((unsigned)((int)a.n_real + b) * lddu + col)) =
-          make_float4(gri * (dyv.x - gv.x * dot), gri * (dyv.y - gv.y * dot), gri * (dyv.z - gv.z * dot), gri * (dyv.w - gv.w * dot));
+      st_out(reinterpret_cast<float4*>(a.du + (size_t)((unsigned)((int)a.n_real + b) * lddu + col)),
+             make_float4(gri * (dyv.x - gv.x * dot), gri * (dyv.y - gv.y * dot), gri * (dyv.z - gv.z * dot), gri * (dyv.w - gv.w * dot)));
   }
 }
 

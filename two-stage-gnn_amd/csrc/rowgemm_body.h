@@ -200,7 +200,7 @@ __device__ __forceinline__ void rowgemm_body(const RowGemmArgs& g, float* smem_a
     }
     if (rsub < rpp) {
       for (int64_t r = rsub; r < g.fill_rows; r += rpp) {
-        *reinterpret_cast<float4*>(g.c + (g.rows + r) * g.ldc + 4 * c4) = out;
+        st_out(reinterpret_cast<float4*>(g.c + (g.rows + r) * g.ldc + 4 * c4), out);
         if (g.rinv && c4 == 0) g.rinv[g.rows + r] = sc;
       }
       if constexpr (READOUT) {

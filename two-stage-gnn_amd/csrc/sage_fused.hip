@@ -156,7 +156,7 @@ __device__ __forceinline__ void slot_post_body(const SlotArgs& s, const int n, f
     const int64_t pad_lo = s.graph_ptr[s.B], npad = s.n_real - pad_lo;
     for (int64_t i = (int64_t)blockIdx.x * BT + tid; i < npad * F4; i += (int64_t)gridDim.x * BT) {
       const int64_t r = pad_lo + i / F4;
-      st4(du + r * lddu + 4 * (i % F4), make_float4(0.f, 0.f, 0.f, 0.f));
+      st_out(reinterpret_cast<float4*>(du + r * lddu + 4 * (i % F4)), make_float4(0.f, 0.f, 0.f, 0.f));
     }
   }
   // the readout winners and their gradients depend on (graph, column) only: issued first, they fly while the row is resolved
@@ -337,9 +337,12 @@ __device__ __forceinline__ void slot_post_body(const SlotArgs& s, const int n, f
 #pragma unroll
     for (int q = 0; q < NV; ++q) {
       const int c4 = c + TPR * q;
-      if (c4 < F4)
-        st4(dst + 4 * c4, make_float4(ri * (dv[q].x - vv[q].x * dot), ri * (dv[q].y - vv[q].y * dot),
-                                      ri * (dv[q].z - vv[q].z * dot), ri * (dv[q].w - vv[q].w * dot)));
+      if (c4 < F4) {
+        const float4 o = make_float4(ri * (dv[q].x - vv[q].x * dot), ri * (dv[q].y - vv[q].y * dot),
+                                     ri * (dv[q].z - vv[q].z * dot), ri * (dv[q].w - vv[q].w * dot));
+        if constexpr (TO_LDS) st4(dst + 4 * c4, o);
+        else st_out(reinterpret_cast<float4*>(dst + 4 * c4), o);
+      }
     }
   }
   if constexpr (!TO_LDS) {
@@ -348,7 +351,7 @@ __device__ __forceinline__ void slot_post_body(const SlotArgs& s, const int n, f
 #pragma unroll
       for (int q = 0; q < NV; ++q) {
         const int c4 = c + TPR * q;
-        if (c4 < F4) st4(du + gr * lddu + 4 * c4, make_float4(0.f, 0.f, 0.f, 0.f));
+        if (c4 < F4) st_out(reinterpret_cast<float4*>(du + gr * lddu + 4 * c4), make_float4(0.f, 0.f, 0.f, 0.f));
       }
     }
   }

@@ -58,10 +58,10 @@ __global__ __launch_bounds__(256) void sage_relu_readout_bwd_kernel(const float*
   if (relu) {
     d.x = hv.x > 0.f ? d.x : 0.f; d.y = hv.y > 0.f ? d.y : 0.f; d.z = hv.z > 0.f ? d.z : 0.f; d.w = hv.w > 0.f ? d.w : 0.f;
   }
-  st_out(reinterpret_cast<float4*>(du + r * lddu + c), d);
+  *reinterpret_cast<float4*>(du + r * lddu + c) = d;
   if (dus) {                                              // the same rows scaled by 1 / deg: what the next launch GATHERS
     const float sc = row_scale[r];
-    st_out(reinterpret_cast<float4*>(dus + r * lddus + c), make_float4(d.x * sc, d.y * sc, d.z * sc, d.w * sc));
+    *reinterpret_cast<float4*>(dus + r * lddus + c) = make_float4(d.x * sc, d.y * sc, d.z * sc, d.w * sc);
   }
 }
 

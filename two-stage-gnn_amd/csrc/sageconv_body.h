@@ -151,7 +151,7 @@ __device__ __forceinline__ void sageconv_body(const SageConvArgs& g, float* smem
       if (nvc < 2) v.y = 0.f;
       if (nvc < 1) v.x = 0.f;
       *reinterpret_cast<float4*>(P + pr * SC_LDP + 4 * (c4 ^ (pr & 15))) = v;
-      if (g.zout && nvc > 0 && row < g.rows) st_out(reinterpret_cast<float4*>(g.zout + row * g.ldz + 4 * c4), v);
+      if (g.zout && nvc > 0 && row < g.rows) *reinterpret_cast<float4*>(g.zout + row * g.ldz + 4 * c4) = v;
     }
   };
   va[0] = sc_zero4(); va[1] = sc_zero4();
@@ -362,7 +362,7 @@ __device__ __forceinline__ void sageconv_body(const SageConvArgs& g, float* smem
     float* cp = g.out + (m0 + 4 * h) * g.ldo + cn;
     if ((m0 + 32) <= g.rows && okc) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) st_out(cp + (int64_t)((r & 3) + 8 * (r >> 2)) * g.ldo, acc[r] * scale[r]);
+      for (int r = 0; r < 16; ++r) cp[(int64_t)((r & 3) + 8 * (r >> 2)) * g.ldo] = acc[r] * scale[r];
     } else {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
