@@ -1100,9 +1100,11 @@ int tsgnn_head2_bwd_du_f32(const float* out, int64_t ldo, const float* vec, cons
                            int64_t n_real, int n_ghost_rows, int max_nodes, const float* v, int64_t ldv, const float* rinv, const int* arg,
                            int seg_off, int F, float* du, int64_t lddu, tsgnn_stream_t stream);
 /* the same with the dU workgroups LISTED by the host: du_map[n_map] = graph << 8 | chunk for every chunk of du_chunk (64 or 128) rows
- * that holds rows — chunk 0 of EVERY graph (it also writes the graph's ghost contribution row); graph == B with chunks 0 .. k-1 for a
- * capacity-padded batch's padding rows (zero-filled by k workgroups) —, so that an exact batch launches no workgroup that only
- * returns and the launch's duration does not depend on where the batch's large graphs sit.  du_map NULL: the dense grid above
+ * that holds rows — chunk 0 of EVERY graph (it also writes the graph's ghost contribution row); for a capacity-padded batch's
+ * padding rows graph == B with EVERY chunk 0 .. k-1, k = ceil(max_nodes / du_chunk): the k workgroups zero-fill the rows 32 at a
+ * time in strides of k, so with fewer entries some padding rows are never written (an exact batch lists none) —, so that an exact
+ * batch launches no workgroup that only returns and the launch's duration does not depend on where the batch's large graphs sit.
+ * du_map NULL: the dense grid above
  * (n_map = 0), or — n_map < 0, B <= 64 — the same compact order resolved INSIDE the kernel from graph_ptr (a 64-lane prefix sum of
  * the graphs' chunk counts): for batches whose sizes live on the device (capacity-padded ingest batches). */
 int tsgnn_head2_bwd_du_map_f32(const float* out, int64_t ldo, const float* vec, const float* y, const int64_t* label, float* loss,

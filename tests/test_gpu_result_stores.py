@@ -12,41 +12,13 @@ import pytest
 import torch
 
 from fp32_yardstick import _check
+from guard_buf import GUARD, PAT, Out, _du_ref, _owned  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-PAT = 0x7FC0BEEF                        # a quiet NaN with a payload of its own
-GUARD = 64
-
 
 def _nat():
     from two_stage_gnn_amd import _native as nat
     return nat
-
-
-class Out:
-    """[rows, ld] float32 on the device, every word PAT, GUARD words of PAT behind it"""
-
-    def __init__(self, rows, ld):
-        self.rows, self.ld = rows, ld
-        self.bits = torch.full((rows * ld + GUARD,), PAT, dtype=torch.int32, device="cuda")
-        self.mat = self.bits[:rows * ld].view(torch.float32).view(rows, ld)
-
-    def rest_untouched(self, what, owned):
-        """owned: bool [rows, ld] on the CPU — the elements the launch may write"""
-        torch.cuda.synchronize()
-        b = self.bits.cpu()
-        body, guard = b[:self.rows * self.ld].view(self.rows, self.ld), b[self.rows * self.ld:]
-        assert bool((guard == PAT).all()), "%s: %d guard words overwritten" % (what, int((guard != PAT).sum()))
-        bad = (body != PAT) & ~owned
-        assert not bool(bad.any()), "%s: %d elements written outside the launch's own (first at %s)" % (
-            what, int(bad.sum()), bad.nonzero()[0].tolist())
-
-
-def _owned(rows, ld, r0, r1, c0, c1):
-    m = torch.zeros(rows, ld, dtype=torch.bool)
-    m[r0:r1, c0:c1] = True
-    return m
 
 
 def _ell(rows, n_src, ell_w, seed):
@@ -252,25 +224,6 @@ def test_slot_post_bwd_rows(ghosts):
     torch.cuda.synchronize()
     T.check_bwd("slot_post_bwd B6 F128 %s" % ("ghost" if ghosts else "noghost"), c, D.mat[:L.rows, :F])
     D.rest_untouched("slot_post_bwd du", _owned(D.rows, lddu, 0, L.rows, 0, F))
-
-
-def _du_ref(v, rinv, arg, dout, off, graph_ptr, n_real, n_ghost, dtype):
-    """rows of the last layer's dU as the head backward's dU role leaves them: du[r] = rinv_r (g_r - v_r <v_r, g_r>) with g_r[f] =
-    dout[b, off + f] where r won (graph b, column f); graph b's ghost contribution (its first ghost row, n_real + size_b) at n_real + b"""
-    B, F = arg.shape
-    v, rinv, dout = v.to(dtype), rinv.to(dtype), dout.to(dtype)
-    out = torch.zeros(n_real + B, F, dtype=dtype)
-
-    def row(r, b):
-        g = torch.where(arg[b] == r, dout[b, off:off + F], torch.zeros(F, dtype=dtype))
-        return rinv[r] * (g - v[r] * (v[r] * g).sum())
-    for b in range(B):
-        for r in range(int(graph_ptr[b]), int(graph_ptr[b + 1])):
-            out[r] = row(r, b)
-        sz = int(graph_ptr[b + 1] - graph_ptr[b])
-        if sz < n_ghost:
-            out[n_real + b] = row(n_real + sz, b)
-    return out
 
 
 def test_head_du_role():

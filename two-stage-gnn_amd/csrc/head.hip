@@ -504,7 +504,8 @@ struct DuArgs {
   // the device); the blocks behind the last pair (compact = their number) zero-fill the padding rows
   int compact;
 };
-// (graph, chunk) of dU block d; pad_k >= 0: not a pair but the pad_k-th of pad_n zero-fill blocks
+// (graph, chunk) of dU block d; pad_k >= 0: not a pair but the pad_k-th of pad_n zero-fill blocks (host map: pad_n = a.chunks, so the
+// list must hold graph == B with every chunk 0 .. a.chunks - 1)
 template <int DU_CHUNK>
 __device__ __forceinline__ void du_resolve(const DuArgs& a, int d, int B, int& b, int& c, int& pad_k, int& pad_n) {
   pad_k = -1; pad_n = a.chunks;
@@ -1102,8 +1103,9 @@ int tsgnn_head2_bwd_du_f32(const float* out, int64_t ldo, const float* vec, cons
 }
 
 /* the same with the dU workgroups LISTED by the host: du_map[n_map] = graph << 8 | chunk for every chunk of du_chunk (64 or 128) rows
- * that holds rows (chunk 0 of EVERY graph: it also writes the graph's ghost contribution row; graph == B, chunks 0 .. k-1: the
- * padding rows of a capacity-padded batch, zero-filled by k workgroups) — an exact batch launches no workgroup that only returns.
+ * that holds rows (chunk 0 of EVERY graph: it also writes the graph's ghost contribution row; graph == B, EVERY chunk 0 .. k-1 with
+ * k = ceil(max_nodes / du_chunk): the padding rows of a capacity-padded batch, zero-filled by these k workgroups in strides of k — with
+ * fewer entries rows stay unwritten) — an exact batch launches no workgroup that only returns.
  * du_map NULL: the dense (B + 1) x chunks grid of tsgnn_head2_bwd_du_f32. */
 int tsgnn_head2_bwd_du_map_f32(const float* out, int64_t ldo, const float* vec, const float* y, const int64_t* label, float* loss,
                                const float* dy, const float* dvec, const float* w1, const float* w2, int B, int P, int E, int C,
