@@ -567,6 +567,36 @@ int tsgnn_dense_stack_max_resident(void);
  * stores 1.0 to *err, as a dense-stack launch does whose workgroups were not all resident. */
 int tsgnn_dense_stack_barrier_selftest(unsigned* sync, float* err, int expect, tsgnn_stream_t stream);
 
+/* ---------------------------------------------------------------- pooled-level GCN layers, per-graph statistics (dense_stack_pg.hip) */
+
+/* The layers of a pooled DiffPool level when every graph keeps the statistics it would have alone in its batch (the triplet step and
+ * stage two; message_passing._RowLn): BatchNorm1d(K) on [1, K, F] is a layer norm of every row, every post-op is row-local, and a
+ * layer is ONE launch without any synchronisation between workgroups.  One workgroup per 16-row tile of one graph (grid =
+ * B * ceil(K / 16)), rows past K masked; x[B*K, ldx], adj[B, K, K] dense, w[fin, ldw].  No atomics.
+ * 1 if the entry points below take the shape: B >= 1, 4 <= K <= 128, 4 <= fin <= 384, 4 <= n <= 128, K, fin, n multiples of 4
+ * (host only, no device needed). */
+int tsgnn_dense_pg_supported(int B, int K, int fin, int n);
+/* agg = A_b[rows, :K] . x_b (kept for dW), u = agg W + bias (nullable), rinv = 1 / max(|u|_2, 1e-12), v = u rinv;
+ * hidden = 1: y = (relu(v) - mean) rstd with the row's mean and biased variance over its n features, eps 1e-5
+ * (tsgnn_row_ln_fwd_f32's arithmetic); hidden = 0 (conv_last, encoders.py:165): y = v.  y[B*K, ldy] may be a column block of the
+ * concatenation; agg[B*K, fin], v[B*K, n] (hidden only), rinv / mean / rstd [B*K] are what the backward reads: all nullable
+ * (a forward-only call).  x, w, agg 16-byte aligned, ldx, ldw multiples of 4. */
+int tsgnn_dense_pg_layer_fwd_f32(const float* x, int64_t ldx, const float* adj, const float* w, int64_t ldw, const float* bias, int B, int K,
+                                 int fin, int n, int hidden, float* agg, float* v, float* rinv, float* mean, float* rstd, float* y,
+                                 int64_t ldy, tsgnn_stream_t stream);
+/* Backward of one layer: dy = dcat[B*K, lddc] (the layer's column block of the concatenation's gradient) + (A_b[:, rows])^T
+ * dagg_next[B*K, n] (nullable: the dagg the launch of the layer above wrote); dy -> dv (row layer norm + ReLU, hidden = 1) -> du
+ * = rinv (dv - v <v, dv>); v[B*K, ldv]: the forward's v, for the last layer its output block.  dagg[B*K, fin] = du W^T
+ * (nullable); slab (nullable; needs agg): B * ceil(K / 16) slabs [fin + 1][n], workgroup g's partial of dW = agg^T du and, in row
+ * fin, of db — a plain record of tsgnn_wgrad_reduce_sets_f32 with kn = 1; dadj[B, K, K] (nullable; needs xin[B*K, ldx], the layer's
+ * input) = or += (accumulate) dagg xin_b^T: a workgroup owns the same rows in every layer's launch. */
+int tsgnn_dense_pg_layer_bwd_f32(const float* adj, const float* w, int64_t ldw, const float* agg, const float* v, int64_t ldv,
+                                 const float* rinv, const float* mean, const float* rstd, const float* xin, int64_t ldx, const float* dcat,
+                                 int64_t lddc, const float* dagg_next, int B, int K, int fin, int n, int hidden, float* dagg, float* slab,
+                                 float* dadj, int accumulate, tsgnn_stream_t stream);
+/* the stack's input gradient dx_b[rows] = (A_b[:, rows])^T dagg_0: dagg[B*K, fin] -> dx[B*K, lddx] */
+int tsgnn_dense_pg_dx_f32(const float* adj, const float* dagg, int B, int K, int fin, float* dx, int64_t lddx, tsgnn_stream_t stream);
+
 /* ---------------------------------------------------------------- edge-softmax attention (attention.hip) */
 
 /* s[r,h] = <x[r, head h], a[h]>  — the two per-node scalars a1.h_i / a2.h_j that replace the reference's

@@ -52,6 +52,7 @@ SOFTMAX_IN_CONTRACT = os.environ.get("TSGNN_SOFTMAX_IN_CONTRACT", "1") != "0"   
 READOUT_COLUMNS = os.environ.get("TSGNN_READOUT_COLUMNS", "1") != "0"   # DiffPool: the levels' readouts written into one buffer (no cat)
 FUSED_STACK = True             # GcnEncoderGraph: run the conv stack as one fused autograd node when it qualifies
 PER_GRAPH_STACK = os.environ.get("TSGNN_PER_GRAPH_STACK", "1") != "0"   # ... also with per-graph statistics (the triplet step)
+PER_GRAPH_DENSE = os.environ.get("TSGNN_PER_GRAPH_DENSE", "1") != "0"   # pooled DiffPool levels under per-graph statistics: one launch per layer (dense_stack_pg.py)
 DENSE_ADJ_MAX_NODES = 128      # at or below this many nodes per graph a dense batched MFMA product is used
 
 
@@ -387,6 +388,12 @@ class SoftPoolingGcnEncoder(GcnEncoderGraph):
     def gcn_forward_dense(self, x, adj, conv_first, conv_block, conv_last):
         B, K, _ = x.shape
         g = GraphBatch.uniform(B, K, x.device)
+        if self.per_graph_bn and self.bn and PER_GRAPH_DENSE:
+            # per-graph statistics (the triplet step, stage two): every post-op is row-local, a layer is one launch of independent tiles
+            from . import dense_stack_pg
+            convs = [conv_first] + list(conv_block) + [conv_last]
+            if dense_stack_pg.eligible(x, adj, convs):
+                return dense_stack_pg.dense_gcn_stack_pg(x, adj, convs), g
         if FUSED_DENSE_STACK:
             from . import dense_stack
             convs = [conv_first] + list(conv_block) + [conv_last]
@@ -443,7 +450,7 @@ class SoftPoolingGcnEncoder(GcnEncoderGraph):
                 [self.assign_conv_first_modules[0]] + list(self.assign_conv_block_modules[0]) + [self.assign_conv_last_modules[0]],
                 masked)
         else:
-            emb = self.gcn_forward_rows(x, g, self.conv_first, self.conv_block, self.conv_last, mask_ghost=masked)
+            emb = self.gcn_forward_rows(x, g, self.conv_first, self.conv_block, self.conv_last, mask_ghost=masked, per_graph_stack=True)
         # the levels' readouts land in their column blocks of ONE buffer (no torch.cat launch; mp.ReadoutColumns)
         cols = mp.ReadoutColumns(g.B, emb.size(1) * (self.num_pooling + 1), emb.device) if (self.concat and READOUT_COLUMNS) else None
         ro_next = None              # (READOUT_IN_CONTRACT) the readout of this level's embeddings, made by the contraction that reads them
@@ -466,7 +473,7 @@ class SoftPoolingGcnEncoder(GcnEncoderGraph):
             if i == 0:
                 a = a0 if a0 is not None else self.gcn_forward_rows(
                     x_a, g, self.assign_conv_first_modules[0], self.assign_conv_block_modules[0],
-                    self.assign_conv_last_modules[0], mask_ghost=masked)
+                    self.assign_conv_last_modules[0], mask_ghost=masked, per_graph_stack=True)
                 s = dp.row_softmax(mp.linear_oi(a, lin.weight, lin.bias),                    # encoders.py:369
                                    g.n_rows if (masked and g.n_ghost) else None)              # :371 (ghost rows -> 0)
                 self.assign_tensor = s
