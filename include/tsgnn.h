@@ -1184,6 +1184,32 @@ int tsgnn_contract_rows_bwd_ro_f32(const float* S, int64_t ldS, const float* Z, 
                                    int64_t zero_from, int64_t zero_to, const float* ro_dout, int64_t ro_ldo, const int* ro_arg,
                                    tsgnn_stream_t stream);
 
+/* ---- the same level-1 contraction on a CAPACITY-PADDED batch (csrc/contract_cap.hip; ingest.CapacityBatch as the gather launch of
+ * a stream writes it): rows [0, n_tot) real with n_tot = graph_ptr[B] read on the DEVICE, [n_tot, row_cap) padding rows of a dummy
+ * graph, [row_cap, row_cap + nmax) ghost-slot rows; neighbours from the table `ell` (width W = 4 / 8 / 16) and its CSR tail
+ * (tail_ptr [row_cap + nmax + 1], tail_col [tail_cap]; both NULL: no tail).  The kernels rely on UNIT weights and a SYMMETRIC
+ * adjacency (triplet_stream.pack_arena admits nothing else).  1 <= B <= 8.  The forward is tsgnn_ell_rowsum_f32 +
+ * tsgnn_ragged_tn_direct_ro_f32 (n_real = row_cap, ghost_zero = 1). */
+/* host-only: 1 if the kernels take K clusters and F features: 4 <= K <= 128, 4 <= F <= 384, both multiples of 4 (what
+ * tsgnn_dense_pg_supported, the consumer of the result, takes) */
+int tsgnn_contract_cap_supported(int K, int F);
+/* host-only: the slab bound of the backward's grid, ceil(row_cap / 32) + B >= sum_b ceil(n_b / 32) for every batch of B graphs with
+ * sum_b n_b <= row_cap (each graph wastes less than one slab); TSGNN_EINVAL for row_cap < 0 or B outside 1..8 */
+int tsgnn_contract_cap_slabs(int64_t row_cap, int B);
+/* out[i] = sum_{j in N(i)} S[j] (K <= 128 floats, K % 4 == 0) for the real rows: the table's entries in order, then the tail's; rows
+ * [n_tot, row_cap + nmax) of out are STORED as zeros, whatever S holds there.  16-byte aligned rows. */
+int tsgnn_ell_rowsum_f32(const int* ell, int W, const int* tail_ptr, const int* tail_col, int64_t tail_cap, const int* graph_ptr, int B,
+                         int64_t row_cap, int nmax, const float* S, int64_t ldS, int K, float* out, int64_t ldo, tsgnn_stream_t stream);
+/* one launch: dZ_b = S_b dX'_b, dS_b = Z_b dX'_b^T + (AS)_b (dA'_b + dA'_b^T) on the real rows of graph b (dxo [B, K, F],
+ * dao [B, K, K]; d(AS) is never formed: A = A^T with unit weights), rows [n_tot, row_cap + nmax) of dZ and dS stored as zeros.
+ * ro_dout (nullable; [B, F], leading dimension ro_ldo) / ro_arg [B, F]: the max readout's gradient is added to dZ[ro_arg[b, c], c]
+ * where ro_arg names a real row of graph b (a ghost-row winner is dropped).  split: workgroups a slab's 32 x 32 tiles are dealt to
+ * (1..4; 0: the library's choice) — the result does not depend on it, bit for bit.  No atomics, one writer per word. */
+int tsgnn_contract_cap_bwd_f32(const float* S, int64_t ldS, const float* Z, int64_t ldZ, const float* AS, int64_t ldAS, const float* dxo,
+                               const float* dao, const int* graph_ptr, int B, int K, int F, int64_t row_cap, int nmax, float* dZ,
+                               int64_t lddZ, float* dS, int64_t lddS, const float* ro_dout, int64_t ro_ldo, const int* ro_arg, int split,
+                               tsgnn_stream_t stream);
+
 /* paired forms for two stacks that share batch and shapes (grid.y = 2; sage_stack._SageStackPair): tsgnn_slot_bn_fwd_f32 without
  * the readout-buffer clear, tsgnn_slot_post_bwd_f32 without a readout gradient, and the slab reduction of up to 8 sets described
  * in HOST memory, desc = [n, n x (ws, nslab, K, N, dw, db)] */

@@ -320,10 +320,73 @@ class _ContractRows(torch.autograd.Function):
         return dS, dZ, None, None
 
 
+class _ContractCap(torch.autograd.Function):
+    """_ContractRows on a CAPACITY-PADDED batch (ingest.CapacityBatch, written on the device by a stream's gather launch): no CSR
+    arrays, no host-side sizes, no host-built slab lists — the launches read ``graph_ptr`` on the device (csrc/contract_cap.hip).
+    Forward: the neighbour table's row sum + the products' launch (readout inside); backward: ONE launch, the transposed SpMM of the
+    CSR route folded into it (unit weights, symmetric adjacency: what ``pack_arena`` admits).  Same outputs as _ContractRows.
+    Padding and ghost rows of dS and dZ come back as exact zeros."""
+
+    @staticmethod
+    def forward(ctx, S, Z, g, ro=None):
+        S, Z = S.contiguous(), Z.contiguous()
+        K, F, R, dev = int(S.size(1)), int(Z.size(1)), g.total_rows, S.device
+        if S.size(0) != R or Z.size(0) != R or g.n_ghost != g.nmax:
+            raise RuntimeError("the capacity-batch contraction takes every row of the batch, ghost-slot rows included")
+        L = nat.lib()
+        if not (L.tsgnn_contract_cap_supported(K, F) and L.tsgnn_ragged_tn_direct_supported(K, int(g.nmax)) and 1 <= g.B <= 8):
+            raise RuntimeError("DiffPool contraction on a capacity-padded batch: K = %d clusters, F = %d features, %d graphs of up to "
+                               "%d nodes lie outside the kernels' range (tsgnn_contract_cap_supported)" % (K, F, g.B, g.nmax))
+        ctx.ro = None
+        out = arg = None
+        if ro is not None:                                     # the max readout of Z, as in _ContractRows
+            ghost_unused, into, ghost_zero = ro
+            if not (ghost_unused and ghost_zero):
+                raise RuntimeError("the capacity-batch contraction makes the readout of MASKED embeddings only (ghost rows zero)")
+            ctx.ro = (True,)
+            ctx.set_materialize_grads(False)
+            out = into.t if into is not None else _f32(g.B, F, device=dev)
+            arg = torch.empty(g.B, F, dtype=torch.int32, device=dev)
+        ell, ell_w, tail = g._ell
+        tp, tc = tail if tail is not None else (None, None)
+        AS = _f32(R, K, device=dev)
+        nat.call("ell_rowsum_f32", ell, ell_w, tp, tc, tc.numel() if tc is not None else 0, g.graph_ptr, g.B, g.n_rows, g.nmax, S, S.stride(0),
+                 K, AS, AS.stride(0))
+        xo, ao = _f32(g.B, K, F, device=dev), _f32(g.B, K, K, device=dev)
+        # (its ghost row is n_real + size: row_cap + size here, a zero row of the masked embeddings)
+        nat.call("ragged_tn_direct_ro_f32", S, S.stride(0), K, g.graph_ptr, g.B, Z, Z.stride(0), F, xo, AS, AS.stride(0), K, ao,
+                 out, out.stride(0) if out is not None else 0, arg, g.nmax, g.n_rows, 1)
+        ctx.g = g
+        if ro is not None:
+            ctx.save_for_backward(S, Z, AS, arg)
+            return xo, ao, out
+        ctx.save_for_backward(S, Z, AS)
+        return xo, ao
+
+    @staticmethod
+    def backward(ctx, dxo, dao, dro=None):
+        S, Z, AS = ctx.saved_tensors[:3]
+        arg = ctx.saved_tensors[3] if ctx.ro is not None else None
+        g = ctx.g
+        R, K, F = S.size(0), S.size(1), Z.size(1)
+        if ctx.ro is not None and (dxo is None or dao is None):   # (materialisation is off for the readout's sake)
+            dxo = dxo if dxo is not None else torch.zeros(g.B, K, F, device=S.device)
+            dao = dao if dao is not None else torch.zeros(g.B, K, K, device=S.device)
+        dxo, dao = dxo.contiguous(), dao.contiguous()
+        dZ, dS = _f32(R, F, device=S.device), _f32(R, K, device=S.device)
+        dro_ = mp.readout_dout_in_place(dro) if dro is not None else None
+        nat.call("contract_cap_bwd_f32", S, S.stride(0), Z, Z.stride(0), AS, AS.stride(0), dxo, dao, g.graph_ptr, g.B, K, F, g.n_rows, g.nmax,
+                 dZ, dZ.stride(0), dS, dS.stride(0), dro_, dro_.stride(0) if dro_ is not None else 0, arg if dro_ is not None else None, 0)
+        return dS, dZ, None, None
+
+
 def diffpool_contract_rows(S, Z, g, readout=None):
     """readout = (ghost_unused, column block or None, ghost_zero): the max readout of Z (encoders.py:353) as a third output of the
     same node — made by the products' launch when the padded slots' rows are known to be zeros (ghost_zero: masked embeddings) or
-    absent, and its gradient is added inside the launch that produces dZ (ghost_unused: the caller discards the ghost rows' share)"""
+    absent, and its gradient is added inside the launch that produces dZ (ghost_unused: the caller discards the ghost rows' share).
+    A batch without CSR arrays (capacity-padded, neighbour table only) takes _ContractCap; every other batch _ContractRows."""
+    if g.rowptr is None and getattr(g, "_ell", None) is not None:
+        return _ContractCap.apply(S, Z, g, readout)
     return _ContractRows.apply(S, Z, g, readout)
 
 

@@ -1,0 +1,105 @@
+"""DiffPool triplet stream: a NEW triplet at every replay of ONE hipGraph for ``triplet.tripletnet`` over a ``SoftPoolingGcnEncoder``
+(train_triplet.py --method=soft-assign: ``sampler()`` -> ``TNet(a, p, n)`` -> margin loss -> clip -> Adam, thousands of times per epoch).
+
+``triplet_stream.TripletStream`` does this for the GraphSage family; the DiffPool encoder was refused there because of one node, the
+level-0 contraction X' = S^T Z, A' = S^T A S (``diffpool._ContractRows``), which read CSR arrays, host-side sizes and host-built slab
+lists.  On the capacity-padded batch the gather launch writes, ``diffpool._ContractCap`` (csrc/contract_cap.hip) takes its place; the
+rest of the step already has a fixed shape: both level-0 stacks run as the fused per-graph node on the batch with all of its
+ghost-slot rows, the pooled levels are [3, K, .] (``dense_stack_pg``), the tail is ``triplet._TripletTail``.
+
+The arena carries ONE feature table: a dataset whose ``assign_feats`` differ from ``feats`` is refused (``ValueError``)."""
+import numpy as np
+import torch
+
+from . import _native as nat
+from .triplet_stream import ArenaStream, _graph_dict, check_schedule, pack_arena, schedule_of  # noqa: F401  (the stream's vocabulary)
+
+EAGER = "; use the eager drop-in, tripletnet.forward(a, p, n)"
+# SoftPoolingGcnEncoder.forward derives `masked` from ``batch_num_nodes is not None`` and make_batch ignores the argument for a
+# GraphBatch: the node counts themselves live on the device (graph_ptr), this stands in for them
+SIZES_ON_DEVICE = ("the node counts are in graph_ptr, on the device",)
+
+
+def check_assign_feats(graphs):
+    """ValueError naming the first graph whose ``assign_feats`` differ from ``feats`` on its real rows [:n]"""
+    for i, obj in enumerate(graphs):
+        d = _graph_dict(obj)
+        if "assign_feats" not in d or d["assign_feats"] is d["feats"]:
+            continue
+        n = int(d["num_nodes"])
+        fa, ff = np.asarray(d["assign_feats"]), np.asarray(d["feats"])
+        if fa.ndim != 2 or fa.shape[1:] != ff.shape[1:] or fa.shape[0] < n or not np.array_equal(fa[:n], ff[:n]):
+            raise ValueError("graph %d: assign_feats differ from feats on [:num_nodes] (the arena carries one feature table)%s" % (i, EAGER))
+
+
+class TripletStream(ArenaStream):
+    """``net``: a ``triplet.tripletnet`` over a ``SoftPoolingGcnEncoder`` with concat and bn, num_pooling >= 1 and
+    final_dim == "output_dim"; ``graphs``: the dataset's graph objects.  The interface of ``triplet_stream.TripletStream``: ``load``,
+    ``gather``, ``embed``, ``loss(criterion, target)``, ``position``, ``len``.  TypeError (ending in the eager drop-in) for a model
+    whose stacks do not run as the fused per-graph nodes on the gathered batch or whose first contraction lies outside
+    ``tsgnn_contract_cap_supported``."""
+
+    NAME = "diffpool_stream.TripletStream"
+
+    def __init__(self, net, graphs, nmax=None, max_steps=None):
+        graphs = list(graphs)
+        model = getattr(net, "model", None)
+        if not self._model_ok(model):
+            raise TypeError("%s %s%s" % (self.NAME, self._TAKES, EAGER))
+        check_assign_feats(graphs)
+        super().__init__(model, graphs, 3, nmax, max_steps, name=self.NAME, takes=self._TAKES, eager=EAGER)
+        self.net = net
+        self._warm_up_schedule()
+
+    _TAKES = "takes a tripletnet over a SoftPoolingGcnEncoder with concat and bn, num_pooling >= 1 and final_dim == \"output_dim\""
+
+    def _model_ok(self, model):
+        from .dense_encoders import SoftPoolingGcnEncoder
+        return (type(model) is SoftPoolingGcnEncoder and bool(model.concat) and bool(model.bn) and int(model.num_pooling) >= 1
+                and model.final_dim == "output_dim")
+
+    def _stacks_ok(self, model):
+        """both level-0 stacks as the fused per-graph node on the gathered batch, every pooled stack on dense_stack_pg, the first
+        contraction inside tsgnn_contract_cap_supported; a TypeError of its own names what failed"""
+        from . import dense_encoders as E
+        from . import dense_stack_pg, sage_stack
+
+        def refuse(what):
+            raise TypeError("%s: %s%s" % (self.NAME, what, EAGER))
+        if not (E.FUSED_STACK and E.PER_GRAPH_STACK and E.PER_GRAPH_DENSE and E.READOUT_PASS and E.READOUT_IN_CONTRACT and E.READOUT_COLUMNS):
+            refuse("a fused route of dense_encoders is switched off")
+        g, x, fin = self.g, self.x, self.arena.fin
+        emb = [model.conv_first] + list(model.conv_block) + [model.conv_last]
+        asg = [model.assign_conv_first_modules[0]] + list(model.assign_conv_block_modules[0]) + [model.assign_conv_last_modules[0]]
+        for what, convs in (("embedding", emb), ("assignment", asg)):
+            if convs[0].input_dim != fin or not sage_stack.eligible(g, convs, model.bn, x) or g.row_graph is None or g.n_ghost != g.nmax:
+                refuse("the level-0 %s stack does not run as the fused per-graph node on this dataset" % what)
+        F = int(model.pred_input_dim)
+        lib = nat.lib()
+        for i in range(model.num_pooling):
+            K = int(model.assign_pred_modules[i].out_features)
+            if K < 1:
+                refuse("pooling level %d has no clusters" % i)
+            if i == 0 and not (lib.tsgnn_contract_cap_supported(K, F) and lib.tsgnn_ragged_tn_direct_supported(K, int(g.nmax))):
+                refuse("the first contraction (K = %d clusters, F = %d features) lies outside tsgnn_contract_cap_supported" % (K, F))
+            xk = torch.empty(3, K, F, dtype=torch.float32, device=self.device)
+            ak = torch.empty(3, K, K, dtype=torch.float32, device=self.device)
+            stacks = [[model.conv_first_after_pool[i]] + list(model.conv_block_after_pool[i]) + [model.conv_last_after_pool[i]]]
+            if i + 1 < model.num_pooling:
+                stacks.append([model.assign_conv_first_modules[i + 1]] + list(model.assign_conv_block_modules[i + 1])
+                              + [model.assign_conv_last_modules[i + 1]])
+            if not all(dense_stack_pg.eligible(xk, ak, convs) for convs in stacks):
+                refuse("a stack of pooled level %d (K = %d) lies outside dense_stack_pg" % (i, K))
+        return True
+
+    def embed(self):
+        """gather + the model on the gathered batch -> (dist_p, dist_n, embed_a, embed_p, embed_n), as ``tripletnet.forward`` returns"""
+        self.gather()
+        return self.net._embed(self.x, self.g, SIZES_ON_DEVICE, self.x)
+
+    def loss(self, criterion, target):
+        """-> callable for ``GraphedStep``: gather launch + ``net._embed`` on the gathered batch + ``criterion(dist_p, dist_n, target)``"""
+        def step():
+            out = self.embed()
+            return criterion(out[0], out[1], target)
+        return step

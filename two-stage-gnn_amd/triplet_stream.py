@@ -146,14 +146,14 @@ class ArenaStream:
     ``TripletStream``; 1: the anchor of the 2stg+ post-training step, ``post_train.PostTrainStream``): the eligibility checks, the arena
     upload, the capacity-padded batch the gather launch writes, the schedule buffer with cursor and ticket counter, ``load``,
     ``gather`` and ``position``.  ``model``: a plain ``GcnEncoderGraph`` with concat and bn whose conv stack runs as the fused
-    per-graph node on the gathered batch; anything else is a TypeError that ends in ``eager`` (where the caller's eager drop-in is)."""
+    per-graph node on the gathered batch; anything else is a TypeError that ends in ``eager`` (where the caller's eager drop-in is).
+    The two checks are methods (``_model_ok``, ``_stacks_ok``): a stream for another encoder family (``diffpool_stream.TripletStream``)
+    overrides them."""
 
     def __init__(self, model, graphs, batch, nmax=None, max_steps=None, name="ArenaStream", takes="takes a GcnEncoderGraph with concat and bn",
                  eager=""):
-        from . import sage_stack
-        from .dense_encoders import GcnEncoderGraph
         from .ingest import CapacityBatch, ELL_W
-        if type(model) is not GcnEncoderGraph or not model.concat or not model.bn:
+        if not self._model_ok(model):
             raise TypeError("%s %s%s" % (name, takes, eager))
         dev = next(model.parameters()).device
         if dev.type != "cuda":
@@ -170,8 +170,7 @@ class ArenaStream:
         # (edge_cap: the compact staging layout's CSR columns, which this path never fills)
         self.batch = CapacityBatch(self.B, ar.nmax, self.row_cap, 4, ar.fin, dev, ghost_slots=ghost, tail_cap=self.tail_cap)
         self.g, self.x = self.batch.g, self.batch.x
-        convs = [model.conv_first] + list(model.conv_block) + [model.conv_last]
-        if not sage_stack.eligible(self.g, convs, model.bn, self.x) or convs[0].output_dim > 256 or model.conv_first.input_dim != ar.fin:
+        if not self._stacks_ok(model):
             raise TypeError("%s: the model's conv stack does not run as the fused per-graph node on this dataset%s" % (name, eager))
         self.records = torch.from_numpy(ar.records).to(dev)
         self.buf = torch.from_numpy(ar.buf).to(dev)
@@ -181,6 +180,18 @@ class ArenaStream:
         # int32 [HEAD + max_steps * B]: {cursor, T} as two int64, the ticket counter (+ 3 spare words), then the schedule
         self._sched = self._host = None
         self.T = 0
+
+    def _model_ok(self, model):
+        """the model check, before anything is packed (a subclass for another encoder family overrides both checks)"""
+        from .dense_encoders import GcnEncoderGraph
+        return type(model) is GcnEncoderGraph and bool(model.concat) and bool(model.bn)
+
+    def _stacks_ok(self, model):
+        """... and on the gathered batch (self.g, self.x, self.arena exist): do the model's stacks run as the fused per-graph node?"""
+        from . import sage_stack
+        convs = [model.conv_first] + list(model.conv_block) + [model.conv_last]
+        return bool(sage_stack.eligible(self.g, convs, model.bn, self.x) and convs[0].output_dim <= 256
+                    and model.conv_first.input_dim == self.arena.fin)
 
     def _warm_up_schedule(self):
         """with ``max_steps``: the one-entry schedule of graph 0, so that a ``GraphedStep`` can be built before the first epoch's exists"""
