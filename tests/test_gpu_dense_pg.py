@@ -160,7 +160,7 @@ def _pooled_run(m, x, adj, G, flag):
     """the pooled-level embedding stack of m on (x, adj) with per-graph statistics -> (out, dx, dadj, parameter gradients, trace)"""
     from two_stage_gnn_amd import dense_encoders as E
     nat = _nat()
-    convs = [m.conv_first_after_pool[0]] + list(m.conv_block_after_pool[0]) + [m.conv_last_after_pool[0]]
+    convs = m.conv_stack(1)
     params = [p for c in convs for p in (c.weight, c.bias)]
     xg, ag = x.clone().requires_grad_(True), adj.clone().requires_grad_(True)
     old, m.per_graph_bn, nat.trace = E.PER_GRAPH_DENSE, True, []
@@ -215,7 +215,7 @@ def test_node_writes_weight_gradients_into_the_flat_bucket():
     from two_stage_gnn_amd.data_parallel import FlatTrainer
     B, K, L = 3, 20, 3
     m = _encoder(80, 12, L)
-    convs = torch.nn.ModuleList([m.conv_first_after_pool[0]] + list(m.conv_block_after_pool[0]) + [m.conv_last_after_pool[0]])
+    convs = torch.nn.ModuleList(m.conv_stack(1))
     gen = torch.Generator().manual_seed(9)
     x = torch.randn(B, K, m.pred_input_dim, generator=gen).cuda().requires_grad_(True)
     adj = (torch.rand(B, K, K, generator=gen) * 0.9 + 0.1).cuda().requires_grad_(True)

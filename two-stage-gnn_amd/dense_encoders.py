@@ -44,16 +44,62 @@ def _batch_from_dense(adj, sizes, layout):
 
 
 FUSED_HEAD = True              # the two chained nn.Linear after the readout as one HIP launch (+1 backward)
-FUSED_DENSE_POST = True       # pooled DiffPool levels: transform + normalise + ReLU + slot BN as one node
 FUSED_DENSE_STACK = True    # pooled DiffPool levels: the whole GCN stack as one autograd node (dense_stack.py)
-READOUT_PASS = True            # DiffPool: readout backward and the contraction's gradient of the same embeddings in one pass
-READOUT_IN_CONTRACT = os.environ.get("TSGNN_READOUT_IN_CONTRACT", "1") != "0"   # ... and inside the contraction's node (no backward pass of its own)
+# DiffPool: the readout of embeddings that a contraction reads too is made inside the contraction's node (no backward pass of its own);
+# off: by a node of its own that passes the embeddings through, so that one backward pass sums both gradients (mp._ReadoutMax)
+READOUT_IN_CONTRACT = os.environ.get("TSGNN_READOUT_IN_CONTRACT", "1") != "0"
 SOFTMAX_IN_CONTRACT = os.environ.get("TSGNN_SOFTMAX_IN_CONTRACT", "1") != "0"   # pooled levels: the assignment softmax inside the contraction's launches
 READOUT_COLUMNS = os.environ.get("TSGNN_READOUT_COLUMNS", "1") != "0"   # DiffPool: the levels' readouts written into one buffer (no cat)
 FUSED_STACK = True             # GcnEncoderGraph: run the conv stack as one fused autograd node when it qualifies
 PER_GRAPH_STACK = os.environ.get("TSGNN_PER_GRAPH_STACK", "1") != "0"   # ... also with per-graph statistics (the triplet step)
 PER_GRAPH_DENSE = os.environ.get("TSGNN_PER_GRAPH_DENSE", "1") != "0"   # pooled DiffPool levels under per-graph statistics: one launch per layer (dense_stack_pg.py)
 DENSE_ADJ_MAX_NODES = 128      # at or below this many nodes per graph a dense batched MFMA product is used
+
+
+def _stack(first, block, last):
+    """a conv stack as a list, input layer first (the encoders keep the reference's conv_first / conv_block / conv_last attributes)"""
+    return [first, *block, last]
+
+
+def per_graph_node_ok(g, convs):
+    """may the fused GraphSage node (sage_stack) run the stack ``convs`` under per-graph statistics on batch ``g``?"""
+    # Its row-local launches take a batch whose rows know their graph and which carries every ghost-slot row.  The width bound is the
+    # one of tsgnn_row_post_bwd_f32 / tsgnn_row_post_nodes_bwd_f32 (csrc/bn_readout.hip refuses F > 256); sage_stack.eligible, which
+    # every caller asks as well, stops at 128 columns, so the bound never decides.  (The PER_GRAPH_STACK switch is for the encoders to
+    # consult: a stream's batch either has the shape or not.)
+    return g.row_graph is not None and g.n_ghost == g.nmax and convs[0].output_dim <= 256
+
+
+class _Readouts:
+    """the max readouts of an encoder's layers or levels, asked for one by one (``of``) in the order of their concatenation"""
+    # (READOUT_COLUMNS: they land in their column blocks of ONE buffer: no torch.cat launch, no slice copies backwards)
+
+    def __init__(self, B, width, device, concat):
+        self.concat = concat
+        self.cols = mp.ReadoutColumns(B, width, device) if (concat and READOUT_COLUMNS) else None
+        self.out = []
+
+    def of(self, x, g, shared=False, ghost_unused=False):
+        """the readout of the rows ``x`` on batch ``g`` -> (x, request): the one place that picks the readout's route"""
+        # shared: a DiffPool contraction reads x next.  Then the contraction makes the readout, as a third output of its node, and adds
+        # the readout's gradient inside the launch that produces the embeddings' gradient (diffpool._ContractRows / _ContractDense):
+        # request = (into,), the column block to hand it, and the caller appends what comes back to `out`.  READOUT_IN_CONTRACT off:
+        # a pass-through node makes it here, the contraction reads the x returned.  Not shared: a plain readout_max.  request is None
+        # wherever the readout is made here.
+        into = self.cols and self.cols.take(x.size(1))
+        if shared and READOUT_IN_CONTRACT:
+            return x, (into,)
+        if shared:
+            ro, x = mp.readout_max_pass(x, g, ghost_unused=ghost_unused, into=into)
+        else:
+            ro = mp.readout_max(x, g, into=into)
+        self.out.append(ro)
+        return x, None
+
+    def joined(self):
+        if not self.concat:
+            return self.out[-1]
+        return self.cols.join(self.out) if self.cols is not None else torch.cat(self.out, dim=1)
 
 
 class _DenseBmm(torch.autograd.Function):
@@ -226,28 +272,37 @@ class GcnEncoderGraph(nn.Module):
         """ReLU then (optionally) slot batch-norm: encoders.py:179-181."""
         return mp.bn_slots(v, g, relu=True, bn=self.bn, per_graph=self.per_graph_bn)
 
+    def conv_stack(self, level=0):
+        """the conv stack as a list; ``level`` >= 1, in the encoders that pool: the embedding stack after the level-th pooling"""
+        if level == 0:
+            return _stack(self.conv_first, self.conv_block, self.conv_last)
+        i = level - 1
+        return _stack(self.conv_first_after_pool[i], self.conv_block_after_pool[i], self.conv_last_after_pool[i])
+
     def gcn_forward_rows(self, x, g, conv_first, conv_block, conv_last, mask_ghost=False, per_graph_stack=False):
-        """gcn_forward (encoders.py:140-167) on rows: per-layer outputs concatenated on the feature axis;
-        ``mask_ghost`` = multiply by the embedding mask (zeroes every ghost row).  ``per_graph_stack``: the caller allows the fused
-        node under per-graph statistics too (masked output on a batch with its full set of ghost-slot rows)."""
+        """gcn_forward (encoders.py:140-167) on rows, with the reference's signature; see ``_gcn_rows``"""
+        return self._gcn_rows(x, g, _stack(conv_first, conv_block, conv_last), mask_ghost, per_graph_stack)
+
+    def _gcn_rows(self, x, g, convs, mask_ghost=False, per_graph_stack=False):
+        """per-layer outputs of the stack ``convs`` concatenated on the feature axis"""
+        # mask_ghost = multiply by the embedding mask (zeroes every ghost row).  per_graph_stack: the caller allows the fused node under
+        # per-graph statistics too.
         # the fused node: slot statistics, or — where the caller allows it — the per-graph statistics of the triplet step (masked
         # output on a batch with its full set of ghost-slot rows: the row-local launches tsgnn_row_ln_fwd_f32 /
         # tsgnn_row_post_nodes_bwd_f32 in place of the slot ones)
         per_graph = bool(self.per_graph_bn)
         allowed = (mask_ghost or not g.n_ghost) if not per_graph else \
-            (per_graph_stack and PER_GRAPH_STACK and mask_ghost and g.row_graph is not None and g.n_ghost == g.nmax)
+            (per_graph_stack and PER_GRAPH_STACK and mask_ghost and per_graph_node_ok(g, convs))
         if FUSED_STACK and allowed:
             from . import sage_stack
-            convs = [conv_first] + list(conv_block) + [conv_last]
             if sage_stack.eligible(g, convs, self.bn, x):
                 with sage_stack.per_graph_stats(per_graph):
                     return sage_stack.sage_stack_nodes(x, g, convs, mask_ghost)     # one autograd node, layers write into the cat
-        x = self._post(conv_first.forward_rows(x, g), g)
-        x_all = [x]
-        for conv in conv_block:
+        x_all = []
+        for conv in convs[:-1]:
             x = self._post(conv.forward_rows(x, g), g)
             x_all.append(x)
-        x_all.append(conv_last.forward_rows(x, g))
+        x_all.append(convs[-1].forward_rows(x, g))
         t = torch.cat(x_all, dim=1)
         if mask_ghost and g.n_ghost:
             t = mp.mask_ghost_rows(t, g)
@@ -256,69 +311,58 @@ class GcnEncoderGraph(nn.Module):
     def readouts_rows(self, x, g):
         """encoders.py:177-205 up to the concatenated max readout."""
         from . import sage_stack
-        convs = [self.conv_first] + list(self.conv_block) + [self.conv_last]
+        convs = self.conv_stack()
         if self.concat and FUSED_STACK and sage_stack.eligible(g, convs, self.bn, x) and \
-                (not self.per_graph_bn or (PER_GRAPH_STACK and g.row_graph is not None and g.n_ghost == g.nmax
-                                           and convs[0].output_dim <= 256)):
+                (not self.per_graph_bn or (PER_GRAPH_STACK and per_graph_node_ok(g, convs))):
             # (per-graph statistics, the triplet step: the same node with the row-local batch-norm launches, sage_stack.per_graph_stats)
             with sage_stack.per_graph_stats(self.per_graph_bn):
                 return sage_stack.sage_stack_readouts(x, g, convs)
-        # the layers' readouts land in their column blocks of ONE buffer (no torch.cat launch, no slice copies backwards)
-        cols = mp.ReadoutColumns(g.B, self.pred_input_dim, x.device) if (self.concat and READOUT_COLUMNS) else None
-        x = self._post(self.conv_first.forward_rows(x, g), g)
-        out_all = [mp.readout_max(x, g, into=cols and cols.take(x.size(1)))]
-        for conv in self.conv_block:
+        ro = _Readouts(g.B, self.pred_input_dim, x.device, self.concat)
+        for conv in convs[:-1]:
             x = self._post(conv.forward_rows(x, g), g)
-            out_all.append(mp.readout_max(x, g, into=cols and cols.take(x.size(1))))
-        x = self.conv_last.forward_rows(x, g)
-        out_all.append(mp.readout_max(x, g, into=cols and cols.take(x.size(1))))
-        if not self.concat:
-            return out_all[-1]
-        return cols.join(out_all) if cols is not None else torch.cat(out_all, dim=1)
+            ro.of(x, g)
+        ro.of(convs[-1].forward_rows(x, g), g)
+        return ro.joined()
+
+    def _head(self):
+        """final_dim -> (lin1, lin2, swap): the two chained nn.Linear after the readout; swap: (lin2's output, lin1's) is returned"""
+        if self.final_dim == "pretrain":          # 2stg+
+            return self.map_model, self.map2_model, True
+        if self.final_dim != "output_dim":        # original
+            return self.pre_pred_model, self.pred_model, False
+        return None                               # 2stg: the first output IS the readout
+
+    def _ordered(self, vec, y):
+        """(lin1's output, lin2's) in the order ``final_dim`` returns them"""
+        return (y, vec) if self._head()[2] else (vec, y)
 
     def _head_linears(self):
-        """the two chained nn.Linear after the readout (None for the 2stg setting, whose first output IS the readout)"""
-        if getattr(self, "_defer_map", False):
-            return None
-        if self.final_dim == "pretrain":
-            return self.map_model, self.map2_model
-        if self.final_dim != "output_dim":
-            return self.pre_pred_model, self.pred_model
-        return None
+        """the two chained nn.Linear after the readout (None where ``forward`` applies none: 2stg, and triplet.tripletnet's _defer_map)"""
+        head = None if getattr(self, "_defer_map", False) else self._head()
+        return head and head[:2]
 
     def _heads(self, output):
-        if self.final_dim == "pretrain":          # 2stg+
-            if getattr(self, "_defer_map", False):
-                return None, output                 # (tripletnet reads the embedding only; it applies map_model to `output` itself)
-            if FUSED_HEAD and mp.head2_ok(output, self.map_model, self.map2_model):
-                out, ypred = mp.head2(output, self.map_model, self.map2_model)
-                return ypred, out
-            out = self.map_model(output)
-            return self.map2_model(out), out
-        if self.final_dim != "output_dim":        # original
-            if FUSED_HEAD and mp.head2_ok(output, self.pre_pred_model, self.pred_model):
-                return mp.head2(output, self.pre_pred_model, self.pred_model)
-            vec = self.pre_pred_model(output)
-            return vec, self.pred_model(vec)
-        if getattr(self, "_defer_map", False):    # triplet.tripletnet applies map_model itself (embeddings + distances, one launch)
-            return output, None
-        return output, self.map_model(output)     # 2stg
-
-    def _stack_fusable(self, x, g):
-        from . import sage_stack
-        convs = [self.conv_first] + list(self.conv_block) + [self.conv_last]
-        ok = self.concat and FUSED_STACK and not self.per_graph_bn and sage_stack.eligible(g, convs, self.bn, x)
-        return ok, convs
+        head, defer = self._head(), getattr(self, "_defer_map", False)
+        if head is None:             # (triplet.tripletnet applies map_model itself: embeddings + distances, one launch)
+            return output, (None if defer else self.map_model(output))
+        if defer and self.final_dim == "pretrain":
+            return None, output      # (tripletnet reads the embedding only; it applies map_model to `output` itself)
+        lin1, lin2, _ = head
+        if FUSED_HEAD and mp.head2_ok(output, lin1, lin2):
+            return self._ordered(*mp.head2(output, lin1, lin2))
+        vec = lin1(output)
+        return self._ordered(vec, lin2(vec))
 
     def forward(self, x, adj, batch_num_nodes=None, **kwargs):
         x, g = self.make_batch(x, adj, batch_num_nodes)
-        if FUSED_HEAD and type(self) is GcnEncoderGraph and self.final_dim != "output_dim":
+        head = self._head()
+        if FUSED_HEAD and type(self) is GcnEncoderGraph and head is not None:
             from . import sage_stack
-            ok, convs = self._stack_fusable(x, g)
-            lin1, lin2 = (self.map_model, self.map2_model) if self.final_dim == "pretrain" else (self.pre_pred_model, self.pred_model)
-            if ok and sage_stack.head_ok(g, convs, lin1, lin2):
-                vec, y = sage_stack.sage_stack_head(x, g, convs, lin1, lin2)       # stack + readout tail + head: one autograd node
-                return (y, vec) if self.final_dim == "pretrain" else (vec, y)
+            convs, (lin1, lin2, _) = self.conv_stack(), head
+            if self.concat and FUSED_STACK and not self.per_graph_bn and sage_stack.eligible(g, convs, self.bn, x) \
+                    and sage_stack.head_ok(g, convs, lin1, lin2):
+                # stack + readout tail + head: one autograd node
+                return self._ordered(*sage_stack.sage_stack_head(x, g, convs, lin1, lin2))
         return self._heads(self.readouts_rows(x, g))
 
     def loss(self, pred, label, type="softmax"):
@@ -384,163 +428,154 @@ class SoftPoolingGcnEncoder(GcnEncoderGraph):
         self._init_convs()
         self.to(_default_device())
 
-    # gcn_forward on dense pooled tensors x[B,K,F], adj[B,K,K] (encoders.py:378-380; mask is None there)
+    def assign_stack(self, level):
+        """the assignment conv stack of ``level`` (0: the input graphs) as a list; its embedding stack is ``conv_stack(level)``"""
+        return _stack(self.assign_conv_first_modules[level], self.assign_conv_block_modules[level], self.assign_conv_last_modules[level])
+
+    def assign_linear(self, level):
+        """the nn.Linear from the level's assignment stack output to its cluster logits"""
+        return self.assign_pred_modules[level]
+
     def gcn_forward_dense(self, x, adj, conv_first, conv_block, conv_last):
+        """gcn_forward on dense pooled tensors x[B,K,F], adj[B,K,K] (encoders.py:378-380; mask is None there) -> (cat, uniform batch)"""
+        return self._gcn_dense(x, adj, _stack(conv_first, conv_block, conv_last))
+
+    def _gcn_dense(self, x, adj, convs):
         B, K, _ = x.shape
         g = GraphBatch.uniform(B, K, x.device)
         if self.per_graph_bn and self.bn and PER_GRAPH_DENSE:
             # per-graph statistics (the triplet step, stage two): every post-op is row-local, a layer is one launch of independent tiles
             from . import dense_stack_pg
-            convs = [conv_first] + list(conv_block) + [conv_last]
             if dense_stack_pg.eligible(x, adj, convs):
                 return dense_stack_pg.dense_gcn_stack_pg(x, adj, convs), g
         if FUSED_DENSE_STACK:
             from . import dense_stack
-            convs = [conv_first] + list(conv_block) + [conv_last]
             if dense_stack.eligible(x, adj, g, convs, self.bn, self.per_graph_bn):
                 return dense_stack.dense_gcn_stack(x, adj, g, convs), g       # one autograd node, layers write into the cat
-
-        def post(v):
-            return mp.bn_slots(v.reshape(B * K, -1), g, relu=True, bn=self.bn, per_graph=self.per_graph_bn).reshape(B, K, -1)
 
         def hidden(conv, x):
             # transform + normalise + ReLU + slot BN as one node (one launch for the BN forward, one for the backward of
             # BN + ReLU + normalise) when the fused slot kernels take the shape; else the composed ops
-            if (FUSED_DENSE_POST and self.bn and not self.per_graph_bn and conv.normalize_embedding and conv.dropout <= 0.001
+            if (self.bn and not self.per_graph_bn and conv.normalize_embedding and conv.dropout <= 0.001
                     and mp.linear_norm_bn_ok(g, conv.output_dim)):
                 y = _DenseBmm.apply(adj.float(), x.float(), conv.add_self)
                 return mp.linear_norm_bn(y.reshape(B * K, -1), conv.weight, conv.bias, g).reshape(B, K, -1)
-            return post(conv(x, adj))
-        x = hidden(conv_first, x)
-        x_all = [x]
-        for conv in conv_block:
+            v = conv(x, adj).reshape(B * K, -1)
+            return mp.bn_slots(v, g, relu=True, bn=self.bn, per_graph=self.per_graph_bn).reshape(B, K, -1)
+        x_all = []
+        for conv in convs[:-1]:
             x = hidden(conv, x)
             x_all.append(x)
-        x_all.append(conv_last(x, adj))
+        x_all.append(convs[-1](x, adj))
         return torch.cat(x_all, dim=2), g
 
     def _level0_pair_ok(self, x, x_a, g, masked):
-        """both first-level stacks take the fused stack path (gcn_forward_rows) and may share launches"""
+        """both first-level stacks take the fused stack path (_gcn_rows) and may share launches"""
         from . import sage_stack
         if not (FUSED_STACK and sage_stack.PAIR_LAUNCHES and not self.per_graph_bn and (masked or not g.n_ghost)):
             return False
-        for xx, convs in ((x, [self.conv_first] + list(self.conv_block) + [self.conv_last]),
-                          (x_a, [self.assign_conv_first_modules[0]] + list(self.assign_conv_block_modules[0])
-                           + [self.assign_conv_last_modules[0]])):
-            if not (torch.is_tensor(xx) and xx.dim() == 2 and sage_stack.eligible(g, convs, self.bn, xx)):
-                return False
-        return True
+        return all(torch.is_tensor(xx) and xx.dim() == 2 and sage_stack.eligible(g, convs, self.bn, xx)
+                   for xx, convs in ((x, self.conv_stack()), (x_a, self.assign_stack(0))))
 
-    def forward(self, x, adj, batch_num_nodes, **kwargs):
-        from . import diffpool as dp
-        from .pyg import linear
-        x_a = kwargs["assign_x"] if "assign_x" in kwargs else x
+    # ------------------------------------------------------------------ the stages of forward
+    def _inputs(self, x, adj, batch_num_nodes, x_a):
+        """1. -> (rows of x, rows of the assignment input x_a, batch, masked): packed rows (+ghost reps) if masked, else padded"""
         same_input = x_a is x
-        masked = batch_num_nodes is not None
-        x, g = self.make_batch(x, adj, batch_num_nodes)             # packed rows (+ghost reps) if masked, else padded
-        x_a = x if same_input else (mp.pack_rows(x_a, g, (x_a.size(2) + 3) // 4 * 4 if g.layout == "packed" else None)
-                                    if x_a.dim() == 3 else x_a)
-        a0 = None
+        x, g = self.make_batch(x, adj, batch_num_nodes)
+        if same_input:
+            x_a = x
+        elif x_a.dim() == 3:
+            x_a = mp.pack_rows(x_a, g, (x_a.size(2) + 3) // 4 * 4 if g.layout == "packed" else None)
+        return x, x_a, g, batch_num_nodes is not None
+
+    def _level0_stacks(self, x, x_a, g, masked):
+        """2. -> (embeddings, the first assignment stack's output: None without pooling), rows on the input batch"""
         if self.num_pooling > 0 and self._level0_pair_ok(x, x_a, g, masked):
             # the embedding and the first assignment stack run on the same graph: one autograd node whose launches are shared
             # pairwise (sage_stack._SageStackPair) — each kernel of one stack alone fills about half of the CUs
             from . import sage_stack
-            emb, a0 = sage_stack.sage_stack_nodes_pair(
-                x, x_a, g, [self.conv_first] + list(self.conv_block) + [self.conv_last],
-                [self.assign_conv_first_modules[0]] + list(self.assign_conv_block_modules[0]) + [self.assign_conv_last_modules[0]],
-                masked)
-        else:
-            emb = self.gcn_forward_rows(x, g, self.conv_first, self.conv_block, self.conv_last, mask_ghost=masked, per_graph_stack=True)
-        # the levels' readouts land in their column blocks of ONE buffer (no torch.cat launch; mp.ReadoutColumns)
-        cols = mp.ReadoutColumns(g.B, emb.size(1) * (self.num_pooling + 1), emb.device) if (self.concat and READOUT_COLUMNS) else None
-        ro_next = None              # (READOUT_IN_CONTRACT) the readout of this level's embeddings, made by the contraction that reads them
-        if self.num_pooling > 0 and READOUT_PASS and READOUT_IN_CONTRACT:
-            # the embeddings feed the readout AND the contraction: the readout is a third output of the contraction's node and its
-            # gradient is added inside the launch that produces the embeddings' gradient (diffpool._ContractRows / _ContractDense);
-            # masked: the ghost rows of `emb` are constants (zeros), their gradient is discarded by the stack's backward
-            ro_next = (bool(masked and g.n_ghost), cols and cols.take(emb.size(1)), bool(masked and g.n_ghost))
-            out_all = []
-        elif self.num_pooling > 0 and READOUT_PASS:
-            # ... or a node of its own that passes the embeddings through: one backward pass sums both gradients (mp._ReadoutMax)
-            ro, emb = mp.readout_max_pass(emb, g, ghost_unused=bool(masked and g.n_ghost), into=cols and cols.take(emb.size(1)))
-            out_all = [ro]
-        else:
-            out_all = [mp.readout_max(emb, g, into=cols and cols.take(emb.size(1)))]
-        dense_x = dense_adj = None
-        a_next = None
-        for i in range(self.num_pooling):
-            lin = self.assign_pred_modules[i]
-            if i == 0:
-                a = a0 if a0 is not None else self.gcn_forward_rows(
-                    x_a, g, self.assign_conv_first_modules[0], self.assign_conv_block_modules[0],
-                    self.assign_conv_last_modules[0], mask_ghost=masked, per_graph_stack=True)
-                s = dp.row_softmax(mp.linear_oi(a, lin.weight, lin.bias),                    # encoders.py:369
-                                   g.n_rows if (masked and g.n_ghost) else None)              # :371 (ghost rows -> 0)
-                self.assign_tensor = s
-                self._link_graph, self._link_masked = g, masked
-                if ro_next is not None:
-                    dense_x, dense_adj, ro = dp.diffpool_contract_rows(s, emb, g, readout=ro_next)     # :374-375 (+ :353)
-                    out_all.append(ro)
-                    ro_next = None
-                else:
-                    dense_x, dense_adj = dp.diffpool_contract_rows(s, emb, g)                 # :374-375
-            else:
-                if a_next is not None:
-                    a = a_next                  # came out of the launch that ran this level's embedding stack
-                else:
-                    a, _ = self.gcn_forward_dense(dense_x, dense_adj, self.assign_conv_first_modules[i],
-                                                  self.assign_conv_block_modules[i], self.assign_conv_last_modules[i])
-                Bq, Kq, Cq = a.shape
-                logits = mp.linear_oi(a.reshape(Bq * Kq, Cq), lin.weight, lin.bias)
-                if SOFTMAX_IN_CONTRACT:
-                    # nn.Softmax(dim=-1) (:369) on the operand the contraction stages anyway, its backward in the backward launch
-                    res = dp.diffpool_contract_dense(logits.reshape(Bq, Kq, -1), emb_dense, dense_adj, readout=ro_next, softmax=True)
-                    s = res[-1]
-                else:
-                    s = dp.row_softmax(logits).reshape(Bq, Kq, -1)
-                    res = dp.diffpool_contract_dense(s, emb_dense, dense_adj, readout=ro_next)
-                self.assign_tensor = s
-                dense_x, dense_adj = res[0], res[1]
-                if ro_next is not None:
-                    out_all.append(res[2])
-                    ro_next = None
-            a_next = None
-            emb_convs = [self.conv_first_after_pool[i]] + list(self.conv_block_after_pool[i]) + [self.conv_last_after_pool[i]]
-            if i + 1 < self.num_pooling and FUSED_DENSE_STACK and self.bn and not self.per_graph_bn:
-                # this level's embedding stack and the NEXT level's assignment stack read the same (x, adjacency): one launch
-                # forward and one backward for both (dense_stack.py)
-                from . import dense_stack
-                asg_convs = ([self.assign_conv_first_modules[i + 1]] + list(self.assign_conv_block_modules[i + 1])
-                             + [self.assign_conv_last_modules[i + 1]])
-                if dense_stack.ONE_LAUNCH and dense_stack.one_launch_ok(dense_x, dense_adj, [emb_convs, asg_convs]):
-                    # (the next contraction reads the adjacency through this node's pass-through: one gradient sum, inside
-                    # the stacks' backward launch)
-                    emb_dense, a_next, dense_adj = dense_stack.dense_gcn_stacks(dense_x, dense_adj, [emb_convs, asg_convs],
-                                                                                adj_pass=True)
-                    gd = GraphBatch.uniform(dense_x.size(0), dense_x.size(1), dense_x.device)
-            if a_next is None:
-                emb_dense, gd = self.gcn_forward_dense(dense_x, dense_adj, self.conv_first_after_pool[i],
-                                                       self.conv_block_after_pool[i], self.conv_last_after_pool[i])
-            Bq, Kq, Cq = emb_dense.shape
-            if i + 1 < self.num_pooling and READOUT_PASS and READOUT_IN_CONTRACT:
-                ro_next = (gd, cols and cols.take(Cq))         # made by the next level's contraction
-            elif i + 1 < self.num_pooling and READOUT_PASS:
-                ro, e2 = mp.readout_max_pass(emb_dense.reshape(Bq * Kq, Cq), gd, into=cols and cols.take(Cq))
-                emb_dense = e2.reshape(Bq, Kq, Cq)
-                out_all.append(ro)
-            else:
-                lins = self._head_linears()
-                if (i + 1 == self.num_pooling and self.concat and lins is not None and FUSED_HEAD and gd.n_ghost == 0
-                        and mp.head2_tail_ok(cols, emb_dense, Kq, *lins)):
-                    # the LAST level's readout fills its column block inside the head's own launches (mp._Head2Tail)
-                    a, b = mp.head2_tail(cols, out_all, emb_dense.reshape(Bq * Kq, Cq), Kq, *lins)
-                    return (b, a) if self.final_dim == "pretrain" else (a, b)
-                out_all.append(mp.readout_max(emb_dense.reshape(Bq * Kq, Cq), gd, into=cols and cols.take(Cq)))
-        if not self.concat:
-            output = out_all[-1]
-        else:
-            output = cols.join(out_all) if cols is not None else torch.cat(out_all, dim=1)
-        return self._heads(output)
+            return sage_stack.sage_stack_nodes_pair(x, x_a, g, self.conv_stack(), self.assign_stack(0), masked)
+        emb = self._gcn_rows(x, g, self.conv_stack(), mask_ghost=masked, per_graph_stack=True)
+        if self.num_pooling == 0:
+            return emb, None
+        return emb, self._gcn_rows(x_a, g, self.assign_stack(0), mask_ghost=masked, per_graph_stack=True)
+
+    def _pool_rows(self, a, emb, g, masked, ro):
+        """3. at level 0: S = softmax(linear(a)) on the input batch's rows, X' = S^T Z, A' = S^T A S -> (X', A'); Z's readout -> ro"""
+        from . import diffpool as dp
+        ghost = bool(masked and g.n_ghost)
+        # masked: the ghost rows of `emb` are constants (zeros), their gradient is discarded by the stack's backward
+        emb, request = ro.of(emb, g, shared=True, ghost_unused=ghost)
+        lin = self.assign_linear(0)
+        s = dp.row_softmax(mp.linear_oi(a, lin.weight, lin.bias), g.n_rows if ghost else None)   # encoders.py:369, :371 (ghost rows -> 0)
+        self.assign_tensor = s
+        self._link_graph, self._link_masked = g, masked
+        res = dp.diffpool_contract_rows(s, emb, g, readout=request and (ghost, *request, ghost))   # :374-375 (+ :353, the readout)
+        ro.out.extend(res[2:])
+        return res[0], res[1]
+
+    def _pool_dense(self, level, x, adj, emb, a, ro):
+        """3. at a pooled level >= 1 with inputs (x, adj) and embeddings emb [B, K, C]; a: the assignment stack's output, if made"""
+        from . import diffpool as dp
+        B, K, C = emb.shape
+        rows, g = self._level_rows(emb)
+        rows, request = ro.of(rows, g, shared=True)
+        if a is None:
+            a, _ = self._gcn_dense(x, adj, self.assign_stack(level))
+        lin = self.assign_linear(level)
+        logits = mp.linear_oi(a.reshape(B * K, -1), lin.weight, lin.bias)
+        # SOFTMAX_IN_CONTRACT: nn.Softmax(dim=-1) (:369) on the operand the contraction stages anyway, its backward in the backward
+        # launch; S comes back as the last output
+        s = (logits if SOFTMAX_IN_CONTRACT else dp.row_softmax(logits)).reshape(B, K, -1)
+        res = dp.diffpool_contract_dense(s, rows.reshape(B, K, C), adj, readout=request and (g, *request), softmax=SOFTMAX_IN_CONTRACT)
+        self.assign_tensor = res[-1] if SOFTMAX_IN_CONTRACT else s
+        if request is not None:
+            ro.out.append(res[2])
+        return res[0], res[1]
+
+    def _pooled_stacks(self, level, x, adj):
+        """3. the embedding stack of ``level`` >= 1 on (x, adj) -> (embeddings [B, K, C], assignment stack's output or None, adj)"""
+        # (the assignment stack's output where one launch serves both stacks; adj: what the level's contraction is to read)
+        convs = self.conv_stack(level)
+        if level < self.num_pooling and FUSED_DENSE_STACK and self.bn and not self.per_graph_bn:
+            # the embedding stack and the level's assignment stack read the same (x, adjacency): one launch forward and one
+            # backward for both (dense_stack.py)
+            from . import dense_stack
+            stacks = [convs, self.assign_stack(level)]
+            if dense_stack.ONE_LAUNCH and dense_stack.one_launch_ok(x, adj, stacks):
+                # (the contraction reads the adjacency through this node's pass-through: one gradient sum, inside the stacks'
+                # backward launch)
+                return dense_stack.dense_gcn_stacks(x, adj, stacks, adj_pass=True)
+        return self._gcn_dense(x, adj, convs)[0], None, adj
+
+    @staticmethod
+    def _level_rows(emb):
+        """a pooled level's embeddings [B, K, C] -> (rows [B * K, C], their uniform batch)"""
+        B, K, C = emb.shape
+        return emb.reshape(B * K, C), GraphBatch.uniform(B, K, emb.device)
+
+    def _levels_head(self, ro, rows, g):
+        """4. + 5. the last level's readout (its embeddings: ``rows`` on ``g``) and the head on the levels' readouts"""
+        lins = self._head_linears()
+        if (self.num_pooling > 0 and self.concat and lins is not None and FUSED_HEAD and g.n_ghost == 0
+                and mp.head2_tail_ok(ro.cols, rows, g.nmax, *lins)):
+            # the LAST level's readout fills its column block inside the head's own launches (mp._Head2Tail)
+            return self._ordered(*mp.head2_tail(ro.cols, ro.out, rows, g.nmax, *lins))
+        ro.of(rows, g)
+        return self._heads(ro.joined())
+
+    def forward(self, x, adj, batch_num_nodes, **kwargs):
+        x, x_a, g, masked = self._inputs(x, adj, batch_num_nodes, kwargs.get("assign_x", x))
+        emb, a = self._level0_stacks(x, x_a, g, masked)
+        ro = _Readouts(g.B, emb.size(1) * (self.num_pooling + 1), emb.device, self.concat)
+        if self.num_pooling == 0:
+            return self._levels_head(ro, emb, g)
+        x_l, adj_l = self._pool_rows(a, emb, g, masked, ro)
+        for level in range(1, self.num_pooling + 1):
+            emb, a, adj_l = self._pooled_stacks(level, x_l, adj_l)
+            if level < self.num_pooling:
+                x_l, adj_l = self._pool_dense(level, x_l, adj_l, emb, a, ro)
+        return self._levels_head(ro, *self._level_rows(emb))
 
     linkpred_clamp = 1.0        # the reference clamps pred_adj with an UNINITIALISED tensor (encoders.py:424); see DESIGN.md
 

@@ -66,28 +66,23 @@ class TripletStream(ArenaStream):
 
         def refuse(what):
             raise TypeError("%s: %s%s" % (self.NAME, what, EAGER))
-        if not (E.FUSED_STACK and E.PER_GRAPH_STACK and E.PER_GRAPH_DENSE and E.READOUT_PASS and E.READOUT_IN_CONTRACT and E.READOUT_COLUMNS):
+        if not (E.FUSED_STACK and E.PER_GRAPH_STACK and E.PER_GRAPH_DENSE and E.READOUT_IN_CONTRACT and E.READOUT_COLUMNS):
             refuse("a fused route of dense_encoders is switched off")
         g, x, fin = self.g, self.x, self.arena.fin
-        emb = [model.conv_first] + list(model.conv_block) + [model.conv_last]
-        asg = [model.assign_conv_first_modules[0]] + list(model.assign_conv_block_modules[0]) + [model.assign_conv_last_modules[0]]
-        for what, convs in (("embedding", emb), ("assignment", asg)):
-            if convs[0].input_dim != fin or not sage_stack.eligible(g, convs, model.bn, x) or g.row_graph is None or g.n_ghost != g.nmax:
+        for what, convs in (("embedding", model.conv_stack()), ("assignment", model.assign_stack(0))):
+            if convs[0].input_dim != fin or not sage_stack.eligible(g, convs, model.bn, x) or not E.per_graph_node_ok(g, convs):
                 refuse("the level-0 %s stack does not run as the fused per-graph node on this dataset" % what)
         F = int(model.pred_input_dim)
         lib = nat.lib()
         for i in range(model.num_pooling):
-            K = int(model.assign_pred_modules[i].out_features)
+            K = int(model.assign_linear(i).out_features)
             if K < 1:
                 refuse("pooling level %d has no clusters" % i)
             if i == 0 and not (lib.tsgnn_contract_cap_supported(K, F) and lib.tsgnn_ragged_tn_direct_supported(K, int(g.nmax))):
                 refuse("the first contraction (K = %d clusters, F = %d features) lies outside tsgnn_contract_cap_supported" % (K, F))
             xk = torch.empty(3, K, F, dtype=torch.float32, device=self.device)
             ak = torch.empty(3, K, K, dtype=torch.float32, device=self.device)
-            stacks = [[model.conv_first_after_pool[i]] + list(model.conv_block_after_pool[i]) + [model.conv_last_after_pool[i]]]
-            if i + 1 < model.num_pooling:
-                stacks.append([model.assign_conv_first_modules[i + 1]] + list(model.assign_conv_block_modules[i + 1])
-                              + [model.assign_conv_last_modules[i + 1]])
+            stacks = [model.conv_stack(i + 1)] + ([model.assign_stack(i + 1)] if i + 1 < model.num_pooling else [])
             if not all(dense_stack_pg.eligible(xk, ak, convs) for convs in stacks):
                 refuse("a stack of pooled level %d (K = %d) lies outside dense_stack_pg" % (i, K))
         return True

@@ -60,7 +60,7 @@ class WavePoolingGcnEncoder(E.GcnEncoderGraph):
         self.to(E._default_device())
 
     def _stack(self, x, g, convs, masked, per_graph_stack=False):
-        emb = self.gcn_forward_rows(x, g, convs[0], convs[1], convs[2], mask_ghost=masked, per_graph_stack=per_graph_stack)
+        emb = self._gcn_rows(x, g, convs, mask_ghost=masked, per_graph_stack=per_graph_stack)
         return emb if self.concat else emb[:, emb.size(1) - self.embedding_dim:]
 
     def forward(self, x, adj, adj_pooled_list=None, batch_num_nodes=None, batch_num_nodes_list=None, pool_matrices_dic=None,
@@ -79,7 +79,7 @@ class WavePoolingGcnEncoder(E.GcnEncoderGraph):
         if x.dim() == 3:
             x = mp.pack_rows(x, g, (x.size(2) + 3) // 4 * 4)
         # level 0: always masked; under per-graph statistics (eigen_triplet) it may still run as the fused node
-        emb = self._stack(x, g, (self.conv_first, self.conv_block, self.conv_last), True, per_graph_stack=True)
+        emb = self._stack(x, g, self.conv_stack(), True, per_graph_stack=True)
         C = emb.size(1)
         head_in = self.pred_model[0].in_features if isinstance(self.pred_model, nn.Sequential) else self.pred_model.in_features
         cols = mp.ReadoutColumns(g.B, head_in, emb.device) if self.concat else None
@@ -94,8 +94,7 @@ class WavePoolingGcnEncoder(E.GcnEncoderGraph):
             else:
                 xp = ep.eigen_pool(emb, g, eb.levels[i], ghost_mode)
             g = eb.levels[i].g
-            emb = self._stack(xp, g, (self.conv_first_after_pool[i], self.conv_block_after_pool[i], self.conv_last_after_pool[i]),
-                              bool(self.mask))
+            emb = self._stack(xp, g, self.conv_stack(i + 1), bool(self.mask))
             ghost_mode = 1 if self.mask else 2
         want_ro = L == 0 or bool(self.con_final) or Jf == 0
         if Jf > 0:

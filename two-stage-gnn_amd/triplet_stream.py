@@ -188,10 +188,10 @@ class ArenaStream:
 
     def _stacks_ok(self, model):
         """... and on the gathered batch (self.g, self.x, self.arena exist): do the model's stacks run as the fused per-graph node?"""
-        from . import sage_stack
-        convs = [model.conv_first] + list(model.conv_block) + [model.conv_last]
-        return bool(sage_stack.eligible(self.g, convs, model.bn, self.x) and convs[0].output_dim <= 256
-                    and model.conv_first.input_dim == self.arena.fin)
+        from . import dense_encoders as E, sage_stack
+        convs = model.conv_stack()
+        return bool(sage_stack.eligible(self.g, convs, model.bn, self.x) and E.per_graph_node_ok(self.g, convs)
+                    and convs[0].input_dim == self.arena.fin)
 
     def _warm_up_schedule(self):
         """with ``max_steps``: the one-entry schedule of graph 0, so that a ``GraphedStep`` can be built before the first epoch's exists"""
