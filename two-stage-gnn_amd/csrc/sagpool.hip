@@ -1346,9 +1346,10 @@ int tsgnn_sag_supported(int F) { return (F > 0 && F % 4 == 0 && F <= 256) ? 1 : 
 int tsgnn_sag_pool_gather_f32(const float* y, int64_t ldy, const float* score, const int* perm, const int* new_id,
                               const int* rowptr, const int* col, int64_t K, int F, int relu_in, float* xp, int64_t ldo, int* cnt,
                               tsgnn_stream_t stream) {
-  if (K < 0 || !score || !perm || !new_id || !rowptr || !cnt || ((y == nullptr) != (xp == nullptr))) return TSGNN_EINVAL;
+  if (K < 0 || !score || !perm || !new_id || !rowptr || !cnt || ((y == nullptr) != (xp == nullptr)) || (y && (ldy < F || ldo < F)))
+    return TSGNN_EINVAL;
   if (!tsgnn_sag_supported(F)) return TSGNN_EUNSUPPORTED;
-  if (y && (ldy % 4 || ldo % 4 || !aligned16(y) || !aligned16(xp) || ldy < F || ldo < F)) return TSGNN_EUNSUPPORTED;
+  if (y && (ldy % 4 || ldo % 4 || !aligned16(y) || !aligned16(xp))) return TSGNN_EUNSUPPORTED;
   if (K == 0) return TSGNN_OK;
   SAG_DISPATCH(F, (sag_pool_gather<G><<<(unsigned)ceil_div64(K, 256 / G), 256, 0, stream>>>(y, ldy, score, perm, new_id, rowptr, col, K,
                                                                                             F, relu_in, xp, ldo, cnt)));
@@ -1433,7 +1434,9 @@ int tsgnn_sag_pool_bwd_f32(const float* y, int64_t ldy, const float* score, cons
                            const int* graph_ptr_new, const int* arg, const float* dxp, int64_t lddxp, const float* dread,
                            int64_t lddr, int64_t N, int F, int relu_in, float* dyb, int64_t lddy, float* dscore,
                            tsgnn_stream_t stream) {
-  if (N < 0 || !y || !score || !new_id || !row_graph_new || !graph_ptr_new || !arg || !dread || !dyb || !dscore) return TSGNN_EINVAL;
+  if (N < 0 || !y || !score || !new_id || !row_graph_new || !graph_ptr_new || !arg || !dread || !dyb || !dscore || ldy < F || lddy < F ||
+      lddr < 2 * F || (dxp && lddxp < F))
+    return TSGNN_EINVAL;
   if (!tsgnn_sag_supported(F) || ldy % 4 || lddy % 4 || lddr % 4 || (dxp && (lddxp % 4 || !aligned16(dxp))) || !aligned16(y) ||
       !aligned16(dyb) || !aligned16(dread) || !aligned16(arg))
     return TSGNN_EUNSUPPORTED;
@@ -1454,8 +1457,9 @@ int tsgnn_sag_pool_graph_bwd_f32(const float* y, int64_t ldy, const float* score
                                  tsgnn_stream_t stream) {
   if (dagg_next && (dxp || !rowptr_n || !rowend_n || !col_n || !dinv_n || !self_w_n || lddagg < F)) return TSGNN_EINVAL;
   if (dagg_next && (lddagg % 4 || !aligned16(dagg_next))) return TSGNN_EUNSUPPORTED;
-  if (!y || !score || !new_id || !graph_ptr || !graph_ptr_new || !arg || !dread || !rowptr || !dinv || !self_w || !w_s || !du || !part ||
-      ((dws == nullptr) != (dbs == nullptr)) || B <= 0 || max_seg < 0)
+  if (!y || !score || !new_id || !graph_ptr || !graph_ptr_new || !arg || !dread || !rowptr || !col || !dinv || !self_w || !w_s || !du ||
+      !part || ((dws == nullptr) != (dbs == nullptr)) || B <= 0 || max_seg < 0 || ldy < F || lddu < F || lddr < 2 * F ||
+      (dxp && lddxp < F))
     return TSGNN_EINVAL;
   if (!tsgnn_sag_supported(F) || max_seg > PG_MAX_NODES || ldy % 4 || lddu % 4 || lddr % 4 || (dxp && (lddxp % 4 || !aligned16(dxp))) ||
       !aligned16(y) || !aligned16(du) || !aligned16(dread) || !aligned16(arg) || !aligned16(w_s) || !aligned16(part))
@@ -1510,7 +1514,8 @@ int tsgnn_sag_du_blocks(int64_t N, int F) {
 int tsgnn_sag_du_f32(const int* rowptr, const int* rowend, const int* col, const float* dinv, const float* self_w, const float* dscore, const float* y,
                      int64_t ldy, const float* w_s, float* dyb, int64_t lddy, int64_t N, int F, float* part, float* dws, float* dbs,
                      tsgnn_stream_t stream) {
-  if (N <= 0 || !rowptr || !dinv || !self_w || !dscore || !y || !w_s || !dyb || !part || !dws || !dbs) return TSGNN_EINVAL;
+  if (N <= 0 || !rowptr || !dinv || !self_w || !dscore || !y || !w_s || !dyb || !part || !dws || !dbs || ldy < F || lddy < F)
+    return TSGNN_EINVAL;
   if (!tsgnn_sag_supported(F) || ldy % 4 || lddy % 4 || !aligned16(y) || !aligned16(dyb) || !aligned16(w_s) || !aligned16(part))
     return TSGNN_EUNSUPPORTED;
   const unsigned nb = (unsigned)tsgnn_sag_du_blocks(N, F);
