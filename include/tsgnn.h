@@ -186,6 +186,25 @@ int tsgnn_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int
                              int32_t* row_graph, int32_t* row_slot, int32_t* ell, int32_t* tail_ptr, int32_t* tail_col,
                              int32_t* ell_slots, int32_t* tail_slots, float* x, int64_t ldx, int32_t* ids_out, tsgnn_stream_t stream);
 
+/* The SAGPool family's gather launch (sag_stream.hip; host side: sag_stream.py): schedule entry number `cursor` of an epoch's
+ * triplets [T, 3] -> what sag_stack's node reads of the three graphs as one batch, padded to capacities.  Cursor, T and the ticket
+ * counter as tsgnn_triplet_gather_f32 (the same [HEAD | schedule] buffer); always three graphs per entry.
+ * Inputs: records int32[n_graphs][8] = (n, nnz, first row, first entry, index, 0, 0, 0); arena int32[arena_words] with the sections
+ *           rowptr (graph g's n + 1 graph-local row pointers start at first row + g) and col at the given word offsets (each a
+ *           multiple of 4); feats [nodes][ldf]; need_rows / need_nnz: three times the arena's largest n / nnz.
+ * Outputs, rewritten by every launch: rowptr[row_cap + 1] (every entry from the batch's row count on = the batch's nnz: padding
+ * rows are empty), col[: nnz] (node ids offset per graph; entries past the batch's nnz are not touched), x [row_cap][ldx], ldx ==
+ * ldf (zero on padding rows), dinv / self_w [row_cap] = tsgnn_gcn_coef_f32's values on the batch rows, 0 / 0 on padding rows,
+ * graph_ptr int32[depth + 1][4]: level l's graph pointer, k_b = min(n_b, ceil(ratio * n_b)) in float32 applied l times (PyG's topk,
+ * sag_stack.SagPlan), ids_out[3].
+ * TSGNN_EINVAL without a launch: a null pointer, row_cap < need_rows or nnz_cap < need_nnz, depth outside 1..7, ratio outside (0, 1],
+ * sections out of order; TSGNN_EUNSUPPORTED without a launch: a buffer or a section off 16 bytes, ldf % 4, ldx != ldf, sizes past 2^31. */
+int tsgnn_sag_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t off_rowptr, int64_t off_col,
+                                 int64_t arena_words, const float* feats, int64_t ldf, int64_t need_rows, int64_t need_nnz,
+                                 const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket, int64_t row_cap,
+                                 int64_t nnz_cap, float ratio, int depth, int32_t* rowptr, int32_t* col, float* x, int64_t ldx,
+                                 float* dinv, float* self_w, int32_t* graph_ptr, int32_t* ids_out, tsgnn_stream_t stream);
+
 /* CSR transpose (A^T for dX = A^T dY); rows of the result sorted by column; src_e[p] = source entry */
 int tsgnn_csr_transpose(const int* rowptr, const int* col, const float* val, int64_t n_rows, int64_t n_cols,
                         int64_t nnz, int* rowptr_t, int* col_t, float* val_t, int* src_e, int* cnt_ws,
@@ -966,6 +985,25 @@ int tsgnn_sag_pool_graph_bwd_f32(const float* y, int64_t ldy, const float* score
                                  float* dws, float* dbs, const float* dagg_next, int64_t lddagg, const int* rowptr_n,
                                  const int* rowend_n, const int* col_n, const float* dinv_n, const float* self_w_n,
                                  tsgnn_stream_t stream);
+/* Capacity forms of the two launches above, for a batch whose row counts live on the device only (sag_stream.py: a new triplet per
+ * hipGraph replay).  The same kernel bodies on the B graphs, always as 1,024-thread workgroups; a few more workgroups of the same
+ * launch read graph_ptr_new[B] (forward) / graph_ptr[B] (backward) on the device and store +0 to the rows from there to the
+ * allocation's end: xp and agg_next [cap_rows_new][.] in the forward, du [cap_rows][.] in the backward (columns [0, F)).  The
+ * caller's allocations come from torch.empty, and those rows go on into the weight-gradient products, where 0 * NaN is NaN.
+ * cap_rows_new / cap_rows < 0 or max_seg < 1: TSGNN_EINVAL; everything else as the forms above. */
+int tsgnn_sag_pool_graph_cap_f32(const float* y, int64_t ldy, const int* rowptr, const int* rowend, const int* col, const float* dinv,
+                                 const float* self_w, const float* w_s, const float* b_s, const int* graph_ptr,
+                                 const int* graph_ptr_new, int B, int max_seg, int F, float* score, int* perm, int* new_id, float* xp,
+                                 int64_t ldo, int* cnt, float* out, int64_t ldout, int* arg, int accumulate, int* rowptr_new,
+                                 int* rowend_new, int* col_new, float* dinv_new, float* self_w_new, float* agg_next, int64_t ldagg,
+                                 int64_t cap_rows_new, tsgnn_stream_t stream);
+int tsgnn_sag_pool_graph_bwd_cap_f32(const float* y, int64_t ldy, const float* score, const int* new_id, const int* graph_ptr,
+                                     const int* graph_ptr_new, const int* arg, const float* dxp, int64_t lddxp, const float* dread,
+                                     int64_t lddr, const int* rowptr, const int* rowend, const int* col, const float* dinv,
+                                     const float* self_w, const float* w_s, int B, int max_seg, int F, float* du, int64_t lddu,
+                                     float* part, float* dws, float* dbs, const float* dagg_next, int64_t lddagg, const int* rowptr_n,
+                                     const int* rowend_n, const int* col_n, const float* dinv_n, const float* self_w_n,
+                                     int64_t cap_rows, tsgnn_stream_t stream);
 /* The GraphConv-scorer forms of the two per-graph level kernels (PyG SAGPooling's default GNN, unit edge weights, symmetric adjacency):
  *   score_i = w_rel . sum_{j in N(i)} relu(y_j) + w_root . relu(y_i) + b      (w_rel / b = gnn.lin_l.{weight, bias}, w_root = gnn.lin_r.weight;
  *                                                                             b nullable)

@@ -179,6 +179,16 @@ __device__ __forceinline__ float group_max(float v) {
   return v;
 }
 
+// (dinv, self_w) of PyG gcn_norm for one row of a unit-weight graph: deg entries, has_self = one of them is the row itself
+// (add_remaining_self_loops keeps an existing self loop).  ONE expression for tsgnn_gcn_coef_f32 and for the SAGPool stream's gather
+// launch (csrc/sag_stream.hip), so a streamed batch carries the bits the drop-in's coefficient launch gives.
+__device__ __forceinline__ void gcn_norm_coef(int deg, bool has_self, float& dinv, float& self_w) {
+  const float d = (float)deg + (has_self ? 0.f : 1.f);
+  const float di = 1.0f / sqrtf(d);
+  dinv = di;
+  self_w = has_self ? 0.f : di * di;
+}
+
 // ---------------------------------------------------------------- Philox4x32-10 (Salmon et al., SC'11), counter-based
 __device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
 #pragma unroll

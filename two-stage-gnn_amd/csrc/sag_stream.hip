@@ -1,0 +1,186 @@
+// SAGPool triplet stream: a NEW triplet every replay of one hipGraph (Code/sag/train_triplet.py:198-214: tripletsampler_tr.sampler() ->
+// TNet(a, p, n) -> margin loss -> Adam, once per optimiser step).  csrc/triplet_stream.hip does this for the GraphSage family; this
+// is the launch for sag_layers.Net.  The dataset lives on the device whole (the arena of sag_stream.pack_arena: per-graph records, one
+// int32 buffer of graph-local CSR rows, one feature table), the sampler's epoch is an index array [T, 3] behind {cursor, T}, and ONE
+// launch per step reads "entry number cursor" and writes what sag_stack's node reads of a batch, padded to capacities that do not
+// depend on the triplet:
+//   rowptr [row_cap + 1]     rows at or past n_tot are empty: every entry from n_tot on is the batch's nnz
+//   col [: nnz]              node ids offset by the graphs before
+//   x [row_cap][ldx]         feature rows, zero on padding rows
+//   dinv / self_w [row_cap]  tsgnn_gcn_coef_f32's values on the batch rows (gcn_norm_coef, common.h), 0 / 0 on padding rows
+//   gp [depth + 1][4]        the graph pointer of EVERY level: k_b = min(n_b, ceil(float32(ratio) * float32(n_b))) level after level,
+//                            what sag_stack.SagPlan computes on the host with np.float32
+//   ids_out [3]
+// Cursor and ticket counter: the protocol of csrc/triplet_stream.hip, on the same [HEAD | schedule] buffer.
+// One writer per word, plain vector stores (16 bytes wherever the destination's alignment is known: the feature rows, four rows'
+// row pointers and coefficients per store, a level's graph pointer; the columns land at a data-dependent offset and go out as
+// coalesced dwords), the ticket counter is the only atomic.
+#include "common.h"
+#include "../../include/tsgnn.h"
+
+namespace {
+
+constexpr int SS_B = 3;                   // a triplet
+constexpr int SS_REC = 8;                 // int32 words of a record: n, nnz, first row, first entry, index, 0, 0, 0
+constexpr int SS_MAX_DEPTH = 7;
+constexpr int SS_EG = 8;                  // lanes per row
+constexpr int SS_ROWS = 256 / SS_EG;      // rows per workgroup
+
+struct SagGatherArgs {
+  const int32_t* rec; int64_t n_graphs;
+  const int32_t *rowptr, *col;            // the arena's sections: graph g's n + 1 row pointers (graph-local) start at first row + g
+  const float* feats; int64_t ldf; int ld4;
+  const int32_t* sched; int64_t sched_cap; int64_t* state; unsigned* ticket;      // state = {cursor, T}
+  int64_t row_cap, nnz_cap; float ratio; int depth;
+  int32_t *rowptr_out, *col_out; float* x; int64_t ldx; float *dinv, *self_w; int32_t *gp, *ids_out;
+};
+
+// 8 lanes per row, 32 rows per workgroup; the four rows of a 32-lane group leave their row pointers and coefficients as one
+// 16-byte store each through the group's first lane.
+__global__ __launch_bounds__(256) void sag_triplet_gather_kernel(SagGatherArgs a) {
+  __shared__ int32_t rec_s[SS_B][SS_REC];
+  __shared__ long long cur_s;
+  const int tid = threadIdx.x;
+  if (tid < SS_B) {
+    // (agent-scope load: the word is stored by the last workgroup of the previous launch, never through this CU's scalar cache)
+    const long long cur = __hip_atomic_load(reinterpret_cast<long long*>(a.state), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    int64_t T = a.state[1];                                 // the loaded schedule's length: the host's word, kept inside the buffer
+    T = T < 1 ? 1 : (T > a.sched_cap ? a.sched_cap : T);
+    const int64_t c = (int64_t)((unsigned long long)cur % (unsigned long long)T);
+    int64_t id = a.sched[c * SS_B + tid];
+    id = id < 0 ? 0 : (id >= a.n_graphs ? a.n_graphs - 1 : id);      // (load() validated it; an index never leaves the records)
+    const int4 r0 = *reinterpret_cast<const int4*>(a.rec + id * SS_REC);
+    rec_s[tid][0] = r0.x; rec_s[tid][1] = r0.y; rec_s[tid][2] = r0.z; rec_s[tid][3] = r0.w;
+    rec_s[tid][4] = (int32_t)id;
+    if (tid == 0) cur_s = cur;
+  }
+  __syncthreads();
+  // Every workgroup has READ the cursor by now (its value went through LDS), so it may draw its ticket: the workgroup that draws the
+  // last one knows that all have, leaves the counter at zero for the next launch and advances the cursor.
+  if (tid == 0) {
+    const unsigned t = atomicAdd(a.ticket, 1u);
+    if (t == gridDim.x - 1) {
+      atomicExch(a.ticket, 0u);
+      __hip_atomic_store(reinterpret_cast<long long*>(a.state), cur_s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+  }
+
+  const int64_t r = (int64_t)blockIdx.x * SS_ROWS + (tid >> 3);
+  const int sub = tid & (SS_EG - 1);
+  // the graph whose rows hold r, and the batch's totals: one pass over the three records, no data-dependent branch
+  int n_tot = 0, e_tot = 0;
+  int b = SS_B, g0 = 0, eb = 0, row0 = 0, ent0 = 0, gid = 0;
+  for (int k = 0; k < SS_B; ++k) {
+    const int nk = rec_s[k][0], ek = rec_s[k][1];
+    const bool mine = r >= n_tot && r < (int64_t)n_tot + nk;
+    b = mine ? k : b;
+    g0 = mine ? n_tot : g0;
+    eb = mine ? e_tot : eb;
+    row0 = mine ? rec_s[k][2] : row0;
+    ent0 = mine ? rec_s[k][3] : ent0;
+    gid = mine ? rec_s[k][4] : gid;
+    n_tot += nk;
+    e_tot += ek;
+  }
+  if (blockIdx.x == 0) {                                    // the batch's own small arrays: one writer per word
+    if (tid <= a.depth) {                                   // level tid: the k chain applied tid times, then the prefix
+      int s[SS_B];
+      for (int k = 0; k < SS_B; ++k) s[k] = rec_s[k][0];
+      for (int l = 0; l < tid; ++l)
+        for (int k = 0; k < SS_B; ++k) {
+          const int kk = (int)ceilf(a.ratio * (float)s[k]);       // float32, as PyG's topk and SagPlan compute it
+          s[k] = kk < s[k] ? kk : s[k];
+        }
+      *reinterpret_cast<int4*>(a.gp + 4 * tid) = make_int4(0, s[0], s[0] + s[1], s[0] + s[1] + s[2]);
+    }
+    if (tid >= 32 && tid < 32 + SS_B) a.ids_out[tid - 32] = rec_s[tid - 32][4];
+    if (tid == 64) a.rowptr_out[a.row_cap] = e_tot;
+  }
+  const bool in_cap = r < a.row_cap;
+  const bool real = b < SS_B && in_cap;
+  const int lr = (int)(r - g0);
+  int e0 = 0, e1 = 0;
+  if (real) {
+    const int32_t* rp = a.rowptr + (int64_t)row0 + gid + lr;
+    e0 = rp[0]; e1 = rp[1];
+  }
+  bool has_self = false;
+  for (int e = e0 + sub; e < e1; e += SS_EG) {
+    const int c = a.col[(int64_t)ent0 + e];
+    has_self |= (c == lr);
+    const int64_t o = (int64_t)eb + e;
+    if (o < a.nnz_cap) a.col_out[o] = c + g0;
+  }
+  // (every lane of the wave is here: rows past row_cap only skip their stores)
+  const int lane = tid & 63;
+  has_self = ((unsigned)(__ballot(has_self) >> (lane & ~(SS_EG - 1))) & ((1u << SS_EG) - 1u)) != 0u;
+  float di = 0.f, sw = 0.f;
+  if (real) gcn_norm_coef(e1 - e0, has_self, di, sw);
+  const int rp_out = real ? eb + e0 : e_tot;
+  {
+    const int q0 = lane & ~31;                              // the 32-lane group's first lane: rows r .. r + 3 of a multiple of four
+    const int4 rp4 = make_int4(rp_out, __shfl(rp_out, q0 + 8, 64), __shfl(rp_out, q0 + 16, 64), __shfl(rp_out, q0 + 24, 64));
+    const float4 di4 = make_float4(di, __shfl(di, q0 + 8, 64), __shfl(di, q0 + 16, 64), __shfl(di, q0 + 24, 64));
+    const float4 sw4 = make_float4(sw, __shfl(sw, q0 + 8, 64), __shfl(sw, q0 + 16, 64), __shfl(sw, q0 + 24, 64));
+    if ((tid & 31) == 0 && in_cap) {
+      if (r + 3 < a.row_cap) {
+        *reinterpret_cast<int4*>(a.rowptr_out + r) = rp4;
+        *reinterpret_cast<float4*>(a.dinv + r) = di4;
+        *reinterpret_cast<float4*>(a.self_w + r) = sw4;
+      } else {                                              // the last rows of a capacity that is no multiple of four
+        const int rp_[4] = {rp4.x, rp4.y, rp4.z, rp4.w};
+        const float di_[4] = {di4.x, di4.y, di4.z, di4.w}, sw_[4] = {sw4.x, sw4.y, sw4.z, sw4.w};
+#pragma unroll
+        for (int u = 0; u < 4; ++u)
+          if (r + u < a.row_cap) {
+            a.rowptr_out[r + u] = rp_[u];
+            a.dinv[r + u] = di_[u];
+            a.self_w[r + u] = sw_[u];
+          }
+      }
+    }
+  }
+  if (in_cap) {
+    const float4* src = reinterpret_cast<const float4*>(a.feats + ((int64_t)row0 + lr) * a.ldf);
+    for (int c4 = sub; c4 < a.ld4; c4 += SS_EG) {
+      const float4 v = real ? src[c4] : make_float4(0.f, 0.f, 0.f, 0.f);
+      *reinterpret_cast<float4*>(a.x + r * a.ldx + 4 * c4) = v;
+    }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+/* see include/tsgnn.h */
+int tsgnn_sag_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t off_rowptr, int64_t off_col,
+                                 int64_t arena_words, const float* feats, int64_t ldf, int64_t need_rows, int64_t need_nnz,
+                                 const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket, int64_t row_cap,
+                                 int64_t nnz_cap, float ratio, int depth, int32_t* rowptr, int32_t* col, float* x, int64_t ldx,
+                                 float* dinv, float* self_w, int32_t* graph_ptr, int32_t* ids_out, tsgnn_stream_t stream) {
+  if (!records || !arena || !feats || !sched || !state || !ticket || !rowptr || !col || !x || !dinv || !self_w || !graph_ptr || !ids_out)
+    return TSGNN_EINVAL;
+  if (sched_cap <= 0 || n_graphs <= 0 || row_cap <= 0 || nnz_cap < 1 || ldf <= 0 || need_rows < 0 || need_nnz < 0 || depth < 1 ||
+      depth > SS_MAX_DEPTH || !(ratio > 0.f) || !(ratio <= 1.f))
+    return TSGNN_EINVAL;
+  // no schedule entry can overflow a slot: the capacities cover the arena's bounds (three times its largest n / nnz).  need_rows and
+  // need_nnz are the caller's word, as the arena is (see tsgnn_triplet_gather_f32)
+  if (row_cap < need_rows || nnz_cap < need_nnz) return TSGNN_EINVAL;
+  if (off_rowptr < 0 || off_col < off_rowptr || arena_words < off_col) return TSGNN_EINVAL;
+  if (row_cap >= ((int64_t)1 << 31) - SS_ROWS || nnz_cap >= ((int64_t)1 << 31) || sched_cap >= ((int64_t)1 << 31) / SS_B)
+    return TSGNN_EUNSUPPORTED;
+  if ((ldf % 4) || ldx != ldf || ((off_rowptr | off_col) & 3)) return TSGNN_EUNSUPPORTED;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(arena) | reinterpret_cast<uintptr_t>(feats) |
+                       reinterpret_cast<uintptr_t>(rowptr) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dinv) |
+                       reinterpret_cast<uintptr_t>(self_w) | reinterpret_cast<uintptr_t>(graph_ptr) | reinterpret_cast<uintptr_t>(state);
+  if (al & 15) return TSGNN_EUNSUPPORTED;
+  SagGatherArgs a{records, n_graphs, arena + off_rowptr, arena + off_col, feats, ldf, (int)(ldf / 4), sched, sched_cap, state, ticket,
+                  row_cap, nnz_cap, ratio, depth, rowptr, col, x, ldx, dinv, self_w, graph_ptr, ids_out};
+  TSGNN_KNAME("sag_triplet_gather_kernel");
+  sag_triplet_gather_kernel<<<(unsigned)ceil_div64(row_cap, SS_ROWS), 256, 0, stream>>>(a);
+  TSGNN_CHECK_LAUNCH();
+  return TSGNN_OK;
+}
+
+}  // extern "C"

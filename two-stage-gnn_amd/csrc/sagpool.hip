@@ -37,10 +37,10 @@ __global__ void gcn_coef_kernel(const int* __restrict__ rowptr, const int* __res
   const int e0 = rowptr[i], e1 = rowptr[i + 1];
   bool has_self = false;                                   // add_remaining_self_loops keeps an existing self loop
   for (int e = e0; e < e1; ++e) has_self |= (col[e] == (int)i);
-  const float d = (float)(e1 - e0) + (has_self ? 0.f : 1.f);
-  const float di = 1.0f / sqrtf(d);
+  float di, sw;
+  gcn_norm_coef(e1 - e0, has_self, di, sw);
   dinv[i] = di;
-  self_w[i] = has_self ? 0.f : di * di;
+  self_w[i] = sw;
 }
 
 struct PropArgs {
@@ -471,14 +471,40 @@ struct PoolGraphArgs {
   // with the filter: the NEXT level's aggregation A^' xp (nullable) — one launch less per level (gcn_propagate on the pooled rows)
   float* agg_next; int64_t ldagg;
   const float* w_root;                      // GC scorer only: lin_r's weight (w_s = lin_l's weight, b_s = its bias); dinv / self_w unused
+  // capacity form only (CAP): the batch fills rows [0, gp_new[cap_B]) of xp / agg_next, whose allocations have cap_rows rows; the
+  // workgroups beyond cap_B store zeros to the rows between
+  int cap_B; int64_t cap_rows;
 };
+
+// CAP: rows [first, cap) of a [cap][ld] array <- +0 over columns [0, F), 16-byte stores, shared word by word among the nblk padding
+// workgroups (first is read on the device: a capacity-padded batch's row count changes from replay to replay, its allocation does not)
+constexpr int PG_CAP_BLOCKS = 4;
+__device__ __forceinline__ void pg_zero_rows(float* __restrict__ p, int64_t ld, int F, int64_t first, int64_t cap, int blk, int nblk,
+                                             int tid, int bt) {
+  const int nvec = F >> 2;
+  first = first < 0 ? 0 : first;
+  const int64_t total = (cap - first) * nvec;
+  for (int64_t i = (int64_t)blk * bt + tid; i < total; i += (int64_t)nblk * bt) {
+    const int64_t r = first + i / nvec;
+    const int c = (int)(i % nvec);
+    *reinterpret_cast<float4*>(p + r * ld + 4 * c) = make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+}
 
 // BT threads per workgroup: 1,024 for graphs of up to 4,096 nodes, 256 when no graph of the batch exceeds 256 nodes (TU graphs:
 // four times the resident graphs per CU; at 8,192 IMDB-B graphs per launch 266 -> see profiles)
-template <int G, int BT, bool GC>
+template <int G, int BT, bool GC, bool CAP = false>
 __global__ __launch_bounds__(BT) void sag_pool_graph_kernel(PoolGraphArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long pg_smem[];
   const int b = blockIdx.x, tid = threadIdx.x;
+  if constexpr (CAP) {
+    if (b >= a.cap_B) {                                     // a padding workgroup: the rows no graph of this replay owns
+      const int64_t first = a.gp_new[a.cap_B];
+      pg_zero_rows(a.xp, a.ldo, a.F, first, a.cap_rows, b - a.cap_B, PG_CAP_BLOCKS, tid, BT);
+      if (a.agg_next != nullptr) pg_zero_rows(a.agg_next, a.ldagg, a.F, first, a.cap_rows, b - a.cap_B, PG_CAP_BLOCKS, tid, BT);
+      return;
+    }
+  }
   const int g0 = a.gp[b], n = a.gp[b + 1] - g0;
   const int k0 = a.gp_new[b], k = a.gp_new[b + 1] - k0;
   if (n <= 0) return;
@@ -949,10 +975,17 @@ struct PoolGraphBwdArgs {
   const float* dagg_next; int64_t lddagg;
   const int* rowptr_n; const int* rowend_n; const int* col_n; const float* dinv_n; const float* self_w_n;
   const float* w_root;                        // GC scorer only (w_s = w_rel); dinv / self_w unused
+  int cap_B; int64_t cap_rows;                // capacity form only (CAP): du has cap_rows rows, the batch fills [0, gp[cap_B])
 };
-template <int G, int BT, bool GC>
+template <int G, int BT, bool GC, bool CAP = false>
 __global__ __launch_bounds__(BT) void sag_pool_graph_bwd_kernel(PoolGraphBwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float pb_smem[];
+  if constexpr (CAP) {
+    if ((int)blockIdx.x >= a.cap_B) {                       // a padding workgroup: du of the rows no graph of this replay owns
+      pg_zero_rows(a.du, a.lddu, a.F, a.gp[a.cap_B], a.cap_rows, (int)blockIdx.x - a.cap_B, PG_CAP_BLOCKS, threadIdx.x, BT);
+      return;
+    }
+  }
   constexpr int NG = BT / G;
   constexpr int EG = 8;                       // lanes per row of the adjacency walk (B), as in the forward kernel
   const int b = blockIdx.x, tid = threadIdx.x;
@@ -1199,6 +1232,23 @@ void launch_pool_graph_g(const PoolGraphArgs& a, int B, int max_seg, size_t lds,
   }
 }
 
+// the capacity form: B graph workgroups + PG_CAP_BLOCKS padding workgroups (a triplet's three graphs: always the 1,024-thread shape)
+template <int G>
+void launch_pool_graph_cap_g(const PoolGraphArgs& a, int B, size_t lds, hipStream_t stream) {
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sag_pool_graph_kernel<G, PG_THREADS, false, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  sag_pool_graph_kernel<G, PG_THREADS, false, true><<<(unsigned)(B + PG_CAP_BLOCKS), PG_THREADS, lds, stream>>>(a);
+}
+inline void launch_pool_graph_cap(const PoolGraphArgs& a, int B, size_t lds, hipStream_t stream) {
+  switch (group_of(a.F)) {
+    case 8: launch_pool_graph_cap_g<8>(a, B, lds, stream); break;
+    case 16: launch_pool_graph_cap_g<16>(a, B, lds, stream); break;
+    case 32: launch_pool_graph_cap_g<32>(a, B, lds, stream); break;
+    default: launch_pool_graph_cap_g<64>(a, B, lds, stream); break;
+  }
+}
+
 template <bool GC>
 void launch_pool_graph(const PoolGraphArgs& a, int B, int max_seg, size_t lds, hipStream_t stream) {
   switch (group_of(a.F)) {
@@ -1222,6 +1272,23 @@ void launch_pool_graph_bwd_g(const PoolGraphBwdArgs& a, int B, int max_seg, hipS
       (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sag_pool_graph_bwd_kernel<G, PG_THREADS, GC>),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     sag_pool_graph_bwd_kernel<G, PG_THREADS, GC><<<(unsigned)B, PG_THREADS, lds, stream>>>(a);
+  }
+}
+
+template <int G>
+void launch_pool_graph_bwd_cap_g(const PoolGraphBwdArgs& a, int B, int max_seg, hipStream_t stream) {
+  const size_t lds = sizeof(float) * (5 * (size_t)((max_seg + 3) & ~3) + (size_t)(PG_THREADS / G) * a.F);
+  if (lds > 64 * 1024)
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sag_pool_graph_bwd_kernel<G, PG_THREADS, false, true>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  sag_pool_graph_bwd_kernel<G, PG_THREADS, false, true><<<(unsigned)(B + PG_CAP_BLOCKS), PG_THREADS, lds, stream>>>(a);
+}
+inline void launch_pool_graph_bwd_cap(const PoolGraphBwdArgs& a, int B, int max_seg, hipStream_t stream) {
+  switch (group_of(a.F)) {
+    case 8: launch_pool_graph_bwd_cap_g<8>(a, B, max_seg, stream); break;
+    case 16: launch_pool_graph_bwd_cap_g<16>(a, B, max_seg, stream); break;
+    case 32: launch_pool_graph_bwd_cap_g<32>(a, B, max_seg, stream); break;
+    default: launch_pool_graph_bwd_cap_g<64>(a, B, max_seg, stream); break;
   }
 }
 
@@ -1359,11 +1426,13 @@ int tsgnn_sag_pool_gather_f32(const float* y, int64_t ldy, const float* score, c
 
 int tsgnn_sag_pool_graph_max_nodes(void) { return PG_MAX_NODES; }
 
-int tsgnn_sag_pool_graph_f32(const float* y, int64_t ldy, const int* rowptr, const int* rowend, const int* col, const float* dinv,
-                             const float* self_w, const float* w_s, const float* b_s, const int* graph_ptr, const int* graph_ptr_new,
-                             int B, int max_seg, int F, float* score, int* perm, int* new_id, float* xp, int64_t ldo, int* cnt,
-                             float* out, int64_t ldout, int* arg, int accumulate, int* rowptr_new, int* rowend_new, int* col_new,
-                             float* dinv_new, float* self_w_new, float* agg_next, int64_t ldagg, tsgnn_stream_t stream) {
+/* cap_rows_new < 0: tsgnn_sag_pool_graph_f32; >= 0: its capacity form */
+static int sag_pool_graph_fwd(const float* y, int64_t ldy, const int* rowptr, const int* rowend, const int* col, const float* dinv,
+                              const float* self_w, const float* w_s, const float* b_s, const int* graph_ptr, const int* graph_ptr_new,
+                              int B, int max_seg, int F, float* score, int* perm, int* new_id, float* xp, int64_t ldo, int* cnt,
+                              float* out, int64_t ldout, int* arg, int accumulate, int* rowptr_new, int* rowend_new, int* col_new,
+                              float* dinv_new, float* self_w_new, float* agg_next, int64_t ldagg, int64_t cap_rows_new,
+                              tsgnn_stream_t stream) {
   if (agg_next && (!col_new || ldagg < F)) return TSGNN_EINVAL;
   if (agg_next && (ldagg % 4 || !aligned16(agg_next))) return TSGNN_EUNSUPPORTED;
   if ((col_new != nullptr) != (rowptr_new != nullptr) || (col_new != nullptr) != (rowend_new != nullptr) ||
@@ -1378,9 +1447,38 @@ int tsgnn_sag_pool_graph_f32(const float* y, int64_t ldy, const int* rowptr, con
   const size_t lds = pool_graph_lds(max_seg, F);
   PoolGraphArgs a{y, ldy, rowptr, rowend, col, dinv, self_w, w_s, b_s, graph_ptr, graph_ptr_new, score, perm, new_id, xp, ldo, cnt,
                   out, ldout, arg, accumulate, F, rowptr_new, rowend_new, col_new, dinv_new, self_w_new, agg_next, ldagg, nullptr};
-  launch_pool_graph<false>(a, B, max_seg, lds, stream);
+  if (cap_rows_new >= 0) {
+    a.cap_B = B;
+    a.cap_rows = cap_rows_new;
+    launch_pool_graph_cap(a, B, lds, stream);
+  } else {
+    launch_pool_graph<false>(a, B, max_seg, lds, stream);
+  }
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
+}
+
+int tsgnn_sag_pool_graph_f32(const float* y, int64_t ldy, const int* rowptr, const int* rowend, const int* col, const float* dinv,
+                             const float* self_w, const float* w_s, const float* b_s, const int* graph_ptr, const int* graph_ptr_new,
+                             int B, int max_seg, int F, float* score, int* perm, int* new_id, float* xp, int64_t ldo, int* cnt,
+                             float* out, int64_t ldout, int* arg, int accumulate, int* rowptr_new, int* rowend_new, int* col_new,
+                             float* dinv_new, float* self_w_new, float* agg_next, int64_t ldagg, tsgnn_stream_t stream) {
+  return sag_pool_graph_fwd(y, ldy, rowptr, rowend, col, dinv, self_w, w_s, b_s, graph_ptr, graph_ptr_new, B, max_seg, F, score, perm,
+                            new_id, xp, ldo, cnt, out, ldout, arg, accumulate, rowptr_new, rowend_new, col_new, dinv_new, self_w_new,
+                            agg_next, ldagg, -1, stream);
+}
+
+/* see include/tsgnn.h */
+int tsgnn_sag_pool_graph_cap_f32(const float* y, int64_t ldy, const int* rowptr, const int* rowend, const int* col, const float* dinv,
+                                 const float* self_w, const float* w_s, const float* b_s, const int* graph_ptr,
+                                 const int* graph_ptr_new, int B, int max_seg, int F, float* score, int* perm, int* new_id, float* xp,
+                                 int64_t ldo, int* cnt, float* out, int64_t ldout, int* arg, int accumulate, int* rowptr_new,
+                                 int* rowend_new, int* col_new, float* dinv_new, float* self_w_new, float* agg_next, int64_t ldagg,
+                                 int64_t cap_rows_new, tsgnn_stream_t stream) {
+  if (cap_rows_new < 0 || max_seg < 1) return TSGNN_EINVAL;
+  return sag_pool_graph_fwd(y, ldy, rowptr, rowend, col, dinv, self_w, w_s, b_s, graph_ptr, graph_ptr_new, B, max_seg, F, score, perm,
+                            new_id, xp, ldo, cnt, out, ldout, arg, accumulate, rowptr_new, rowend_new, col_new, dinv_new, self_w_new,
+                            agg_next, ldagg, cap_rows_new, stream);
 }
 
 /* the GraphConv-scorer form (PyG SAGPooling's default GNN): score_i = w_rel . sum_{j in N(i)} relu(y_j) + w_root . relu(y_i) + b */
@@ -1448,13 +1546,14 @@ int tsgnn_sag_pool_bwd_f32(const float* y, int64_t ldy, const float* score, cons
   return TSGNN_OK;
 }
 
-int tsgnn_sag_pool_graph_bwd_f32(const float* y, int64_t ldy, const float* score, const int* new_id, const int* graph_ptr,
-                                 const int* graph_ptr_new, const int* arg, const float* dxp, int64_t lddxp, const float* dread,
-                                 int64_t lddr, const int* rowptr, const int* rowend, const int* col, const float* dinv,
-                                 const float* self_w, const float* w_s, int B, int max_seg, int F, float* du, int64_t lddu, float* part,
-                                 float* dws, float* dbs, const float* dagg_next, int64_t lddagg, const int* rowptr_n,
-                                 const int* rowend_n, const int* col_n, const float* dinv_n, const float* self_w_n,
-                                 tsgnn_stream_t stream) {
+/* cap_rows < 0: tsgnn_sag_pool_graph_bwd_f32; >= 0: its capacity form */
+static int sag_pool_graph_bwd(const float* y, int64_t ldy, const float* score, const int* new_id, const int* graph_ptr,
+                              const int* graph_ptr_new, const int* arg, const float* dxp, int64_t lddxp, const float* dread,
+                              int64_t lddr, const int* rowptr, const int* rowend, const int* col, const float* dinv,
+                              const float* self_w, const float* w_s, int B, int max_seg, int F, float* du, int64_t lddu, float* part,
+                              float* dws, float* dbs, const float* dagg_next, int64_t lddagg, const int* rowptr_n,
+                              const int* rowend_n, const int* col_n, const float* dinv_n, const float* self_w_n, int64_t cap_rows,
+                              tsgnn_stream_t stream) {
   if (dagg_next && (dxp || !rowptr_n || !rowend_n || !col_n || !dinv_n || !self_w_n || lddagg < F)) return TSGNN_EINVAL;
   if (dagg_next && (lddagg % 4 || !aligned16(dagg_next))) return TSGNN_EUNSUPPORTED;
   if (!y || !score || !new_id || !graph_ptr || !graph_ptr_new || !arg || !dread || !rowptr || !col || !dinv || !self_w || !w_s || !du ||
@@ -1467,10 +1566,42 @@ int tsgnn_sag_pool_graph_bwd_f32(const float* y, int64_t ldy, const float* score
   if (max_seg == 0) return TSGNN_OK;
   PoolGraphBwdArgs a{y, ldy, score, new_id, graph_ptr, graph_ptr_new, arg, dxp, lddxp, dread, lddr, rowptr, rowend, col, dinv, self_w,
                      w_s, du, lddu, part, F, dagg_next, lddagg, rowptr_n, rowend_n, col_n, dinv_n, self_w_n, nullptr};
-  launch_pool_graph_bwd<false>(a, B, max_seg, stream);
+  if (cap_rows >= 0) {
+    a.cap_B = B;
+    a.cap_rows = cap_rows;
+    launch_pool_graph_bwd_cap(a, B, max_seg, stream);
+  } else {
+    launch_pool_graph_bwd<false>(a, B, max_seg, stream);
+  }
   if (dws != nullptr) launch_du_reduce(part, (int)B, F, dws, dbs, stream);   // NULL: reduced by tsgnn_linear_wgrad_du_f32
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
+}
+
+int tsgnn_sag_pool_graph_bwd_f32(const float* y, int64_t ldy, const float* score, const int* new_id, const int* graph_ptr,
+                                 const int* graph_ptr_new, const int* arg, const float* dxp, int64_t lddxp, const float* dread,
+                                 int64_t lddr, const int* rowptr, const int* rowend, const int* col, const float* dinv,
+                                 const float* self_w, const float* w_s, int B, int max_seg, int F, float* du, int64_t lddu, float* part,
+                                 float* dws, float* dbs, const float* dagg_next, int64_t lddagg, const int* rowptr_n,
+                                 const int* rowend_n, const int* col_n, const float* dinv_n, const float* self_w_n,
+                                 tsgnn_stream_t stream) {
+  return sag_pool_graph_bwd(y, ldy, score, new_id, graph_ptr, graph_ptr_new, arg, dxp, lddxp, dread, lddr, rowptr, rowend, col, dinv,
+                            self_w, w_s, B, max_seg, F, du, lddu, part, dws, dbs, dagg_next, lddagg, rowptr_n, rowend_n, col_n, dinv_n,
+                            self_w_n, -1, stream);
+}
+
+/* see include/tsgnn.h */
+int tsgnn_sag_pool_graph_bwd_cap_f32(const float* y, int64_t ldy, const float* score, const int* new_id, const int* graph_ptr,
+                                     const int* graph_ptr_new, const int* arg, const float* dxp, int64_t lddxp, const float* dread,
+                                     int64_t lddr, const int* rowptr, const int* rowend, const int* col, const float* dinv,
+                                     const float* self_w, const float* w_s, int B, int max_seg, int F, float* du, int64_t lddu,
+                                     float* part, float* dws, float* dbs, const float* dagg_next, int64_t lddagg, const int* rowptr_n,
+                                     const int* rowend_n, const int* col_n, const float* dinv_n, const float* self_w_n,
+                                     int64_t cap_rows, tsgnn_stream_t stream) {
+  if (cap_rows < 0 || max_seg < 1) return TSGNN_EINVAL;
+  return sag_pool_graph_bwd(y, ldy, score, new_id, graph_ptr, graph_ptr_new, arg, dxp, lddxp, dread, lddr, rowptr, rowend, col, dinv,
+                            self_w, w_s, B, max_seg, F, du, lddu, part, dws, dbs, dagg_next, lddagg, rowptr_n, rowend_n, col_n, dinv_n,
+                            self_w_n, cap_rows, stream);
 }
 
 /* the GraphConv-scorer form: part gets B rows of 2F + 4 floats [dw_rel (F) | db | 3 unused | dw_root (F)], summed by a partial-row

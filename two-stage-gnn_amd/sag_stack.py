@@ -172,7 +172,14 @@ class _SagStack(torch.autograd.Function):
         if g.val is not None:
             raise NotImplementedError("edge weights are never passed by the reference (network.py:34)")
         dev = x.device
-        x = x.contiguous().float()
+        # a capacity plan (sag_stream.CapacityPlan): the batch's row counts live in the graph pointers on the device, every host value
+        # below is a capacity, and the per-graph level kernels zero the padding rows behind the batch (their capacity forms)
+        cap = bool(getattr(plan, "capacity", False))
+        if cap:
+            if x.dtype != torch.float32 or x.stride(1) != 1:
+                raise ValueError("a capacity plan takes float32 feature rows with unit column stride")
+        else:
+            x = x.contiguous().float()
         H = params[0].size(1)
         B = plan.levels[0].B
         rowptr, col, rowend = g.rowptr, g.col, None          # rowend: explicit row ends once a level was filtered in-kernel
@@ -209,6 +216,9 @@ class _SagStack(torch.autograd.Function):
             xp, cnt = _f32(K, H, device=dev), _i32(max(K, 1), device=dev)
             arg = _i32(B, H, device=dev)
             fused_filter = False
+            if cap and not (sym and L.max_seg <= pool_graph_max and PER_GRAPH_POOL):
+                raise RuntimeError("a capacity plan runs on the per-graph level kernels only (symmetric graphs of at most %d nodes)"
+                                   % pool_graph_max)
             if L.max_seg <= pool_graph_max and PER_GRAPH_POOL:
                 # score layer, top-k, gated gather, readout and (symmetric graphs) the CSR filter: one workgroup per graph,
                 # one launch; the pooled adjacency keeps each graph at its old segment base -> explicit row ends
@@ -221,9 +231,10 @@ class _SagStack(torch.autograd.Function):
                         agg_next = _f32(K, H, device=dev)       # the next level's A^ xp, formed by the same launch
                 else:
                     rp_n = re_n = col_n = dinv_n = self_w_n = None
-                nat.call("sag_pool_graph_f32", y, y.stride(0), rowptr, rowend, col, dinv, self_w, wsv, bs, L.gp, Ln.gp, B, L.max_seg, H,
-                         score, perm, new_id, xp, xp.stride(0), cnt, read, read.stride(0), arg, int(l > 0),
-                         rp_n, re_n, col_n, dinv_n, self_w_n, agg_next, H if agg_next is not None else 0)
+                # (capacity form: the same body + the workgroups that zero rows [Ln.gp[B], K) of xp / agg_next)
+                nat.call("sag_pool_graph_cap_f32" if cap else "sag_pool_graph_f32", y, y.stride(0), rowptr, rowend, col, dinv, self_w, wsv,
+                         bs, L.gp, Ln.gp, B, L.max_seg, H, score, perm, new_id, xp, xp.stride(0), cnt, read, read.stride(0), arg, int(l > 0),
+                         rp_n, re_n, col_n, dinv_n, self_w_n, agg_next, H if agg_next is not None else 0, *((K,) if cap else ()))
             else:
                 if rowend is not None:
                     raise RuntimeError("explicit row ends only arise from the per-graph kernel, whose size limit applies to every level")
@@ -261,6 +272,7 @@ class _SagStack(torch.autograd.Function):
         depth = plan.depth
         dread = dread.contiguous()
         dev = dread.device
+        cap = bool(getattr(plan, "capacity", False))
         grads = [None] * (4 * depth)
         pool_graph_max = int(nat.lib().tsgnn_sag_pool_graph_max_nodes())
         sym = ctx.sym
@@ -279,10 +291,12 @@ class _SagStack(torch.autograd.Function):
                 # pooled-row gradients -> score-layer backward -> du: one workgroup per graph; the partial rows of (dw_s, db_s) it leaves are
                 # summed by the closing reduction
                 part = _f32(L.B * (H + 4), device=dev)
-                nat.call("sag_pool_graph_bwd_f32", y, y.stride(0), score, new_id, L.gp, Ln.gp, arg, dxp,
-                         dxp.stride(0) if dxp is not None else 0, dread, dread.stride(0), rowptr, rowend, col, dinv, self_w, wsv,
+                # (capacity form: the same body + the workgroups that zero rows [L.gp[B], N) of du)
+                nat.call("sag_pool_graph_bwd_cap_f32" if cap else "sag_pool_graph_bwd_f32", y, y.stride(0), score, new_id, L.gp, Ln.gp, arg,
+                         dxp, dxp.stride(0) if dxp is not None else 0, dread, dread.stride(0), rowptr, rowend, col, dinv, self_w, wsv,
                          L.B, L.max_seg, H, dyb, dyb.stride(0), part, None, None,
-                         *((nxt[0], nxt[0].stride(0)) + nxt[1:] if nxt is not None else (None, 0, None, None, None, None, None)))
+                         *((nxt[0], nxt[0].stride(0)) + nxt[1:] if nxt is not None else (None, 0, None, None, None, None, None)),
+                         *((N,) if cap else ()))
                 du_job = (part, L.B, H)
             else:
                 if nxt is not None:
