@@ -55,11 +55,13 @@ int tsgnn_dense_adj_fill(const float* adj, int B, int nmax, const int* graph_ptr
 
 /* COO edge list (PyG edge_index rows, int64; Code/sag/network.py:31) -> CSR grouped by `key`
  * (key = edge_index[1] = target for message passing).  Stable: entries of a row keep edge order;
- * eid[p] = original edge id.  bad_flag != 0 afterwards if any key was out of range. */
+ * eid[p] = original edge id.  bad_flag != 0 afterwards if any key was out of range (tsgnn_coo_count clears it first), or if any
+ * `other` id was outside [0, n_cols) (tsgnn_coo_fill only ever sets it; decided on the int64 value; such an entry is stored
+ * as col = -1).  tsgnn_coo_fill's bad_flag is nullable: the caller vouches for `other`. */
 int tsgnn_coo_count(const int64_t* key, int64_t E, int64_t n_rows, int* cnt, int* bad_flag,
                     tsgnn_stream_t stream);
-int tsgnn_coo_fill(const int64_t* key, const int64_t* other, int64_t E, int64_t n_rows, const int* rowptr,
-                   int* cursor, int* col, int* eid, tsgnn_stream_t stream);
+int tsgnn_coo_fill(const int64_t* key, const int64_t* other, int64_t E, int64_t n_rows, int64_t n_cols, const int* rowptr,
+                   int* cursor, int* col, int* eid, int* bad_flag, tsgnn_stream_t stream);
 
 /* ---------------------------------------------------------------- mini-batch ingest (ingest.hip)
  *

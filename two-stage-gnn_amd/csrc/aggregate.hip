@@ -369,6 +369,7 @@ int tsgnn_csr_spmm_f32(const int* rowptr, const int* col, const float* val, cons
                       ((reinterpret_cast<uintptr_t>(x) & 15) == 0) && ((reinterpret_cast<uintptr_t>(y) & 15) == 0);
   if (feat == 1) {
     const unsigned nblk = (unsigned)ceil_div64(n_rows, 256);
+    TSGNN_KNAME("spmv_rows<%s>", val ? "true" : "false");
     if (val) spmv_rows<true><<<nblk, 256, 0, stream>>>(a);
     else spmv_rows<false><<<nblk, 256, 0, stream>>>(a);
   } else if (vec_ok && !relu_in && n_rows >= RB_MIN_ROWS && feat / 4 <= 32 && feat / 4 > 8) {
@@ -393,6 +394,7 @@ int tsgnn_csr_spmm_f32(const int* rowptr, const int* col, const float* val, cons
     else launch_vec4<64>(a, stream);
   } else {
     const unsigned nblk = (unsigned)ceil_div64(n_rows, 4);
+    TSGNN_KNAME("spmm_scalar<%s,%s>", val ? "true" : "false", relu_in ? "true" : "false");
     if (val) {
       if (relu_in) spmm_scalar<true, true><<<nblk, 256, 0, stream>>>(a, nblk);
       else spmm_scalar<true, false><<<nblk, 256, 0, stream>>>(a, nblk);

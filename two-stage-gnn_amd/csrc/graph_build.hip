@@ -155,15 +155,20 @@ __global__ void coo_hist(const int64_t* __restrict__ key, int64_t E, int64_t n_r
 // stable placement: edge e goes to rowptr[key] + (#edges e' < e with the same key).  Rank is
 // obtained without atomics-order dependence by a per-row insertion afterwards: we place with an
 // atomic cursor, then sort each row's slice by original edge id (rows are short).
+// `other` is checked as the int64 it arrives as, before it is narrowed: an id outside [0, n_cols) is stored as -1 and raises *bad
+// (nullable: the caller vouches for the ids), so nothing downstream gathers through it.
 __global__ void coo_place(const int64_t* __restrict__ key, const int64_t* __restrict__ other, int64_t E,
-                          int64_t n_rows, const int* __restrict__ rowptr, int* __restrict__ cursor,
-                          int* __restrict__ col, int* __restrict__ eid) {
+                          int64_t n_rows, int64_t n_cols, const int* __restrict__ rowptr, int* __restrict__ cursor,
+                          int* __restrict__ col, int* __restrict__ eid, int* __restrict__ bad) {
   int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (e >= E) return;
   int64_t k = key[e];
   if (k < 0 || k >= n_rows) return;
   int p = rowptr[k] + atomicAdd(&cursor[k], 1);
-  col[p] = (int)other[e];
+  const int64_t o = other[e];
+  const bool ok = o >= 0 && o < n_cols;
+  if (!ok && bad) atomicOr(bad, 1);
+  col[p] = ok ? (int)o : -1;
   eid[p] = (int)e;
 }
 __global__ void csr_sort_rows_by_eid(const int* __restrict__ rowptr, int64_t n_rows, int* __restrict__ col,
@@ -278,12 +283,14 @@ int tsgnn_coo_count(const int64_t* key, int64_t E, int64_t n_rows, int* cnt /*n_
   return TSGNN_OK;
 }
 
-int tsgnn_coo_fill(const int64_t* key, const int64_t* other, int64_t E, int64_t n_rows, const int* rowptr,
-                   int* cursor /*n_rows scratch*/, int* col, int* eid, hipStream_t stream) {
-  if (E < 0 || n_rows < 0 || !rowptr || !cursor || (E > 0 && (!key || !other || !col || !eid))) return TSGNN_EINVAL;
+int tsgnn_coo_fill(const int64_t* key, const int64_t* other, int64_t E, int64_t n_rows, int64_t n_cols, const int* rowptr,
+                   int* cursor /*n_rows scratch*/, int* col, int* eid, int* bad_flag /*nullable; only ever set*/,
+                   hipStream_t stream) {
+  if (E < 0 || n_rows < 0 || n_cols < 0 || !rowptr || !cursor || (E > 0 && (!key || !other || !col || !eid))) return TSGNN_EINVAL;
   if (E == 0 || n_rows == 0) return TSGNN_OK;
   (void)hipMemsetAsync(cursor, 0, sizeof(int) * (size_t)n_rows, stream);
-  coo_place<<<(unsigned)ceil_div64(E, 256), 256, 0, stream>>>(key, other, E, n_rows, rowptr, cursor, col, eid);
+  coo_place<<<(unsigned)ceil_div64(E, 256), 256, 0, stream>>>(key, other, E, n_rows, n_cols, rowptr, cursor, col, eid,
+                                                              bad_flag);
   csr_sort_rows_by_eid<<<(unsigned)ceil_div64(n_rows, 256), 256, 0, stream>>>(rowptr, n_rows, col, eid);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;

@@ -270,8 +270,8 @@ def level_from_dense(P, g, g1, bad):
     nat.call("coo_count", key, R, nb, cnt, bad)
     lv.bptr = exclusive_scan(cnt)
     lv.members = torch.empty(max(R, 1), dtype=torch.int32, device=dev)
-    nat.call("coo_fill", key, torch.arange(max(R, 1), dtype=torch.int64, device=dev), R, nb, lv.bptr,
-             torch.empty(nb, dtype=torch.int32, device=dev), lv.members, torch.empty(max(R, 1), dtype=torch.int32, device=dev))
+    nat.call("coo_fill", key, torch.arange(max(R, 1), dtype=torch.int64, device=dev), R, nb, max(R, 1), lv.bptr,
+             torch.empty(nb, dtype=torch.int32, device=dev), lv.members, torch.empty(max(R, 1), dtype=torch.int32, device=dev), None)
     return lv
 
 

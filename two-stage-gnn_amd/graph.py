@@ -219,7 +219,8 @@ class GraphBatch:
 
     @classmethod
     def from_edge_index(cls, edge_index, num_nodes, sizes=None, nmax=None, assume_symmetric=False, ghosts=False):
-        """edge_index: int64 [2,E] (PyG: row 0 = source j, row 1 = target i).  CSR row = target."""
+        """edge_index: int64 [2,E] (PyG: row 0 = source j, row 1 = target i).  CSR row = target.  An id of either row outside
+        [0, num_nodes) raises IndexError (checked on the device, on the int64 value, by the two launches that build the CSR)."""
         g = cls()
         g.layout = "packed"
         dev = edge_index.device
@@ -241,7 +242,7 @@ class GraphBatch:
         g.nnz = E
         g.col = _i32(max(E, 1), dev)
         g.eid = _i32(max(E, 1), dev)
-        nat.call("coo_fill", key, other, E, R, g.rowptr, _i32(max(R, 1), dev), g.col, g.eid)
+        nat.call("coo_fill", key, other, E, R, R, g.rowptr, _i32(max(R, 1), dev), g.col, g.eid, bad)
         if int(bad.item()) != 0:
             raise IndexError("edge_index contains node ids outside [0, num_nodes)")
         g.val = None
