@@ -761,6 +761,23 @@ int tsgnn_gat_assemble_piece_words(void);
 int tsgnn_gat_assemble_max_pieces(void);
 int tsgnn_gat_assemble_layout(int64_t nr, int64_t nnz, int64_t k, int64_t ldf, int64_t* off);
 int tsgnn_gat_assemble_f32(const int64_t* desc, tsgnn_stream_t stream);
+/* The GAT family's gather launch (gat_stream.hip; host side: gat_stream.py): schedule entry number `cursor` of an epoch's triplets
+ * [T, 3] -> the arrays tsgnn_gat_assemble_f32 writes for the three graphs' pieces, found on the device, at capacities that do not
+ * depend on the triplet.  Cursor, T and the ticket counter as tsgnn_triplet_gather_f32 (the same [HEAD | schedule] buffer).
+ * Inputs: records int32[n_graphs][8] = (the piece's word offset in the arena, a multiple of 4; n, nr, nnz, k, Nmax - n, index, 0);
+ *           arena int32[arena_words]: every graph's piece buffer (tsgnn_gat_assemble_layout); max_nr / max_nnz / max_k: the arena's
+ *           largest nr / nnz / k.
+ *         desc (HOST memory): the HEADER of tsgnn_gat_assemble_f32's description (K is ignored) with R, E, I = the capacities the
+ *           outputs are allocated for and B = 3.
+ * Outputs, rewritten by every launch: the parts [:R'] / [:E'] / [:I'] of the triplet's own sizes as tsgnn_gat_assemble_f32 writes
+ * them; behind them rowptr / rowptr_t (R' .. R] = E' (padding rows are empty both ways), x rows +0, row_mult 0, the iso_cols rows 0,
+ * row_graph 2, row_slot 0, graph_ptr[3] = R', iso_ptr[3] = I'; col, col_t, src_e_t, inv past E' and iso_idx, iso_w past I' are not
+ * touched; ids_out[3] = the entry.
+ * TSGNN_EINVAL without a launch: a null pointer, a header tsgnn_gat_assemble_f32 refuses, B != 3, a capacity below three times the
+ * arena's largest piece; TSGNN_EUNSUPPORTED without a launch: records / arena / state off 16 bytes, sizes past 2^31. */
+int tsgnn_gat_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words, int64_t max_nr,
+                                 int64_t max_nnz, int64_t max_k, const int32_t* sched, int64_t sched_cap, int64_t* state,
+                                 unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream);
 /* Resident one-graph pieces of the EigenGCN encoder -> the complete EigenBatch of a chunk (eigen_pool.concat_batches of the same
  * one-graph batches, word for word): per level graph i = 0..L rowptr [R_i + Nmax + 1] (the Nmax ghost-slot rows empty), col, val,
  * graph_ptr [B + 1], row_graph, row_slot, slot_count [Nmax]; per pooling level i < L cluster_of [R_i] (-1 kept), coef [R_i, J],

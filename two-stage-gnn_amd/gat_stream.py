@@ -1,0 +1,205 @@
+"""GAT triplet stream: a NEW triplet at every replay of ONE hipGraph for ``gat_triplet.tripletnet`` over a
+``gat_encoders.DGATEncoderGraph`` (Code/sage+gat+diffpool/train_triplet.py:247-287 with --method=GAT: ``tripletsampler_tr.sampler()``
+-> ``TNet(a, p, n)`` -> margin loss -> clip -> Adam, thousands of times per epoch).
+
+``triplet_stream.TripletStream`` does this for the GraphSage family, ``diffpool_stream.TripletStream`` for DiffPool and
+``sag_stream.TripletStream`` for SAGPool.  ``gat_triplet.assemble`` writes arrays whose shapes (R rows, E entries, I listed edge-less
+columns) are host numbers that change with the triplet, so no captured step can hold its batch.  Here the dataset's graph objects are
+packed once into a device-resident arena of the pieces the assembler already reads (``pack_arena``), an epoch's triplets go up as
+one index array (``load``), and the step's first launch (``tsgnn_gat_triplet_gather_f32``, csrc/gat_stream.hip) picks the three
+pieces of "schedule entry number ``cursor``" on the device, writes the batch at capacities of three times the largest piece —
+everything behind the triplet's own R / E / I is inert padding — and advances the cursor.  The fused GAT layers, the readout and the
+triplet tail run unchanged on that batch: its host-side sizes are the capacities, the triplet's own sizes live in the row pointers,
+``graph_ptr`` and ``iso_ptr`` on the device.
+
+No dropout (a ghost representative is exact only while its copies stay identical); anything the stream does not take is a TypeError
+that names the eager drop-in."""
+import numpy as np
+import torch
+
+from . import _native as nat
+from . import gat_triplet as gt
+from . import resident as R
+from .graph import GraphBatch
+from .triplet_stream import HEAD, ArenaStream, check_schedule, schedule_of  # noqa: F401  (the stream's vocabulary)
+
+REC_WORDS = 8          # int32 words of a graph's record: piece offset (words), n, nr, nnz, k, Nmax - n, index, 0
+EAGER = "; use the eager drop-in, tripletnet.forward(a, p, n)"
+
+
+class Arena:
+    """host arrays of a packed dataset (``pack_arena``):
+      records  int32 [G, 8]    the piece's word offset in ``buf``, n, nr, nnz, k, mult = Nmax - n, the graph's index, 0
+      buf      int32 [words]   every graph's ``gat_triplet.piece_buffer`` (sections at ``tsgnn_gat_assemble_layout``'s offsets, piece-local
+                               indices), one behind the other, each piece on 16 bytes
+      top      (nr, nnz, k)    the largest of each over the dataset
+      caps     (rows, nnz, k)  three times ``top``: no triplet needs more, also when one object fills all three places (a sampler may
+                               draw an anchor as its own negative's positive; the three largest DISTINCT graphs would not cover that)
+      nmax, fin, ldf           what every graph shares: the padded size, the feature width, the 16-byte row stride of the feature rows"""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def pack_arena(graphs, limit=1 << 31):
+    """graph objects (``.graph`` = {'adj', 'feats', 'num_nodes', ...} as cross_val.split_train_val prepares them) -> ``Arena``.
+    ValueError, naming the graph's index, for what one ghost representative cannot stand for (``pack_host``'s ``exact`` is False: the
+    padded feature rows differ, or ``adj`` is positive outside ``[:n, :n]``), for an Nmax or a feature width that differs from the
+    other graphs', and for offsets that reach ``limit`` (the records are int32).  Host work only: no GPU is touched."""
+    graphs = list(graphs)
+    if not graphs:
+        raise ValueError("pack_arena: no graphs")
+    G = len(graphs)
+    rec = np.zeros((G, REC_WORDS), dtype=np.int64)
+    bufs = []
+    nmax = fin = ldf = None
+    words = 0
+    for i, obj in enumerate(graphs):
+        try:
+            p = gt.pack_host(obj)
+        except ValueError as e:
+            raise ValueError("graph %d: %s" % (i, e)) from None
+        if not p["exact"]:
+            raise ValueError("graph %d: one representative cannot stand for its padded rows (the rows feats[n:] differ, or adj has a "
+                             "positive entry outside [:n, :n])" % i)
+        if nmax is None:
+            nmax, fin, ldf = p["nmax"], p["fin"], int(p["feats"].shape[1])
+        if p["nmax"] != nmax:
+            raise ValueError("graph %d: Nmax = %d differs from the other graphs' %d" % (i, p["nmax"], nmax))
+        if p["fin"] != fin:
+            raise ValueError("graph %d: feature width %d differs from the other graphs' %d" % (i, p["fin"], fin))
+        b = gt.piece_buffer(p)
+        rec[i] = (words, p["n"], p["nr"], p["nnz"], p["k"], p["mult"], i, 0)
+        bufs.append(b)
+        words += int(b.size)                                                # (a piece's length is a multiple of 4 words)
+        if words >= int(limit):
+            raise ValueError("graph %d: pack_arena: offsets reach %d (int32 records): %d buffer words" % (i, limit, words))
+    top = tuple(int(rec[:, c].max()) for c in (2, 3, 4))
+    caps = tuple(3 * t for t in top)
+    if max(caps[0] * ldf, caps[1]) >= int(limit):
+        raise ValueError("pack_arena: offsets reach %d (int32 records): a batch of %d rows x %d, %d entries" % (limit, caps[0], ldf, caps[1]))
+    return Arena(records=rec.astype(np.int32), buf=np.concatenate(bufs), words=words, top=top, caps=caps, nmax=nmax, fin=fin, ldf=ldf,
+                 n_graphs=G)
+
+
+def _layers(model):
+    return [model.conv_first] + (list(model.conv_block) if model.conv_block is not None else []) + [model.conv_last]
+
+
+class TripletStream(ArenaStream):
+    """``net``: a ``gat_triplet.tripletnet``; ``graphs``: the dataset's graph objects (they are packed once).  The interface of
+    ``triplet_stream.TripletStream``: ``load(schedule)`` (``[T, 3]`` indices into ``graphs``), ``gather``, ``embed``,
+    ``loss(criterion, target)`` (the step for ``GraphedStep``: every call, every replay, consumes the next entry), ``position``,
+    ``ids_out``, ``len``; with ``max_steps`` the stream starts on the one-entry schedule [0, 0, 0].  TypeError (ending in the eager
+    drop-in) for anything that is not a ``gat_triplet.tripletnet``, a model on the CPU, ``resident.RESIDENT`` off, a layer the fused
+    GAT kernels do not take, more than four distinct head counts, attention or input dropout > 0 on any head (whatever the mode)."""
+
+    NAME = "gat_stream.TripletStream"
+
+    def __init__(self, net, graphs, max_steps=None):
+        from . import gat_fused as gf
+        from .gat_encoders import DGATHead, DGATLayer, _fused_layer_ok
+
+        def refuse(what):
+            raise TypeError("%s %s%s" % (self.NAME, what, EAGER))
+        if not isinstance(net, gt.tripletnet):
+            refuse("takes a gat_triplet.tripletnet")
+        model = net.model
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            refuse("runs on the GPU only")
+        if not R.RESIDENT:
+            refuse("needs the resident pieces (resident.RESIDENT is off)")
+        layers = _layers(model)
+        heads = sorted(set(gt.head_counts(model)))
+        if len(heads) > 4:
+            refuse("writes the edge-less indicator for at most four distinct head counts (%d)" % len(heads))
+        if len(layers) > gf._LMAX or not all(isinstance(l, DGATLayer) and gf.heads_ok(l.attentions) for l in layers):
+            refuse("needs layers the fused GAT kernels take (gat_fused.heads_ok, at most %d layers)" % gf._LMAX)
+        if any(hd.dropout > 0 for hd in model.modules() if isinstance(hd, DGATHead)) or any(l.dropout > 0 for l in layers):
+            refuse("takes no attention or input dropout (a ghost representative is exact only while its copies stay identical)")
+        ar = self.arena = pack_arena(graphs)
+        if ar.fin != int(model.conv_first.attentions[0].input_dim):
+            raise ValueError("%s: the dataset has %d features per node, the model takes %d"
+                             % (self.NAME, ar.fin, model.conv_first.attentions[0].input_dim))
+        self.net, self.model, self.device, self.B, self.heads = net, model, dev, 3, heads
+        self.row_cap, self.nnz_cap, self.iso_cap = ar.caps
+        self._allocate()
+        if not all(_fused_layer_ok(l.attentions, self.g, self.row_cap) for l in layers) or not gf.readout_ok(self.g, self.row_cap):
+            refuse("needs the fused GAT node on the gathered batch (the dataset's graphs list up to %d edge-less columns per triplet)"
+                   % self.iso_cap)
+        self.records = torch.from_numpy(ar.records).to(dev)
+        self.buf = torch.from_numpy(ar.buf).to(dev)
+        self.ids_out = torch.zeros(3, dtype=torch.int32, device=dev)
+        self.max_steps = int(max_steps) if max_steps is not None else None
+        self._sched = self._host = self._parts = None
+        self.T = 0
+        self._warm_up_schedule()
+
+    def _allocate(self):
+        """the persistent batch: every array ``gat_fused`` / ``attention`` look up on a ``GraphBatch``, once, at capacity (two
+        allocations, every array on 16 bytes: ``gat_triplet.assemble``'s layout with R, E, I = the capacities)"""
+        ar, dev, B = self.arena, self.device, self.B
+        Rc, E, I = self.row_cap, max(self.nnz_cap, 1), max(self.iso_cap, 1)
+        isz = [Rc + 1, Rc + 1, E, E, E, E, B + 1, Rc, Rc, I, B + 1]
+        fsz = [Rc, I, Rc * ar.ldf] + [Rc * h for h in self.heads]
+        ioff = np.concatenate([[0], np.cumsum([gt._a4(s) for s in isz])])
+        foff = np.concatenate([[0], np.cumsum([gt._a4(s) for s in fsz])])
+        self._ibuf = torch.zeros(int(ioff[-1]), dtype=torch.int32, device=dev)
+        self._fbuf = torch.zeros(int(foff[-1]), dtype=torch.float32, device=dev)
+        self._views(self._ibuf, self._fbuf, ioff, isz, foff, fsz)
+
+    def _views(self, ibuf, fbuf, ioff, isz, foff, fsz):
+        """the arrays as views of the two buffers, the launch's description and the ``GraphBatch`` over them (tests hand in guarded
+        buffers of their own)"""
+        ar, dev, B, Rc = self.arena, self.device, self.B, self.row_cap
+        iv = [ibuf[int(o):int(o) + s] for o, s in zip(ioff, isz)]
+        fv = [fbuf[int(o):int(o) + s] for o, s in zip(foff, fsz)]
+        rowptr, rowptr_t, col, col_t, src_e_t, inv, graph_ptr, row_graph, row_slot, iso_idx, iso_ptr = iv
+        row_mult, iso_w, x = fv[0], fv[1], fv[2].view(Rc, ar.ldf)
+        iso_cols = {h: fv[3 + j].view(Rc, h) for j, h in enumerate(self.heads)}
+        d = np.zeros(int(nat.lib().tsgnn_gat_assemble_header_words()), dtype=np.int64)
+        d[1:7] = (Rc, self.nnz_cap, self.iso_cap, B, ar.ldf, len(self.heads))
+        d[7:7 + len(self.heads)] = self.heads
+        d[11:25] = [t.data_ptr() for t in (rowptr, col, rowptr_t, col_t, src_e_t, inv, row_mult, graph_ptr, row_graph, row_slot, iso_idx,
+                                           iso_w, iso_ptr, x)]
+        for j, h in enumerate(self.heads):
+            d[25 + j] = iso_cols[h].data_ptr()
+        g = GraphBatch()
+        g.layout, g.B, g.nmax, g.device = "packed", B, ar.nmax, dev
+        g.sizes = np.full(B, ar.top[0], dtype=np.int64)         # (host-side sizes are capacities; the triplet's own live on the device)
+        g.real_sizes = g.sizes
+        g.n_rows, g.n_ghost = Rc, 0
+        g.graph_ptr, g.row_graph, g.row_slot, g.slot_count = graph_ptr, row_graph, row_slot, gt._no_slot_counts(ar.nmax, dev)
+        g.rowptr, g.col, g.val, g.nnz, g.symmetric = rowptr, col, None, self.nnz_cap, False
+        g.row_mult = row_mult
+        g._t, g.src_e_t, g._inv_e_t = (rowptr_t, col_t, None), src_e_t, inv
+        g._iso_cols = iso_cols
+        g._iso_list = (iso_idx, iso_w, iso_ptr, self.iso_cap)
+        g._raw = (ibuf, fbuf, ioff, isz, foff, fsz)
+        self._desc, self.g, self.x = d, g, x
+
+    def gather(self):
+        """enqueue (current stream; capturable) the launch that writes the batch of the cursor's entry and advances the cursor"""
+        if self._sched is None:
+            raise RuntimeError("%s: load(schedule) before the first step" % self.NAME)
+        ar = self.arena
+        if self._parts is None or self._parts[0] is not self._sched:        # (views of the schedule buffer, made once: load() keeps it)
+            self._parts = (self._sched, self._sched[HEAD:], self._sched[4:HEAD])
+        nat.call("gat_triplet_gather_f32", self.records, ar.n_graphs, self.buf, ar.words, ar.top[0], ar.top[1], ar.top[2],
+                 self._parts[1], self.max_steps, self._sched, self._parts[2], self._desc.ctypes.data, self.ids_out)
+
+    def embed(self):
+        """gather + the encoder on the gathered batch + the triplet tail -> (dist_p, dist_n, embed_a, embed_p, embed_n), as
+        ``tripletnet.forward`` returns"""
+        if gt.dropout_active(self.model):
+            raise RuntimeError("%s: dropout became active on the model after the stream was built%s" % (self.NAME, EAGER))
+        self.gather()
+        return self.net.embed((self.x, self.g))
+
+    def loss(self, criterion, target):
+        """-> callable for ``GraphedStep``: gather launch + the encoder + the tail + ``criterion(dist_p, dist_n, target)``"""
+        def step():
+            out = self.embed()
+            return criterion(out[0], out[1], target)
+        return step
