@@ -162,10 +162,8 @@ def test_streamed_step_equals_the_drop_in_and_the_module(name, cfg, mode):
     those of ``tripletnet.forward`` on the same objects (the rows are computed by the same row-local kernels, whatever the row count);
     outputs and every parameter gradient against three B = 1 dense calls of a deep copy of the module at ``_check_against``'s bounds.
     The largest gradient difference to the drop-in is printed: the slab plan of the weight gradients depends on the row count, here
-    the capacity, so those sums are not bit for bit.
-    NOT CHECKED against the module: the three entries of the small schedule that name the n = 1 graph or the edge-less graph
-    ([2, 3, 9], [3, 2, 3], [7, 2, 0]).  The module's dense B = 1 call of a graph without any edge faulted on the GPU (see
-    gat_stream_util.three_calls); those entries are checked against the drop-in only, whose batch has no such word."""
+    the capacity, so those sums are not bit for bit.  Every entry is checked against the module, the three of the small schedule that
+    name the n = 1 graph or the edge-less graph ([2, 3, 9], [3, 2, 3], [7, 2, 0]) included."""
     m, net, objs, st = _stream(name, cfg, mode)
     sched = U.schedule(name)
     st.load(sched)
@@ -174,9 +172,8 @@ def test_streamed_step_equals_the_drop_in_and_the_module(name, cfg, mode):
     for k, ids in enumerate(sched):
         outs, loss, gs = _streamed_entry(m, st, crit, tgt)
         assert st.ids_out.tolist() == ids.tolist() and float(loss) > 0
-        if U.every_graph_has_an_edge(name, ids):
-            _check_against_module(m, outs, U.three_calls(name, cfg, ids))
-            with_module += 1
+        _check_against_module(m, outs, U.three_calls(name, cfg, ids))
+        with_module += 1
         m.zero_grad(set_to_none=True)
         outd = net(*[objs[i] for i in ids])
         crit(outd[0], outd[1], tgt).backward()
@@ -187,7 +184,7 @@ def test_streamed_step_equals_the_drop_in_and_the_module(name, cfg, mode):
                  max(float(v.abs().max()) for v in gd.values()), worst))
         for what, a, b in zip(("dist_p", "dist_n", "embed_a", "embed_p", "embed_n"), outs, outd):
             assert _same_bits(a, b), (k, what, float((a - b).abs().max()))
-    assert st.position() == len(sched) and with_module == (len(sched) if name == "big" else len(sched) - 3)
+    assert st.position() == len(sched) and with_module == len(sched)
 
 
 # ------------------------------------------------------------------------------------------------ 3. the reference's fixtures

@@ -176,6 +176,28 @@ def test_tripletnet_equals_three_single_graph_calls(layers, final_dim):
     _check_against(m1, o1, m2, o2)
 
 
+def test_tripletnet_with_graphs_without_any_edge_equals_three_single_graph_calls():
+    """the n = 1 graph (no self loop) and the edge-less graph of ASM_GRAPHS next to a graph with edges: the module's B = 1 calls of the
+    graphs with nnz = 0 are made like any other, and the drop-in's batch gives their outputs and gradients"""
+    from two_stage_gnn_amd import gat_triplet as GT
+    fin = 8
+    objs = [H.make_obj(100 + i, ASM_GRAPHS[i][0], nmax=ASM_NMAX, fin=fin, kind=ASM_GRAPHS[i][1]) for i in (2, 3, 0)]
+    adj = torch.as_tensor(np.stack([(np.asarray(o.graph["adj"]) > 0).astype(np.float32) for o in objs]))
+    x = torch.as_tensor(np.stack([np.asarray(o.graph["feats"], dtype=np.float32) for o in objs]))
+    sz = np.array([int(o.graph["num_nodes"]) for o in objs], dtype=np.int64)
+    assert adj.sum(dim=(1, 2)).gt(0).tolist() == [False, False, True] and sz.tolist() == [1, 7, 9]
+    torch.manual_seed(3)
+    m1 = _model(fin, 2, "output_dim")
+    m2 = copy.deepcopy(m1)
+    o1 = GT.tripletnet(m1)(*objs)
+    GT.MarginRankingLoss(margin=MARGIN)(o1[0], o1[1], torch.full_like(o1[0], -1.0)).backward()
+    o2 = _three_calls(m2, x, adj, sz)
+    loss2 = torch.nn.MarginRankingLoss(margin=MARGIN)(o2[0], o2[1], torch.full_like(o2[0], -1.0))
+    assert float(loss2.detach()) > 0
+    loss2.backward()
+    _check_against(m1, o1, m2, o2)
+
+
 def test_flag_is_restored_on_an_exception(monkeypatch):
     from two_stage_gnn_amd import gat_triplet as GT
     objs, *_ = _objs(71, [20, 9, 14], 20, 8)

@@ -57,9 +57,12 @@ def _inverse_entry_map(g, src_e_t):
     """inv[e] = p with src_e_t[p] = e: where A's entry e sits in A^T's entry order (cached on the graph)"""
     inv = getattr(g, "_inv_e_t", None)
     if inv is None:
-        n = src_e_t.numel()
-        inv = torch.empty(n, dtype=torch.int32, device=src_e_t.device)
-        inv[src_e_t.long()] = torch.arange(n, dtype=torch.int32, device=src_e_t.device)
+        n = int(g.nnz)                                     # src_e_t holds one placeholder word at nnz = 0: never an index
+        if n == 0:
+            inv = torch.zeros(1, dtype=torch.int32, device=src_e_t.device)
+        else:
+            inv = torch.empty(n, dtype=torch.int32, device=src_e_t.device)
+            inv[src_e_t[:n].long()] = torch.arange(n, dtype=torch.int32, device=src_e_t.device)
         g._inv_e_t = inv
     return inv
 

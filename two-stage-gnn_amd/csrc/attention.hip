@@ -84,6 +84,7 @@ inline void launch_node_scores_vec4(int lph, unsigned grid, hipStream_t stream, 
     case 8: node_scores_vec4_kernel<8><<<grid, 256, 0, stream>>>(args...); break;
     default: node_scores_vec4_kernel<16><<<grid, 256, 0, stream>>>(args...); break;
   }
+  TSGNN_KNAME("node_scores_vec4_kernel<%d>", lph);
 }
 
 // EG lanes per (row, head): numerically-stable softmax over the row's entries.  A DD row has ~5 entries: one pass of the lane
@@ -548,8 +549,10 @@ int tsgnn_node_scores_f32(const float* x, int64_t ldx, int64_t rows, int H, int 
   if (node_scores_vec4_ok(x, ldx, H, Fh, a, lda, nullptr, 0))
     launch_node_scores_vec4(Fh / 4, (unsigned)ceil_div64(rows, 4), stream, x, ldx, rows, H, Fh, a, lda, s, (const float*)nullptr, (int64_t)0,
                             (float*)nullptr);
-  else
+  else {
     node_scores_kernel<<<(unsigned)ceil_div64(rows, 4), 256, 0, stream>>>(x, ldx, rows, H, Fh, a, lda, s, nullptr, 0, nullptr);
+    TSGNN_KNAME("node_scores_kernel");
+  }
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -560,8 +563,10 @@ int tsgnn_node_scores2_f32(const float* x, int64_t ldx, int64_t rows, int H, int
   if (rows == 0) return TSGNN_OK;
   if (node_scores_vec4_ok(x, ldx, H, Fh, a1, lda1, a2, lda2))
     launch_node_scores_vec4(Fh / 4, (unsigned)ceil_div64(rows, 4), stream, x, ldx, rows, H, Fh, a1, lda1, s1, a2, lda2, s2);
-  else
+  else {
     node_scores_kernel<<<(unsigned)ceil_div64(rows, 4), 256, 0, stream>>>(x, ldx, rows, H, Fh, a1, lda1, s1, a2, lda2, s2);
+    TSGNN_KNAME("node_scores_kernel");
+  }
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -571,6 +576,7 @@ int tsgnn_edge_softmax_fwd_f32(const int* rowptr, const int* col, int64_t rows, 
   if (!rowptr || !s_grp || !s_oth || !alpha || rows < 0 || H <= 0 || mod < 0) return TSGNN_EINVAL;
   if (rows == 0) return TSGNN_OK;
   edge_softmax_fwd_kernel<<<(unsigned)ceil_div64(rows * H * SM_EG, 256), 256, 0, stream>>>(rowptr, col, rows, H, s_grp, s_oth, mod, slope, alpha);
+  TSGNN_KNAME("edge_softmax_fwd_kernel");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -582,6 +588,7 @@ int tsgnn_edge_softmax_bwd_f32(const int* rowptr, const int* col, int64_t rows, 
   if (rows == 0) return TSGNN_OK;
   edge_softmax_bwd_kernel<<<(unsigned)ceil_div64(rows * H * SM_EG, 256), 256, 0, stream>>>(rowptr, col, rows, H, s_grp, s_oth, mod, slope,
                                                                                   alpha, dalpha, dt, ds_grp);
+  TSGNN_KNAME("edge_softmax_bwd_kernel");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -591,6 +598,7 @@ int tsgnn_edge_permute_f32(const float* src, const int* perm, int64_t n, int H, 
   if (n == 0) return TSGNN_OK;
   if (scatter) scatter_rows_small<<<(unsigned)ceil_div64(n * H, 256), 256, 0, stream>>>(src, perm, n, H, dst);
   else gather_rows_small<<<(unsigned)ceil_div64(n * H, 256), 256, 0, stream>>>(src, perm, n, H, dst);
+  TSGNN_KNAME(scatter ? "scatter_rows_small" : "gather_rows_small");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -599,6 +607,7 @@ int tsgnn_csr_row_sum_f32(const int* rowptr, const float* val, int64_t rows, int
   if (!rowptr || !val || !out || rows < 0 || H <= 0) return TSGNN_EINVAL;
   if (rows == 0) return TSGNN_OK;
   csr_row_sum_kernel<<<(unsigned)ceil_div64(rows * H * SM_EG, 256), 256, 0, stream>>>(rowptr, val, rows, H, out, nullptr);
+  TSGNN_KNAME("csr_row_sum_kernel");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -608,6 +617,7 @@ int tsgnn_csr_row_sum_perm_f32(const int* rowptr, const float* val, const int* e
   if (!rowptr || !val || !eperm || !out || rows < 0 || H <= 0) return TSGNN_EINVAL;
   if (rows == 0) return TSGNN_OK;
   csr_row_sum_kernel<<<(unsigned)ceil_div64(rows * H * SM_EG, 256), 256, 0, stream>>>(rowptr, val, rows, H, out, eperm);
+  TSGNN_KNAME("csr_row_sum_kernel[eperm]");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -623,11 +633,13 @@ static int spmm_heads_launch(const int* rowptr, const int* col, const float* alp
     if (nvec <= 16) spmm_heads_vec4<16><<<(unsigned)ceil_div64(rows, 16), 256, 0, stream>>>(rowptr, col, alpha, H, Fh, x, ldx, mod, y, ldy, rows, nvec, epi);
     else if (nvec <= 32) spmm_heads_vec4<32><<<(unsigned)ceil_div64(rows, 8), 256, 0, stream>>>(rowptr, col, alpha, H, Fh, x, ldx, mod, y, ldy, rows, nvec, epi);
     else spmm_heads_vec4<64><<<(unsigned)ceil_div64(rows, 4), 256, 0, stream>>>(rowptr, col, alpha, H, Fh, x, ldx, mod, y, ldy, rows, nvec, epi);
+    TSGNN_KNAME("spmm_heads_vec4<%d>", nvec <= 16 ? 16 : (nvec <= 32 ? 32 : 64));
     TSGNN_CHECK_LAUNCH();
     return TSGNN_OK;
   }
   const unsigned nblk = (unsigned)ceil_div64(rows, 4);
   spmm_heads_kernel<<<nblk, 256, 0, stream>>>(rowptr, col, alpha, H, Fh, x, ldx, mod, y, ldy, rows, nblk, epi);
+  TSGNN_KNAME("spmm_heads_kernel");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -659,10 +671,12 @@ int tsgnn_csr_sddmm_heads_f32(const int* rowptr, const int* col, int H, int Fh, 
     if (nvec <= 16) sddmm_heads_vec4<16><<<(unsigned)ceil_div64(rows, 16), 256, 0, stream>>>(rowptr, col, H, Fh, dy, lddy, x, ldx, mod, dalpha, rows, nvec);
     else if (nvec <= 32) sddmm_heads_vec4<32><<<(unsigned)ceil_div64(rows, 8), 256, 0, stream>>>(rowptr, col, H, Fh, dy, lddy, x, ldx, mod, dalpha, rows, nvec);
     else sddmm_heads_vec4<64><<<(unsigned)ceil_div64(rows, 4), 256, 0, stream>>>(rowptr, col, H, Fh, dy, lddy, x, ldx, mod, dalpha, rows, nvec);
+    TSGNN_KNAME("sddmm_heads_vec4<%d>", nvec <= 16 ? 16 : (nvec <= 32 ? 32 : 64));
     TSGNN_CHECK_LAUNCH();
     return TSGNN_OK;
   }
   sddmm_heads_kernel<<<(unsigned)ceil_div64(rows, 4), 256, 0, stream>>>(rowptr, col, H, Fh, dy, lddy, x, ldx, mod, dalpha, rows);
+  TSGNN_KNAME("sddmm_heads_kernel");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -679,6 +693,7 @@ int tsgnn_segment_wsum_f32(const float* x, int64_t ldx, const float* w, int H, i
   segment_wsum_kernel<<<grid, 256, 0, stream>>>(x, ldx, w, H, Fh, seg_ptr, rows, C, ws, nseg, nullptr, nullptr);
   segment_wsum_final<<<dim3((unsigned)((C + 63) / 64), (unsigned)nseg), 1024, 0, stream>>>(ws, nchunk, nseg, C, seg_ptr, rows, scale, mean, out, ldo,
                                                                                            nullptr, nullptr);
+  TSGNN_KNAME("segment_wsum_kernel + segment_wsum_final");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -700,6 +715,7 @@ int tsgnn_segment_wsum2_f32(const float* x, int64_t ldx, const float* w1, const 
   segment_wsum_kernel<<<grid, 256, 0, stream>>>(x, ldx, w1, H, Fh, seg_ptr, rows, C, ws, nseg, w2, ws2);
   segment_wsum_final<<<dim3((unsigned)((C + 63) / 64), (unsigned)nseg, 2), 1024, 0, stream>>>(ws, nchunk, nseg, C, seg_ptr, rows, scale, 0, out1,
                                                                                               ldo, ws2, out2);
+  TSGNN_KNAME("segment_wsum_kernel + segment_wsum_final");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -708,6 +724,7 @@ int tsgnn_gather_wsum_f32(const float* x, int64_t ldx, const int* idx, const flo
                           float* out, int64_t ldo, tsgnn_stream_t stream) {
   if (!x || !idx || !w || !seg_ptr || !out || nseg <= 0 || C <= 0 || ldx < C || ldo < C) return TSGNN_EINVAL;
   gather_wsum_kernel<<<(unsigned)nseg, 256, 0, stream>>>(x, ldx, idx, w, seg_ptr, C, scale, out, ldo);
+  TSGNN_KNAME("gather_wsum_kernel");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -718,6 +735,7 @@ int tsgnn_broadcast_add_f32(float* y, int64_t ldy, int64_t rows, int H, int Fh, 
   if (rows == 0) return TSGNN_OK;
   broadcast_add_kernel<<<(unsigned)ceil_div64(rows * H * Fh, 256), 256, 0, stream>>>(y, ldy, rows, H, Fh, w, a, lda, u, ldu,
                                                                                     rows_per_seg, scale);
+  TSGNN_KNAME("broadcast_add_kernel");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -727,10 +745,13 @@ int tsgnn_elu_heads_fwd_f32(const float* x, int64_t rows, int H, int Fh, int mea
   if (rows == 0) return TSGNN_OK;
   const int Co = mean_heads ? Fh : H * Fh;
   const int64_t n = rows * (int64_t)H * Fh;
-  if (!mean_heads && n % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0)
+  if (!mean_heads && n % 4 == 0 && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15) == 0) {
     elu_vec4_fwd_kernel<<<(unsigned)ceil_div64(n / 4, 256), 256, 0, stream>>>(x, n / 4, apply_elu, y);
-  else
+    TSGNN_KNAME("elu_vec4_fwd_kernel");
+  } else {
     elu_heads_fwd_kernel<<<(unsigned)ceil_div64(rows * Co, 256), 256, 0, stream>>>(x, rows, H, Fh, mean_heads, apply_elu, y);
+    TSGNN_KNAME("elu_heads_fwd_kernel");
+  }
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -741,10 +762,13 @@ int tsgnn_elu_heads_bwd_f32(const float* x, const float* dy, int64_t rows, int H
   if (rows == 0) return TSGNN_OK;
   const int64_t n = rows * (int64_t)H * Fh;
   if (!mean_heads && n % 4 == 0 &&
-      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0)
+      ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy) | reinterpret_cast<uintptr_t>(dx)) & 15) == 0) {
     elu_vec4_bwd_kernel<<<(unsigned)ceil_div64(n / 4, 256), 256, 0, stream>>>(x, dy, n / 4, apply_elu, dx);
-  else
+    TSGNN_KNAME("elu_vec4_bwd_kernel");
+  } else {
     elu_heads_bwd_kernel<<<(unsigned)ceil_div64(rows * H * Fh, 256), 256, 0, stream>>>(x, dy, rows, H, Fh, mean_heads, apply_elu, dx);
+    TSGNN_KNAME("elu_heads_bwd_kernel");
+  }
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -761,6 +785,7 @@ int tsgnn_pack_heads_f32(const float* w0, const float* w1, const float* w2, cons
     if (!p.w[h] || !p.a[h]) return TSGNN_EINVAL;
   const int64_t n = (int64_t)Fin * H * Fo + (int64_t)2 * H * Fo;
   pack_heads_kernel<<<(unsigned)ceil_div64(n, 256), 256, 0, stream>>>(p, H, Fin, Fo, W, A);
+  TSGNN_KNAME("pack_heads_kernel");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -770,6 +795,7 @@ int tsgnn_unpack_heads_f32(const float* dW, const float* dA0, const float* dA1, 
   if (H <= 0 || Fin <= 0 || Fo <= 0 || !gw || !ga) return TSGNN_EINVAL;
   const int64_t n = (int64_t)Fin * H * Fo + (int64_t)2 * H * Fo;
   unpack_heads_kernel<<<(unsigned)ceil_div64(n, 256), 256, 0, stream>>>(dW, dA0, dA1, H, Fin, Fo, gw, ga);
+  TSGNN_KNAME("unpack_heads_kernel");
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }

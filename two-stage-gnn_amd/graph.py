@@ -468,6 +468,11 @@ class GraphBatch:
             col_t = _i32(max(self.nnz, 1), dev)
             val_t = torch.empty(max(self.nnz, 1), dtype=torch.float32, device=dev) if self.val is not None else None
             src_e = _i32(max(self.nnz, 1), dev)
+            if self.nnz == 0:                                  # csr_transpose writes no entry: the one-word placeholders stay defined
+                col_t.zero_()
+                src_e.zero_()
+                if val_t is not None:
+                    val_t.zero_()
             nat.call("csr_transpose", self.rowptr, self.col, self.val, R1, R1, self.nnz, rowptr_t, col_t, val_t,
                      src_e, _i32(max(R1, 1), dev), _scan_ws(R1, dev))
             self._t = (rowptr_t, col_t, val_t)
@@ -490,7 +495,11 @@ class GraphBatch:
         t = self._ensure_transpose()
         if val is self.val:
             return t
-        return t[0], t[1], (val[self.src_e_t.long()] if val is not None else None)
+        if val is None:
+            return t[0], t[1], None
+        if self.nnz == 0:                                      # no entry to permute: a zero-filled one-word placeholder, as val_t
+            return t[0], t[1], torch.zeros(1, dtype=val.dtype, device=val.device)
+        return t[0], t[1], val[self.src_e_t[:self.nnz].long()]
 
     # ------------------------------------------------------------------ feature (un)packing helpers
     def new_features(self, feat, zero=False):
