@@ -807,6 +807,27 @@ int tsgnn_eigen_assemble_max_pieces(void);
 int tsgnn_eigen_assemble_max_levels(void);
 int tsgnn_eigen_assemble_layout(int nlev, int J, int Jf, int64_t ldf, const int64_t* n, const int64_t* nnz, int64_t* off);
 int tsgnn_eigen_assemble_f32(const int64_t* desc, tsgnn_stream_t stream);
+/* The EigenGCN family's gather launch (eigen_stream.hip; host side: eigen_stream.py): schedule entry number `cursor` of an epoch's
+ * triplets [T, 3] -> every array tsgnn_eigen_assemble_f32 writes for the three graphs' pieces (B = 3), found on the device, at
+ * capacities that do not depend on the triplet.  Cursor, T and the ticket counter as tsgnn_triplet_gather_f32 (the same
+ * [HEAD | schedule] buffer).
+ * Inputs: records int32[n_graphs][12] = (the piece's word offset in the arena, a multiple of 4; the graph's index; n[0..3]; nnz[0..3];
+ *           0, 0), unused levels 0; arena int32[arena_words]: every graph's piece buffer (tsgnn_eigen_assemble_layout);
+ *           top_n / top_nnz (HOST memory, nlev words each): the arena's largest n_i / nnz_i per level graph.
+ *         desc (HOST memory): the HEADER of tsgnn_eigen_assemble_f32's description with K = B = 3, first = 1 and R_i, E_i = the
+ *           capacities the outputs are allocated for: rowptr_i [R_i + Nmax + 1], x [R_0 + Nmax, ldf], bptr_i [R_{i+1} + 4], the
+ *           others as tsgnn_eigen_assemble_f32 states them with R_i, E_i.
+ * Outputs, rewritten by every launch: the parts [:R'_i] / [:E'_i] of the triplet's own sizes as tsgnn_eigen_assemble_f32 writes them
+ * (bptr_i: the 3 (k + 1) bucket starts); behind them rowptr_i (R'_i .. R_i + Nmax] = E'_i (padding rows and the Nmax ghost-slot
+ * rows, which sit behind the row CAPACITY, are empty), graph_ptr_i[3] = R'_i, row_graph_i 2, row_slot_i 0, cluster_of_i -1, coef_i
+ * and final rows +0, x rows [R'_0 .. R_0 + Nmax) +0, bptr_i [R'_{i+1} + 3 .. R_{i+1} + 3] = R'_i, slot_count_i[s] = the pieces with
+ * n_i > s; col_i, val_i past E'_i and members_i past R'_i are not touched; ids_out[3] = the entry.
+ * TSGNN_EINVAL without a launch: a null pointer, a header tsgnn_eigen_assemble_f32 refuses, B != 3, a capacity below three times the
+ * arena's largest piece at any level; TSGNN_EUNSUPPORTED without a launch: records / arena / state off 16 bytes, sizes past 2^31, a
+ * grid of 65,536 or more chunks. */
+int tsgnn_eigen_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words,
+                                   const int64_t* top_n, const int64_t* top_nnz, const int32_t* sched, int64_t sched_cap, int64_t* state,
+                                   unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream);
 /* ELU (encoders_GAT.py:47) / mean over heads then ELU (:78-83) */
 int tsgnn_elu_heads_fwd_f32(const float* x, int64_t rows, int H, int Fh, int mean_heads, int apply_elu, float* y, tsgnn_stream_t stream);
 int tsgnn_elu_heads_bwd_f32(const float* x, const float* dy, int64_t rows, int H, int Fh, int mean_heads, int apply_elu, float* dx,
@@ -1436,6 +1457,14 @@ int tsgnn_eigen_pool_fwd_f32(const float* z, int64_t ldz, int C, const int* grap
                              int ghost_mode, const int* graph_ptr1, const int* bptr, const int* members, const float* coef, int J,
                              int final_level, float* out, int64_t ldo, int64_t n_rows1, int n_ghost1, float* fsum, float* ro,
                              int64_t ldro, int* arg, tsgnn_stream_t stream);
+/* The same launch on a capacity batch (eigen_stream.py): n_rows1 is the pooled level's row CAPACITY, graph_ptr1[B] its real row count
+ * on the device.  Pooled levels only (final_level must be 0).  Beside what tsgnn_eigen_pool_fwd_f32 writes, the rows
+ * [graph_ptr1[B], n_rows1) of out are zeroed (+0) by the share-out loop that zeroes the ghost rows: every row of out is defined.  The
+ * member-order sums are the same code: real rows are bit for bit those of tsgnn_eigen_pool_fwd_f32. */
+int tsgnn_eigen_pool_fwd_cap_f32(const float* z, int64_t ldz, int C, const int* graph_ptr0, int B, int nmax, int64_t n_rows0,
+                                 int ghost_mode, const int* graph_ptr1, const int* bptr, const int* members, const float* coef, int J,
+                                 int final_level, float* out, int64_t ldo, int64_t n_rows1, int n_ghost1, float* fsum, float* ro,
+                                 int64_t ldro, int* arg, tsgnn_stream_t stream);
 /* dz [rows_total, lddz] (every element written) = sum_j coef[r, j] * dX'[cluster_of[r], j * C + f] (final: dX'[graph, .] where
  * s >= 0) + the readout gradient dro at the rows arg names.  Ghost rows: 0, or with ghost_mode 2 the readout gradient of the
  * graphs they won (summed in graph order).  One launch; no atomics. */

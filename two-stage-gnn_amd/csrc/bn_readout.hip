@@ -403,7 +403,9 @@ __global__ __launch_bounds__(256) void readout_max_direct(SlotArgs s, const floa
     arg[(int64_t)b * F + f] = best ? (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull)) : -1;
   }
 }
-// dx[arg[b,f], f] += dout[b,f]   (ghost rows can be chosen by several graphs -> atomic)
+// dx[arg[b,f], f] += dout[b,f].  A ghost row can be chosen by several graphs: the lowest of them adds all their gradients in graph
+// order (a float atomic would add three or more in the order the workgroups arrive: a triplet whose graphs share their first
+// ghost row then gives other bits from run to run)
 __global__ void readout_max_bwd(const float* __restrict__ dout, int64_t ldo, const int* __restrict__ arg, int B, int F,
                                 const float* __restrict__ x, int64_t ldx_in, int relu, int64_t n_real,
                                 float* __restrict__ dx, int64_t ldx) {
@@ -413,9 +415,14 @@ __global__ void readout_max_bwd(const float* __restrict__ dout, int64_t ldo, con
   const int r = arg[i];
   if (r < 0) return;
   if (relu && !(x[(int64_t)r * ldx_in + f] > 0.f)) return;
-  const float g = dout[(int64_t)b * ldo + f];
-  if (r >= n_real) atomicAdd(&dx[(int64_t)r * ldx + f], g);
-  else dx[(int64_t)r * ldx + f] += g;
+  float g = dout[(int64_t)b * ldo + f];
+  if (r >= n_real) {
+    for (int b2 = 0; b2 < b; ++b2)
+      if (arg[(int64_t)b2 * F + f] == r) return;               // a lower graph owns this element
+    for (int b2 = b + 1; b2 < B; ++b2)
+      if (arg[(int64_t)b2 * F + f] == r) g += dout[(int64_t)b2 * ldo + f];
+  }
+  dx[(int64_t)r * ldx + f] += g;
 }
 
 // the same as a dense pass for batches WITHOUT ghost rows: every element of dx is written (no zero fill beforehand, no atomics):

@@ -60,7 +60,9 @@ struct EpFwd {
   int B;
 };
 
-template <bool FINAL, bool V4>
+// CAP (pooled levels of a capacity batch, eigen_stream.py): n_rows1 is the row capacity of the next level and gp1[B] its real row
+// count; the padding rows [gp1[B], n_rows1) are zeroed with the ghost rows
+template <bool FINAL, bool V4, bool CAP = false>
 __global__ __launch_bounds__(256) void eigen_pool_fwd(EpFwd a) {
   __shared__ float s_val[EP_GROUPS][EP_TILE];
   __shared__ int s_row[EP_GROUPS][EP_TILE];
@@ -140,7 +142,9 @@ __global__ __launch_bounds__(256) void eigen_pool_fwd(EpFwd a) {
         if (j < a.J) st4<V4>(a.out + (int64_t)c * a.ldo + (int64_t)j * a.C, f, a.C, acc[j]);
     }
     // the next level's ghost-slot rows are zero (rows >= K_b of the padded P^T Z); shared out over the batch's workgroups
-    for (int s = b + a.B * grp; s < a.n_ghost1; s += a.B * EP_GROUPS) {
+    // (CAP: and so are the padding rows behind the batch's last real cluster, which sit right in front of them)
+    const int64_t pad = CAP ? a.n_rows1 - a.gp1[a.B] : 0;
+    for (int64_t s = b + a.B * grp - pad; s < a.n_ghost1; s += a.B * EP_GROUPS) {
       const float zero4[4] = {0.f, 0.f, 0.f, 0.f};
       for (int j = 0; j < a.J; ++j) st4<V4>(a.out + (a.n_rows1 + s) * a.ldo + (int64_t)j * a.C, f, a.C, zero4);
     }
@@ -186,6 +190,7 @@ __global__ __launch_bounds__(256) void eigen_pool_fwd(EpFwd a) {
   }
 }
 
+// (A capacity batch needs no form of its own: its padding rows have cluster_of = -1, zero coef and a valid row_graph, and win no readout.)
 // dZ[r, f] = sum_j u_j(r) dX'[cluster(r), j*C + f]  (+ dro[b, f] where r won graph b's readout).  One thread per (row, 4 columns);
 // ghost rows: 0 (ghost_mode 1: the caller discards them) or the readout gradient of the graphs they won (ghost_mode 2, summed
 // over b in order).  FINAL: dX' is the gradient of out = max(s, 0), passed where s >= 0 (torch.max's first index: row 0 on a tie).
@@ -284,15 +289,15 @@ __global__ __launch_bounds__(256) void eigen_pool_from_dense(const float* __rest
 
 }  // namespace
 
-extern "C" {
-
-int tsgnn_eigen_pool_fwd_f32(const float* z, int64_t ldz, int C, const int* graph_ptr0, int B, int nmax, int64_t n_rows0,
-                             int ghost_mode, const int* graph_ptr1, const int* bptr, const int* members, const float* coef, int J,
-                             int final_level, float* out, int64_t ldo, int64_t n_rows1, int n_ghost1, float* fsum, float* ro,
-                             int64_t ldro, int* arg, tsgnn_stream_t stream) {
+// both forms of the forward launch (cap: tsgnn_eigen_pool_fwd_cap_f32)
+static int ep_fwd_launch(const float* z, int64_t ldz, int C, const int* graph_ptr0, int B, int nmax, int64_t n_rows0,
+                         int ghost_mode, const int* graph_ptr1, const int* bptr, const int* members, const float* coef, int J,
+                         int final_level, float* out, int64_t ldo, int64_t n_rows1, int n_ghost1, float* fsum, float* ro,
+                         int64_t ldro, int* arg, bool cap, tsgnn_stream_t stream) {
   if (!z || !graph_ptr0 || !coef || !out || B <= 0 || nmax <= 0 || C <= 0 || J < 1 || J > EP_JMAX || ldz < C ||
       ghost_mode < 0 || ghost_mode > 2 || (ro && (!arg || ldro < C)) || n_rows0 < 0 || n_rows1 < 0 || n_ghost1 < 0)
     return TSGNN_EINVAL;
+  if (cap && final_level) return TSGNN_EINVAL;
   if (final_level ? (!fsum || ldo < (int64_t)J * C) : (!graph_ptr1 || !bptr || !members || ldo < (int64_t)J * C))
     return TSGNN_EINVAL;
   EpFwd a{z, ldz, C, graph_ptr0, n_rows0, nmax, ghost_mode, graph_ptr1, bptr, members, coef, J, out, ldo, n_rows1, n_ghost1, fsum,
@@ -304,12 +309,36 @@ int tsgnn_eigen_pool_fwd_f32(const float* z, int64_t ldz, int C, const int* grap
     else eigen_pool_fwd<true, false><<<grid, 256, 0, stream>>>(a);
     TSGNN_KNAME("eigen_pool_fwd<final,%d>", (int)v4);
   } else {
-    if (v4) eigen_pool_fwd<false, true><<<grid, 256, 0, stream>>>(a);
-    else eigen_pool_fwd<false, false><<<grid, 256, 0, stream>>>(a);
-    TSGNN_KNAME("eigen_pool_fwd<pooled,%d>", (int)v4);
+    if (cap) {
+      if (v4) eigen_pool_fwd<false, true, true><<<grid, 256, 0, stream>>>(a);
+      else eigen_pool_fwd<false, false, true><<<grid, 256, 0, stream>>>(a);
+      TSGNN_KNAME("eigen_pool_fwd<pooled,%d,cap>", (int)v4);
+    } else {
+      if (v4) eigen_pool_fwd<false, true><<<grid, 256, 0, stream>>>(a);
+      else eigen_pool_fwd<false, false><<<grid, 256, 0, stream>>>(a);
+      TSGNN_KNAME("eigen_pool_fwd<pooled,%d>", (int)v4);
+    }
   }
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
+}
+
+extern "C" {
+
+int tsgnn_eigen_pool_fwd_f32(const float* z, int64_t ldz, int C, const int* graph_ptr0, int B, int nmax, int64_t n_rows0,
+                             int ghost_mode, const int* graph_ptr1, const int* bptr, const int* members, const float* coef, int J,
+                             int final_level, float* out, int64_t ldo, int64_t n_rows1, int n_ghost1, float* fsum, float* ro,
+                             int64_t ldro, int* arg, tsgnn_stream_t stream) {
+  return ep_fwd_launch(z, ldz, C, graph_ptr0, B, nmax, n_rows0, ghost_mode, graph_ptr1, bptr, members, coef, J, final_level, out, ldo,
+                       n_rows1, n_ghost1, fsum, ro, ldro, arg, false, stream);
+}
+
+int tsgnn_eigen_pool_fwd_cap_f32(const float* z, int64_t ldz, int C, const int* graph_ptr0, int B, int nmax, int64_t n_rows0,
+                                 int ghost_mode, const int* graph_ptr1, const int* bptr, const int* members, const float* coef, int J,
+                                 int final_level, float* out, int64_t ldo, int64_t n_rows1, int n_ghost1, float* fsum, float* ro,
+                                 int64_t ldro, int* arg, tsgnn_stream_t stream) {
+  return ep_fwd_launch(z, ldz, C, graph_ptr0, B, nmax, n_rows0, ghost_mode, graph_ptr1, bptr, members, coef, J, final_level, out, ldo,
+                       n_rows1, n_ghost1, fsum, ro, ldro, arg, true, stream);
 }
 
 int tsgnn_eigen_pool_bwd_f32(const float* dxp, int64_t lddxp, const float* fsum, const int* cluster_of, const int* row_graph,

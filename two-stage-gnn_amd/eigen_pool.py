@@ -399,7 +399,9 @@ class _EigenPool(torch.autograd.Function):
         else:
             g1 = lvl.g
             out = torch.empty(g1.total_rows, J * C, dtype=torch.float32, device=dev)
-            nat.call("eigen_pool_fwd_f32", z, z.stride(0), C, g.graph_ptr, g.B, g.nmax, g.n_rows, ghost_mode, g1.graph_ptr, lvl.bptr,
+            # a capacity batch (eigen_stream.py): g1.n_rows is a capacity, and the launch also zeroes the padding rows behind the
+            # batch's own clusters — the pooled level's stack forms X^T dY over every row of `out`
+            nat.call("eigen_pool_fwd_cap_f32" if getattr(g1, "capacity", False) else "eigen_pool_fwd_f32", z, z.stride(0), C, g.graph_ptr, g.B, g.nmax, g.n_rows, ghost_mode, g1.graph_ptr, lvl.bptr,
                      lvl.members, coef, J, 0, out, out.stride(0), g1.n_rows, g1.n_ghost, None, ro, ro.stride(0) if ro is not None else 0, arg)
             ctx.save_for_backward(coef, lvl.cluster_of, arg)
         ctx.g, ctx.final, ctx.ghost_mode, ctx.C, ctx.J, ctx.rows = g, final, ghost_mode, C, J, z.size(0)

@@ -9,8 +9,8 @@ capacity-padded batch (``ingest.CapacityBatch``) of "schedule entry number ``cur
 replayed T times, trains the epoch with no host work per step beyond the replay.
 
 For the GraphSage-family step (``triplet.tripletnet`` over a ``GcnEncoderGraph`` whose conv stack runs as the fused node under
-per-graph statistics); DiffPool, SAGPool and GAT have streams of their own on this module's protocol (``diffpool_stream``,
-``sag_stream``, ``gat_stream``), the EigenGCN family has an assembler of its own.
+per-graph statistics); DiffPool, SAGPool, GAT and EigenGCN have streams of their own on this module's protocol (``diffpool_stream``,
+``sag_stream``, ``gat_stream``, ``eigen_stream``).
 
 ``ArenaStream`` holds what does not depend on the number of graphs a schedule entry names; ``TripletStream`` (three) and
 ``post_train.PostTrainStream`` (one: the anchor of the 2stg+ post-training step) are its users.
