@@ -1494,6 +1494,29 @@ int tsgnn_knn_classify_f32(const float* train, int64_t ld_train, const int* trai
                            int64_t ld_query, int64_t n_query, int64_t dim, int k, int n_classes, const int* query_class, int* confusion,
                            int* pred, int* nbr_index, float* nbr_dist, tsgnn_stream_t stream);
 
+/* ---------------------------------------------------------------- hard / semi-hard negative mining on a schedule (mine.hip)
+ * The reference's TripletSampler.sampler(embed, hardness) (Code/sage+gat+diffpool/triplet_sampler.py:51-77) as ONE launch on the
+ * [T, 3] schedule (anchor, pos, neg: indices into the n_graphs rows of emb) the stream kernels gather from: column 2 is rewritten in
+ * place, columns 0 and 1 are never written, nothing else is written but n_changed.  Distances are sum_d (x_a,d - x_j,d)^2 in
+ * difference form (as the kNN vote above), every one through the same summation order.  The negative CLASS of an entry is
+ * class_of[drawn negative]; its candidates are members[class_ptr[c] .. class_ptr[c + 1]) in that order (the sampler's list order).
+ *   mode 2, hardest:   start from the drawn negative, walk the candidates in list order, take one only when it is strictly closer than
+ *                      the best so far: the drawn negative wins a tie for the minimum, among other tied candidates the earliest list
+ *                      position wins.
+ *   mode 1, semi-hard: the first candidate in list order with d(a, j) < d(a, pos); none: the drawn negative stays.
+ * A comparison with a NaN distance is false, as in the reference.  n_changed (nullable) [1]: += the entries whose negative changed
+ * (an atomic on that word alone; the schedule has one writer per entry and plain stores, so two launches on the same inputs give the
+ * same bytes).  Rows of emb are 16-byte aligned with a stride that is a multiple of 4 floats (what the padding holds does not
+ * matter).  Indices read on the device (sched, class_of, members) are clamped into [0, n_graphs) / [0, n_classes) and the class
+ * pointers into [0, class_ptr[n_classes]] before use: a bad index never leaves the tables.
+ * TSGNN_EINVAL without a launch: a null pointer (n_changed excepted), T < 1, n_graphs < 1, dim < 1, n_classes < 2, mode outside
+ * {1, 2}, ld < dim; TSGNN_EUNSUPPORTED without a launch: emb off 16 bytes, ld % 4 != 0, dim > 1024 (tsgnn_mine_supported), n_graphs
+ * or 3 T at or past 2^31. */
+int tsgnn_mine_supported(int64_t dim, int n_classes);
+int tsgnn_mine_negatives_f32(const float* emb, int64_t ld, int64_t n_graphs, int64_t dim, const int32_t* class_of,
+                             const int32_t* class_ptr, const int32_t* members, int n_classes, int32_t* sched, int64_t T, int mode,
+                             int32_t* n_changed, tsgnn_stream_t stream);
+
 /* ---------------------------------------------------------------- stage two: the MLP probe (mlp_probe.hip)
  * The reference's evaluate_mlp() (Code/sage+gat+diffpool/train_triplet.py:105-183): Linear(dim, h1) - LeakyReLU - Linear(h1, h2) -
  * LeakyReLU - Linear(h2, n_classes), trained with ONE torch.optim.Adam step per training row on the cross-entropy of that row, in row

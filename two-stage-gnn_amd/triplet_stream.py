@@ -232,6 +232,37 @@ class ArenaStream:
         self.T = T
         return T
 
+    def mine(self, emb, index, hardness, count=False):
+        """hard / semi-hard negative mining of the LOADED schedule, in place on the device (``mining.mine_negatives`` on
+        ``self._sched[HEAD:HEAD + 3 T]`` viewed as [T, 3]): ``emb`` = ``two_stage.embed_dataset``'s rows of this stream's graphs,
+        ``index`` = ``mining.class_index(sampler.graphs, graphs)``, ``hardness`` 0 nothing / 0.5 semi-hard / any other positive value
+        hardest.  ``count=True`` -> a one-element int32 device tensor holding the number of entries whose negative changed (else None).
+
+        An epoch boundary, ordered as ``load``'s copy is, by synchronising: a ``GraphedStep`` replays on a stream of its own and
+        does not wait for the caller's, so this waits for the device before the launch (no replay still reads the entries it
+        rewrites) and for the launch after it (every later replay, on whichever stream, finds the mined schedule).  The launch
+        itself runs on the current stream, behind the ``embed_dataset`` that produced ``emb``.
+
+        RuntimeError before ``load``, on a stream whose entries are not triplets (``post_train.PostTrainStream``), and for
+        embeddings with fewer rows than the arena has graphs."""
+        from . import mining
+        name = type(self).__name__
+        if self._sched is None or self.T < 1:
+            raise RuntimeError("%s: load(schedule) before mine()" % name)
+        if self.B != 3:
+            raise RuntimeError("%s: a schedule entry names %d graph(s), not a triplet: there is no negative to mine" % (name, self.B))
+        if emb.dim() != 2 or emb.size(0) < self.arena.n_graphs:
+            raise RuntimeError("%s: embeddings of shape %s do not cover the arena's %d graphs" % (name, tuple(emb.shape), self.arena.n_graphs))
+        if index.n_graphs != self.arena.n_graphs:
+            raise ValueError("%s: the class index was built over %d graphs, the arena holds %d" % (name, index.n_graphs, self.arena.n_graphs))
+        cnt = torch.zeros(1, dtype=torch.int32, device=self.device) if count else None
+        if mining.mode_of(hardness) == 0:
+            return cnt
+        torch.cuda.synchronize(self.device)
+        mining.mine_negatives(emb, self._sched[HEAD:HEAD + 3 * self.T].view(self.T, 3), index, hardness, n_changed=cnt)
+        torch.cuda.current_stream(self.device).synchronize()
+        return cnt
+
     def gather(self):
         """enqueue (current stream; capturable) the launch that writes the batch of the cursor's entry and advances the cursor"""
         if self._sched is None:
