@@ -778,6 +778,14 @@ int tsgnn_gat_assemble_f32(const int64_t* desc, tsgnn_stream_t stream);
 int tsgnn_gat_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words, int64_t max_nr,
                                  int64_t max_nnz, int64_t max_k, const int32_t* sched, int64_t sched_cap, int64_t* state,
                                  unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream);
+/* The same launch for ONE piece per schedule entry: the anchor of the 2stg+ post-training step (train_triplet_pre_train.py:233-262;
+ * host side: gat_stream.PostTrainStream).  The schedule is [T, 1], desc's B = 1, the capacities cover once the arena's largest piece,
+ * the grid is (chunks of the largest piece, 1 + 1); behind the anchor's own [:R'] / [:E'] / [:I'] the padding as above with
+ * row_graph 0, graph_ptr[1] = R', iso_ptr[1] = I'; ids_out[1] = the anchor's index.  The same cursor / ticket protocol on the same
+ * buffer, the same statuses (TSGNN_EINVAL for B != 1 or a capacity below the arena's largest piece). */
+int tsgnn_gat_anchor_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words, int64_t max_nr,
+                                int64_t max_nnz, int64_t max_k, const int32_t* sched, int64_t sched_cap, int64_t* state,
+                                unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream);
 /* Resident one-graph pieces of the EigenGCN encoder -> the complete EigenBatch of a chunk (eigen_pool.concat_batches of the same
  * one-graph batches, word for word): per level graph i = 0..L rowptr [R_i + Nmax + 1] (the Nmax ghost-slot rows empty), col, val,
  * graph_ptr [B + 1], row_graph, row_slot, slot_count [Nmax]; per pooling level i < L cluster_of [R_i] (-1 kept), coef [R_i, J],
@@ -1569,6 +1577,17 @@ int tsgnn_posttrain_head_bwd_f32(const float* r, int64_t ldr, int R, int P, cons
                                  int64_t n_labels, const float* out, const float* z1, const float* z2, const float* p, const float* g_loss,
                                  float* dr, int64_t lddr, float* dw0, float* db0, float* dw1, float* db1, float* dw2, float* db2, float* dw3,
                                  float* db3, tsgnn_stream_t stream);
+/* The same loss on rows z [R, C] (ldz >= C) that are the step's `pred` themselves: a DGATEncoderGraph with final_dim 'output_dim'
+ * returns its max-readout row first (encoders_GAT.py:189-198), so the post-training loop takes F.cross_entropy(F.softmax(pred), label)
+ * over the embedding_dim columns of that row.  _fwd: p [R, C] = softmax(z) (dense), loss[1] = mean_i (logsumexp(p_i) -
+ * p_i[labels[ids[i]]]); _bwd: dz [R, C] (lddz >= C) from p, g_loss (nullable = 1) a device float.  ids / labels as above, read on the
+ * device and clamped.  One launch of one wave each, every sum in a fixed order, no atomics.  2 <= C <= 1024, 1 <= R <= 8
+ * (tsgnn_posttrain_rowloss_supported); TSGNN_EINVAL / TSGNN_EUNSUPPORTED without a launch. */
+int tsgnn_posttrain_rowloss_supported(int C, int R);
+int tsgnn_posttrain_rowloss_fwd_f32(const float* z, int64_t ldz, int R, int C, const int32_t* ids, const int32_t* labels, int64_t n_labels,
+                                    float* p, float* loss, tsgnn_stream_t stream);
+int tsgnn_posttrain_rowloss_bwd_f32(const float* p, int R, int C, const int32_t* ids, const int32_t* labels, int64_t n_labels,
+                                    const float* g_loss, float* dz, int64_t lddz, tsgnn_stream_t stream);
 
 #ifdef __cplusplus
 }

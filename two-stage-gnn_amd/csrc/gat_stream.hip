@@ -18,12 +18,18 @@
 // over the padding.  Cursor and ticket counter: the protocol of csrc/triplet_stream.hip, on the same [HEAD | schedule] buffer.
 // One writer per word, plain vector stores (16 bytes wherever the destination sits on 16 bytes: ga_copy_add, the padding feature
 // rows), the ticket counter is the only atomic.
+//
+// The number of pieces a schedule entry names is a template parameter of the body: 3 is the triplet launch above, 1 the ANCHOR launch of
+// the 2stg+ post-training step (train_triplet_pre_train.py:233-262: one Adam step per anchor graph at B = 1; gat_stream.PostTrainStream).
+// With one piece the schedule entries are one word, the grid is (chunks of the largest piece, 1 + 1), padding rows get row_graph 0,
+// graph_ptr[1] = R, iso_ptr[1] = I and ids_out[0] is the anchor's index.
 #include "gat_assemble_body.h"
 #include "../../include/tsgnn.h"
 
 namespace {
 
 constexpr int GS_B = 3;                   // a triplet
+constexpr int GS_ANCHOR = 1;              // the anchor of a post-training step
 constexpr int GS_REC = 8;                 // int32 words of a record: piece offset (words), n, nr, nnz, k, Nmax - n, index, 0
 
 struct GsArgs {
@@ -33,17 +39,18 @@ struct GsArgs {
   GA_OUTPUT_FIELDS
 };
 
-__global__ __launch_bounds__(256) void gat_triplet_gather_kernel(GsArgs a) {
-  __shared__ int32_t rec_s[GS_B][GS_REC];
+template <int NB>
+__device__ __forceinline__ void gs_gather_body(const GsArgs& a) {
+  __shared__ int32_t rec_s[NB][GS_REC];
   __shared__ long long cur_s;
   const int tid = threadIdx.x;
-  if (tid < GS_B) {
+  if (tid < NB) {
     // (agent-scope load: the word is stored by the last workgroup of the previous launch, never through this CU's scalar cache)
     const long long cur = __hip_atomic_load(reinterpret_cast<long long*>(a.state), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     int64_t T = a.state[1];                                 // the loaded schedule's length: the host's word, kept inside the buffer
     T = T < 1 ? 1 : (T > a.sched_cap ? a.sched_cap : T);
     const int64_t c = (int64_t)((unsigned long long)cur % (unsigned long long)T);
-    int64_t id = a.sched[c * GS_B + tid];
+    int64_t id = a.sched[c * NB + tid];
     id = id < 0 ? 0 : (id >= a.n_graphs ? a.n_graphs - 1 : id);      // (load() validated it; an index never leaves the records)
     const int4 r0 = *reinterpret_cast<const int4*>(a.rec + id * GS_REC);
     const int4 r1 = *reinterpret_cast<const int4*>(a.rec + id * GS_REC + 4);
@@ -62,27 +69,28 @@ __global__ __launch_bounds__(256) void gat_triplet_gather_kernel(GsArgs a) {
     }
   }
   // where each piece goes, and the batch's totals
-  int row0[GS_B + 1], e0[GS_B + 1], i0[GS_B + 1];
+  int row0[NB + 1], e0[NB + 1], i0[NB + 1];
   row0[0] = e0[0] = i0[0] = 0;
 #pragma unroll
-  for (int k = 0; k < GS_B; ++k) {
+  for (int k = 0; k < NB; ++k) {
     row0[k + 1] = row0[k] + rec_s[k][2];
     e0[k + 1] = e0[k] + rec_s[k][3];
     i0[k + 1] = i0[k] + rec_s[k][4];
   }
-  const int64_t R = row0[GS_B], E = e0[GS_B], I = i0[GS_B];
+  const int64_t R = row0[NB], E = e0[NB], I = i0[NB];
   // (the entry point checked the capacities against the arena's bounds; records that break them write nothing)
   if (R > a.row_cap || E > a.nnz_cap || I > a.iso_cap) return;
 
-  if (blockIdx.y < GS_B) {
+  if (blockIdx.y < NB) {
     const int y = blockIdx.y;
     GaPiece q;
     q.src = a.arena + rec_s[y][0];
     q.n = rec_s[y][1]; q.nr = rec_s[y][2]; q.nnz = rec_s[y][3]; q.k = rec_s[y][4]; q.mult = rec_s[y][5];
-    q.row0 = y == 0 ? row0[0] : (y == 1 ? row0[1] : row0[2]);
-    q.e0 = y == 0 ? e0[0] : (y == 1 ? e0[1] : e0[2]);
-    q.i0 = y == 0 ? i0[0] : (y == 1 ? i0[1] : i0[2]);
-    q.gidx = y; q.last = y == GS_B - 1;
+    q.row0 = q.e0 = q.i0 = 0;
+#pragma unroll
+    for (int k = 1; k < NB; ++k)                // (selects, not an indexed read: the prefix arrays stay in registers)
+      if (y == k) { q.row0 = row0[k]; q.e0 = e0[k]; q.i0 = i0[k]; }
+    q.gidx = y; q.last = y == NB - 1;
     int64_t b = blockIdx.x;
     const int kind = ga_kind_of(q, a.ldf, b);
     if (kind == GA_KINDS) return;               // (the grid is sized for the largest piece of the dataset)
@@ -100,7 +108,7 @@ __global__ __launch_bounds__(256) void gat_triplet_gather_kernel(GsArgs a) {
   }
   for (int64_t r = R + i; r < a.row_cap; r += S) {
     a.row_mult[r] = 0.f;
-    a.row_graph[r] = GS_B - 1;
+    a.row_graph[r] = NB - 1;
     a.row_slot[r] = 0;
   }
   for (int v = 0; v < a.nH; ++v) {
@@ -114,23 +122,23 @@ __global__ __launch_bounds__(256) void gat_triplet_gather_kernel(GsArgs a) {
   }
 }
 
-}  // namespace
+__global__ __launch_bounds__(256) void gat_triplet_gather_kernel(GsArgs a) { gs_gather_body<GS_B>(a); }
+__global__ __launch_bounds__(256) void gat_anchor_gather_kernel(GsArgs a) { gs_gather_body<GS_ANCHOR>(a); }
 
-extern "C" {
-
-/* see include/tsgnn.h */
-int tsgnn_gat_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words, int64_t max_nr,
-                                 int64_t max_nnz, int64_t max_k, const int32_t* sched, int64_t sched_cap, int64_t* state,
-                                 unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream) {
+// what the two entry points share: the checks, the description and the launch for NB pieces per schedule entry
+template <int NB>
+int gs_launch(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words, int64_t max_nr, int64_t max_nnz,
+              int64_t max_k, const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket, const int64_t* desc,
+              int32_t* ids_out, hipStream_t stream) {
   if (!records || !arena || !sched || !state || !ticket || !desc || !ids_out) return TSGNN_EINVAL;
   if (n_graphs <= 0 || sched_cap <= 0 || arena_words <= 0 || max_nr < 1 || max_nnz < 0 || max_k < 0 || max_k > max_nr) return TSGNN_EINVAL;
   GsArgs a{};
   int64_t R, E, I, B;
-  if (!ga_unpack_header(desc, a, R, E, I, B) || B != GS_B) return TSGNN_EINVAL;
-  // no schedule entry can overflow an array: the capacities cover three times the arena's largest piece, also when one object fills
-  // all three places.  max_nr / max_nnz / max_k are the caller's word, as the arena is (see tsgnn_triplet_gather_f32)
-  if (R < GS_B * max_nr || E < GS_B * max_nnz || I < GS_B * max_k) return TSGNN_EINVAL;
-  if (arena_words >= ((int64_t)1 << 31) || sched_cap >= ((int64_t)1 << 31) / GS_B || R * a.ldf >= ((int64_t)1 << 31)) return TSGNN_EUNSUPPORTED;
+  if (!ga_unpack_header(desc, a, R, E, I, B) || B != NB) return TSGNN_EINVAL;
+  // no schedule entry can overflow an array: the capacities cover NB times the arena's largest piece, also when one object fills
+  // all of a triplet's three places.  max_nr / max_nnz / max_k are the caller's word, as the arena is (see tsgnn_triplet_gather_f32)
+  if (R < NB * max_nr || E < NB * max_nnz || I < NB * max_k) return TSGNN_EINVAL;
+  if (arena_words >= ((int64_t)1 << 31) || sched_cap >= ((int64_t)1 << 31) / NB || R * a.ldf >= ((int64_t)1 << 31)) return TSGNN_EUNSUPPORTED;
   const uintptr_t al = reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(arena) | reinterpret_cast<uintptr_t>(state);
   if (al & 15) return TSGNN_EUNSUPPORTED;
   a.rec = records; a.n_graphs = n_graphs; a.arena = arena; a.sched = sched; a.sched_cap = sched_cap; a.state = state; a.ticket = ticket;
@@ -140,10 +148,34 @@ int tsgnn_gat_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const
   int64_t most = 0;
   for (int kind = 0; kind < GA_KINDS; ++kind) most += ga_chunks(top, kind, a.ldf);
   if (most >= 65536) return TSGNN_EUNSUPPORTED;
-  TSGNN_KNAME("gat_triplet_gather_kernel");
-  gat_triplet_gather_kernel<<<dim3((unsigned)most, GS_B + 1), 256, 0, stream>>>(a);
+  if (NB == GS_B) {
+    TSGNN_KNAME("gat_triplet_gather_kernel");
+    gat_triplet_gather_kernel<<<dim3((unsigned)most, NB + 1), 256, 0, stream>>>(a);
+  } else {
+    TSGNN_KNAME("gat_anchor_gather_kernel");
+    gat_anchor_gather_kernel<<<dim3((unsigned)most, NB + 1), 256, 0, stream>>>(a);
+  }
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* see include/tsgnn.h */
+int tsgnn_gat_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words, int64_t max_nr,
+                                 int64_t max_nnz, int64_t max_k, const int32_t* sched, int64_t sched_cap, int64_t* state,
+                                 unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream) {
+  return gs_launch<GS_B>(records, n_graphs, arena, arena_words, max_nr, max_nnz, max_k, sched, sched_cap, state, ticket, desc, ids_out, stream);
+}
+
+/* see include/tsgnn.h */
+int tsgnn_gat_anchor_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words, int64_t max_nr,
+                                int64_t max_nnz, int64_t max_k, const int32_t* sched, int64_t sched_cap, int64_t* state,
+                                unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream) {
+  return gs_launch<GS_ANCHOR>(records, n_graphs, arena, arena_words, max_nr, max_nnz, max_k, sched, sched_cap, state, ticket, desc, ids_out,
+                              stream);
 }
 
 }  // extern "C"

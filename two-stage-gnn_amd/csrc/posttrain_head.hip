@@ -324,6 +324,78 @@ __global__ __launch_bounds__(256) void posttrain_head_bwd_kernel(const PtBwd a) 
   }
 }
 
+// The loss alone, on rows that ARE the step's `pred` (DGATEncoderGraph with final_dim 'output_dim' returns the readout row first,
+// encoders_GAT.py:189-198, so train_triplet_pre_train.py:256 takes both soft-maxes over its embedding_dim columns): one wave, lanes
+// along the C <= 1024 columns, rows in order; every sum is a DPP wave sum of per-lane partial sums taken in column order, so two runs
+// give the same bits.
+struct PtRowLoss {
+  const float* z;
+  int64_t ldz;
+  const int *ids, *labels;
+  int n_labels, R, C;
+  float *p, *loss;
+};
+
+struct PtRowLossBwd {
+  const float* p;
+  const int *ids, *labels;
+  const float* g;
+  int n_labels, R, C;
+  float* dz;
+  int64_t lddz;
+};
+
+constexpr int PT_ROW_MAXC = 1024;
+
+__global__ __launch_bounds__(64) void posttrain_rowloss_fwd_kernel(const PtRowLoss a) {
+  const int lane = threadIdx.x, C = a.C;
+  float total = 0.f;
+  for (int i = 0; i < a.R; ++i) {
+    const float* const zi = a.z + (int64_t)i * a.ldz;
+    float m = -INFINITY;
+    for (int c = lane; c < C; c += 64) m = fmaxf(m, zi[c]);
+    m = wave_max(m);
+    float se = 0.f;
+    for (int c = lane; c < C; c += 64) se += expf(zi[c] - m);
+    const float inv = 1.f / wave_sum(se);
+    float pm = 0.f;
+    for (int c = lane; c < C; c += 64) {
+      const float pv = expf(zi[c] - m) * inv;
+      a.p[i * C + c] = pv;
+      pm = fmaxf(pm, pv);
+    }
+    pm = wave_max(pm);
+    float sp = 0.f;
+    for (int c = lane; c < C; c += 64) sp += expf(expf(zi[c] - m) * inv - pm);
+    sp = wave_sum(sp);
+    const int y = pt_label(a.ids, a.labels, a.n_labels, C, i);
+    total += (pm + logf(sp)) - expf(zi[y] - m) * inv;
+  }
+  if (lane == 0) a.loss[0] = total / (float)a.R;
+}
+
+// dp = g (softmax(p) - onehot) / R with the true class as minus the others' sum, then dz_c = p_c (dp_c - sum_k p_k dp_k): what
+// posttrain_head_bwd_kernel does for its logits
+__global__ __launch_bounds__(64) void posttrain_rowloss_bwd_kernel(const PtRowLossBwd a) {
+  const int lane = threadIdx.x, C = a.C;
+  const float scale = (a.g ? a.g[0] : 1.f) / (float)a.R;
+  for (int i = 0; i < a.R; ++i) {
+    const float* const pi = a.p + i * C;
+    const int y = pt_label(a.ids, a.labels, a.n_labels, C, i);
+    float pm = 0.f;
+    for (int c = lane; c < C; c += 64) pm = fmaxf(pm, pi[c]);
+    pm = wave_max(pm);
+    float so = 0.f;
+    for (int c = lane; c < C; c += 64) so += c == y ? 0.f : expf(pi[c] - pm);
+    so = wave_sum(so);
+    const float inv = scale / (expf(pi[y] - pm) + so);
+    float dot = 0.f;
+    for (int c = lane; c < C; c += 64) dot = fmaf(pi[c], (c == y ? -so : expf(pi[c] - pm)) * inv, dot);
+    dot = wave_sum(dot);
+    for (int c = lane; c < C; c += 64) a.dz[(int64_t)i * a.lddz + c] = pi[c] * ((c == y ? -so : expf(pi[c] - pm)) * inv - dot);
+  }
+}
+
 bool pt_dims_ok(int P, int E, int h1, int h2, int C, int R) {
   return P >= 4 && P % 4 == 0 && P <= PT_MAXP && E >= 1 && E <= PT_MAXE && h1 >= 1 && h1 <= PT_MAXH && h2 >= 1 && h2 <= PT_MAXH && C >= 2 &&
          C <= PT_MAXC && R >= 1 && R <= PT_MAXR;
@@ -390,5 +462,31 @@ int tsgnn_posttrain_head_bwd_f32(const float* r, int64_t ldr, int R, int P, cons
 }
 
 #undef TSGNN_PT_DISPATCH
+
+int tsgnn_posttrain_rowloss_supported(int C, int R) { return (C >= 2 && C <= PT_ROW_MAXC && R >= 1 && R <= PT_MAXR) ? 1 : 0; }
+
+int tsgnn_posttrain_rowloss_fwd_f32(const float* z, int64_t ldz, int R, int C, const int32_t* ids, const int32_t* labels, int64_t n_labels,
+                                    float* p, float* loss, hipStream_t stream) {
+  if (!z || !ids || !labels || !p || !loss || n_labels < 1 || n_labels > 0x7fffffff || R < 1 || C < 2 || ldz < C) return TSGNN_EINVAL;
+  if (!tsgnn_posttrain_rowloss_supported(C, R)) return TSGNN_EUNSUPPORTED;
+  PtRowLoss a;
+  a.z = z; a.ldz = ldz; a.ids = ids; a.labels = labels; a.n_labels = (int)n_labels; a.R = R; a.C = C; a.p = p; a.loss = loss;
+  TSGNN_KNAME("posttrain_rowloss_fwd_kernel");
+  posttrain_rowloss_fwd_kernel<<<1, 64, 0, stream>>>(a);
+  TSGNN_CHECK_LAUNCH();
+  return TSGNN_OK;
+}
+
+int tsgnn_posttrain_rowloss_bwd_f32(const float* p, int R, int C, const int32_t* ids, const int32_t* labels, int64_t n_labels,
+                                    const float* g_loss, float* dz, int64_t lddz, hipStream_t stream) {
+  if (!p || !ids || !labels || !dz || n_labels < 1 || n_labels > 0x7fffffff || R < 1 || C < 2 || lddz < C) return TSGNN_EINVAL;
+  if (!tsgnn_posttrain_rowloss_supported(C, R)) return TSGNN_EUNSUPPORTED;
+  PtRowLossBwd a;
+  a.p = p; a.ids = ids; a.labels = labels; a.g = g_loss; a.n_labels = (int)n_labels; a.R = R; a.C = C; a.dz = dz; a.lddz = lddz;
+  TSGNN_KNAME("posttrain_rowloss_bwd_kernel");
+  posttrain_rowloss_bwd_kernel<<<1, 64, 0, stream>>>(a);
+  TSGNN_CHECK_LAUNCH();
+  return TSGNN_OK;
+}
 
 }  // extern "C"

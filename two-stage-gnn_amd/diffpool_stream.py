@@ -7,11 +7,16 @@ lists.  On the capacity-padded batch the gather launch writes, ``diffpool._Contr
 rest of the step already has a fixed shape: both level-0 stacks run as the fused per-graph node on the batch with all of its
 ghost-slot rows, the pooled levels are [3, K, .] (``dense_stack_pg``), the tail is ``triplet._TripletTail``.
 
+``PostTrainStream`` is the same batch at ONE graph per schedule entry: the anchor steps of the 2stg+ post-training phase
+(train_triplet_pre_train.py:233-262 with --method=soft-assign), the concatenated readout rows of every level into the fused head of
+csrc/posttrain_head.hip.  ``DiffPoolChecks`` holds the eligibility checks the two share.
+
 The arena carries ONE feature table: a dataset whose ``assign_feats`` differ from ``feats`` is refused (``ValueError``)."""
 import numpy as np
 import torch
 
 from . import _native as nat
+from . import post_train as PT
 from .triplet_stream import ArenaStream, _graph_dict, check_schedule, pack_arena, schedule_of  # noqa: F401  (the stream's vocabulary)
 
 EAGER = "; use the eager drop-in, tripletnet.forward(a, p, n)"
@@ -32,31 +37,12 @@ def check_assign_feats(graphs):
             raise ValueError("graph %d: assign_feats differ from feats on [:num_nodes] (the arena carries one feature table)%s" % (i, EAGER))
 
 
-class TripletStream(ArenaStream):
-    """``net``: a ``triplet.tripletnet`` over a ``SoftPoolingGcnEncoder`` with concat and bn, num_pooling >= 1 and
-    final_dim == "output_dim"; ``graphs``: the dataset's graph objects.  The interface of ``triplet_stream.TripletStream``: ``load``,
-    ``gather``, ``embed``, ``loss(criterion, target)``, ``position``, ``len``.  TypeError (ending in the eager drop-in) for a model
-    whose stacks do not run as the fused per-graph nodes on the gathered batch or whose first contraction lies outside
-    ``tsgnn_contract_cap_supported``."""
+class DiffPoolChecks:
+    """the eligibility checks of the DiffPool streams, whatever the number ``self.B`` of graphs a schedule entry names"""
 
-    NAME = "diffpool_stream.TripletStream"
-
-    def __init__(self, net, graphs, nmax=None, max_steps=None):
-        graphs = list(graphs)
-        model = getattr(net, "model", None)
-        if not self._model_ok(model):
-            raise TypeError("%s %s%s" % (self.NAME, self._TAKES, EAGER))
-        check_assign_feats(graphs)
-        super().__init__(model, graphs, 3, nmax, max_steps, name=self.NAME, takes=self._TAKES, eager=EAGER)
-        self.net = net
-        self._warm_up_schedule()
-
-    _TAKES = "takes a tripletnet over a SoftPoolingGcnEncoder with concat and bn, num_pooling >= 1 and final_dim == \"output_dim\""
-
-    def _model_ok(self, model):
+    def _family_ok(self, model):
         from .dense_encoders import SoftPoolingGcnEncoder
-        return (type(model) is SoftPoolingGcnEncoder and bool(model.concat) and bool(model.bn) and int(model.num_pooling) >= 1
-                and model.final_dim == "output_dim")
+        return type(model) is SoftPoolingGcnEncoder and bool(model.concat) and bool(model.bn) and int(model.num_pooling) >= 1
 
     def _stacks_ok(self, model):
         """both level-0 stacks as the fused per-graph node on the gathered batch, every pooled stack on dense_stack_pg, the first
@@ -65,7 +51,7 @@ class TripletStream(ArenaStream):
         from . import dense_stack_pg, sage_stack
 
         def refuse(what):
-            raise TypeError("%s: %s%s" % (self.NAME, what, EAGER))
+            raise TypeError("%s: %s%s" % (self.NAME, what, self.EAGER))
         if not (E.FUSED_STACK and E.PER_GRAPH_STACK and E.PER_GRAPH_DENSE and E.READOUT_IN_CONTRACT and E.READOUT_COLUMNS):
             refuse("a fused route of dense_encoders is switched off")
         g, x, fin = self.g, self.x, self.arena.fin
@@ -80,12 +66,38 @@ class TripletStream(ArenaStream):
                 refuse("pooling level %d has no clusters" % i)
             if i == 0 and not (lib.tsgnn_contract_cap_supported(K, F) and lib.tsgnn_ragged_tn_direct_supported(K, int(g.nmax))):
                 refuse("the first contraction (K = %d clusters, F = %d features) lies outside tsgnn_contract_cap_supported" % (K, F))
-            xk = torch.empty(3, K, F, dtype=torch.float32, device=self.device)
-            ak = torch.empty(3, K, K, dtype=torch.float32, device=self.device)
+            xk = torch.empty(self.B, K, F, dtype=torch.float32, device=self.device)
+            ak = torch.empty(self.B, K, K, dtype=torch.float32, device=self.device)
             stacks = [model.conv_stack(i + 1)] + ([model.assign_stack(i + 1)] if i + 1 < model.num_pooling else [])
             if not all(dense_stack_pg.eligible(xk, ak, convs) for convs in stacks):
                 refuse("a stack of pooled level %d (K = %d) lies outside dense_stack_pg" % (i, K))
         return True
+
+
+class TripletStream(DiffPoolChecks, ArenaStream):
+    """``net``: a ``triplet.tripletnet`` over a ``SoftPoolingGcnEncoder`` with concat and bn, num_pooling >= 1 and
+    final_dim == "output_dim"; ``graphs``: the dataset's graph objects.  The interface of ``triplet_stream.TripletStream``: ``load``,
+    ``gather``, ``embed``, ``loss(criterion, target)``, ``position``, ``len``.  TypeError (ending in the eager drop-in) for a model
+    whose stacks do not run as the fused per-graph nodes on the gathered batch or whose first contraction lies outside
+    ``tsgnn_contract_cap_supported``."""
+
+    NAME = "diffpool_stream.TripletStream"
+    EAGER = EAGER
+
+    def __init__(self, net, graphs, nmax=None, max_steps=None):
+        graphs = list(graphs)
+        model = getattr(net, "model", None)
+        if not self._model_ok(model):
+            raise TypeError("%s %s%s" % (self.NAME, self._TAKES, EAGER))
+        check_assign_feats(graphs)
+        super().__init__(model, graphs, 3, nmax, max_steps, name=self.NAME, takes=self._TAKES, eager=EAGER)
+        self.net = net
+        self._warm_up_schedule()
+
+    _TAKES = "takes a tripletnet over a SoftPoolingGcnEncoder with concat and bn, num_pooling >= 1 and final_dim == \"output_dim\""
+
+    def _model_ok(self, model):
+        return self._family_ok(model) and model.final_dim == "output_dim"
 
     def embed(self):
         """gather + the model on the gathered batch -> (dist_p, dist_n, embed_a, embed_p, embed_n), as ``tripletnet.forward`` returns"""
@@ -98,3 +110,34 @@ class TripletStream(ArenaStream):
             out = self.embed()
             return criterion(out[0], out[1], target)
         return step
+
+
+class PostTrainStream(PT.PostTrainSteps, DiffPoolChecks, ArenaStream):
+    """An epoch of the 2stg+ post-training steps with --method=soft-assign from ONE hipGraph: ``post_train.PostTrainStream`` for a
+    ``SoftPoolingGcnEncoder(final_dim='pretrain')`` with concat and bn and num_pooling >= 1 under the installed head
+    (``post_train.install_head``).  Per replay: the gather launch at one graph, ``TripletStream``'s fused levels on it, every level's
+    readout concatenated (P = pred_input_dim * (num_pooling + 1) columns) and the fused head of csrc/posttrain_head.hip, whose label is
+    ``labels[ids_out[0]]`` read on the device.  ``load(anchors)``, ``step()`` -> (loss, pred, out), ``step_loss()``, ``position``,
+    ``len`` as ``post_train.PostTrainStream``; TypeErrors end in ``post_train.post_train_step``; ``mine()`` refuses (no negative)."""
+
+    NAME = "diffpool_stream.PostTrainStream"
+    EAGER = PT.EAGER
+    SIZES = SIZES_ON_DEVICE
+    _TAKES = "takes a SoftPoolingGcnEncoder with concat and bn, num_pooling >= 1 and final_dim == \"pretrain\""
+
+    def __init__(self, model, graphs, nmax=None, max_steps=None):
+        graphs = list(graphs)
+        if not self._model_ok(model):
+            raise TypeError("%s %s%s" % (self.NAME, self._TAKES, self.EAGER))
+        check_assign_feats(graphs)
+        layers = PT.head_layers(model)
+        if layers is not None:                     # (a label the head has no class for: named before anything is packed or uploaded)
+            PT.label_table(graphs, layers[3].out_features)
+        super().__init__(model, graphs, 1, nmax, max_steps, name=self.NAME, takes=self._TAKES, eager=self.EAGER)
+        self._init_post_train(model, graphs, self.NAME, self.EAGER)
+
+    def _model_ok(self, model):
+        return self._family_ok(model) and model.final_dim == "pretrain"
+
+    def _readout_width(self, model):
+        return int(model.pred_input_dim) * (int(model.num_pooling) + 1)

@@ -12,6 +12,10 @@ everything behind the triplet's own R / E / I is inert padding — and advances 
 triplet tail run unchanged on that batch: its host-side sizes are the capacities, the triplet's own sizes live in the row pointers,
 ``graph_ptr`` and ``iso_ptr`` on the device.
 
+``PostTrainStream`` is the same machinery at ONE piece per schedule entry (``tsgnn_gat_anchor_gather_f32``): the anchor steps of the
+2stg+ post-training phase (train_triplet_pre_train.py:233-262), with the loss on the readout row.  ``GatArenaStream`` holds what the two
+share.
+
 No dropout (a ghost representative is exact only while its copies stay identical); anything the stream does not take is a TypeError
 that names the eager drop-in."""
 import numpy as np
@@ -33,7 +37,7 @@ class Arena:
       buf      int32 [words]   every graph's ``gat_triplet.piece_buffer`` (sections at ``tsgnn_gat_assemble_layout``'s offsets, piece-local
                                indices), one behind the other, each piece on 16 bytes
       top      (nr, nnz, k)    the largest of each over the dataset
-      caps     (rows, nnz, k)  three times ``top``: no triplet needs more, also when one object fills all three places (a sampler may
+      caps     (rows, nnz, k)  ``batch`` (3) times ``top``: no triplet needs more, also when one object fills all three places (a sampler may
                                draw an anchor as its own negative's positive; the three largest DISTINCT graphs would not cover that)
       nmax, fin, ldf           what every graph shares: the padded size, the feature width, the 16-byte row stride of the feature rows"""
 
@@ -41,11 +45,12 @@ class Arena:
         self.__dict__.update(kw)
 
 
-def pack_arena(graphs, limit=1 << 31):
+def pack_arena(graphs, limit=1 << 31, batch=3):
     """graph objects (``.graph`` = {'adj', 'feats', 'num_nodes', ...} as cross_val.split_train_val prepares them) -> ``Arena``.
     ValueError, naming the graph's index, for what one ghost representative cannot stand for (``pack_host``'s ``exact`` is False: the
     padded feature rows differ, or ``adj`` is positive outside ``[:n, :n]``), for an Nmax or a feature width that differs from the
-    other graphs', and for offsets that reach ``limit`` (the records are int32).  Host work only: no GPU is touched."""
+    other graphs', and for offsets that reach ``limit`` (the records are int32).  ``batch``: the pieces a schedule entry names (3: a
+    triplet; 1: the anchor of a post-training step); ``caps = batch * top``.  Host work only: no GPU is touched."""
     graphs = list(graphs)
     if not graphs:
         raise ValueError("pack_arena: no graphs")
@@ -75,66 +80,74 @@ def pack_arena(graphs, limit=1 << 31):
         if words >= int(limit):
             raise ValueError("graph %d: pack_arena: offsets reach %d (int32 records): %d buffer words" % (i, limit, words))
     top = tuple(int(rec[:, c].max()) for c in (2, 3, 4))
-    caps = tuple(3 * t for t in top)
+    caps = tuple(int(batch) * t for t in top)
     if max(caps[0] * ldf, caps[1]) >= int(limit):
         raise ValueError("pack_arena: offsets reach %d (int32 records): a batch of %d rows x %d, %d entries" % (limit, caps[0], ldf, caps[1]))
     return Arena(records=rec.astype(np.int32), buf=np.concatenate(bufs), words=words, top=top, caps=caps, nmax=nmax, fin=fin, ldf=ldf,
-                 n_graphs=G)
+                 n_graphs=G, batch=int(batch))
 
 
 def _layers(model):
     return [model.conv_first] + (list(model.conv_block) if model.conv_block is not None else []) + [model.conv_last]
 
 
-class TripletStream(ArenaStream):
-    """``net``: a ``gat_triplet.tripletnet``; ``graphs``: the dataset's graph objects (they are packed once).  The interface of
-    ``triplet_stream.TripletStream``: ``load(schedule)`` (``[T, 3]`` indices into ``graphs``), ``gather``, ``embed``,
-    ``loss(criterion, target)`` (the step for ``GraphedStep``: every call, every replay, consumes the next entry), ``position``,
-    ``ids_out``, ``len``; with ``max_steps`` the stream starts on the one-entry schedule [0, 0, 0].  TypeError (ending in the eager
-    drop-in) for anything that is not a ``gat_triplet.tripletnet``, a model on the CPU, ``resident.RESIDENT`` off, a layer the fused
-    GAT kernels do not take, more than four distinct head counts, attention or input dropout > 0 on any head (whatever the mode)."""
+class GatArenaStream(ArenaStream):
+    """What the GAT streams share, whatever the number ``batch`` of pieces a schedule entry names (3: ``TripletStream``; 1: the anchor
+    of the 2stg+ post-training step, ``PostTrainStream``): the refusals, the arena at ``batch`` times the largest piece, the persistent
+    capacity batch and the gather launch (``tsgnn_gat_triplet_gather_f32`` / ``tsgnn_gat_anchor_gather_f32``).  ``NAME`` and ``EAGER``
+    (where the caller's eager drop-in is) end every TypeError."""
 
-    NAME = "gat_stream.TripletStream"
+    NAME = "gat_stream.GatArenaStream"
+    EAGER = EAGER
+    ENTRY = {3: "gat_triplet_gather_f32", 1: "gat_anchor_gather_f32"}
 
-    def __init__(self, net, graphs, max_steps=None):
-        from . import gat_fused as gf
-        from .gat_encoders import DGATHead, DGATLayer, _fused_layer_ok
+    def _refuse(self, what):
+        raise TypeError("%s %s%s" % (self.NAME, what, self.EAGER))
 
-        def refuse(what):
-            raise TypeError("%s %s%s" % (self.NAME, what, EAGER))
-        if not isinstance(net, gt.tripletnet):
-            refuse("takes a gat_triplet.tripletnet")
-        model = net.model
+    def _refuse_device(self, model):
         dev = next(model.parameters()).device
         if dev.type != "cuda":
-            refuse("runs on the GPU only")
+            self._refuse("runs on the GPU only")
         if not R.RESIDENT:
-            refuse("needs the resident pieces (resident.RESIDENT is off)")
+            self._refuse("needs the resident pieces (resident.RESIDENT is off)")
+        return dev
+
+    def _refuse_layers(self, model):
+        from . import gat_fused as gf
+        from .gat_encoders import DGATLayer
         layers = _layers(model)
         heads = sorted(set(gt.head_counts(model)))
         if len(heads) > 4:
-            refuse("writes the edge-less indicator for at most four distinct head counts (%d)" % len(heads))
+            self._refuse("writes the edge-less indicator for at most four distinct head counts (%d)" % len(heads))
         if len(layers) > gf._LMAX or not all(isinstance(l, DGATLayer) and gf.heads_ok(l.attentions) for l in layers):
-            refuse("needs layers the fused GAT kernels take (gat_fused.heads_ok, at most %d layers)" % gf._LMAX)
-        if any(hd.dropout > 0 for hd in model.modules() if isinstance(hd, DGATHead)) or any(l.dropout > 0 for l in layers):
-            refuse("takes no attention or input dropout (a ghost representative is exact only while its copies stay identical)")
-        ar = self.arena = pack_arena(graphs)
+            self._refuse("needs layers the fused GAT kernels take (gat_fused.heads_ok, at most %d layers)" % gf._LMAX)
+        return heads
+
+    def _refuse_dropout(self, model):
+        from .gat_encoders import DGATHead
+        if any(hd.dropout > 0 for hd in model.modules() if isinstance(hd, DGATHead)) or any(l.dropout > 0 for l in _layers(model)):
+            self._refuse("takes no attention or input dropout (a ghost representative is exact only while its copies stay identical)")
+
+    def _build(self, model, dev, heads, graphs, batch, max_steps):
+        """the arena, the capacity batch and the uploads, once the model passed the refusals"""
+        from . import gat_fused as gf
+        from .gat_encoders import _fused_layer_ok
+        ar = self.arena = pack_arena(graphs, batch=batch)
         if ar.fin != int(model.conv_first.attentions[0].input_dim):
             raise ValueError("%s: the dataset has %d features per node, the model takes %d"
                              % (self.NAME, ar.fin, model.conv_first.attentions[0].input_dim))
-        self.net, self.model, self.device, self.B, self.heads = net, model, dev, 3, heads
+        self.model, self.device, self.B, self.heads = model, dev, int(batch), heads
         self.row_cap, self.nnz_cap, self.iso_cap = ar.caps
         self._allocate()
-        if not all(_fused_layer_ok(l.attentions, self.g, self.row_cap) for l in layers) or not gf.readout_ok(self.g, self.row_cap):
-            refuse("needs the fused GAT node on the gathered batch (the dataset's graphs list up to %d edge-less columns per triplet)"
-                   % self.iso_cap)
+        if not all(_fused_layer_ok(l.attentions, self.g, self.row_cap) for l in _layers(model)) or not gf.readout_ok(self.g, self.row_cap):
+            self._refuse("needs the fused GAT node on the gathered batch (the dataset's graphs list up to %d edge-less columns per %s)"
+                         % (self.iso_cap, "triplet" if self.B == 3 else "entry"))
         self.records = torch.from_numpy(ar.records).to(dev)
         self.buf = torch.from_numpy(ar.buf).to(dev)
-        self.ids_out = torch.zeros(3, dtype=torch.int32, device=dev)
+        self.ids_out = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.max_steps = int(max_steps) if max_steps is not None else None
         self._sched = self._host = self._parts = None
         self.T = 0
-        self._warm_up_schedule()
 
     def _allocate(self):
         """the persistent batch: every array ``gat_fused`` / ``attention`` look up on a ``GraphBatch``, once, at capacity (two
@@ -186,8 +199,30 @@ class TripletStream(ArenaStream):
         ar = self.arena
         if self._parts is None or self._parts[0] is not self._sched:        # (views of the schedule buffer, made once: load() keeps it)
             self._parts = (self._sched, self._sched[HEAD:], self._sched[4:HEAD])
-        nat.call("gat_triplet_gather_f32", self.records, ar.n_graphs, self.buf, ar.words, ar.top[0], ar.top[1], ar.top[2],
+        nat.call(self.ENTRY[self.B], self.records, ar.n_graphs, self.buf, ar.words, ar.top[0], ar.top[1], ar.top[2],
                  self._parts[1], self.max_steps, self._sched, self._parts[2], self._desc.ctypes.data, self.ids_out)
+
+
+class TripletStream(GatArenaStream):
+    """``net``: a ``gat_triplet.tripletnet``; ``graphs``: the dataset's graph objects (they are packed once).  The interface of
+    ``triplet_stream.TripletStream``: ``load(schedule)`` (``[T, 3]`` indices into ``graphs``), ``gather``, ``embed``,
+    ``loss(criterion, target)`` (the step for ``GraphedStep``: every call, every replay, consumes the next entry), ``position``,
+    ``ids_out``, ``len``; with ``max_steps`` the stream starts on the one-entry schedule [0, 0, 0].  TypeError (ending in the eager
+    drop-in) for anything that is not a ``gat_triplet.tripletnet``, a model on the CPU, ``resident.RESIDENT`` off, a layer the fused
+    GAT kernels do not take, more than four distinct head counts, attention or input dropout > 0 on any head (whatever the mode)."""
+
+    NAME = "gat_stream.TripletStream"
+
+    def __init__(self, net, graphs, max_steps=None):
+        if not isinstance(net, gt.tripletnet):
+            self._refuse("takes a gat_triplet.tripletnet")
+        model = net.model
+        dev = self._refuse_device(model)
+        heads = self._refuse_layers(model)
+        self._refuse_dropout(model)
+        self.net = net
+        self._build(model, dev, heads, graphs, 3, max_steps)
+        self._warm_up_schedule()
 
     def embed(self):
         """gather + the encoder on the gathered batch + the triplet tail -> (dist_p, dist_n, embed_a, embed_p, embed_n), as
@@ -202,4 +237,63 @@ class TripletStream(ArenaStream):
         def step():
             out = self.embed()
             return criterion(out[0], out[1], target)
+        return step
+
+
+class PostTrainStream(GatArenaStream):
+    """An epoch of the 2stg+ post-training steps with --method=GAT (train_triplet_pre_train.py:233-262) from ONE hipGraph: per replay
+    the one-piece gather launch (the anchor of "schedule entry number cursor"), the fused GAT layers and the readout over ONE graph's
+    capacity, and the loss on the readout row.
+
+    ``DGATEncoderGraph(final_dim='output_dim')`` returns ``(x, map2_model(map_model(x)))`` with ``x`` the max-readout row
+    (encoders_GAT.py:189-198), so the driver's ``pred`` IS the readout row [1, embedding_dim]: the loss is the reference's doubled
+    soft-max cross-entropy over ``embedding_dim`` columns, ``map_model`` and ``map2_model`` receive no gradient (under
+    ``FlatTrainer(clip=0)`` they do not move: zero moments, which equals Adam skipping them), and a label >= ``embedding_dim`` is an
+    error.  That order is a quirk of the reference, kept literally like the doubled soft-max.
+
+    ``model``: a ``gat_encoders.DGATEncoderGraph`` with ``final_dim == 'output_dim'`` (not a tripletnet); the layer and dropout refusals
+    of ``TripletStream``; TypeErrors end in ``post_train.post_train_step``.  ``load(anchors)``: [T] or [T, 1] indices into ``graphs``
+    (``post_train.check_anchors``).  ``step()`` -> ``(loss, pred, out)``; the label is ``labels[ids_out[0]]``, read on the device.
+    ``out = map2_model(map_model(pred))`` is what the reference's loop binds and never uses: it is computed outside the autograd graph
+    (on ``pred.detach()`` under ``no_grad``), and NOT AT ALL by ``step_loss()``, the callable for ``GraphedStep`` (``step(with_out=False)``
+    returns None in its place).  ``mine()`` refuses: an entry names one graph, there is no negative to mine."""
+
+    NAME = "gat_stream.PostTrainStream"
+    EAGER = "; use the eager drop-in, post_train.post_train_step(model, graph)"
+
+    def __init__(self, model, graphs, max_steps=None):
+        from . import post_train as PT
+        from .gat_encoders import DGATEncoderGraph
+        if not isinstance(model, DGATEncoderGraph):
+            self._refuse("takes a gat_encoders.DGATEncoderGraph")
+        if model.final_dim != "output_dim":
+            self._refuse("takes a model with final_dim = 'output_dim' (the reference's --method=GAT constructor)")
+        self._refuse_dropout(model)
+        graphs = list(graphs)
+        labels = PT.label_table(graphs, model.pred_input_dim)     # (pred has embedding_dim columns: a label past them is an error)
+        dev = self._refuse_device(model)
+        heads = self._refuse_layers(model)
+        self._build(model, dev, heads, graphs, 1, max_steps)
+        self.n_classes = int(model.pred_input_dim)
+        self.labels = torch.from_numpy(labels).to(dev)
+        self._warm_up_schedule()
+
+    def _checked(self, anchors):
+        from . import post_train as PT
+        return PT.check_anchors(anchors, self.arena.n_graphs)
+
+    def step(self, with_out=True):
+        """gather launch + the encoder's readout row + the loss on it -> (loss, pred, out) of the cursor's entry"""
+        from . import post_train as PT
+        if gt.dropout_active(self.model):
+            raise RuntimeError("%s: dropout became active on the model after the stream was built%s" % (self.NAME, self.EAGER))
+        self.gather()
+        pred = gt.readout_rows(self.model, self.x, self.g)
+        loss = PT.row_loss(pred, self.ids_out, self.labels)
+        return loss, pred, (PT.readout_out(self.model, pred) if with_out else None)
+
+    def step_loss(self):
+        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
+        def step():
+            return self.step(with_out=False)[0]
         return step

@@ -11,6 +11,11 @@ twice, kept literally), thousands of times per epoch, without gradient clipping 
 ``map_model``, the three layers, both soft-maxes and the loss are one launch forward and one backward (csrc/posttrain_head.hip) on the
 readout rows of the conv stack; the label of a streamed step is read on the device from the index the gather launch wrote
 (``ids_out``), so a replayed step needs no host word.  ``two_stage.evaluate_pred`` is the phase's ``evaluate()`` (:36-72).
+
+The driver's other two methods: ``diffpool_stream.PostTrainStream`` (``SoftPoolingGcnEncoder``: the same head on the readout rows of every
+level; ``PostTrainSteps`` is what the two share) and ``gat_stream.PostTrainStream`` (``DGATEncoderGraph(final_dim='output_dim')`` returns its
+readout row first, so ``pred`` is that row: ``row_loss`` on it, ``evaluate_readout`` for ``evaluate()``).  ``post_train_step`` has a resident
+branch for each.
 """
 import numpy as np
 import torch
@@ -142,6 +147,53 @@ def apply_head(model, r, ids, labels):
     return head_torch(model, r, labels[ids.long()].long())
 
 
+# ----------------------------------------------------------------------------- the loss on rows that ARE `pred` (the GAT encoder)
+def row_loss_ok(z):
+    """the row-loss launches take the rows ``z`` [R, C]: fp32 on the GPU, unit column stride, widths of ``tsgnn_posttrain_rowloss_supported``"""
+    return (z is not None and z.is_cuda and z.dim() == 2 and z.dtype == torch.float32 and z.stride(1) == 1 and z.stride(0) >= z.size(1)
+            and bool(nat.lib().tsgnn_posttrain_rowloss_supported(int(z.size(1)), int(z.size(0)))))
+
+
+class _RowLoss(torch.autograd.Function):
+    """(rows z [R, C], ids [R] int32, label table int32) -> ``F.cross_entropy(F.softmax(z), labels[ids])``, the label read on the
+    device: tsgnn_posttrain_rowloss_fwd_f32 / _bwd_f32, one launch each way"""
+
+    @staticmethod
+    def forward(ctx, z, ids, labels):
+        R_, C = int(z.size(0)), int(z.size(1))
+        p = torch.empty(R_, C, dtype=torch.float32, device=z.device)
+        loss = torch.empty(1, dtype=torch.float32, device=z.device)
+        nat.call("posttrain_rowloss_fwd_f32", z, z.stride(0), R_, C, ids, labels, int(labels.numel()), p, loss)
+        ctx.save_for_backward(p, ids, labels)
+        ctx.set_materialize_grads(False)
+        return loss.view(())
+
+    @staticmethod
+    def backward(ctx, g):
+        if g is None:
+            return None, None, None
+        p, ids, labels = ctx.saved_tensors
+        R_, C = int(p.size(0)), int(p.size(1))
+        dz = torch.empty(R_, C, dtype=torch.float32, device=p.device)
+        nat.call("posttrain_rowloss_bwd_f32", p, R_, C, ids, labels, int(labels.numel()), g.contiguous().float(), dz, C)
+        return dz, None, None
+
+
+def row_loss(z, ids, labels):
+    """the step's loss on rows that are the reference's ``pred`` themselves (``DGATEncoderGraph``, final_dim 'output_dim'): the fused
+    pair where ``row_loss_ok``, else the torch expression on ``labels[ids]``"""
+    if row_loss_ok(z):
+        return _RowLoss.apply(z, ids, labels)
+    return F.cross_entropy(F.softmax(z, dim=1), labels[ids.long()].long())
+
+
+def readout_out(model, pred):
+    """``out = map2_model(map_model(pred))`` of a ``DGATEncoderGraph`` step (encoders_GAT.py:191-198): the reference's loop binds it and
+    never reads it, so it is computed outside the autograd graph"""
+    with torch.no_grad():
+        return model.map2_model(model.map_model(pred.detach()))
+
+
 def _readout(model, x, g, sizes, assign_x):
     """the model up to its concatenated readout rows under the statistics of a B = 1 call (``_heads`` honours ``_defer_map`` for
     "pretrain"); the flag is put back on every exit path"""
@@ -180,13 +232,29 @@ def post_train_step(model, graph):
     """forward of the reference's post-training step (:240-256) on one graph object (``.graph`` = {'adj', 'feats', 'num_nodes',
     'assign_feats', 'label'}) -> (loss, pred, out); the caller runs ``backward`` and the optimiser.  A plain ``GcnEncoderGraph`` with
     final_dim "pretrain" takes the graph's resident pieces from the model's ``ResidentCache`` and applies the fused head to its readout
-    row; any other model gets the module call on the dense arrays and the torch expression."""
+    row; so does a ``SoftPoolingGcnEncoder`` (its rows hold every level's readout: P = pred_input_dim * (num_pooling + 1)).
+    A ``gat_encoders.DGATEncoderGraph`` with final_dim "output_dim" (no dropout active, a graph one ghost representative stands
+    for) takes its resident piece through ``gat_triplet.assemble`` at B = 1: ``pred`` is the max-readout row itself
+    (encoders_GAT.py:189-198: the model returns it first), the loss is ``row_loss`` over its ``embedding_dim`` columns, ``map_model`` and
+    ``map2_model`` receive no gradient and ``out`` is computed outside the autograd graph; a label >= ``embedding_dim`` is a ValueError.
+    Any other model gets the module call on the dense arrays and the torch expression."""
+    from . import gat_triplet as GT
     from . import triplet as T
-    from .dense_encoders import GcnEncoderGraph
+    from .dense_encoders import GcnEncoderGraph, SoftPoolingGcnEncoder
+    from .gat_encoders import DGATEncoderGraph
     dev = next(model.parameters()).device
     d = graph.graph
     label = _label_of(d)
-    if (R.RESIDENT and dev.type == "cuda" and type(model) is GcnEncoderGraph and model.final_dim == "pretrain"
+    if isinstance(model, DGATEncoderGraph) and model.final_dim == "output_dim":
+        if not 0 <= label < int(model.pred_input_dim):
+            raise ValueError("label %d lies outside [0, %d): pred is the readout row of embedding_dim columns" % (label, model.pred_input_dim))
+        if GT.packable(model, dev):
+            piece = GT.resident_piece(graph, dev, R.resident_cache(model))
+            if piece.exact:
+                x, g = GT.assemble([piece], dev, GT.head_counts(model))
+                pred = GT.readout_rows(model, x, g)
+                return row_loss(pred, _const_i32(dev, 0), _const_i32(dev, label)), pred, readout_out(model, pred)
+    if (R.RESIDENT and dev.type == "cuda" and type(model) in (GcnEncoderGraph, SoftPoolingGcnEncoder) and model.final_dim == "pretrain"
             and isinstance(getattr(model, "map_model", None), nn.Linear)):
         g, x, xa, sizes = T.assemble([T.resident_graph(graph, dev, R.resident_cache(model))], dev)
         r = _readout(model, x, g, sizes, x if xa is None else xa)
@@ -218,25 +286,26 @@ def check_anchors(anchors, n_graphs):
     return check_schedule(s, n_graphs, 1)
 
 
-class PostTrainStream(ArenaStream):
-    """An epoch of post-training steps from ONE hipGraph: the arena of ``triplet_stream.pack_arena(..., batch=1)``, a device label
-    table, and per replay the gather launch (the anchor of "schedule entry number cursor"), the fused per-graph conv stack on the
-    gathered capacity-padded batch and the fused head, whose label is ``labels[ids_out[0]]`` read on the device.
+class PostTrainSteps:
+    """What the post-training streams over an ``ArenaStream`` at ``batch=1`` share (this module's for the plain ``GcnEncoderGraph``,
+    ``diffpool_stream.PostTrainStream`` for DiffPool): the final_dim and head refusals, the device label table, ``check_anchors`` and
+    the step — the model's concatenated readout rows under per-graph statistics with ``_defer_map``, then the fused head, whose
+    label is ``labels[ids_out[0]]`` read on the device.  ``SIZES``: what the model's forward gets as ``batch_num_nodes``;
+    ``_readout_width(model)``: the columns of its concatenated readout rows."""
 
-    ``model``: what ``TripletStream`` takes (a plain ``GcnEncoderGraph`` with concat and bn whose stack runs as the fused node on the
-    gathered batch) with final_dim "pretrain" and the installed head of ``head_ok``'s shape; anything else is a TypeError pointing to
-    ``post_train_step``.  ``load(anchors)``: [T] or [T, 1] indices into ``graphs`` (``schedule_of(sampler, graphs)[:, :1]`` is the
-    reference's epoch).  ``step_loss()`` is the callable for ``GraphedStep``.  ``max_steps``: as ``TripletStream``."""
+    SIZES = None
 
-    def __init__(self, model, graphs, nmax=None, max_steps=None):
-        graphs = list(graphs)
-        super().__init__(model, graphs, 1, nmax, max_steps, name="PostTrainStream",
-                         takes="takes a GcnEncoderGraph with concat and bn", eager=EAGER)
+    def _readout_width(self, model):
+        return int(model.pred_input_dim)
+
+    def _init_post_train(self, model, graphs, name, eager):
+        self._pt_name, self._pt_eager = name, eager
         if model.final_dim != "pretrain":
-            raise TypeError("PostTrainStream takes a model with final_dim = 'pretrain'" + EAGER)
+            raise TypeError("%s takes a model with final_dim = 'pretrain'%s" % (name, eager))
         layers = head_layers(model)
-        if not _layers_fit(layers, 1, self.device) or layers[0].in_features != model.pred_input_dim or model.pred_input_dim % 4:
-            raise TypeError("PostTrainStream: map_model / map2_model are not the head the fused launches take (post_train.install_head)" + EAGER)
+        P = self._readout_width(model)
+        if not _layers_fit(layers, 1, self.device) or layers[0].in_features != P or P % 4:
+            raise TypeError("%s: map_model / map2_model are not the head the fused launches take (post_train.install_head)%s" % (name, eager))
         self.n_classes = int(layers[3].out_features)
         self.labels = torch.from_numpy(label_table(graphs, self.n_classes)).to(self.device)
         self._warm_up_schedule()
@@ -247,9 +316,9 @@ class PostTrainStream(ArenaStream):
     def step(self):
         """gather launch + the stack's readout row + the head -> (loss, pred, out) of the cursor's entry"""
         self.gather()
-        r = _readout(self.model, self.x, self.g, None, self.x)
+        r = _readout(self.model, self.x, self.g, self.SIZES, self.x)
         if not head_ok(self.model, r):
-            raise RuntimeError("PostTrainStream: the fused head does not take this model's readout rows" + EAGER)
+            raise RuntimeError("%s: the fused head does not take this model's readout rows%s" % (self._pt_name, self._pt_eager))
         return apply_head(self.model, r, self.ids_out, self.labels)
 
     def step_loss(self):
@@ -257,3 +326,68 @@ class PostTrainStream(ArenaStream):
         def step():
             return self.step()[0]
         return step
+
+
+class PostTrainStream(PostTrainSteps, ArenaStream):
+    """An epoch of post-training steps from ONE hipGraph: the arena of ``triplet_stream.pack_arena(..., batch=1)``, a device label
+    table, and per replay the gather launch (the anchor of "schedule entry number cursor"), the fused per-graph conv stack on the
+    gathered capacity-padded batch and the fused head, whose label is ``labels[ids_out[0]]`` read on the device.
+
+    ``model``: what ``TripletStream`` takes (a plain ``GcnEncoderGraph`` with concat and bn whose stack runs as the fused node on the
+    gathered batch) with final_dim "pretrain" and the installed head of ``head_ok``'s shape; anything else is a TypeError pointing to
+    ``post_train_step``.  ``load(anchors)``: [T] or [T, 1] indices into ``graphs`` (``schedule_of(sampler, graphs)[:, :1]`` is the
+    reference's epoch).  ``step_loss()`` is the callable for ``GraphedStep``.  ``max_steps``: as ``TripletStream``.
+    ``gat_stream.PostTrainStream`` and ``diffpool_stream.PostTrainStream`` are the same phase for the other two methods of the driver."""
+
+    def __init__(self, model, graphs, nmax=None, max_steps=None):
+        graphs = list(graphs)
+        super().__init__(model, graphs, 1, nmax, max_steps, name="PostTrainStream",
+                         takes="takes a GcnEncoderGraph with concat and bn", eager=EAGER)
+        self._init_post_train(model, graphs, "PostTrainStream", EAGER)
+
+
+# ----------------------------------------------------------------------------- evaluate() of a model whose `pred` is its readout row
+def predict_readout(graphs, model, chunk=None):
+    """class index per graph, int32 on the model's device: the argmax (a tie to the lowest index) of the readout row of a
+    ``gat_encoders.DGATEncoderGraph`` — the reference's ``evaluate()`` (train_triplet_pre_train.py:36-72) takes ``torch.max`` of the
+    model's FIRST output, which for final_dim 'output_dim' is that row.  The rows come from the packed chunks ``two_stage.embed_dataset``
+    builds for GAT (``gat_triplet.assemble`` of resident pieces; a chunk holding a graph that cannot be packed takes one dense B = 1
+    call per graph), in eval mode without autograd"""
+    from . import gat_triplet as GT
+    from . import two_stage as TS
+    from .gat_encoders import DGATEncoderGraph
+    if not isinstance(model, DGATEncoderGraph):
+        raise TypeError("predict_readout takes a gat_encoders.DGATEncoderGraph; two_stage.predict_dataset serves the other encoders")
+    graphs = TS._flatten(graphs)
+    dev = next(model.parameters()).device
+    if not graphs:
+        return torch.zeros(0, dtype=torch.int32, device=dev)
+    step = int(chunk) if chunk is not None else GT.DEFAULT_CHUNK
+    if step < 1:
+        raise ValueError("chunk must be at least 1")
+    cache, rows = R.cache_for(model), []
+    with TS._eval_mode(model):
+        for i in range(0, len(graphs), step):
+            part = graphs[i:i + step]
+            pieces = [GT.resident_piece(o, dev, cache) for o in part] if GT.packable(model, dev) else None
+            if pieces is not None and all(q.exact for q in pieces):
+                rows.append(GT.readout_rows(model, *GT.assemble(pieces, dev, GT.head_counts(model))))
+            else:
+                for o in part:
+                    dd = o.graph
+                    adj = torch.as_tensor(np.asarray(dd["adj"], dtype=np.float32)[None], device=dev)
+                    h0 = torch.as_tensor(np.asarray(dd["feats"], dtype=np.float32)[None], device=dev)
+                    rows.append(model(h0, adj, None)[0])
+        z = torch.cat(rows)
+    return (z == z.max(dim=1, keepdim=True).values).int().argmax(dim=1).int()      # (the first maximum: the lowest index)
+
+
+def evaluate_readout(graphs, model, chunk=None):
+    """``two_stage.evaluate_pred`` for a model whose ``pred`` is its readout row (``predict_readout``): the same metrics dictionary
+    {'prec' (macro), 'recall' (macro), 'acc', 'F1' (micro)} against ``graph.graph['label']``"""
+    from . import two_stage as TS
+    graphs = TS._flatten(graphs)
+    y = TS._labels(graphs).reshape(-1)
+    pred = predict_readout(graphs, model, chunk).cpu().numpy().astype(np.int64)
+    labels = np.unique(np.concatenate([y.astype(np.int64), pred]))
+    return TS.metrics_from_confusion(TS.confusion_matrix(y, pred, labels))
