@@ -206,6 +206,15 @@ int tsgnn_sag_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const
                                  const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket, int64_t row_cap,
                                  int64_t nnz_cap, float ratio, int depth, int32_t* rowptr, int32_t* col, float* x, int64_t ldx,
                                  float* dinv, float* self_w, int32_t* graph_ptr, int32_t* ids_out, tsgnn_stream_t stream);
+/* The same body for ONE graph per entry: the anchor of the 2stg+ post-training step (Code/sag/train_triplet_pre_train.py:219-263).
+ * Schedule [T, 1]; need_rows / need_nnz: ONCE the arena's largest n / nnz (a capacity below them: TSGNN_EINVAL); graph_ptr row of
+ * level l = (0, k_l, k_l, k_l) (one 16-byte store: words 2 and 3 repeat the total); ids_out[1]; rowptr[row_cap] = the anchor's nnz;
+ * padding rows as above (empty, x = +0, dinv = self_w = 0).  Same cursor / ticket protocol, same statuses without a launch. */
+int tsgnn_sag_anchor_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t off_rowptr, int64_t off_col,
+                                int64_t arena_words, const float* feats, int64_t ldf, int64_t need_rows, int64_t need_nnz,
+                                const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket, int64_t row_cap,
+                                int64_t nnz_cap, float ratio, int depth, int32_t* rowptr, int32_t* col, float* x, int64_t ldx,
+                                float* dinv, float* self_w, int32_t* graph_ptr, int32_t* ids_out, tsgnn_stream_t stream);
 
 /* CSR transpose (A^T for dX = A^T dY); rows of the result sorted by column; src_e[p] = source entry */
 int tsgnn_csr_transpose(const int* rowptr, const int* col, const float* val, int64_t n_rows, int64_t n_cols,
@@ -836,6 +845,14 @@ int tsgnn_eigen_assemble_f32(const int64_t* desc, tsgnn_stream_t stream);
 int tsgnn_eigen_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words,
                                    const int64_t* top_n, const int64_t* top_nnz, const int32_t* sched, int64_t sched_cap, int64_t* state,
                                    unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream);
+/* The same body for ONE piece per entry: the anchor of the 2stg+ post-training step (Code/eigengcn/train_triplet_pre_train.py:192-247).
+ * Schedule [T, 1]; the header's K = B = 1; capacities cover ONCE top_n[i] / top_nnz[i] per level (below that: TSGNN_EINVAL); grid
+ * (most, 1 + 1); padding row_graph_i 0; graph_ptr_i[1] = the anchor's rows; bptr_i sized for one graph ([R_{i+1} + 2], closing entry at
+ * R'_{i+1} + 1); ids_out[1]; everything behind the anchor's own R'_i / E'_i inert as above.  Same cursor / ticket protocol, same statuses
+ * without a launch. */
+int tsgnn_eigen_anchor_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words,
+                                  const int64_t* top_n, const int64_t* top_nnz, const int32_t* sched, int64_t sched_cap, int64_t* state,
+                                  unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream);
 /* ELU (encoders_GAT.py:47) / mean over heads then ELU (:78-83) */
 int tsgnn_elu_heads_fwd_f32(const float* x, int64_t rows, int H, int Fh, int mean_heads, int apply_elu, float* y, tsgnn_stream_t stream);
 int tsgnn_elu_heads_bwd_f32(const float* x, const float* dy, int64_t rows, int H, int Fh, int mean_heads, int apply_elu, float* dx,
@@ -1588,6 +1605,44 @@ int tsgnn_posttrain_rowloss_fwd_f32(const float* z, int64_t ldz, int R, int C, c
                                     float* p, float* loss, tsgnn_stream_t stream);
 int tsgnn_posttrain_rowloss_bwd_f32(const float* p, int R, int C, const int32_t* ids, const int32_t* labels, int64_t n_labels,
                                     const float* g_loss, float* dz, int64_t lddz, tsgnn_stream_t stream);
+
+/* ---- classification heads of the post-training step of SAGPool and EigenGCN (posttrain_cls.hip): the "original" setting's step at
+ * B = 1 on a graph the stream's schedule names.  Readout rows r [R, .] (ldr >= the row, ldr % 4 == 0, 16-byte aligned; what the
+ * padding holds does not matter), 1 <= R <= 8; ids [R] / labels [n_labels] as tsgnn_posttrain_head_fwd_f32 takes them: read on the
+ * device and clamped into their ranges.  Weights in nn.Linear's [out, in] layout, dense; biases nullable.  _fwd: ONE launch of one
+ * workgroup.  _bwd: ONE launch, a grid over 32-column slices of r that owns dr (nullable, lddr >= the row) and the first layer's weight
+ * gradient, every workgroup re-deriving the short chain in LDS; g_loss (nullable = 1): the upstream gradient of loss, a device float.
+ * Every output element is written once, every reduction runs in a fixed order, no atomic read-modify-write, no hand-off between
+ * workgroups: two runs give the same bits.  TSGNN_EINVAL / TSGNN_EUNSUPPORTED without a launch.
+ *
+ * mlp3 + nll (Code/sag/train_triplet_pre_train.py:219-263 on network.py:48-53): a1 [R, D1] = dropout(relu(lin1(r))), a2 [R, D2] =
+ * relu(lin2(a1)) (both kept for the backward), logp [R, C] = log_softmax(lin3(a2)), loss[1] = mean_i -logp[i, label_i].  p > 0: the
+ * mask is made inside the launch exactly as tsgnn_mlp3_fwd_drop_f32 makes it for B = R (same seed / state / used words: the launch
+ * advances state[0] — one workgroup, so a plain agent-scope load and store —, tsgnn_mlp3_dropout_mask_f32(p, seed, used[0], R, D1)
+ * regenerates the mask); p == 0: state / used unused.  keep_scale = 1 / (1 - p) for the backward.  Taken: the widths of
+ * tsgnn_mlp3_triplet_supported with 2 <= C; w1 / w2 / w3 16-byte aligned. */
+int tsgnn_posttrain_mlp3_nll_supported(int D0, int D1, int D2, int C, int R);
+int tsgnn_posttrain_mlp3_nll_fwd_f32(const float* r, int64_t ldr, int R, const float* w1, const float* b1, float p, uint64_t seed,
+                                     unsigned long long* state, unsigned long long* used, const float* w2, const float* b2,
+                                     const float* w3, const float* b3, int D0, int D1, int D2, int C, const int32_t* ids,
+                                     const int32_t* labels, int64_t n_labels, float* a1, float* a2, float* logp, float* loss,
+                                     tsgnn_stream_t stream);
+int tsgnn_posttrain_mlp3_nll_bwd_f32(const float* r, int64_t ldr, int R, const float* w1, const float* w2, const float* w3, int D0, int D1,
+                                     int D2, int C, float keep_scale, const int32_t* ids, const int32_t* labels, int64_t n_labels,
+                                     const float* a1, const float* a2, const float* logp, const float* g_loss, float* dr, int64_t lddr,
+                                     float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, tsgnn_stream_t stream);
+/* mlp2 + cross-entropy (Code/eigengcn/train_triplet_pre_train.py:170-249: WavePoolingGcnEncoder.pred_model = Linear - ReLU - Linear,
+ * then model.loss = F.cross_entropy): h [R, H] = relu(W1 r + b1) (kept), z [R, C] = W2 h + b2 (the step's ypred), p [R, C] =
+ * softmax(z) (kept), loss[1] = mean_i (logsumexp(z_i) - z_i[label_i]).  Taken: the widths of tsgnn_mlp2_triplet_supported (D % 4 == 0,
+ * D <= 2048, H <= 512, C <= 512) with 2 <= C; H need not be a multiple of 4 (pred_hidden_dims = [50]); w1 16-byte aligned. */
+int tsgnn_posttrain_mlp2_ce_supported(int D, int H, int C, int R);
+int tsgnn_posttrain_mlp2_ce_fwd_f32(const float* r, int64_t ldr, int R, const float* w1, const float* b1, const float* w2, const float* b2,
+                                    int D, int H, int C, const int32_t* ids, const int32_t* labels, int64_t n_labels, float* h, float* z,
+                                    float* p, float* loss, tsgnn_stream_t stream);
+int tsgnn_posttrain_mlp2_ce_bwd_f32(const float* r, int64_t ldr, int R, const float* w1, const float* w2, int D, int H, int C,
+                                    const int32_t* ids, const int32_t* labels, int64_t n_labels, const float* h, const float* p,
+                                    const float* g_loss, float* dr, int64_t lddr, float* dw1, float* db1, float* dw2, float* db2,
+                                    tsgnn_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -21,11 +21,18 @@
 // that strides over the closing entries, the padding and the slot counts.  Cursor and ticket counter: the protocol of
 // csrc/triplet_stream.hip, on the same [HEAD | schedule] buffer.  One writer per word, plain vector stores (16 bytes wherever the
 // destination sits on 16 bytes: ea_copy, es_fill), the ticket counter is the only atomic.
+//
+// The number of pieces a schedule entry names is a template parameter of the body: 3 is the triplet launch above, 1 the ANCHOR launch of
+// the 2stg+ post-training step (Code/eigengcn/train_triplet_pre_train.py:192-247: one optimiser step on the sampler's anchor at
+// B = 1) — a schedule [T, 1], a header with B = 1, capacities of ONE largest piece per level, grid (most, 1 + 1), padding row_graph 0,
+// graph_ptr_i[1] = the anchor's rows, bucket pointers sized for one graph, ids_out [1]; everything behind the anchor's own R_i / E_i
+// inert as above.
 #include "eigen_assemble_body.h"
 
 namespace {
 
 constexpr int ES_B = 3;                   // a triplet
+constexpr int ES_ANCHOR = 1;              // the anchor alone
 constexpr int ES_REC = 12;                // int32 words of a record: piece offset (words), index, n[0..3], nnz[0..3], 0, 0
 
 struct EsArgs {
@@ -46,18 +53,19 @@ __device__ __forceinline__ void es_fill(int* __restrict__ dst, int64_t lo, int64
   for (int64_t w = (v0 >> 2) + i; w < (v1 >> 2); w += S) reinterpret_cast<ea_i4*>(dst)[w] = o;
 }
 
-__global__ __launch_bounds__(256) void eigen_triplet_gather_kernel(EsArgs a) {
-  __shared__ int32_t rec_s[ES_B][ES_REC];
+template <int NB>
+__device__ __forceinline__ void es_gather_body(const EsArgs& a) {
+  __shared__ int32_t rec_s[NB][ES_REC];
   __shared__ long long cur_s;
   __shared__ EaPiece q_s;                     // this workgroup's piece (LDS: ea_piece_block indexes its levels at run time)
   const int tid = threadIdx.x;
-  if (tid < ES_B) {
+  if (tid < NB) {
     // (agent-scope load: the word is stored by the last workgroup of the previous launch, never through this CU's scalar cache)
     const long long cur = __hip_atomic_load(reinterpret_cast<long long*>(a.state), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     int64_t T = a.state[1];                                 // the loaded schedule's length: the host's word, kept inside the buffer
     T = T < 1 ? 1 : (T > a.sched_cap ? a.sched_cap : T);
     const int64_t c = (int64_t)((unsigned long long)cur % (unsigned long long)T);
-    int64_t id = a.sched[c * ES_B + tid];
+    int64_t id = a.sched[c * NB + tid];
     id = id < 0 ? 0 : (id >= a.n_graphs ? a.n_graphs - 1 : id);      // (load() validated it; an index never leaves the records)
     const int4* r = reinterpret_cast<const int4*>(a.rec + id * ES_REC);
     const int4 r0 = r[0], r1 = r[1], r2 = r[2];
@@ -87,7 +95,7 @@ __global__ __launch_bounds__(256) void eigen_triplet_gather_kernel(EsArgs a) {
     R[i] = E[i] = 0;
     if (i < nlev) {
 #pragma unroll
-      for (int k = 0; k < ES_B; ++k) {
+      for (int k = 0; k < NB; ++k) {
         const int n = rec_s[k][2 + i], z = rec_s[k][2 + EA_LMAX + i];
         ok = ok && n >= 0 && n <= h.nmax && z >= 0 && R[i] <= h.R[i] - n && E[i] <= h.E[i] - z;
         R[i] += n; E[i] += z;
@@ -96,7 +104,7 @@ __global__ __launch_bounds__(256) void eigen_triplet_gather_kernel(EsArgs a) {
   }
   if (!ok) return;
 
-  if (blockIdx.y < ES_B) {
+  if (blockIdx.y < NB) {
     const int y = blockIdx.y;
     EaPiece& q = q_s;
     if (tid == 0) {
@@ -121,18 +129,18 @@ __global__ __launch_bounds__(256) void eigen_triplet_gather_kernel(EsArgs a) {
 
   // the closing entries, the padding and the slot counts: this row of workgroups strides over them
   const int64_t i = (int64_t)blockIdx.x * 256 + tid, S = (int64_t)gridDim.x * 256;
-  if (i < ES_B) a.ids_out[i] = rec_s[i][1];
+  if (i < NB) a.ids_out[i] = rec_s[i][1];
 #pragma unroll
   for (int v = 0; v < EA_LMAX; ++v) {
     if (v >= nlev) continue;
     es_fill(h.rowptr[v], R[v], (int64_t)h.R[v] + h.nmax + 1, E[v], i, S);
-    es_fill(h.row_graph[v], R[v], h.R[v], ES_B - 1, i, S);
+    es_fill(h.row_graph[v], R[v], h.R[v], NB - 1, i, S);
     es_fill(h.row_slot[v], R[v], h.R[v], 0, i, S);
-    if (i == 0) h.graph_ptr[v][ES_B] = R[v];
+    if (i == 0) h.graph_ptr[v][NB] = R[v];
     for (int64_t s = i; s < h.nmax; s += S) {
       int cnt = 0;
 #pragma unroll
-      for (int k = 0; k < ES_B; ++k) cnt += rec_s[k][2 + v] > s ? 1 : 0;
+      for (int k = 0; k < NB; ++k) cnt += rec_s[k][2 + v] > s ? 1 : 0;
       h.slot_count[v][s] = cnt;
     }
   }
@@ -144,35 +152,34 @@ __global__ __launch_bounds__(256) void eigen_triplet_gather_kernel(EsArgs a) {
     if (v >= L) continue;
     es_fill(h.cluster_of[v], R[v], h.R[v], -1, i, S);
     es_fill(reinterpret_cast<int*>(h.coef[v]), (int64_t)R[v] * h.J, (int64_t)h.R[v] * h.J, 0, i, S);
-    es_fill(h.bptr[v], (int64_t)R[v + 1] + ES_B, (int64_t)h.R[v + 1] + ES_B + 1, R[v], i, S);
+    es_fill(h.bptr[v], (int64_t)R[v + 1] + NB, (int64_t)h.R[v + 1] + NB + 1, R[v], i, S);
   }
   if (h.Jf > 0) es_fill(reinterpret_cast<int*>(h.final_coef), (int64_t)RL * h.Jf, (int64_t)h.R[L] * h.Jf, 0, i, S);
   es_fill(reinterpret_cast<int*>(h.x), (int64_t)R[0] * h.ldf, ((int64_t)h.R[0] + h.nmax) * h.ldf, 0, i, S);
 }
 
-}  // namespace
+__global__ __launch_bounds__(256) void eigen_triplet_gather_kernel(EsArgs a) { es_gather_body<ES_B>(a); }
+__global__ __launch_bounds__(256) void eigen_anchor_gather_kernel(EsArgs a) { es_gather_body<ES_ANCHOR>(a); }
 
-extern "C" {
-
-/* see include/tsgnn.h */
-int tsgnn_eigen_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words,
-                                   const int64_t* top_n, const int64_t* top_nnz, const int32_t* sched, int64_t sched_cap, int64_t* state,
-                                   unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream) {
+template <int NB>
+int es_gather_launch(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words, const int64_t* top_n,
+                     const int64_t* top_nnz, const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket, const int64_t* desc,
+                     int32_t* ids_out, tsgnn_stream_t stream) {
   if (!records || !arena || !top_n || !top_nnz || !sched || !state || !ticket || !desc || !ids_out) return TSGNN_EINVAL;
   if (n_graphs <= 0 || sched_cap <= 0 || arena_words <= 0) return TSGNN_EINVAL;
   EsArgs a{};
-  if (!ea_unpack_header(desc, a.h) || a.h.B != ES_B) return TSGNN_EINVAL;
+  if (!ea_unpack_header(desc, a.h) || a.h.B != NB) return TSGNN_EINVAL;
   const EaHead& h = a.h;
-  // no schedule entry can overflow an array: the capacities cover three times the arena's largest piece at every level, also when
-  // one object fills all three places.  top_n / top_nnz are the caller's word, as the arena is (see tsgnn_triplet_gather_f32)
+  // no schedule entry can overflow an array: the capacities cover NB times the arena's largest piece at every level, also when
+  // one object fills every place.  top_n / top_nnz are the caller's word, as the arena is (see tsgnn_triplet_gather_f32)
   EaPiece top{};
   for (int i = 0; i < h.nlev; ++i) {
     if (top_n[i] < 1 || top_n[i] > h.nmax || top_nnz[i] < 0) return TSGNN_EINVAL;
-    if (h.R[i] < ES_B * top_n[i] || h.E[i] < ES_B * top_nnz[i]) return TSGNN_EINVAL;
+    if (h.R[i] < NB * top_n[i] || h.E[i] < NB * top_nnz[i]) return TSGNN_EINVAL;
     top.n[i] = (int)top_n[i]; top.nnz[i] = (int)top_nnz[i];
   }
   const int64_t lim = (int64_t)1 << 31;
-  if (arena_words >= lim || sched_cap >= lim / ES_B || n_graphs >= lim / ES_REC) return TSGNN_EUNSUPPORTED;
+  if (arena_words >= lim || sched_cap >= lim / NB || n_graphs >= lim / ES_REC) return TSGNN_EUNSUPPORTED;
   if (((int64_t)h.R[0] + h.nmax) * h.ldf >= lim) return TSGNN_EUNSUPPORTED;
   for (int i = 0; i < h.nlev; ++i)
     if ((int64_t)h.R[i] * (i < h.nlev - 1 ? h.J : (h.Jf > 0 ? h.Jf : 1)) >= lim) return TSGNN_EUNSUPPORTED;
@@ -183,10 +190,33 @@ int tsgnn_eigen_triplet_gather_f32(const int32_t* records, int64_t n_graphs, con
   int64_t most = 0;                                        // the largest piece per kind (no piece of a triplet closes the batch)
   for (int kind = 0; kind < ea_kinds(h.nlev); ++kind) most += ea_chunks(ea_len(h, top, kind));
   if (most >= 65536) return TSGNN_EUNSUPPORTED;
-  TSGNN_KNAME("eigen_triplet_gather_kernel");
-  eigen_triplet_gather_kernel<<<dim3((unsigned)most, ES_B + 1), 256, 0, stream>>>(a);
+  if (NB == ES_B) {
+    TSGNN_KNAME("eigen_triplet_gather_kernel");
+    eigen_triplet_gather_kernel<<<dim3((unsigned)most, NB + 1), 256, 0, stream>>>(a);
+  } else {
+    TSGNN_KNAME("eigen_anchor_gather_kernel");
+    eigen_anchor_gather_kernel<<<dim3((unsigned)most, NB + 1), 256, 0, stream>>>(a);
+  }
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+/* see include/tsgnn.h */
+int tsgnn_eigen_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words,
+                                   const int64_t* top_n, const int64_t* top_nnz, const int32_t* sched, int64_t sched_cap, int64_t* state,
+                                   unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream) {
+  return es_gather_launch<ES_B>(records, n_graphs, arena, arena_words, top_n, top_nnz, sched, sched_cap, state, ticket, desc, ids_out, stream);
+}
+
+int tsgnn_eigen_anchor_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words,
+                                  const int64_t* top_n, const int64_t* top_nnz, const int32_t* sched, int64_t sched_cap, int64_t* state,
+                                  unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream) {
+  return es_gather_launch<ES_ANCHOR>(records, n_graphs, arena, arena_words, top_n, top_nnz, sched, sched_cap, state, ticket, desc, ids_out,
+                                     stream);
 }
 
 }  // extern "C"

@@ -11,6 +11,7 @@
 //             (tsgnn_mlp3_bwd_f32: four block kinds, each recomputing dlogits -> dz2 in LDS) is kept for comparison, 21 us.
 //             Weight gradients are plain sums over the B rows in a fixed order (no atomics, reproducible).
 #include "common.h"
+#include "mlp3_drop.h"
 #include "../../include/tsgnn.h"
 
 namespace {
@@ -52,22 +53,8 @@ __device__ __forceinline__ void dense_row(const float* xs, int P, const float* _
   }
 }
 
-// Dropout mask made inside the launch (tsgnn_mlp3_fwd_drop_f32): element (b, j) of the hidden layer is kept when its 32 Philox bits
-// are >= thresh (= p * 2^32), keyed on (seed + the DEVICE counter state[0]; b, j).  The counter advances once per launch — every
-// block reads it first and draws a ticket (state[1]) when it is done; the block with the last ticket increments it — so a training
-// step replayed from a hipGraph draws a new mask at every replay without a host-side generator (torch's graph-safe generator costs
-// a bernoulli launch plus two fill launches per replay).  used[0] = the counter value of this launch (tests regenerate the mask).
-struct Mlp3Drop {
-  unsigned thresh; unsigned seed_lo, seed_hi;
-  unsigned long long* state;             // [0] launches so far, [1] tickets of the running launch (zero between launches)
-  unsigned long long* used;
-};
-__device__ __forceinline__ float mlp3_keep(unsigned thresh, unsigned klo, unsigned khi, unsigned b, unsigned j) {
-  const uint4 r = philox4x32_10(make_uint4(b, j >> 2, 0u, 0x4D4C5033u), make_uint2(klo, khi));
-  const unsigned v = (j & 3) == 0 ? r.x : (j & 3) == 1 ? r.y : (j & 3) == 2 ? r.z : r.w;
-  return v < thresh ? 0.f : 1.f;
-}
-
+// Dropout mask made inside the launch (tsgnn_mlp3_fwd_drop_f32; Mlp3Drop / mlp3_keep: mlp3_drop.h).  The counter advances once per
+// launch — every block reads it first and draws a ticket (state[1]) when it is done; the block with the last ticket increments it.
 __global__ __launch_bounds__(64 * MH_WAVES) void mlp3_fwd_kernel(const float* __restrict__ x, int64_t ldx, const float* __restrict__ w1,
                                                                  const float* __restrict__ b1, const float* __restrict__ keep,
                                                                  float keep_scale, const float* __restrict__ w2, const float* __restrict__ b2,
@@ -541,11 +528,6 @@ int tsgnn_mlp3_fwd_f32(const float* x, int64_t ldx, const float* w1, const float
                                                                 Mlp3Drop{});
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
-}
-
-static unsigned mlp3_thresh(float p) {
-  const double t = (double)p * 4294967296.0;
-  return t >= 4294967295.0 ? 0xFFFFFFFFu : (unsigned)t;
 }
 
 /* tsgnn_mlp3_fwd_f32 with the dropout mask (probability p of dropping, survivors scaled by 1 / (1 - p)) made INSIDE the launch:

@@ -12,6 +12,10 @@
 //                            what sag_stack.SagPlan computes on the host with np.float32
 //   ids_out [3]
 // Cursor and ticket counter: the protocol of csrc/triplet_stream.hip, on the same [HEAD | schedule] buffer.
+// The number of graphs a schedule entry names is a template parameter of the body: 3 is the triplet launch above, 1 the ANCHOR launch of
+// the 2stg+ post-training step (Code/sag/train_triplet_pre_train.py:219-263: one optimiser step per graph at B = 1) — a schedule
+// [T, 1], capacities of ONE largest graph, gp rows (0, k_l, k_l, k_l) (still one 16-byte store: words 2 and 3 repeat the total),
+// ids_out [1].
 // One writer per word, plain vector stores (16 bytes wherever the destination's alignment is known: the feature rows, four rows'
 // row pointers and coefficients per store, a level's graph pointer; the columns land at a data-dependent offset and go out as
 // coalesced dwords), the ticket counter is the only atomic.
@@ -21,6 +25,7 @@
 namespace {
 
 constexpr int SS_B = 3;                   // a triplet
+constexpr int SS_ANCHOR = 1;              // the anchor alone
 constexpr int SS_REC = 8;                 // int32 words of a record: n, nnz, first row, first entry, index, 0, 0, 0
 constexpr int SS_MAX_DEPTH = 7;
 constexpr int SS_EG = 8;                  // lanes per row
@@ -37,17 +42,18 @@ struct SagGatherArgs {
 
 // 8 lanes per row, 32 rows per workgroup; the four rows of a 32-lane group leave their row pointers and coefficients as one
 // 16-byte store each through the group's first lane.
-__global__ __launch_bounds__(256) void sag_triplet_gather_kernel(SagGatherArgs a) {
-  __shared__ int32_t rec_s[SS_B][SS_REC];
+template <int NB>
+__device__ __forceinline__ void sag_gather_body(const SagGatherArgs& a) {
+  __shared__ int32_t rec_s[NB][SS_REC];
   __shared__ long long cur_s;
   const int tid = threadIdx.x;
-  if (tid < SS_B) {
+  if (tid < NB) {
     // (agent-scope load: the word is stored by the last workgroup of the previous launch, never through this CU's scalar cache)
     const long long cur = __hip_atomic_load(reinterpret_cast<long long*>(a.state), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     int64_t T = a.state[1];                                 // the loaded schedule's length: the host's word, kept inside the buffer
     T = T < 1 ? 1 : (T > a.sched_cap ? a.sched_cap : T);
     const int64_t c = (int64_t)((unsigned long long)cur % (unsigned long long)T);
-    int64_t id = a.sched[c * SS_B + tid];
+    int64_t id = a.sched[c * NB + tid];
     id = id < 0 ? 0 : (id >= a.n_graphs ? a.n_graphs - 1 : id);      // (load() validated it; an index never leaves the records)
     const int4 r0 = *reinterpret_cast<const int4*>(a.rec + id * SS_REC);
     rec_s[tid][0] = r0.x; rec_s[tid][1] = r0.y; rec_s[tid][2] = r0.z; rec_s[tid][3] = r0.w;
@@ -69,8 +75,8 @@ __global__ __launch_bounds__(256) void sag_triplet_gather_kernel(SagGatherArgs a
   const int sub = tid & (SS_EG - 1);
   // the graph whose rows hold r, and the batch's totals: one pass over the three records, no data-dependent branch
   int n_tot = 0, e_tot = 0;
-  int b = SS_B, g0 = 0, eb = 0, row0 = 0, ent0 = 0, gid = 0;
-  for (int k = 0; k < SS_B; ++k) {
+  int b = NB, g0 = 0, eb = 0, row0 = 0, ent0 = 0, gid = 0;
+  for (int k = 0; k < NB; ++k) {
     const int nk = rec_s[k][0], ek = rec_s[k][1];
     const bool mine = r >= n_tot && r < (int64_t)n_tot + nk;
     b = mine ? k : b;
@@ -84,20 +90,22 @@ __global__ __launch_bounds__(256) void sag_triplet_gather_kernel(SagGatherArgs a
   }
   if (blockIdx.x == 0) {                                    // the batch's own small arrays: one writer per word
     if (tid <= a.depth) {                                   // level tid: the k chain applied tid times, then the prefix
-      int s[SS_B];
-      for (int k = 0; k < SS_B; ++k) s[k] = rec_s[k][0];
+      int s[NB];
+      for (int k = 0; k < NB; ++k) s[k] = rec_s[k][0];
       for (int l = 0; l < tid; ++l)
-        for (int k = 0; k < SS_B; ++k) {
+        for (int k = 0; k < NB; ++k) {
           const int kk = (int)ceilf(a.ratio * (float)s[k]);       // float32, as PyG's topk and SagPlan compute it
           s[k] = kk < s[k] ? kk : s[k];
         }
-      *reinterpret_cast<int4*>(a.gp + 4 * tid) = make_int4(0, s[0], s[0] + s[1], s[0] + s[1] + s[2]);
+      int p[4] = {0, 0, 0, 0};                              // the prefix; past NB graphs the words repeat the total
+      for (int k = 0; k < 3; ++k) p[k + 1] = p[k] + (k < NB ? s[k] : 0);
+      *reinterpret_cast<int4*>(a.gp + 4 * tid) = make_int4(p[0], p[1], p[2], p[3]);
     }
-    if (tid >= 32 && tid < 32 + SS_B) a.ids_out[tid - 32] = rec_s[tid - 32][4];
+    if (tid >= 32 && tid < 32 + NB) a.ids_out[tid - 32] = rec_s[tid - 32][4];
     if (tid == 64) a.rowptr_out[a.row_cap] = e_tot;
   }
   const bool in_cap = r < a.row_cap;
-  const bool real = b < SS_B && in_cap;
+  const bool real = b < NB && in_cap;
   const int lr = (int)(r - g0);
   int e0 = 0, e1 = 0;
   if (real) {
@@ -149,6 +157,44 @@ __global__ __launch_bounds__(256) void sag_triplet_gather_kernel(SagGatherArgs a
   }
 }
 
+__global__ __launch_bounds__(256) void sag_triplet_gather_kernel(SagGatherArgs a) { sag_gather_body<SS_B>(a); }
+__global__ __launch_bounds__(256) void sag_anchor_gather_kernel(SagGatherArgs a) { sag_gather_body<SS_ANCHOR>(a); }
+
+template <int NB>
+int sag_gather_launch(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t off_rowptr, int64_t off_col,
+                      int64_t arena_words, const float* feats, int64_t ldf, int64_t need_rows, int64_t need_nnz,
+                      const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket, int64_t row_cap,
+                      int64_t nnz_cap, float ratio, int depth, int32_t* rowptr, int32_t* col, float* x, int64_t ldx,
+                      float* dinv, float* self_w, int32_t* graph_ptr, int32_t* ids_out, tsgnn_stream_t stream) {
+  if (!records || !arena || !feats || !sched || !state || !ticket || !rowptr || !col || !x || !dinv || !self_w || !graph_ptr || !ids_out)
+    return TSGNN_EINVAL;
+  if (sched_cap <= 0 || n_graphs <= 0 || row_cap <= 0 || nnz_cap < 1 || ldf <= 0 || need_rows < 0 || need_nnz < 0 || depth < 1 ||
+      depth > SS_MAX_DEPTH || !(ratio > 0.f) || !(ratio <= 1.f))
+    return TSGNN_EINVAL;
+  // no schedule entry can overflow a slot: the capacities cover the arena's bounds (NB times its largest n / nnz).  need_rows and
+  // need_nnz are the caller's word, as the arena is (see tsgnn_triplet_gather_f32)
+  if (row_cap < need_rows || nnz_cap < need_nnz) return TSGNN_EINVAL;
+  if (off_rowptr < 0 || off_col < off_rowptr || arena_words < off_col) return TSGNN_EINVAL;
+  if (row_cap >= ((int64_t)1 << 31) - SS_ROWS || nnz_cap >= ((int64_t)1 << 31) || sched_cap >= ((int64_t)1 << 31) / NB)
+    return TSGNN_EUNSUPPORTED;
+  if ((ldf % 4) || ldx != ldf || ((off_rowptr | off_col) & 3)) return TSGNN_EUNSUPPORTED;
+  const uintptr_t al = reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(arena) | reinterpret_cast<uintptr_t>(feats) |
+                       reinterpret_cast<uintptr_t>(rowptr) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dinv) |
+                       reinterpret_cast<uintptr_t>(self_w) | reinterpret_cast<uintptr_t>(graph_ptr) | reinterpret_cast<uintptr_t>(state);
+  if (al & 15) return TSGNN_EUNSUPPORTED;
+  SagGatherArgs a{records, n_graphs, arena + off_rowptr, arena + off_col, feats, ldf, (int)(ldf / 4), sched, sched_cap, state, ticket,
+                  row_cap, nnz_cap, ratio, depth, rowptr, col, x, ldx, dinv, self_w, graph_ptr, ids_out};
+  if (NB == SS_B) {
+    TSGNN_KNAME("sag_triplet_gather_kernel");
+    sag_triplet_gather_kernel<<<(unsigned)ceil_div64(row_cap, SS_ROWS), 256, 0, stream>>>(a);
+  } else {
+    TSGNN_KNAME("sag_anchor_gather_kernel");
+    sag_anchor_gather_kernel<<<(unsigned)ceil_div64(row_cap, SS_ROWS), 256, 0, stream>>>(a);
+  }
+  TSGNN_CHECK_LAUNCH();
+  return TSGNN_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -159,28 +205,18 @@ int tsgnn_sag_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const
                                  const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket, int64_t row_cap,
                                  int64_t nnz_cap, float ratio, int depth, int32_t* rowptr, int32_t* col, float* x, int64_t ldx,
                                  float* dinv, float* self_w, int32_t* graph_ptr, int32_t* ids_out, tsgnn_stream_t stream) {
-  if (!records || !arena || !feats || !sched || !state || !ticket || !rowptr || !col || !x || !dinv || !self_w || !graph_ptr || !ids_out)
-    return TSGNN_EINVAL;
-  if (sched_cap <= 0 || n_graphs <= 0 || row_cap <= 0 || nnz_cap < 1 || ldf <= 0 || need_rows < 0 || need_nnz < 0 || depth < 1 ||
-      depth > SS_MAX_DEPTH || !(ratio > 0.f) || !(ratio <= 1.f))
-    return TSGNN_EINVAL;
-  // no schedule entry can overflow a slot: the capacities cover the arena's bounds (three times its largest n / nnz).  need_rows and
-  // need_nnz are the caller's word, as the arena is (see tsgnn_triplet_gather_f32)
-  if (row_cap < need_rows || nnz_cap < need_nnz) return TSGNN_EINVAL;
-  if (off_rowptr < 0 || off_col < off_rowptr || arena_words < off_col) return TSGNN_EINVAL;
-  if (row_cap >= ((int64_t)1 << 31) - SS_ROWS || nnz_cap >= ((int64_t)1 << 31) || sched_cap >= ((int64_t)1 << 31) / SS_B)
-    return TSGNN_EUNSUPPORTED;
-  if ((ldf % 4) || ldx != ldf || ((off_rowptr | off_col) & 3)) return TSGNN_EUNSUPPORTED;
-  const uintptr_t al = reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(arena) | reinterpret_cast<uintptr_t>(feats) |
-                       reinterpret_cast<uintptr_t>(rowptr) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dinv) |
-                       reinterpret_cast<uintptr_t>(self_w) | reinterpret_cast<uintptr_t>(graph_ptr) | reinterpret_cast<uintptr_t>(state);
-  if (al & 15) return TSGNN_EUNSUPPORTED;
-  SagGatherArgs a{records, n_graphs, arena + off_rowptr, arena + off_col, feats, ldf, (int)(ldf / 4), sched, sched_cap, state, ticket,
-                  row_cap, nnz_cap, ratio, depth, rowptr, col, x, ldx, dinv, self_w, graph_ptr, ids_out};
-  TSGNN_KNAME("sag_triplet_gather_kernel");
-  sag_triplet_gather_kernel<<<(unsigned)ceil_div64(row_cap, SS_ROWS), 256, 0, stream>>>(a);
-  TSGNN_CHECK_LAUNCH();
-  return TSGNN_OK;
+  return sag_gather_launch<SS_B>(records, n_graphs, arena, off_rowptr, off_col, arena_words, feats, ldf, need_rows, need_nnz, sched, sched_cap,
+                                 state, ticket, row_cap, nnz_cap, ratio, depth, rowptr, col, x, ldx, dinv, self_w, graph_ptr, ids_out, stream);
+}
+
+int tsgnn_sag_anchor_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t off_rowptr, int64_t off_col,
+                                int64_t arena_words, const float* feats, int64_t ldf, int64_t need_rows, int64_t need_nnz,
+                                const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket, int64_t row_cap,
+                                int64_t nnz_cap, float ratio, int depth, int32_t* rowptr, int32_t* col, float* x, int64_t ldx,
+                                float* dinv, float* self_w, int32_t* graph_ptr, int32_t* ids_out, tsgnn_stream_t stream) {
+  return sag_gather_launch<SS_ANCHOR>(records, n_graphs, arena, off_rowptr, off_col, arena_words, feats, ldf, need_rows, need_nnz, sched,
+                                      sched_cap, state, ticket, row_cap, nnz_cap, ratio, depth, rowptr, col, x, ldx, dinv, self_w, graph_ptr,
+                                      ids_out, stream);
 }
 
 }  // extern "C"

@@ -15,7 +15,13 @@ both tails run unchanged on that batch: its host-side sizes are the capacities, 
 padding rows of the pooled level (``tsgnn_eigen_pool_fwd_cap_f32``): the pooled-level stack forms X^T dY over every row.
 
 No dropout (a padding row must stay a function of nothing); anything the stream does not take is a TypeError that names the eager
-drop-in."""
+drop-in.
+
+The second half of 2stg+ (Code/eigengcn/train_triplet_pre_train.py:170-249: one step of the TRIPLET phase's Adam on the sampler's
+anchor at B = 1, ``model.loss(ypred, label)``; the driver's ``model.map_model`` is never read by ``forward``) is ``PostTrainStream`` on the
+same machinery at ONE piece per entry (``EigenArenaStream`` holds what the two streams share; ``tsgnn_eigen_anchor_gather_f32``;
+``pred_model`` and the cross-entropy in one launch each way, ``post_train.apply_mlp2_ce``), ``post_train_step`` its eager drop-in and
+``evaluate_pred`` the driver's ``evaluate()``."""
 import numpy as np
 import torch
 
@@ -37,9 +43,9 @@ class Arena:
       buf      int32 [words]   every graph's ``eigen_triplet.piece_buffer`` (sections at ``tsgnn_eigen_assemble_layout``'s offsets,
                                piece-local indices), one behind the other, each piece on 16 bytes
       top      (n [L + 1], nnz [L + 1])   the largest of each per level graph over the dataset
-      caps     (rows [L + 1], nnz [L + 1])   three times ``top``: no triplet needs more, also when one object fills all three places
-                               (a sampler may draw an anchor as its own negative's positive; the three largest DISTINCT graphs would
-                               not cover that)
+      caps     (rows [L + 1], nnz [L + 1])   ``batch`` (3: a triplet; 1: the anchor of the post-training step) times ``top``: no entry
+                               needs more, also when one object fills every place (a sampler may draw an anchor as its own
+                               negative's positive; the three largest DISTINCT graphs would not cover that)
       nmax, fin, ldf, L, J, Jf   what every graph shares: the padded size, the feature width, the 16-byte row stride of the feature
                                rows, the pooling levels and the pooling / final matrices per level"""
 
@@ -47,7 +53,7 @@ class Arena:
         self.__dict__.update(kw)
 
 
-def pack_arena(graphs, L, J, Jf, limit=1 << 31):
+def pack_arena(graphs, L, J, Jf, limit=1 << 31, batch=3):
     """graph objects (``.graph`` = {'adj', 'feats', 'num_nodes', 'adj_pool_i', 'num_nodes_i', 'pool_adj_i_j'} as cross_val.py prepares
     them, or bare dicts) -> ``Arena``.  ValueError, naming the graph's index (and the level where one is at fault), for whatever
     ``check_dict`` / ``pack_host`` reject, for an Nmax, a feature width or (L, J, Jf) that differs from the other graphs', for a level
@@ -92,13 +98,13 @@ def pack_arena(graphs, L, J, Jf, limit=1 << 31):
         if words >= int(limit):
             raise ValueError("graph %d: pack_arena: offsets reach %d (int32 records): %d buffer words" % (i, limit, words))
     top = (tuple(int(v) for v in rec[:, 2:2 + nlev].max(axis=0)), tuple(int(v) for v in rec[:, 2 + LMAX:2 + LMAX + nlev].max(axis=0)))
-    caps = (tuple(3 * t for t in top[0]), tuple(3 * t for t in top[1]))
+    caps = (tuple(int(batch) * t for t in top[0]), tuple(int(batch) * t for t in top[1]))
     most = max([(caps[0][0] + nmax) * ldf] + list(caps[1]) + [r * max(J, Jf, 1) for r in caps[0]])
     if most >= int(limit):
         raise ValueError("pack_arena: offsets reach %d (int32 records): a batch of %d + %d rows x %d, %d entries"
                          % (limit, caps[0][0], nmax, ldf, max(caps[1])))
     return Arena(records=rec.astype(np.int32), buf=np.concatenate(bufs), words=words, top=top, caps=caps, nmax=nmax, fin=fin, ldf=ldf,
-                 L=L, J=J, Jf=Jf, n_graphs=G)
+                 L=L, J=J, Jf=Jf, n_graphs=G, batch=int(batch))
 
 
 def _convs(model):
@@ -106,46 +112,47 @@ def _convs(model):
     return [m for m in model.modules() if isinstance(m, GraphConv)]
 
 
-class TripletStream(ArenaStream):
-    """``net``: an ``eigen_triplet.tripletnet``; ``graphs``: the dataset's graph objects (they are packed once).  The interface of
-    ``triplet_stream.TripletStream``: ``load(schedule)`` (``[T, 3]`` indices into ``graphs``), ``gather``, ``embed``,
-    ``loss(criterion, target)`` (the step for ``GraphedStep``: every call, every replay, consumes the next entry), ``position``,
-    ``ids_out``, ``len``; with ``max_steps`` the stream starts on the one-entry schedule [0, 0, 0].  TypeError (ending in the eager
-    drop-in) for anything that is not an ``eigen_triplet.tripletnet``, a model on the CPU, ``resident.RESIDENT`` off, a conv layer
-    with dropout > 0, more pooling levels than the assembler takes; ValueError for a dataset whose feature width is not the model's
-    (and whatever ``pack_arena`` refuses)."""
+class EigenArenaStream(ArenaStream):
+    """What the EigenGCN streams share, whatever the number ``B`` of graphs a schedule entry names (3: ``TripletStream``; 1:
+    ``PostTrainStream``): the model refusals (TypeError ending in the stream's eager drop-in), the arena upload, the allocation, layout
+    and views of the persistent ``EigenBatch`` at ``B`` times the largest piece per level, and the gather launch (``GATHER``: its entry
+    point)."""
 
-    NAME = "eigen_stream.TripletStream"
+    NAME = "eigen_stream.EigenArenaStream"
+    EAGER = EAGER
+    GATHER = "eigen_triplet_gather_f32"
 
-    def __init__(self, net, graphs, max_steps=None):
-        def refuse(what):
-            raise TypeError("%s %s%s" % (self.NAME, what, EAGER))
-        if not isinstance(net, et.tripletnet):
-            refuse("takes an eigen_triplet.tripletnet")
-        model = net.model
+    def _refuse(self, what):
+        raise TypeError("%s %s%s" % (self.NAME, what, self.EAGER))
+
+    def _check_model(self, model, L):
+        """the refusals every EigenGCN stream shares -> the model's device"""
         dev = next(model.parameters()).device
         if dev.type != "cuda":
-            refuse("runs on the GPU only")
+            self._refuse("runs on the GPU only")
         if not R.RESIDENT:
-            refuse("needs the resident pieces (resident.RESIDENT is off)")
+            self._refuse("needs the resident pieces (resident.RESIDENT is off)")
         if any(c.dropout > 0 for c in _convs(model)):
-            refuse("takes no dropout in a conv layer (a padding row must stay a function of nothing)")
-        if net.L > et.max_levels():
-            refuse("takes up to %d pooling levels (the model has %d)" % (et.max_levels(), net.L))
-        ar = self.arena = pack_arena(graphs, net.L, net.J, net.Jf)
+            self._refuse("takes no dropout in a conv layer (a padding row must stay a function of nothing)")
+        if L > et.max_levels():
+            self._refuse("takes up to %d pooling levels (the model has %d)" % (et.max_levels(), L))
+        return dev
+
+    def _init_arena(self, model, graphs, dev, shape, batch, max_steps):
+        """pack and upload the dataset, allocate the batch at ``batch`` times the largest piece per level; ``shape`` = (L, J, Jf)"""
+        ar = self.arena = pack_arena(graphs, *shape, batch=batch)
         if ar.fin != int(model.conv_first.input_dim):
             raise ValueError("%s: the dataset has %d features per node, the model takes %d" % (self.NAME, ar.fin, model.conv_first.input_dim))
-        self.net, self.model, self.device, self.B = net, model, dev, 3
+        self.model, self.device, self.B = model, dev, int(batch)
         self.row_caps, self.nnz_caps = ar.caps
         self._top = (np.array(ar.top[0], dtype=np.int64), np.array(ar.top[1], dtype=np.int64))
         self._allocate()
         self.records = torch.from_numpy(ar.records).to(dev)
         self.buf = torch.from_numpy(ar.buf).to(dev)
-        self.ids_out = torch.zeros(3, dtype=torch.int32, device=dev)
+        self.ids_out = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.max_steps = int(max_steps) if max_steps is not None else None
         self._sched = self._host = self._parts = None
         self.T = 0
-        self._warm_up_schedule()
 
     def layout(self, guard=0):
         """(ioff, isz, foff, fsz): ``eigen_triplet.assemble``'s two-buffer layout with R_i, E_i = the capacities; ``guard`` words behind
@@ -217,8 +224,29 @@ class TripletStream(ArenaStream):
         ar = self.arena
         if self._parts is None or self._parts[0] is not self._sched:        # (views of the schedule buffer, made once: load() keeps it)
             self._parts = (self._sched, self._sched[HEAD:], self._sched[4:HEAD])
-        nat.call("eigen_triplet_gather_f32", self.records, ar.n_graphs, self.buf, ar.words, self._top[0].ctypes.data,
+        nat.call(self.GATHER, self.records, ar.n_graphs, self.buf, ar.words, self._top[0].ctypes.data,
                  self._top[1].ctypes.data, self._parts[1], self.max_steps, self._sched, self._parts[2], self._desc.ctypes.data, self.ids_out)
+
+
+class TripletStream(EigenArenaStream):
+    """``net``: an ``eigen_triplet.tripletnet``; ``graphs``: the dataset's graph objects (they are packed once).  The interface of
+    ``triplet_stream.TripletStream``: ``load(schedule)`` (``[T, 3]`` indices into ``graphs``), ``gather``, ``embed``,
+    ``loss(criterion, target)`` (the step for ``GraphedStep``: every call, every replay, consumes the next entry), ``position``,
+    ``ids_out``, ``len``; with ``max_steps`` the stream starts on the one-entry schedule [0, 0, 0].  TypeError (ending in the eager
+    drop-in) for anything that is not an ``eigen_triplet.tripletnet``, a model on the CPU, ``resident.RESIDENT`` off, a conv layer
+    with dropout > 0, more pooling levels than the assembler takes; ValueError for a dataset whose feature width is not the model's
+    (and whatever ``pack_arena`` refuses)."""
+
+    NAME = "eigen_stream.TripletStream"
+
+    def __init__(self, net, graphs, max_steps=None):
+        if not isinstance(net, et.tripletnet):
+            self._refuse("takes an eigen_triplet.tripletnet")
+        model = net.model
+        dev = self._check_model(model, net.L)
+        self.net = net
+        self._init_arena(model, graphs, dev, (net.L, net.J, net.Jf), 3, max_steps)
+        self._warm_up_schedule()
 
     def embed(self):
         """gather + the encoder on the gathered batch + the triplet tail -> (dist_p, dist_n, embed_a, embed_p, embed_n), as
@@ -234,3 +262,118 @@ class TripletStream(ArenaStream):
             out = self.embed()
             return criterion(out[0], out[1], target)
         return step
+
+
+# ----------------------------------------------------------------------------- the post-training phase of 2stg+ (streamed)
+POST_EAGER = "; use the eager drop-in, eigen_stream.post_train_step(model, graph)"
+
+
+class PostTrainStream(EigenArenaStream):
+    """An epoch of EigenGCN post-training steps (Code/eigengcn/train_triplet_pre_train.py:192-247: one optimiser step on the sampler's
+    ANCHOR at B = 1, ``loss = model.loss(model(...), label)``) from ONE hipGraph: the arena of ``pack_arena(..., batch=1)``, a device
+    label table, and per replay the anchor gather launch (``tsgnn_eigen_anchor_gather_f32``: the whole one-graph ``EigenBatch`` of
+    "schedule entry number cursor" at capacities of the largest piece per level), ``model(x, eb, readout_only=True)`` under per-graph
+    statistics and ``pred_model`` with the cross-entropy in one launch each way (``tsgnn_posttrain_mlp2_ce_*``), whose label is
+    ``labels[ids_out[0]]`` read on the device.
+
+    ``model``: a bare ``WavePoolingGcnEncoder`` (what ``TripletStream`` takes under its ``tripletnet``); a ``map_model`` the caller
+    installed, as the reference does, is never read.  Labels: ``graph.graph['label']`` against ``label_dim``
+    (``post_train.label_table``).  ``load(anchors)``: [T] or [T, 1] indices into ``graphs`` (``schedule_of(sampler, graphs)[:, :1]`` is
+    the reference's epoch); ``step()`` -> (loss, ypred); ``step_loss()`` is the callable for ``GraphedStep``.  The reference steps
+    the TRIPLET phase's Adam here: hand ``step_loss()`` to that phase's own ``FlatTrainer``, whose moments continue.
+
+    COMPOSED, not fused: a one-layer ``pred_model``, or one outside ``tsgnn_posttrain_mlp2_ce_supported``, runs ``pred_model`` as torch
+    modules and ``mp.cross_entropy`` on a device label written from ``labels[ids_out]`` (an index launch and a cast per step)."""
+
+    NAME = "eigen_stream.PostTrainStream"
+    EAGER = POST_EAGER
+    GATHER = "eigen_anchor_gather_f32"
+
+    def __init__(self, model, graphs, max_steps=None):
+        from . import post_train as PT
+        from .eigen_encoders import WavePoolingGcnEncoder
+        if type(model) is not WavePoolingGcnEncoder:
+            self._refuse("takes a bare eigen_encoders.WavePoolingGcnEncoder")
+        shape = et.model_shape(model)
+        dev = self._check_model(model, shape[0])
+        graphs = list(graphs)
+        table = PT.label_table(graphs, int(model.label_dim))
+        self._init_arena(model, graphs, dev, shape, 1, max_steps)
+        self.n_classes = int(model.label_dim)
+        self.labels = torch.from_numpy(table).to(dev)
+        self._warm_up_schedule()
+
+    def _checked(self, anchors):
+        from .post_train import check_anchors
+        return check_anchors(anchors, self.arena.n_graphs)
+
+    def step(self):
+        """gather launch + the encoder's readout row + ``pred_model`` and the loss -> (loss, ypred) of the cursor's entry"""
+        from . import post_train as PT
+        if self.model.training and any(c.dropout > 0 for c in _convs(self.model)):
+            raise RuntimeError("%s: dropout became active on the model after the stream was built%s" % (self.NAME, self.EAGER))
+        self.gather()
+        with R.per_graph_statistics(self.model):
+            r = self.model(self.x, self.eb, readout_only=True)
+        return PT.apply_mlp2_ce(self.model, r, self.ids_out, self.labels)
+
+    def step_loss(self):
+        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
+        def step():
+            return self.step()[0]
+        return step
+
+
+# ----------------------------------------------------------------------------- the post-training phase of 2stg+ (eager)
+def post_train_step(model, graph):
+    """forward of the reference's post-training step (Code/eigengcn/train_triplet_pre_train.py:192-247: ``ypred = model(...)`` on the
+    sampler's ANCHOR at B = 1 under ``model.train()``, ``loss = model.loss(ypred, label)`` = ``F.cross_entropy`` over ``label_dim``
+    columns) on one graph object (or bare ``.graph`` dict) -> (loss, ypred); the caller runs ``backward`` and the optimiser — the
+    reference steps the TRIPLET phase's Adam (its moments and step count continue, with its lr, weight decay and clip), so hand this
+    loss to that ``FlatTrainer``, not to a new one.  A ``map_model`` the caller installed (the reference's dead ``pred_model``) is
+    never read.
+
+    The graph's resident piece (the model's ``ResidentCache``, shared with ``eigen_triplet.tripletnet`` and ``embed_dataset``) goes
+    through ``eigen_triplet.assemble`` at B = 1, the encoder runs under per-graph statistics up to its readout row, and
+    ``pred_model`` = Linear - ReLU - Linear with the loss is one launch each way (``post_train.apply_mlp2_ce``); a one-layer
+    ``pred_model``, or one outside ``tsgnn_posttrain_mlp2_ce_supported``, is ``pred_model`` + ``mp.cross_entropy`` composed."""
+    from . import post_train as PT
+    dev = next(model.parameters()).device
+    if dev.type != "cuda":
+        raise RuntimeError(R.GPU_ONLY)
+    L, J, Jf = et.model_shape(model)
+    d = et.graph_dict(graph)
+    label = PT._label_of(d)
+    if not 0 <= label < int(model.label_dim):
+        raise ValueError("label %d lies outside [0, %d)" % (label, int(model.label_dim)))
+    if R.RESIDENT and L <= et.max_levels():
+        x, eb = et.assemble([et.resident_graph(graph, dev, R.resident_cache(model), L, J, Jf, check=True)], dev)
+    else:
+        et.check_dict(d, L, J, Jf)
+        eb, feats, _ = et.to_device(et.pack_host(d, L, J, Jf), d["feats"], dev)
+        x = torch.cat([feats, R.ghost_zeros(eb.nmax, feats.size(1), dev)])
+    with R.per_graph_statistics(model):
+        r = model(x, eb, readout_only=True)
+    return PT.apply_mlp2_ce(model, r, PT._const_i32(dev, 0), PT._const_i32(dev, label))
+
+
+def predict_pred(graphs, model, chunk=None):
+    """class index per graph, int32 on the model's device: the arg-max (a tie to the lowest class) of the graph's
+    ``two_stage.embed_dataset`` row, which for a ``WavePoolingGcnEncoder`` is ``ypred`` of the eval-mode B = 1 call"""
+    from . import two_stage as TS
+    z = TS.embed_dataset(model, graphs, chunk)
+    if int(z.size(0)) == 0:
+        return torch.zeros(0, dtype=torch.int32, device=z.device)
+    return (z == z.max(dim=1, keepdim=True).values).int().argmax(dim=1).int()      # (the first maximum: the lowest class)
+
+
+def evaluate_pred(graphs, model, chunk=None):
+    """the phase's ``evaluate()`` (Code/eigengcn/train_triplet_pre_train.py:30-90: the arg-max of ``ypred`` against the label) ->
+    {'prec' (macro), 'recall' (macro), 'acc', 'F1' (micro)} through ``two_stage.confusion_matrix`` / ``metrics_from_confusion``.
+    ``graphs``: a ``{class: [graphs]}`` dictionary (iteration order kept) or a sequence; ONE copy of the predictions to the host."""
+    from . import two_stage as TS
+    graphs = TS._flatten(graphs)
+    y = TS._labels(graphs).reshape(-1)
+    pred = predict_pred(graphs, model, chunk).cpu().numpy().astype(np.int64)
+    labels = np.unique(np.concatenate([y.astype(np.int64), pred]))
+    return TS.metrics_from_confusion(TS.confusion_matrix(y, pred, labels))

@@ -16,6 +16,15 @@ The driver's other two methods: ``diffpool_stream.PostTrainStream`` (``SoftPooli
 level; ``PostTrainSteps`` is what the two share) and ``gat_stream.PostTrainStream`` (``DGATEncoderGraph(final_dim='output_dim')`` returns its
 readout row first, so ``pred`` is that row: ``row_loss`` on it, ``evaluate_readout`` for ``evaluate()``).  ``post_train_step`` has a resident
 branch for each.
+
+The other two drivers of the reference, whose post-training step is the "original" setting's classification step at B = 1 (their
+replacement heads are dead code: the models' ``forward`` never reads them):
+``sag_stream.PostTrainStream`` / ``sag_stream.post_train_step`` / ``sag_stream.test_dataset`` for ``sag_layers.Net``
+(Code/sag/train_triplet_pre_train.py:219-263: ``F.nll_loss(model(data), data.y)``, a new Adam without clipping), and
+``eigen_stream.PostTrainStream`` / ``eigen_stream.post_train_step`` / ``eigen_stream.evaluate_pred`` for ``WavePoolingGcnEncoder``
+(Code/eigengcn/train_triplet_pre_train.py:170-249: ``model.loss(ypred, label)`` stepped by the TRIPLET phase's own Adam).  Their heads
+live here: ``apply_mlp3_nll`` and ``apply_mlp2_ce`` (csrc/posttrain_cls.hip: the head, its soft-max and the loss in one launch each
+way, the label read on the device).
 """
 import numpy as np
 import torch
@@ -185,6 +194,155 @@ def row_loss(z, ids, labels):
     if row_loss_ok(z):
         return _RowLoss.apply(z, ids, labels)
     return F.cross_entropy(F.softmax(z, dim=1), labels[ids.long()].long())
+
+
+# ----------------------------------------------------------------------------- the classification heads of SAGPool and EigenGCN
+def _rows_fit(r):
+    """readout rows the head launches take as they are: fp32 on the GPU, unit column stride, 16-byte rows, at most 8 of them"""
+    return (r is not None and r.is_cuda and r.dim() == 2 and r.dtype == torch.float32 and r.stride(1) == 1 and r.stride(0) % 4 == 0
+            and r.stride(0) >= r.size(1) and r.data_ptr() % 16 == 0 and 1 <= r.size(0) <= 8)
+
+
+def _dense_f32(*tensors):
+    return all(t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda) for t in tensors)
+
+
+def mlp3_nll_ok(model, r):
+    """``tsgnn_posttrain_mlp3_nll_*`` take the head ``lin1 / lin2 / lin3`` of ``model`` (a ``sag_layers.Net``) on the readout rows ``r``"""
+    lins = [getattr(model, k, None) for k in ("lin1", "lin2", "lin3")]
+    if not (all(isinstance(l, nn.Linear) for l in lins) and _rows_fit(r) and r.size(1) == lins[0].in_features):
+        return False
+    if not _dense_f32(*[t for l in lins for t in (l.weight, l.bias)]) or any(l.weight.data_ptr() % 16 for l in lins):
+        return False
+    return bool(nat.lib().tsgnn_posttrain_mlp3_nll_supported(int(lins[0].in_features), int(lins[0].out_features), int(lins[1].out_features),
+                                                             int(lins[2].out_features), int(r.size(0))))
+
+
+class _Mlp3Nll(torch.autograd.Function):
+    """(readout rows r [R, D0], ids [R] int32, label table int32, lin1 / lin2 / lin3 weights and biases, (p, seed, state, used) or None)
+    -> (loss, logp [R, C]): ``F.nll_loss(log_softmax(lin3(relu(lin2(dropout(relu(lin1(r))))))), labels[ids])``, one launch each way
+    (tsgnn_posttrain_mlp3_nll_fwd_f32 / _bwd_f32).  ``logp`` is the step's ``out``: read only, not differentiable."""
+
+    @staticmethod
+    def forward(ctx, r, ids, labels, w1, b1, w2, b2, w3, b3, drop):
+        R_, D0, D1, D2, C = int(r.size(0)), int(w1.size(1)), int(w1.size(0)), int(w2.size(0)), int(w3.size(0))
+        dev = r.device
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        a1, a2, logp, loss = new(R_, D1), new(R_, D2), new(R_, C), new(1)
+        p_, seed, state, used = drop if drop is not None else (0.0, 0, None, None)
+        nat.call("posttrain_mlp3_nll_fwd_f32", r, r.stride(0), R_, w1, b1, float(p_), int(seed), state, used, w2, b2, w3, b3, D0, D1, D2, C,
+                 ids, labels, int(labels.numel()), a1, a2, logp, loss)
+        ctx.save_for_backward(r, w1, w2, w3, a1, a2, logp, ids, labels)
+        ctx.keep_scale = 1.0 / (1.0 - float(p_))
+        ctx.params = (w1, b1, w2, b2, w3, b3)                 # (the Parameter objects: their slices of a trainer's flat gradient bucket)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(logp)
+        return loss.view(()), logp
+
+    @staticmethod
+    def backward(ctx, g, _glogp):
+        if g is None:
+            return (None,) * 10
+        r, w1, w2, w3, a1, a2, logp, ids, labels = ctx.saved_tensors
+        R_, D0, D1, D2, C = int(r.size(0)), int(w1.size(1)), int(w1.size(0)), int(w2.size(0)), int(w3.size(0))
+        dev = r.device
+        d_r = torch.empty(R_, D0, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        # straight into the trainer's flat gradient bucket when one is installed (FlatTrainer): no AccumulateGrad copy, no zeroing
+        bufs, grads = mp._sinks_or_new(ctx.params, ((D1, D0), (D1,), (D2, D1), (D2,), (C, D2), (C,)), dev)
+        nat.call("posttrain_mlp3_nll_bwd_f32", r, r.stride(0), R_, w1, w2, w3, D0, D1, D2, C, ctx.keep_scale, ids, labels,
+                 int(labels.numel()), a1, a2, logp, g.contiguous().float(), d_r, D0, *bufs)
+        return (d_r, None, None) + grads + (None,)
+
+
+def mlp3_nll_torch(model, r, label):
+    """the same expression as torch operators (network.py:48-53 + ``F.nll_loss``) -> (loss, logp)"""
+    h = F.relu(F.linear(r, model.lin1.weight, model.lin1.bias))
+    h = F.dropout(h, p=model.dropout_ratio, training=model.training)
+    h = F.relu(F.linear(h, model.lin2.weight, model.lin2.bias))
+    logp = F.log_softmax(F.linear(h, model.lin3.weight, model.lin3.bias), dim=-1)
+    return F.nll_loss(logp, label), logp
+
+
+def apply_mlp3_nll(model, r, ids, labels, drop=None):
+    """readout rows of a ``sag_layers.Net`` -> (loss, out): the fused head where ``mlp3_nll_ok``, else ``mlp3_nll_torch`` on
+    ``labels[ids]``.  ``drop``: the (p, seed, state, used) words of the in-launch mask for an active dropout (train mode, p > 0); when
+    none is given they are ``sag_triplet._in_kernel_dropout``'s (the process seed and device counter every mlp3 launch shares), and a
+    counter that would have to be created inside a stream capture sends the call to the torch expression"""
+    if mlp3_nll_ok(model, r):
+        if model.training and model.dropout_ratio > 0.0 and drop is None:
+            from .sag_triplet import _in_kernel_dropout
+            drop = _in_kernel_dropout(model.dropout_ratio, r.device)
+            if drop is None:
+                return mlp3_nll_torch(model, r, labels[ids.long()].long())
+        if not (model.training and model.dropout_ratio > 0.0):
+            drop = None
+        m = model
+        return _Mlp3Nll.apply(r, ids, labels, m.lin1.weight, m.lin1.bias, m.lin2.weight, m.lin2.bias, m.lin3.weight, m.lin3.bias, drop)
+    return mlp3_nll_torch(model, r, labels[ids.long()].long())
+
+
+def mlp2_layers(model):
+    """(lin1, lin2) when ``model.pred_model`` is Linear - ReLU - Linear (``WavePoolingGcnEncoder`` with one hidden width), else None"""
+    seq = getattr(model, "pred_model", None)
+    if not isinstance(seq, nn.Sequential) or len(seq) != 3:
+        return None
+    l1, act, l2 = seq
+    if not (isinstance(l1, nn.Linear) and isinstance(act, nn.ReLU) and isinstance(l2, nn.Linear)) or l2.in_features != l1.out_features:
+        return None
+    return l1, l2
+
+
+def mlp2_ce_ok(model, r):
+    """``tsgnn_posttrain_mlp2_ce_*`` take ``model.pred_model`` on the readout rows ``r``"""
+    layers = mlp2_layers(model)
+    if layers is None or not _rows_fit(r) or r.size(1) != layers[0].in_features:
+        return False
+    l1, l2 = layers
+    if not _dense_f32(l1.weight, l1.bias, l2.weight, l2.bias) or l1.weight.data_ptr() % 16:
+        return False
+    return bool(nat.lib().tsgnn_posttrain_mlp2_ce_supported(int(l1.in_features), int(l1.out_features), int(l2.out_features), int(r.size(0))))
+
+
+class _Mlp2Ce(torch.autograd.Function):
+    """(readout rows r [R, D], ids [R] int32, label table int32, W1, b1, W2, b2) -> (loss, ypred [R, C]):
+    ``F.cross_entropy(pred_model(r), labels[ids])`` for pred_model = Linear - ReLU - Linear, one launch each way
+    (tsgnn_posttrain_mlp2_ce_fwd_f32 / _bwd_f32).  ``ypred`` is read only: not differentiable."""
+
+    @staticmethod
+    def forward(ctx, r, ids, labels, w1, b1, w2, b2):
+        R_, D, H, C = int(r.size(0)), int(w1.size(1)), int(w1.size(0)), int(w2.size(0))
+        dev = r.device
+        new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        h, z, p, loss = new(R_, H), new(R_, C), new(R_, C), new(1)
+        nat.call("posttrain_mlp2_ce_fwd_f32", r, r.stride(0), R_, w1, b1, w2, b2, D, H, C, ids, labels, int(labels.numel()), h, z, p, loss)
+        ctx.save_for_backward(r, w1, w2, h, p, ids, labels)
+        ctx.params = (w1, b1, w2, b2)
+        ctx.set_materialize_grads(False)
+        ctx.mark_non_differentiable(z)
+        return loss.view(()), z
+
+    @staticmethod
+    def backward(ctx, g, _gz):
+        if g is None:
+            return (None,) * 7
+        r, w1, w2, h, p, ids, labels = ctx.saved_tensors
+        R_, D, H, C = int(r.size(0)), int(w1.size(1)), int(w1.size(0)), int(w2.size(0))
+        dev = r.device
+        d_r = torch.empty(R_, D, dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        bufs, grads = mp._sinks_or_new(ctx.params, ((H, D), (H,), (C, H), (C,)), dev)
+        nat.call("posttrain_mlp2_ce_bwd_f32", r, r.stride(0), R_, w1, w2, D, H, C, ids, labels, int(labels.numel()), h, p,
+                 g.contiguous().float(), d_r, D, *bufs)
+        return (d_r, None, None) + grads
+
+
+def apply_mlp2_ce(model, r, ids, labels):
+    """readout rows of a ``WavePoolingGcnEncoder`` -> (loss, ypred): the fused head where ``mlp2_ce_ok``, else ``pred_model`` and
+    ``model.loss`` (``mp.cross_entropy``) composed on ``labels[ids]``"""
+    if mlp2_ce_ok(model, r):
+        l1, l2 = mlp2_layers(model)
+        return _Mlp2Ce.apply(r, ids, labels, l1.weight, l1.bias, l2.weight, l2.bias)
+    ypred = model.pred_model(r)
+    return model.loss(ypred, labels[ids.long()].long()), ypred
 
 
 def readout_out(model, pred):

@@ -10,7 +10,13 @@ advances the cursor.  ``sag_stack``'s node then runs on a ``CapacityPlan``: ever
 three times the largest graph, the row counts of the replay live in the graph pointers on the device, and the two per-graph level
 kernels zero the padding rows they leave behind (``tsgnn_sag_pool_graph_cap_f32 / _bwd_cap_f32``).
 
-``conv="gcn"`` only (the reference's network); anything else is a TypeError that names the eager drop-in."""
+``conv="gcn"`` only (the reference's network); anything else is a TypeError that names the eager drop-in.
+
+The second half of 2stg+ (Code/sag/train_triplet_pre_train.py:219-263: one optimiser step per graph on ``F.nll_loss(model(data),
+data.y)``; the driver's ``model.map2_model`` is never read by ``Net.forward``) is ``PostTrainStream`` on the same machinery at ONE graph
+per entry (``SagArenaStream`` holds what the two streams share; ``tsgnn_sag_anchor_gather_f32``; the head, its log_softmax and the
+loss in one launch each way, ``post_train.apply_mlp3_nll``), ``post_train_step`` its eager drop-in and ``test_dataset`` the driver's
+``test()``."""
 import numpy as np
 import torch
 
@@ -29,14 +35,15 @@ class Arena:
                                      row pointers (graph-local) start at ``first row + i``, its columns (graph-local, rows are
                                      targets, sources ascending, repeated edges kept: ``sag_triplet.pack_host``'s order) at ``first entry``
       feats    float32 [nodes, ld]   ld = fin rounded up to 4, zero in the pad columns
-      caps     (rows, nnz)           three times the largest n / nnz: no triplet needs more, also when one object fills all three places
+      caps     (rows, nnz)           ``batch`` (3: a triplet, 1: the anchor of the post-training step) times the largest n / nnz: no
+                                     entry needs more, also when one object fills every place
       largest  the largest n"""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
 
 
-def pack_arena(datas, limit=1 << 31):
+def pack_arena(datas, batch=3, limit=1 << 31):
     """``Data``-like objects (``.x [n, F]``, ``.edge_index [2, E]``: row 0 = source, row 1 = target) -> ``Arena``.  ValueError, naming
     the graph's index, for what the fused SAGPool node cannot take on a gathered batch: n < 1, n above
     ``tsgnn_sag_pool_graph_max_nodes()``, an edge id outside the graph, a graph that is not symmetric as a multiset (the in-kernel
@@ -77,7 +84,7 @@ def pack_arena(datas, limit=1 << 31):
     off = {"rowptr": 0, "col": _align4(row0 + G)}
     words = off["col"] + _align4(max(ent0, 1))
     ld = (fin + 3) // 4 * 4
-    top = lambda c: 3 * int(rec[:, c].max())
+    top = lambda c: int(batch) * int(rec[:, c].max())
     if max(words, row0 * ld, top(0) + 64, top(1)) >= int(limit):
         raise ValueError("pack_arena: offsets reach %d (int32 records): %d buffer words, %d nodes" % (limit, words, row0))
     buf = np.zeros(words, dtype=np.int32)
@@ -86,7 +93,7 @@ def pack_arena(datas, limit=1 << 31):
     feats = np.zeros((row0, ld), dtype=np.float32)
     feats[:, :fin] = np.concatenate(fts)
     return Arena(records=rec.astype(np.int32), buf=buf, off=off, words=words, feats=feats, fin=fin, ld=ld, caps=(top(0), top(1)),
-                 largest=int(rec[:, 0].max()), n_graphs=G, total_nodes=row0)
+                 batch=int(batch), largest=int(rec[:, 0].max()), n_graphs=G, total_nodes=row0)
 
 
 def k_chain(n, ratio, depth=3):
@@ -104,19 +111,20 @@ class _CapLevel:
 
 class CapacityPlan:
     """what ``sag_stack._SagStack`` reads from a ``SagPlan`` (``depth``, ``levels[l].B / N / gp / max_seg``) with every host value a
-    capacity: N = 3 k^l(largest n), max_seg = k^l(largest n) (k is monotone in n, so this bounds every graph at every level); ``gp`` are
+    capacity: N = batch k^l(largest n), max_seg = k^l(largest n) (k is monotone in n, so this bounds every graph at every level;
+    ``batch``: 3 graphs per entry, or 1 for the post-training stream); ``gp`` are
     the device tensors the gather launch writes (``gp_all [depth + 1, 4]``; pass ``device=None`` for the host values alone).
     ``capacity = True`` is what ``_SagStack`` asks for."""
 
     capacity = True
 
-    def __init__(self, largest, ratio, depth=3, device=None):
-        self.ratio, self.depth, self.device = float(ratio), int(depth), device
+    def __init__(self, largest, ratio, depth=3, device=None, batch=3):
+        self.ratio, self.depth, self.device, self.batch = float(ratio), int(depth), device, int(batch)
         self.gp_all = torch.zeros(depth + 1, 4, dtype=torch.int32, device=device) if device is not None else None
         self.levels = []
         for l, seg in enumerate(k_chain(largest, ratio, depth)):
             L = _CapLevel()
-            L.B, L.N, L.max_seg, L.sizes, L.row_graph = 3, 3 * seg, seg, None, None
+            L.B, L.N, L.max_seg, L.sizes, L.row_graph = self.batch, self.batch * seg, seg, None, None
             L.gp = self.gp_all[l] if self.gp_all is not None else None
             self.levels.append(L)
 
@@ -133,43 +141,46 @@ class _CapGraph:
         self._gcn_coef = (dinv, self_w)
 
 
-class TripletStream(ArenaStream):
-    """``net``: a ``sag_triplet.tripletnet`` over a ``sag_layers.Net`` with ``conv="gcn"``; ``datas``: the dataset's ``Data`` objects
-    (host or device tensors; they are packed once).  The interface of ``triplet_stream.TripletStream``: ``load(schedule)`` (``[T, 3]``
-    indices into ``datas``), ``gather``, ``embed``, ``loss(criterion, target)`` (the step for ``GraphedStep``: every call, every replay,
-    consumes the next entry), ``position``, ``ids_out``, ``len``; with ``max_steps`` the stream starts on the one-entry schedule
-    [0, 0, 0].  TypeError (ending in the eager drop-in) for ``conv="sage"``, a model whose levels do not run as the fused node, a head
-    the tail kernel does not take, a model that is not on the GPU."""
+class SagArenaStream(ArenaStream):
+    """What the SAGPool streams share, whatever the number ``B`` of graphs a schedule entry names (3: ``TripletStream``; 1:
+    ``PostTrainStream``): the model refusals (TypeError ending in the stream's eager drop-in), the arena upload, the capacity buffers
+    the gather launch writes and the ``CapacityPlan`` over them, the gather launch (``GATHER``: its entry point), ``_params`` and the
+    fused node on the gathered batch (``readout``)."""
 
-    NAME = "sag_stream.TripletStream"
+    NAME = "sag_stream.SagArenaStream"
+    TAKES = "takes a sag_layers.Net"
+    EAGER = EAGER
+    GATHER = "sag_triplet_gather_f32"
     DEPTH = 3
 
-    def __init__(self, net, datas, max_steps=None):
+    def _refuse(self, what):
+        raise TypeError("%s %s%s" % (self.NAME, what, self.EAGER))
+
+    def _check_model(self, model):
+        """the refusals every SAGPool stream shares -> the model's device"""
         from . import sag_stack
         from .sag_layers import Net
-        model = getattr(net, "model", None)
-
-        def refuse(what):
-            raise TypeError("%s %s%s" % (self.NAME, what, EAGER))
         if type(model) is not Net:
-            refuse("takes a sag_triplet.tripletnet over a sag_layers.Net")
+            self._refuse(self.TAKES)
         if model.conv_kind != "gcn":
-            refuse("takes conv=\"gcn\" only (conv=%r)" % (model.conv_kind,))
+            self._refuse("takes conv=\"gcn\" only (conv=%r)" % (model.conv_kind,))
         dev = next(model.parameters()).device
         if dev.type != "cuda":
-            refuse("runs on the GPU only")
+            self._refuse("runs on the GPU only")
         if not model._fused_ok():
-            refuse("needs the fused SAGPool node (fused=True, a hidden width sag_stack supports, tanh gates, biases)")
+            self._refuse("needs the fused SAGPool node (fused=True, a hidden width sag_stack supports, tanh gates, biases)")
         if not (sag_stack.PER_GRAPH_POOL and sag_stack.FUSED_NEXT_PROPAGATE and sag_stack.DEFERRED_REDUCE):
-            refuse("needs sag_stack's per-graph level kernels with the in-kernel filter")
-        if not tail_ok(model, torch.empty(3, 2 * int(model.nhid), dtype=torch.float32, device=dev)):
-            refuse("needs a head the triplet tail kernel takes (tsgnn_mlp3_triplet_supported)")
-        ar = self.arena = pack_arena(datas)
+            self._refuse("needs sag_stack's per-graph level kernels with the in-kernel filter")
+        return dev
+
+    def _init_arena(self, model, datas, dev, batch, max_steps):
+        """pack and upload the dataset, allocate the batch at ``batch`` times the largest graph"""
+        ar = self.arena = pack_arena(datas, batch=batch)
         if ar.fin != int(model.num_features):
             raise ValueError("%s: the dataset has %d features per node, the model takes %d" % (self.NAME, ar.fin, model.num_features))
-        self.net, self.model, self.device, self.B = net, model, dev, 3
+        self.model, self.device, self.B = model, dev, int(batch)
         self.row_cap, self.nnz_cap = ar.caps[0], max(ar.caps[1], 1)
-        self.plan = CapacityPlan(ar.largest, model.pooling_ratio, self.DEPTH, dev)
+        self.plan = CapacityPlan(ar.largest, model.pooling_ratio, self.DEPTH, dev, batch=self.B)
         i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         self.rowptr, self.col = i32(self.row_cap + 1), i32(self.nnz_cap)
@@ -180,18 +191,17 @@ class TripletStream(ArenaStream):
         self.records = torch.from_numpy(ar.records).to(dev)
         self.buf = torch.from_numpy(ar.buf).to(dev)
         self.feats = torch.from_numpy(ar.feats).to(dev)
-        self.ids_out = torch.zeros(3, dtype=torch.int32, device=dev)
+        self.ids_out = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.max_steps = int(max_steps) if max_steps is not None else None
         self._sched = self._host = None
         self.T = 0
-        self._warm_up_schedule()
 
     def gather(self):
         """enqueue (current stream; capturable) the launch that writes the batch of the cursor's entry and advances the cursor"""
         if self._sched is None:
             raise RuntimeError("%s: load(schedule) before the first step" % self.NAME)
         ar = self.arena
-        nat.call("sag_triplet_gather_f32", self.records, ar.n_graphs, self.buf, ar.off["rowptr"], ar.off["col"], ar.words, self.feats,
+        nat.call(self.GATHER, self.records, ar.n_graphs, self.buf, ar.off["rowptr"], ar.off["col"], ar.words, self.feats,
                  ar.ld, ar.caps[0], ar.caps[1], self._sched[HEAD:], self.max_steps, self._sched, self._sched[4:HEAD], self.row_cap,
                  self.nnz_cap, float(self.plan.ratio), self.plan.depth, self.rowptr, self.col, self._x, self._x.stride(0), self.dinv,
                  self.self_w, self.plan.gp_all, self.ids_out)
@@ -203,16 +213,201 @@ class TripletStream(ArenaStream):
             out += [conv.weight, conv.bias, pool.score_layer.weight, pool.score_layer.bias]
         return out
 
+    def readout(self):
+        """the fused SAGPool node on the gathered batch and the capacity plan -> readout rows [B, 2 nhid]"""
+        from . import sag_stack
+        return sag_stack.sag_stack(self.x, self.g, self.plan, self._params())
+
+
+class TripletStream(SagArenaStream):
+    """``net``: a ``sag_triplet.tripletnet`` over a ``sag_layers.Net`` with ``conv="gcn"``; ``datas``: the dataset's ``Data`` objects
+    (host or device tensors; they are packed once).  The interface of ``triplet_stream.TripletStream``: ``load(schedule)`` (``[T, 3]``
+    indices into ``datas``), ``gather``, ``embed``, ``loss(criterion, target)`` (the step for ``GraphedStep``: every call, every replay,
+    consumes the next entry), ``position``, ``ids_out``, ``len``; with ``max_steps`` the stream starts on the one-entry schedule
+    [0, 0, 0].  TypeError (ending in the eager drop-in) for ``conv="sage"``, a model whose levels do not run as the fused node, a head
+    the tail kernel does not take, a model that is not on the GPU."""
+
+    NAME = "sag_stream.TripletStream"
+    TAKES = "takes a sag_triplet.tripletnet over a sag_layers.Net"
+
+    def __init__(self, net, datas, max_steps=None):
+        model = getattr(net, "model", None)
+        dev = self._check_model(model)
+        if not tail_ok(model, torch.empty(3, 2 * int(model.nhid), dtype=torch.float32, device=dev)):
+            self._refuse("needs a head the triplet tail kernel takes (tsgnn_mlp3_triplet_supported)")
+        self.net = net
+        self._init_arena(model, datas, dev, 3, max_steps)
+        self._warm_up_schedule()
+
     def embed(self):
         """gather + the fused SAGPool node on the capacity plan + the triplet tail -> (dist_p, dist_n, embed_a, embed_p, embed_n), as
         ``tripletnet.forward`` returns"""
-        from . import sag_stack
         self.gather()
-        return self.net._tail(sag_stack.sag_stack(self.x, self.g, self.plan, self._params()))
+        return self.net._tail(self.readout())
 
     def loss(self, criterion, target):
         """-> callable for ``GraphedStep``: gather launch + the node + the tail + ``criterion(dist_p, dist_n, target)``"""
         def step():
             out = self.embed()
             return criterion(out[0], out[1], target)
+        return step
+
+
+# ----------------------------------------------------------------------------- the post-training phase of 2stg+ (eager)
+def _const0(dev):
+    from .post_train import _const_i32
+    return _const_i32(dev, 0)
+
+
+def _device_label(data, n_classes, dev, what="data"):
+    """``data.y`` as a one-element int32 device tensor for the head (a label on the host is checked against [0, n_classes) first; one
+    that already lives on the device is not read back: the head clamps it)"""
+    from .post_train import _const_i32
+    y = getattr(data, "y", None)
+    if y is None:
+        raise ValueError("%s carries no label (.y)" % what)
+    if isinstance(y, torch.Tensor) and y.is_cuda:
+        if y.numel() != 1 or y.dtype not in (torch.int64, torch.int32):
+            raise ValueError("%s: .y must be one integer; got %s of %d elements" % (what, y.dtype, y.numel()))
+        return y.reshape(1).to(torch.int32)
+    a = _np(y)
+    if a.size != 1 or not np.issubdtype(a.dtype, np.integer):
+        raise ValueError("%s: .y must be one integer; got %r" % (what, y))
+    v = int(a.reshape(-1)[0])
+    if not 0 <= v < int(n_classes):
+        raise ValueError("%s: label %d lies outside [0, %d)" % (what, v, int(n_classes)))
+    return _const_i32(dev, v)
+
+
+def post_train_step(model, data):
+    """forward of the reference's fine-tuning step (Code/sag/train_triplet_pre_train.py:219-263: ``loss = F.nll_loss(model(data),
+    data.y)`` on ONE graph, under ``model.train()``) -> (loss, out); the caller runs ``backward`` and the optimiser
+    (``FlatTrainer(model, lr=1e-3, clip=0)``).  A ``sag_layers.Net`` on the GPU takes the graph's resident structure from the model's
+    ``ResidentCache`` (what ``sag_triplet.tripletnet`` and ``two_stage.embed_dataset`` share), runs the three levels once and applies
+    the head, its log_softmax and the loss in one launch each way (``post_train.apply_mlp3_nll``: dropout after ``lin1`` is drawn inside
+    the launch); a head outside ``tsgnn_posttrain_mlp3_nll_supported`` is the same expression as torch operators.  Any other model
+    gets ``model(data)`` and ``mp.nll_loss``.  A ``map2_model`` the caller installed (the reference's dead ``pred_model``) is never
+    read."""
+    from . import message_passing as mp
+    from . import post_train as PT
+    from . import sag_triplet as ST
+    from .sag_layers import Net
+    dev = next(model.parameters()).device
+    if type(model) is Net and dev.type == "cuda" and isinstance(data.x, torch.Tensor) and data.x.is_cuda:
+        labels = _device_label(data, model.num_classes, dev)
+        net = ST.tripletnet(model)                          # (a view of the model and of its shared cache: nothing is copied)
+        r = net.readout(net.batch_of((data,)))
+        return PT.apply_mlp3_nll(model, r, _const0(dev), labels)
+    out = model(data)
+    return mp.nll_loss(out, data.y), out
+
+
+def test_dataset(model, datas, chunk=None):
+    """the reference's ``test(model, loader)`` (Code/sag/train_triplet_pre_train.py:21-31) -> (accuracy, summed nll / N) in eval mode:
+    rows of ``two_stage.embed_dataset`` (= ``out`` of every graph alone), arg-max (a tie to the lowest class), nll and the label-range
+    check on the device, ONE device-to-host copy.  ValueError for a label outside [0, num_classes)."""
+    from . import two_stage as TS
+    datas = TS._flatten(datas)
+    if not datas:
+        raise ValueError("test_dataset: no graphs")
+    out = TS.embed_dataset(model, datas, chunk)
+    dev, C = out.device, int(out.size(1))
+    ys = [d.y if isinstance(d.y, torch.Tensor) else torch.as_tensor(np.asarray(d.y)) for d in datas]
+    if all(y.device == dev for y in ys):
+        y = torch.cat([t.reshape(-1)[:1] for t in ys]).long()
+    else:
+        y = torch.from_numpy(np.asarray([int(_np(t).reshape(-1)[0]) for t in ys], dtype=np.int64)).to(dev)
+    pred = (out == out.max(dim=1, keepdim=True).values).int().argmax(dim=1)        # (the first maximum: the lowest index)
+    nll = -out.double().gather(1, y.clamp(0, C - 1).view(-1, 1)).sum()
+    res = torch.stack([(pred == y).sum().double(), nll, y.min().double(), y.max().double()]).cpu().numpy()
+    if res[2] < 0 or res[3] >= C:
+        raise ValueError("test_dataset: labels span [%d, %d], the model has %d classes" % (int(res[2]), int(res[3]), C))
+    return float(res[0]) / len(datas), float(res[1]) / len(datas)
+
+
+test_dataset.__test__ = False       # (pytest: a library function, not a test)
+
+
+# ----------------------------------------------------------------------------- the post-training phase of 2stg+ (streamed)
+POST_EAGER = "; use the eager drop-in, sag_stream.post_train_step(model, data)"
+
+
+def label_table(datas, n_classes, labels=None):
+    """int32 [G] of ``data.y`` (or of ``labels``, one integer per graph); ValueError, naming the graph's index, for a label that is
+    missing, no single integer, or outside [0, n_classes).  Labels that live on the device come to the host in one copy."""
+    datas = list(datas)
+    if labels is None:
+        ys = [getattr(d, "y", None) for d in datas]
+        for i, y in enumerate(ys):
+            if y is None:
+                raise ValueError("graph %d carries no label (.y)" % i)
+        if ys and all(isinstance(y, torch.Tensor) and y.is_cuda and y.numel() == 1 for y in ys):
+            ys = list(torch.cat([y.reshape(1) for y in ys]).cpu().numpy())
+    else:
+        ys = list(_np(labels).reshape(-1)) if not isinstance(labels, (list, tuple)) else list(labels)
+        if len(ys) != len(datas):
+            raise ValueError("%d labels for %d graphs" % (len(ys), len(datas)))
+    out = np.zeros(len(datas), dtype=np.int32)
+    for i, y in enumerate(ys):
+        a = _np(y)
+        if a.size != 1 or not np.issubdtype(a.dtype, np.integer):
+            raise ValueError("graph %d: the label must be one integer; got %r" % (i, y))
+        v = int(a.reshape(-1)[0])
+        if not 0 <= v < int(n_classes):
+            raise ValueError("graph %d: label %d lies outside [0, %d)" % (i, v, int(n_classes)))
+        out[i] = v
+    return out
+
+
+class PostTrainStream(SagArenaStream):
+    """An epoch of the SAGPool fine-tuning steps (Code/sag/train_triplet_pre_train.py:219-263: ``F.nll_loss(model(data), data.y)`` on
+    ONE graph per optimiser step) from ONE hipGraph: the arena of ``pack_arena(datas, batch=1)``, a device label table, and per replay
+    the anchor gather launch (``tsgnn_sag_anchor_gather_f32``: the graph of "schedule entry number cursor" at capacities of one
+    largest graph), ``sag_stack``'s fused node on the B = 1 capacity plan and the head with its log_softmax and the loss in one launch
+    each way (``tsgnn_posttrain_mlp3_nll_*``), whose label is ``labels[ids_out[0]]`` read on the device.
+
+    ``model``: a bare ``sag_layers.Net`` with ``conv="gcn"`` (what ``TripletStream`` takes under its ``tripletnet``); a
+    ``map2_model`` the caller installed, as the reference does, is never read.  Labels: ``data.y`` or ``labels``.
+    ``load(anchors)``: [T] or [T, 1] indices into ``datas``; ``step()`` -> (loss, out); ``step_loss()`` is the callable for
+    ``GraphedStep`` (the reference's trainer here is a NEW ``FlatTrainer(model, lr=1e-3, clip=0)``).  In train mode with
+    ``dropout_ratio`` > 0 the mask after ``lin1`` is drawn inside the head's launch from the process seed and device counter every
+    mlp3 launch shares; they are created here, so a capture never has to.  TypeError ending in the eager drop-in for a model or a head
+    the fused launches do not take."""
+
+    NAME = "sag_stream.PostTrainStream"
+    TAKES = "takes a bare sag_layers.Net"
+    EAGER = POST_EAGER
+    GATHER = "sag_anchor_gather_f32"
+
+    def __init__(self, model, datas, labels=None, max_steps=None):
+        from . import post_train as PT
+        from .sag_triplet import _in_kernel_dropout
+        dev = self._check_model(model)
+        if not PT.mlp3_nll_ok(model, torch.empty(1, 2 * int(model.nhid), dtype=torch.float32, device=dev)):
+            self._refuse("needs a head the fused launches take (tsgnn_posttrain_mlp3_nll_supported)")
+        datas = list(datas)
+        self.n_classes = int(model.num_classes)
+        table = label_table(datas, self.n_classes, labels)
+        self._init_arena(model, datas, dev, 1, max_steps)
+        self.labels = torch.from_numpy(table).to(dev)
+        _in_kernel_dropout(max(float(model.dropout_ratio), 0.0), dev)         # (creates the seed and the device counter)
+        self._warm_up_schedule()
+
+    def _checked(self, anchors):
+        from .post_train import check_anchors
+        return check_anchors(anchors, self.arena.n_graphs)
+
+    def step(self):
+        """gather launch + the fused node's readout row + the head -> (loss, out) of the cursor's entry"""
+        from . import post_train as PT
+        self.gather()
+        r = self.readout()
+        if not PT.mlp3_nll_ok(self.model, r):
+            raise RuntimeError("%s: the fused head does not take this model's readout rows%s" % (self.NAME, self.EAGER))
+        return PT.apply_mlp3_nll(self.model, r, self.ids_out, self.labels)
+
+    def step_loss(self):
+        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
+        def step():
+            return self.step()[0]
         return step
