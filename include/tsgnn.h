@@ -188,6 +188,33 @@ int tsgnn_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const int
                              int32_t* row_graph, int32_t* row_slot, int32_t* ell, int32_t* tail_ptr, int32_t* tail_col,
                              int32_t* ell_slots, int32_t* tail_slots, float* x, int64_t ldx, int32_t* ids_out, tsgnn_stream_t stream);
 
+/* Mini-batch stream (batch_stream.hip; train.py:104-131, one new mini-batch per optimiser step): tsgnn_triplet_gather_f32's launch for
+ * entries of 1 <= B <= 128 graphs — the same records, arena sections, [HEAD | schedule] buffer, cursor and outputs with the same
+ * padding rules, word for word.  The workgroup forms the prefix sums of n and ntail once in LDS, a row finds its graph by
+ * binary search, and a ghost slot's count comes from one ballot over the records' owners.  What it adds:
+ *   labels / label_out   int32 [n_graphs] per-graph label table -> label_out[B] as int64 (on 8 bytes)
+ *   one-hot mode         feats == NULL with node_label != NULL (int32 per arena node, values in [0, fin)): x rows are the one-hot rows
+ *                        of fin columns, ldx == fin rounded up to 4, bit for bit the float table holding those rows (ldf is ignored);
+ *                        exactly one of feats / node_label is given
+ *   ticket               unsigned [33 * 32], zero between launches: 32 shard counters and a top counter, each on 128 bytes of its own
+ *                        (workgroup b draws from shard b % 32, a shard's last drawer from the top: a slot of 32 DD graphs has ~1,400
+ *                        workgroups, and that many atomic adds to ONE word outlast the rest of the launch); still the only atomics
+ *   capacities           max_n / max_tail are the arena's largest n / ntail: row_cap >= max_n and tail_cap >= max_tail are all the
+ *                        launch asks, so a slot may be smaller than B times the largest graph.  Whether every ENTRY fits (the sums of
+ *                        its graphs' n and ntail within row_cap and tail_cap) is checked by whoever uploads the schedule; for an entry
+ *                        that does not, nothing is written outside the arrays (rows and tail entries past the capacities are dropped,
+ *                        graph_ptr and tail_ptr are clamped to them) and the batch's content is not defined.
+ * TSGNN_EINVAL without a launch: a null pointer, both or neither of feats / node_label, B outside 1..128, sched_cap <= 0, ell_w outside
+ * {4, 8, 16}, max_n outside 1..nmax, row_cap < max_n, tail_cap < max_tail, fin < 1 or ldx != fin rounded up to 4 in the one-hot mode,
+ * section offsets out of order; TSGNN_EUNSUPPORTED without a launch: as tsgnn_triplet_gather_f32, and label_out off 8 bytes. */
+int tsgnn_batch_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t off_rowptr, int64_t off_col,
+                           int64_t off_tail_ptr, int64_t off_tail_col, int64_t arena_words, const float* feats, int64_t ldf,
+                           const int32_t* node_label, int fin, const int32_t* labels, int64_t max_n, int64_t max_tail,
+                           const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket, int B, int nmax, int64_t row_cap,
+                           int64_t tail_cap, int ell_w, int32_t* graph_ptr, int32_t* slot_count, int32_t* row_graph, int32_t* row_slot,
+                           int32_t* ell, int32_t* tail_ptr, int32_t* tail_col, int32_t* ell_slots, int32_t* tail_slots, float* x,
+                           int64_t ldx, int32_t* ids_out, int64_t* label_out, tsgnn_stream_t stream);
+
 /* The SAGPool family's gather launch (sag_stream.hip; host side: sag_stream.py): schedule entry number `cursor` of an epoch's
  * triplets [T, 3] -> what sag_stack's node reads of the three graphs as one batch, padded to capacities.  Cursor, T and the ticket
  * counter as tsgnn_triplet_gather_f32 (the same [HEAD | schedule] buffer); always three graphs per entry.

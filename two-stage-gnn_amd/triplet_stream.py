@@ -35,7 +35,9 @@ class Arena:
       caps     (rows, nnz, tail)     ``batch`` times the largest n / nnz / ntail: no batch of that many graphs needs more, also when
                                      one object fills several of its places (a sampler may draw an anchor as its own negative's
                                      positive; the sum of the ``batch`` largest DISTINCT graphs would not cover that)
-      largest  the largest n"""
+      largest  the largest n
+    and, from ``minibatch_stream.pack_arena_tu`` / its graph-object route only: ``labels`` int32 [G] (the graphs' classes) and
+    ``node_label`` int32 [nodes] or None; ``feats`` is None where the gather launch writes one-hot rows from ``node_label``"""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -149,24 +151,28 @@ class ArenaStream:
     ``gather`` and ``position``.  ``model``: a plain ``GcnEncoderGraph`` with concat and bn whose conv stack runs as the fused
     per-graph node on the gathered batch; anything else is a TypeError that ends in ``eager`` (where the caller's eager drop-in is).
     The two checks are methods (``_model_ok``, ``_stacks_ok``): a stream for another encoder family (``diffpool_stream.TripletStream``)
-    overrides them."""
+    overrides them.  ``arena``: an ``Arena`` packed by the caller in place of ``pack_arena(graphs, ...)``; ``row_cap`` / ``tail_cap``:
+    capacities in place of the arena's bounds (``minibatch_stream.MiniBatchStream``, whose ``load`` checks every entry against them).
+    A feature table the arena does not carry (``arena.feats`` None) is not uploaded."""
 
     def __init__(self, model, graphs, batch, nmax=None, max_steps=None, name="ArenaStream", takes="takes a GcnEncoderGraph with concat and bn",
-                 eager=""):
+                 eager="", arena=None, row_cap=None, tail_cap=None):
         from .ingest import CapacityBatch, ELL_W
         if not self._model_ok(model):
             raise TypeError("%s %s%s" % (name, takes, eager))
         dev = next(model.parameters()).device
         if dev.type != "cuda":
             raise TypeError("%s runs on the GPU only%s" % (name, eager))
-        graphs = list(graphs)
-        if nmax is None:
-            nmax = int(np.asarray(_graph_dict(graphs[0])["adj"]).shape[0])
         self.model, self.device, self.B = model, dev, int(batch)
-        ar = self.arena = pack_arena(graphs, nmax, ELL_W, batch=self.B)
+        if arena is None:
+            graphs = list(graphs)
+            if nmax is None:
+                nmax = int(np.asarray(_graph_dict(graphs[0])["adj"]).shape[0])
+            arena = pack_arena(graphs, nmax, ELL_W, batch=self.B)
+        ar = self.arena = arena
         rows, _, tail = ar.caps
-        self.row_cap = (rows + 31) // 32 * 32
-        self.tail_cap = _align4(max(tail, 1))
+        self.row_cap = ((rows if row_cap is None else int(row_cap)) + 31) // 32 * 32
+        self.tail_cap = _align4(max(tail if tail_cap is None else int(tail_cap), 1))
         ghost = min(ar.nmax, ar.largest + 1)
         # (edge_cap: the compact staging layout's CSR columns, which this path never fills)
         self.batch = CapacityBatch(self.B, ar.nmax, self.row_cap, 4, ar.fin, dev, ghost_slots=ghost, tail_cap=self.tail_cap)
@@ -175,7 +181,7 @@ class ArenaStream:
             raise TypeError("%s: the model's conv stack does not run as the fused per-graph node on this dataset%s" % (name, eager))
         self.records = torch.from_numpy(ar.records).to(dev)
         self.buf = torch.from_numpy(ar.buf).to(dev)
-        self.feats = torch.from_numpy(ar.feats).to(dev)
+        self.feats = torch.from_numpy(ar.feats).to(dev) if ar.feats is not None else None
         self.ids_out = torch.zeros(self.B, dtype=torch.int32, device=dev)
         self.max_steps = int(max_steps) if max_steps is not None else None
         # int32 [HEAD + max_steps * B]: {cursor, T} as two int64, the ticket counter (+ 3 spare words), then the schedule
@@ -210,7 +216,8 @@ class ArenaStream:
     def load(self, schedule):
         """validate on the host, ONE host-to-device copy ({cursor = 0, T, ticket counter = 0, schedule}), returns T.  An epoch
         boundary: it waits for the steps already enqueued (they read the buffer it overwrites).  The ticket counter goes up with it, so
-        a launch that was ever cut short cannot leave the cursor stuck for the next epoch."""
+        a launch that was ever cut short cannot leave the cursor stuck for the next epoch.  (``minibatch_stream.MiniBatchStream``
+        keeps its launch's ticket counters in a tensor of its own and zeroes that in its ``load``, behind this one.)"""
         s = self._checked(schedule)
         T = int(s.shape[0])
         if self._sched is None:
