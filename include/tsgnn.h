@@ -242,6 +242,31 @@ int tsgnn_sag_anchor_gather_f32(const int32_t* records, int64_t n_graphs, const 
                                 const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket, int64_t row_cap,
                                 int64_t nnz_cap, float ratio, int depth, int32_t* rowptr, int32_t* col, float* x, int64_t ldx,
                                 float* dinv, float* self_w, int32_t* graph_ptr, int32_t* ids_out, tsgnn_stream_t stream);
+/* The SAGPool MINI-BATCH gather launch (sag_batch_stream.hip; Code/sag/train.py:181-198, one new mini-batch per optimiser step):
+ * tsgnn_sag_triplet_gather_f32's records, arena sections, feature table, [HEAD | schedule] buffer and per-row outputs, word for word
+ * (rowptr, col, x, dinv / self_w with the same padding rules), for entries of 1 <= B <= 128 graphs: schedule [T, B]; the workgroup
+ * forms the prefix sums of n and nnz once in LDS and a row finds its graph by binary search.  256 threads, 8 lanes per row,
+ * ceil(row_cap / 32) workgroups.  What it adds:
+ *   labels / label_out   int32 [n_graphs] per-graph label table -> label_out[B] as int64 (on 8 bytes); ids_out[B]
+ *   graph_ptr            int32 [depth + 1][ldg], ldg >= B + 1 and a multiple of 4 (B + 1 rounded up to 4 is the usual choice): level
+ *                        l holds the prefix of k^l(n_b), k = min(n, ceilf(ratio * (float)n)) in float32; words past B repeat the total
+ *   ticket               unsigned [33 * 32], zero between launches: tsgnn_batch_gather_f32's sharded counters, still the only atomics
+ *   capacities           max_n / max_nnz are the arena's largest n / nnz; level_caps (HOST int64 [depth + 1]) the row capacity of every
+ *                        level, level_caps[0] == row_cap.  The launch asks only row_cap >= max_n, nnz_cap >= max(max_nnz, 1) and
+ *                        level_caps[l] >= k^l(max_n), so a slot may be smaller than B times the largest graph.  Whether every ENTRY
+ *                        fits is checked by whoever uploads the schedule; for an entry that does not, nothing is written outside
+ *                        the arrays (rows and entries past the capacities are dropped, row pointers are clamped to nnz_cap and every
+ *                        graph pointer to its level's capacity) and the batch's content is not defined.
+ * TSGNN_EINVAL without a launch: a null pointer, B outside 1..128, depth outside 1..7, ratio outside (0, 1], sched_cap <= 0, a capacity
+ * below the largest graph at any level, level_caps[0] != row_cap, ldg < B + 1 or ldg % 4, sections out of order;
+ * TSGNN_EUNSUPPORTED without a launch: a buffer or a section off 16 bytes (label_out: 8), ldf % 4, ldx != ldf, sizes past 2^31 (B times
+ * max_n or max_nnz included: the prefix sums are int32). */
+int tsgnn_sag_batch_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t off_rowptr, int64_t off_col,
+                               int64_t arena_words, const float* feats, int64_t ldf, const int32_t* labels, int64_t max_n,
+                               int64_t max_nnz, const int32_t* sched, int64_t sched_cap, int64_t* state, unsigned* ticket, int B,
+                               int64_t row_cap, int64_t nnz_cap, const int64_t* level_caps, float ratio, int depth, int32_t* rowptr,
+                               int32_t* col, float* x, int64_t ldx, float* dinv, float* self_w, int32_t* graph_ptr, int64_t ldg,
+                               int32_t* ids_out, int64_t* label_out, tsgnn_stream_t stream);
 
 /* CSR transpose (A^T for dX = A^T dY); rows of the result sorted by column; src_e[p] = source entry */
 int tsgnn_csr_transpose(const int* rowptr, const int* col, const float* val, int64_t n_rows, int64_t n_cols,

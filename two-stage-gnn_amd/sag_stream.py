@@ -16,7 +16,12 @@ The second half of 2stg+ (Code/sag/train_triplet_pre_train.py:219-263: one optim
 data.y)``; the driver's ``model.map2_model`` is never read by ``Net.forward``) is ``PostTrainStream`` on the same machinery at ONE graph
 per entry (``SagArenaStream`` holds what the two streams share; ``tsgnn_sag_anchor_gather_f32``; the head, its log_softmax and the
 loss in one launch each way, ``post_train.apply_mlp3_nll``), ``post_train_step`` its eager drop-in and ``test_dataset`` the driver's
-``test()``."""
+``test()``.
+
+The family's "original" setting (Code/sag/train.py:181-198: ``DataLoader(batch_size=128, shuffle=True)``, ``F.nll_loss(model(data),
+data.y)``, Adam) is ``MiniBatchStream``: a NEW mini-batch of 1..128 graphs per replay (``tsgnn_sag_batch_gather_f32``,
+csrc/sag_batch_stream.hip), at capacities that default to the ``batch`` largest graphs level by level and are checked per entry at
+``load`` (``level_sums``, ``default_level_caps``, ``schedule_capacity``, ``check_fit``)."""
 import numpy as np
 import torch
 
@@ -43,11 +48,12 @@ class Arena:
         self.__dict__.update(kw)
 
 
-def pack_arena(datas, batch=3, limit=1 << 31):
+def pack_arena(datas, batch=3, limit=1 << 31, n_classes=None, labels=None):
     """``Data``-like objects (``.x [n, F]``, ``.edge_index [2, E]``: row 0 = source, row 1 = target) -> ``Arena``.  ValueError, naming
     the graph's index, for what the fused SAGPool node cannot take on a gathered batch: n < 1, n above
     ``tsgnn_sag_pool_graph_max_nodes()``, an edge id outside the graph, a graph that is not symmetric as a multiset (the in-kernel
-    filter needs it), feature widths that differ; and for offsets that reach ``limit`` (the records are int32).  Pure numpy: no GPU is touched."""
+    filter needs it), feature widths that differ; and for offsets that reach ``limit`` (the records are int32).  With ``n_classes``
+    the arena carries ``labels`` (int32 [G]: ``label_table`` of ``data.y`` or of ``labels``).  Pure numpy: no GPU is touched."""
     datas = list(datas)
     if not datas:
         raise ValueError("pack_arena: no graphs")
@@ -92,8 +98,9 @@ def pack_arena(datas, batch=3, limit=1 << 31):
     buf[off["col"]:off["col"] + ent0] = np.concatenate(cols)
     feats = np.zeros((row0, ld), dtype=np.float32)
     feats[:, :fin] = np.concatenate(fts)
+    table = label_table(datas, n_classes, labels) if n_classes is not None else None
     return Arena(records=rec.astype(np.int32), buf=buf, off=off, words=words, feats=feats, fin=fin, ld=ld, caps=(top(0), top(1)),
-                 batch=int(batch), largest=int(rec[:, 0].max()), n_graphs=G, total_nodes=row0)
+                 batch=int(batch), largest=int(rec[:, 0].max()), n_graphs=G, total_nodes=row0, labels=table)
 
 
 def k_chain(n, ratio, depth=3):
@@ -113,18 +120,25 @@ class CapacityPlan:
     """what ``sag_stack._SagStack`` reads from a ``SagPlan`` (``depth``, ``levels[l].B / N / gp / max_seg``) with every host value a
     capacity: N = batch k^l(largest n), max_seg = k^l(largest n) (k is monotone in n, so this bounds every graph at every level;
     ``batch``: 3 graphs per entry, or 1 for the post-training stream); ``gp`` are
-    the device tensors the gather launch writes (``gp_all [depth + 1, 4]``; pass ``device=None`` for the host values alone).
-    ``capacity = True`` is what ``_SagStack`` asks for."""
+    the device tensors the gather launch writes (``gp_all [depth + 1, ldg]``, ldg = batch + 1 rounded up to 4: 4 for a triplet and
+    for the anchor; pass ``device=None`` for the host values alone).  ``level_caps`` (``MiniBatchStream``): N of every level in place
+    of batch k^l(largest n), where the caller knows that no entry needs that much.  ``capacity = True`` is what ``_SagStack`` asks for."""
 
     capacity = True
 
-    def __init__(self, largest, ratio, depth=3, device=None, batch=3):
+    def __init__(self, largest, ratio, depth=3, device=None, batch=3, level_caps=None):
         self.ratio, self.depth, self.device, self.batch = float(ratio), int(depth), device, int(batch)
-        self.gp_all = torch.zeros(depth + 1, 4, dtype=torch.int32, device=device) if device is not None else None
+        self.ldg = _align4(self.batch + 1)
+        self.gp_all = torch.zeros(depth + 1, self.ldg, dtype=torch.int32, device=device) if device is not None else None
+        chain = k_chain(largest, ratio, depth)
+        if level_caps is not None:
+            level_caps = [int(c) for c in level_caps]
+            if len(level_caps) != depth + 1 or any(c < seg for c, seg in zip(level_caps, chain)):
+                raise ValueError("level_caps %s: one capacity per level, none below the largest graph's %s" % (level_caps, chain))
         self.levels = []
-        for l, seg in enumerate(k_chain(largest, ratio, depth)):
+        for l, seg in enumerate(chain):
             L = _CapLevel()
-            L.B, L.N, L.max_seg, L.sizes, L.row_graph = self.batch, self.batch * seg, seg, None, None
+            L.B, L.N, L.max_seg, L.sizes, L.row_graph = self.batch, level_caps[l] if level_caps is not None else self.batch * seg, seg, None, None
             L.gp = self.gp_all[l] if self.gp_all is not None else None
             self.levels.append(L)
 
@@ -173,14 +187,16 @@ class SagArenaStream(ArenaStream):
             self._refuse("needs sag_stack's per-graph level kernels with the in-kernel filter")
         return dev
 
-    def _init_arena(self, model, datas, dev, batch, max_steps):
-        """pack and upload the dataset, allocate the batch at ``batch`` times the largest graph"""
-        ar = self.arena = pack_arena(datas, batch=batch)
+    def _init_arena(self, model, datas, dev, batch, max_steps, arena=None, row_cap=None, nnz_cap=None, level_caps=None):
+        """pack and upload the dataset (or ``arena``, packed by the caller), allocate the batch at ``batch`` times the largest graph
+        (or at ``row_cap`` / ``nnz_cap`` / ``level_caps``: ``MiniBatchStream``, whose ``load`` checks every entry against them)"""
+        ar = self.arena = pack_arena(datas, batch=batch) if arena is None else arena
         if ar.fin != int(model.num_features):
             raise ValueError("%s: the dataset has %d features per node, the model takes %d" % (self.NAME, ar.fin, model.num_features))
         self.model, self.device, self.B = model, dev, int(batch)
-        self.row_cap, self.nnz_cap = ar.caps[0], max(ar.caps[1], 1)
-        self.plan = CapacityPlan(ar.largest, model.pooling_ratio, self.DEPTH, dev, batch=self.B)
+        self.row_cap = ar.caps[0] if row_cap is None else int(row_cap)
+        self.nnz_cap = max(ar.caps[1] if nnz_cap is None else int(nnz_cap), 1)
+        self.plan = CapacityPlan(ar.largest, model.pooling_ratio, self.DEPTH, dev, batch=self.B, level_caps=level_caps)
         i32 = lambda n: torch.zeros(n, dtype=torch.int32, device=dev)
         f32 = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
         self.rowptr, self.col = i32(self.row_cap + 1), i32(self.nnz_cap)
@@ -411,3 +427,257 @@ class PostTrainStream(SagArenaStream):
         def step():
             return self.step()[0]
         return step
+
+
+# ----------------------------------------------------------------------------- the mini-batch stream (the "original" setting)
+MAX_BATCH = 128
+TICKET_WORDS = 33 * 32   # the launch's ticket counters: 32 shards and the top, each on 128 bytes of its own (csrc/sag_batch_stream.hip)
+BATCH_EAGER = "; use the eager route, MiniBatchStream.eager_loss(ids) / mp.nll_loss(Net(use_batch=True)(collated batch), y)"
+
+
+def size_records(datas):
+    """int64 [G, 2] of (n, nnz) per ``Data``-like object: what the capacity helpers below read of an arena's records, without packing
+    one (``schedule_capacity`` in front of the stream's constructor)"""
+    return np.asarray([[int(d.x.shape[0]), int(np.prod(d.edge_index.shape)) // 2] for d in datas], dtype=np.int64).reshape(-1, 2)
+
+
+def k_levels(n, ratio, depth=3):
+    """``k_chain`` vectorised: int64 [..., depth + 1] of n, k(n), k(k(n)), ... with k = min(n, ceil(float32(ratio) * float32(n)))"""
+    out = [np.asarray(n, dtype=np.int64)]
+    for _ in range(int(depth)):
+        k = np.ceil(np.float32(ratio) * out[-1].astype(np.float32)).astype(np.int64)
+        out.append(np.minimum(out[-1], k))
+    return np.stack(out, axis=-1)
+
+
+def level_sums(records, schedule, ratio, depth=3):
+    """the rows of every level of every schedule entry: int64 [T, depth + 1] (a graph counts as often as the entry names it)"""
+    rec = np.asarray(records, dtype=np.int64)
+    return k_levels(rec[:, 0], ratio, depth)[np.asarray(schedule, dtype=np.int64)].sum(axis=1)
+
+
+def nnz_sums(records, schedule):
+    """the CSR entries of every schedule entry: int64 [T]"""
+    return np.asarray(records, dtype=np.int64)[:, 1][np.asarray(schedule, dtype=np.int64)].sum(axis=1)
+
+
+def _top_sum(v, batch):
+    s = np.sort(np.asarray(v, dtype=np.int64))[::-1][:int(batch)]
+    return int(s.sum() + (int(batch) - s.size) * s[0])
+
+
+def default_level_caps(records, batch, ratio, depth=3):
+    """rows no entry of ``batch`` DISTINCT graphs exceeds, per level: the sum of the ``batch`` largest k^l(n) (k is monotone in n, so
+    these are the ``batch`` largest graphs at every level; a dataset of fewer graphs: the largest stands in for the missing ones)"""
+    K = k_levels(np.asarray(records, dtype=np.int64)[:, 0], ratio, depth)
+    return [_top_sum(K[:, l], batch) for l in range(int(depth) + 1)]
+
+
+def default_nnz_cap(records, batch):
+    """CSR entries no entry of ``batch`` DISTINCT graphs exceeds (at least 1)"""
+    return max(_top_sum(np.asarray(records, dtype=np.int64)[:, 1], batch), 1)
+
+
+def schedule_capacity(records, schedule, ratio, depth=3):
+    """the schedule's own maxima -> {row_cap, nnz_cap, level_caps}, the constructor's keywords: the smallest capacities every entry
+    of ``schedule`` fits (never below the dataset's largest graph).  The default capacity has to cover the ``batch`` largest graphs in
+    one entry, which a shuffled epoch hardly ever draws; a loop that knows its schedules passes these instead"""
+    rec = np.asarray(records, dtype=np.int64)
+    s = np.asarray(schedule)
+    s = check_schedule(s, len(rec), s.shape[1] if s.ndim == 2 else 1)
+    floor = k_levels(rec[:, 0].max(), ratio, depth)
+    caps = np.maximum(level_sums(rec, s, ratio, depth).max(axis=0), floor)
+    return {"row_cap": int(caps[0]), "nnz_cap": int(max(nnz_sums(rec, s).max(), rec[:, 1].max(), 1)), "level_caps": [int(c) for c in caps]}
+
+
+def fits_mask(schedule, records, batch, row_cap, nnz_cap, level_caps, ratio):
+    """bool [T]: the entry's rows at every level and its CSR entries lie within the capacities (duplicates inside an entry count as often
+    as they appear).  ``check_schedule``'s ValueError for a wrong shape, a wrong dtype or an index out of range"""
+    s = check_schedule(schedule, len(records), int(batch))
+    lv = level_sums(records, s, ratio, len(level_caps) - 1)
+    return (lv <= np.asarray(level_caps, dtype=np.int64)).all(axis=1) & (lv[:, 0] <= int(row_cap)) & (nnz_sums(records, s) <= int(nnz_cap))
+
+
+def check_fit(schedule, records, batch, row_cap, nnz_cap, level_caps, ratio):
+    """-> the checked int32 schedule; ValueError naming the first entry that exceeds a capacity, and the eager route"""
+    s = check_schedule(schedule, len(records), int(batch))
+    lv, nz = level_sums(records, s, ratio, len(level_caps) - 1), nnz_sums(records, s)
+    caps = np.asarray(level_caps, dtype=np.int64)
+    bad = np.flatnonzero((lv > caps).any(axis=1) | (lv[:, 0] > int(row_cap)) | (nz > int(nnz_cap)))
+    if bad.size:
+        k = int(bad[0])
+        raise ValueError("schedule entry %d has %s rows (level by level) and %d CSR entries: more than this stream's capacity (row_cap %d, "
+                         "nnz_cap %d, level_caps %s)%s" % (k, lv[k].tolist(), nz[k], int(row_cap), int(nnz_cap), caps.tolist(), BATCH_EAGER))
+    return s
+
+
+class _DeviceData:
+    """a ``Data`` object's tensors on the device, for the eager route of a stream that was given host tensors"""
+    __slots__ = ("x", "edge_index", "__weakref__")
+
+    def __init__(self, d, dev):
+        self.x = torch.as_tensor(_np(d.x)).to(dev)
+        self.edge_index = torch.as_tensor(_np(d.edge_index)).long().reshape(2, -1).to(dev)
+
+
+class MiniBatchStream(SagArenaStream):
+    """An epoch of the SAGPool family's "original" setting (Code/sag/train.py:181-198: ``DataLoader(batch_size=128, shuffle=True)``,
+    ``F.nll_loss(model(data), data.y)``, Adam) from ONE hipGraph: the arena of ``pack_arena(datas, batch=B)``, a device label table, and
+    per replay the batch gather launch (``tsgnn_sag_batch_gather_f32``: the B graphs of "schedule entry number cursor" as one batch at
+    the stream's capacities, the graph pointer of every level, ``label`` int64 [B]), ``sag_stack``'s fused node on the capacity plan and
+    the head with in-kernel dropout and the loss folded into its backward (``mp.mlp3_log_softmax`` + ``mp.nll_loss``):
+
+        st = MiniBatchStream(model, datas, 128, max_steps=len(datas) // 128)
+        gs = GraphedStep(FlatTrainer(model, lr=5e-4, weight_decay=1e-4, clip=0), st.loss())
+        for epoch in ...:
+            full, rest = minibatch_stream.epoch_schedule(len(datas), 128, rng)
+            st.load(full)
+            for _ in range(len(full)): gs.step()
+            gs.synchronize()
+            ... st.eager_loss(rest) ...                          # the epoch's remainder: an exact batch
+
+    ``model``: a bare ``sag_layers.Net`` with ``conv="gcn"`` and, for ``batch`` > 1, ``use_batch=True``: the reference's ``Net`` throws
+    ``data.batch`` away (Code/sag/network.py:32, trap T6) and pools a mini-batch as ONE graph, whose [1, C] output cannot meet B labels;
+    the stream pools per graph.  Labels: ``data.y`` or ``labels``.  ``row_cap`` / ``nnz_cap`` / ``level_caps``: the capacities
+    (default: the sums of the ``batch`` largest graphs, level by level — any entry of distinct graphs fits; ``schedule_capacity`` gives
+    a schedule's own); ``load`` checks every entry against them on the host, so the launch never sees one that does not fit.
+    ``load(schedule [T, batch])``, ``fits(schedule)``, ``gather``, ``step() -> (loss, logp [batch, C])``, ``loss()`` (the callable for
+    ``GraphedStep``), ``eager_step(ids)`` / ``eager_loss(ids)``: the same step on the exact, unpadded batch of 1..``batch`` graphs
+    through ``Net``'s own fused forward with host-known sizes, for entries that do not fit and the epoch's remainder.  ``max_steps``
+    as ``TripletStream`` (the warm-up entry: ``batch`` copies of the smallest graph whose copies fit).  The dropout seed and device
+    counter are created here, so a capture never has to.  TypeError / ValueError ending in the eager route for whatever the fused
+    launches do not take."""
+
+    NAME = "sag_stream.MiniBatchStream"
+    TAKES = "takes a bare sag_layers.Net"
+    EAGER = BATCH_EAGER
+    GATHER = "sag_batch_gather_f32"
+
+    def __init__(self, model, datas, batch, labels=None, row_cap=None, nnz_cap=None, level_caps=None, max_steps=None):
+        from . import message_passing as mp
+        from .sag_triplet import _in_kernel_dropout, tripletnet
+        B = int(batch)
+        if not 1 <= B <= MAX_BATCH:
+            raise ValueError("%s: batch = %d lies outside 1..%d%s" % (self.NAME, B, MAX_BATCH, self.EAGER))
+        dev = self._check_model(model)
+        if B > 1 and not model.use_batch:
+            self._refuse("pools every graph of a mini-batch on its own, which is Net(use_batch=True): use_batch=False keeps the "
+                         "reference's network.py:32, which throws data.batch away and pools the mini-batch as ONE graph, so that its "
+                         "[1, C] output cannot meet %d labels" % B)
+        if not mp.mlp3_ok(torch.empty(B, 2 * int(model.nhid), dtype=torch.float32, device=dev), model.lin1, model.lin2, model.lin3):
+            self._refuse("needs a head the fused launches take at %d rows (tsgnn_mlp3_supported)" % B)
+        datas = list(datas)
+        self.n_classes = int(model.num_classes)
+        try:
+            ar = pack_arena(datas, batch=B, n_classes=self.n_classes, labels=labels)
+        except ValueError as e:
+            raise ValueError("%s: %s%s" % (self.NAME, e, self.EAGER)) from None
+        ratio = float(model.pooling_ratio)
+        self.max_n, self.max_nnz = int(ar.records[:, 0].max()), int(ar.records[:, 1].max())
+        caps = default_level_caps(ar.records, B, ratio, self.DEPTH) if level_caps is None else [int(c) for c in level_caps]
+        if row_cap is not None:
+            if level_caps is not None and int(row_cap) != caps[0]:
+                raise ValueError("%s: row_cap %d is not level_caps[0] = %d%s" % (self.NAME, int(row_cap), caps[0], self.EAGER))
+            caps[0] = int(row_cap)
+            if level_caps is None:                              # (a smaller level 0 bounds the levels behind it: k is monotone)
+                caps = [min(c, caps[0]) for c in caps]
+        nnz_cap = default_nnz_cap(ar.records, B) if nnz_cap is None else int(nnz_cap)
+        chain = k_chain(self.max_n, ratio, self.DEPTH)
+        if len(caps) != self.DEPTH + 1 or any(c < s for c, s in zip(caps, chain)) or nnz_cap < max(self.max_nnz, 1):
+            raise ValueError("%s: level_caps %s / nnz_cap %d lie below the dataset's largest graph (%s rows level by level, %d CSR entries)%s"
+                             % (self.NAME, caps, nnz_cap, chain, self.max_nnz, self.EAGER))
+        self._init_arena(model, datas, dev, B, max_steps, arena=ar, row_cap=caps[0], nnz_cap=nnz_cap, level_caps=caps)
+        self.level_caps = np.asarray(caps, dtype=np.int64)          # (host: the launch reads it at enqueue time)
+        self.labels = torch.from_numpy(ar.labels).to(dev)
+        self.label = torch.zeros(B, dtype=torch.int64, device=dev)  # int64 [B]: what mp.nll_loss takes
+        self._tickets = torch.zeros(TICKET_WORDS, dtype=torch.int32, device=dev)
+        self.datas, self._dev_datas, self._net = datas, {}, tripletnet(model)
+        _in_kernel_dropout(max(float(model.dropout_ratio), 0.0), dev)         # (creates the seed and the device counter)
+        self._warm_up_schedule()
+
+    def _warm_up_schedule(self):
+        """with ``max_steps``: a one-entry schedule for the ``GraphedStep``'s warm-up steps — ``batch`` copies of ONE graph, the
+        smallest whose copies fit every capacity.  ValueError, naming ``max_steps``, when no graph's copies fit: the caller then builds
+        the step after the first ``load``"""
+        if self.max_steps is not None:
+            if self.max_steps < 1:
+                raise ValueError("max_steps must be at least 1")
+            rec = self.arena.records.astype(np.int64)
+            one = np.arange(len(rec), dtype=np.int64).reshape(-1, 1).repeat(self.B, axis=1)
+            ok = np.flatnonzero(self.fits(one))
+            if not ok.size:
+                raise ValueError("%s: max_steps asks for a warm-up entry, and %d copies of no graph fit the capacities (level_caps %s, "
+                                 "nnz_cap %d); leave max_steps out and build the step after the first load(schedule)"
+                                 % (self.NAME, self.B, self.level_caps.tolist(), self.nnz_cap))
+            g = int(ok[np.argmin(rec[ok, 0])])
+            self.load(np.full((1, self.B), g, dtype=np.int64))
+
+    def _checked(self, schedule):
+        return check_fit(schedule, self.arena.records, self.B, self.row_cap, self.nnz_cap, self.level_caps, self.plan.ratio)
+
+    def load(self, schedule):
+        """``ArenaStream.load`` behind the capacity check of every entry; the launch's ticket counters go back to zero with the cursor"""
+        T = super().load(schedule)
+        self._tickets.zero_()
+        torch.cuda.current_stream(self.device).synchronize()     # (a GraphedStep replays on a stream of its own)
+        return T
+
+    def fits(self, schedule):
+        return fits_mask(schedule, self.arena.records, self.B, self.row_cap, self.nnz_cap, self.level_caps, self.plan.ratio)
+
+    def mine(self, *args, **kwargs):
+        raise RuntimeError("%s: a schedule entry names a mini-batch, not a triplet: there is no negative to mine" % self.NAME)
+
+    def gather(self):
+        """enqueue (current stream; capturable) the launch that writes the batch, the graph pointers and the labels of the cursor's
+        entry and advances the cursor"""
+        if self._sched is None:
+            raise RuntimeError("%s: load(schedule) before the first step" % self.NAME)
+        ar = self.arena
+        nat.call(self.GATHER, self.records, ar.n_graphs, self.buf, ar.off["rowptr"], ar.off["col"], ar.words, self.feats, ar.ld,
+                 self.labels, self.max_n, self.max_nnz, self._sched[HEAD:], self.max_steps, self._sched, self._tickets, self.B,
+                 self.row_cap, self.nnz_cap, self.level_caps.ctypes.data, float(self.plan.ratio), self.plan.depth, self.rowptr, self.col,
+                 self._x, self._x.stride(0), self.dinv, self.self_w, self.plan.gp_all, self.plan.ldg, self.ids_out, self.label)
+
+    def _head(self, r, label):
+        from . import message_passing as mp
+        m = self.model
+        if not mp.mlp3_ok(r, m.lin1, m.lin2, m.lin3):
+            raise RuntimeError("%s: the fused head does not take this model's readout rows%s" % (self.NAME, self.EAGER))
+        logp = mp.mlp3_log_softmax(r, m.lin1, m.lin2, m.lin3, m.dropout_ratio, m.training)
+        return mp.nll_loss(logp, label), logp
+
+    def step(self):
+        """gather launch + the fused node's readout rows + the head -> (loss, logp [batch, C]) of the cursor's entry"""
+        self.gather()
+        return self._head(self.readout(), self.label)
+
+    def loss(self):
+        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
+        def step():
+            return self.step()[0]
+        return step
+
+    # ------------------------------------------------------------------ the eager route
+    def _device_data(self, i):
+        d = self.datas[i]
+        if isinstance(d.x, torch.Tensor) and d.x.is_cuda and isinstance(d.edge_index, torch.Tensor) and d.edge_index.is_cuda:
+            return d
+        if i not in self._dev_datas:
+            self._dev_datas[i] = _DeviceData(d, self.device)
+        return self._dev_datas[i]
+
+    def eager_step(self, ids):
+        """the same step on the exact, unpadded batch of ``ids`` (1 to ``batch`` graphs): cached structure concatenated on the device,
+        ``Net``'s fused forward with host-known sizes, the same head -> (loss, logp)"""
+        ids = np.asarray(ids)
+        if ids.ndim != 1 or not 1 <= ids.size <= self.B or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError("eager_loss takes 1 to %d integer indices; got shape %s of %s" % (self.B, ids.shape, ids.dtype))
+        if int(ids.min()) < 0 or int(ids.max()) >= self.arena.n_graphs:
+            raise ValueError("indices must lie in [0, %d)" % self.arena.n_graphs)
+        r = self._net.readout(self._net.batch_of([self._device_data(int(i)) for i in ids]))
+        y = torch.from_numpy(self.arena.labels[ids].astype(np.int64)).to(self.device)
+        return self._head(r, y)
+
+    def eager_loss(self, ids):
+        return self.eager_step(ids)[0]
