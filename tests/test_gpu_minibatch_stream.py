@@ -529,6 +529,50 @@ def test_validator_refuses_without_a_launch():
     assert st.position() == before + 1
 
 
+@pytest.mark.parametrize("B", [3, 65])
+def test_a_schedule_word_past_n_graphs_is_clamped_into_the_records(B):
+    """the raw entry point told that the table holds G - 2 records (it holds G): schedule words G - 1 and G - 2 — outside the launch's
+    range, inside the allocation — must give, word for word in every output array, in ids_out and in the labels, what the same
+    schedule with every index replaced by min(index, G - 3) gives (csrc/stream_protocol.h, stream_entry_id).  B = 65: the words of
+    threads 63 and 64, one in each of the prologue's two waves."""
+    from two_stage_gnn_amd import _native as nat
+    from two_stage_gnn_amd.triplet_stream import HEAD
+    st, _, graphs, ds = _stream(_model(), B, exact=False)
+    G = len(graphs)
+    small = [i for i, n in enumerate(U.SIZES) if n <= 11 and i < G - 3]
+    sched = np.asarray([[small[(i + e) % len(small)] for i in range(B)] for e in range(3)], dtype=np.int64)
+    sched[0, 0], sched[0, B - 1] = G - 1, G - 2
+    sched[1, B // 2] = G - 1
+    sched[2, B - 2], sched[2, B - 1] = G - 2, G - 1
+    ar, g, b = st.arena, st.g, st.batch
+    ell, ell_w, (tail_ptr, tail_col) = g._ell
+    outs = {"graph_ptr": g.graph_ptr, "slot_count": g.slot_count, "row_graph": g.row_graph, "row_slot": g.row_slot, "ell": ell,
+            "tail_ptr": tail_ptr, "tail_col": tail_col, "ell_slots": b.ell_slots, "tail_slots": b.tail_slots, "x": st.x, "ids_out": st.ids_out,
+            "label": st.label}
+
+    def run(schedule):
+        st.load(schedule)
+        got = []
+        for _ in range(len(schedule)):
+            for t in outs.values():
+                t.view(torch.int32).fill_(POISON)                 # (words a launch does not write: the same in both passes)
+            nat.call("batch_gather_f32", st.records, G - 2, st.buf, ar.off["rowptr"], ar.off["col"], ar.off["tail_ptr"], ar.off["tail_col"],
+                     ar.words, st.feats, ar.ld, None, ar.fin, st.labels, st.max_n, st.max_tail, st._sched[HEAD:], st.max_steps, st._sched,
+                     st._tickets, st.B, ar.nmax, st.row_cap, st.tail_cap, ell_w, g.graph_ptr, g.slot_count, g.row_graph, g.row_slot, ell,
+                     tail_ptr, tail_col, b.ell_slots, b.tail_slots, st.x, st.x.stride(0), st.ids_out, st.label)
+            torch.cuda.synchronize()
+            got.append({k: t.view(torch.int32).clone() for k, t in outs.items()})
+        assert st.position() == len(schedule)
+        return got
+
+    want_ids = np.minimum(sched, G - 3)
+    stale, clamped = run(sched), run(want_ids)
+    for k in range(len(sched)):
+        assert clamped[k]["ids_out"].tolist() == want_ids[k].tolist()
+        for name in outs:
+            assert torch.equal(stale[k][name], clamped[k][name]), (k, name, int((stale[k][name] != clamped[k][name]).sum()))
+
+
 def test_constructor_refusals_name_the_eager_route():
     from two_stage_gnn_amd import dense_encoders as E
     from two_stage_gnn_amd import minibatch_stream as MS

@@ -171,6 +171,41 @@ def test_b3_and_b1_equal_the_existing_gather_launches_bit_for_bit(name, B):
                 assert np.array_equal(got[key], new[k][key]), (ratio, k, key)
 
 
+def _walk(st, sched, tickets):
+    """three launches of a three-entry schedule: after each the cursor, every ticket word (zero again) and ``ids_out``"""
+    assert st.load(sched) == 3 and st.position() == 0
+    for k, ids in enumerate(sched):
+        st.gather()
+        assert st.position() == k + 1, (k, "cursor")
+        assert not bool(tickets().any()), (k, "ticket words")
+        assert st.ids_out.tolist() == ids.tolist(), (k, "ids_out")
+
+
+@pytest.mark.parametrize("row_cap,workgroups", [(32, 1), (992, 31), (1024, 32), (1056, 33), (2112, 66)])
+def test_sharded_ticket_at_its_grid_edges(row_cap, workgroups):
+    """``stream_ticket_sharded`` (csrc/stream_protocol.h) where its arithmetic changes: 32 rows per workgroup, so ``row_cap`` sets the
+    grid — one workgroup, S = gridDim.x = 31, S = 32 with one member per shard, 33 (shard 0 has two members, the others one) and 66
+    (two shards of three, thirty of two)"""
+    from two_stage_gnn_amd import sag_stream as S
+    m, datas, st = _stream("fin1", 2, row_cap=row_cap)
+    assert st.row_cap == row_cap and (row_cap + 31) // 32 == workgroups and int(st.level_caps[0]) == row_cap
+    assert st.level_caps.tolist() == [min(c, row_cap) for c in [row_cap] + S.default_level_caps(st.arena.records, 2, M.RATIO, M.DEPTH)[1:]]
+    _walk(st, np.array([[2, 3], [0, 1], [3, 0]], dtype=np.int64), lambda: st._tickets)
+
+
+def test_flat_ticket_on_a_1d_and_a_2d_grid():
+    """``stream_ticket_flat``: ``sag_triplet_gather`` at its default capacity (gridDim.x workgroups) and ``gat_triplet_gather`` on small3
+    (gridDim.x * gridDim.y): the cursor and the single counter after each of three launches"""
+    import gat_stream_util as UG
+    import test_gpu_gat_stream as TG
+    import test_gpu_sag_stream as TS
+    from two_stage_gnn_amd.triplet_stream import HEAD
+    st = TS._stream("small6")[3]
+    _walk(st, U0.SCHEDULES["small6"][:3], lambda: st._sched[4:HEAD])
+    sg = TG._stream("small3")[3]
+    _walk(sg, UG.schedule("small3")[:3], lambda: sg._sched[4:HEAD])
+
+
 # ------------------------------------------------------------------------------------------------ 2. the streamed step
 def _grads(m):
     return {k: p.grad.detach().clone() for k, p in m.named_parameters() if p.grad is not None}

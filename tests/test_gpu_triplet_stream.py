@@ -376,3 +376,40 @@ def test_constructor_refuses_other_models():
                                  assign_input_dim=U.FIN, final_dim="output_dim").cuda()
     with pytest.raises(TypeError, match="eager drop-in"):
         triplet.TripletStream(triplet.tripletnet(sp), graphs)
+
+
+def test_a_schedule_word_past_n_graphs_is_clamped_into_the_records():
+    """the raw entry point told that the table holds G - 2 records (it holds G): schedule words G - 1 and G - 2 — outside the launch's
+    range, inside the allocation — must give, word for word in every output array and in ids_out, what the same schedule with every
+    index replaced by min(index, G - 3) gives (csrc/stream_protocol.h, stream_entry_id)"""
+    from two_stage_gnn_amd import _native as nat
+    graphs = U.dataset()
+    net, st = _stream(_model(), graphs)
+    G = len(graphs)
+    sched = np.asarray([[G - 1, 1, G - 2], [0, G - 2, G - 1], [G - 1, G - 1, 2], [3, G - 3, G - 2]], dtype=np.int64)
+    ar, g, b = st.arena, st.g, st.batch
+    ell, ell_w, (tail_ptr, tail_col) = g._ell
+    outs = {"graph_ptr": g.graph_ptr, "slot_count": g.slot_count, "row_graph": g.row_graph, "row_slot": g.row_slot, "ell": ell,
+            "tail_ptr": tail_ptr, "tail_col": tail_col, "ell_slots": b.ell_slots, "tail_slots": b.tail_slots, "x": st.x, "ids_out": st.ids_out}
+
+    def run(schedule):
+        st.load(schedule)
+        got = []
+        for _ in range(len(schedule)):
+            for t in outs.values():
+                t.view(torch.int32).fill_(POISON)                 # (words a launch does not write: the same in both passes)
+            nat.call("triplet_gather_f32", st.records, G - 2, st.buf, ar.off["rowptr"], ar.off["col"], ar.off["tail_ptr"],
+                     ar.off["tail_col"], ar.words, st.feats, ar.ld, ar.caps[0], ar.caps[2], st._sched[8:], st.max_steps, st._sched,
+                     st._sched[4:8], 3, ar.nmax, st.row_cap, st.tail_cap, ell_w, g.graph_ptr, g.slot_count, g.row_graph, g.row_slot, ell,
+                     tail_ptr, tail_col, b.ell_slots, b.tail_slots, st.x, st.x.stride(0), st.ids_out)
+            torch.cuda.synchronize()
+            got.append({k: t.view(torch.int32).clone() for k, t in outs.items()})
+        assert st.position() == len(schedule)
+        return got
+
+    want_ids = np.minimum(sched, G - 3)
+    stale, clamped = run(sched), run(want_ids)
+    for k in range(len(sched)):
+        assert clamped[k]["ids_out"].tolist() == want_ids[k].tolist()
+        for name in outs:
+            assert torch.equal(stale[k][name], clamped[k][name]), (k, name, int((stale[k][name] != clamped[k][name]).sum()))

@@ -19,7 +19,7 @@
 //   col_i, val_i past E_i and members_i past R_i are NOT written: every reader reaches them through rowptr_i / bptr_i.
 // Grid: x = the chunk count of the dataset's largest piece (summed over its arrays), y = the three pieces + one row of workgroups
 // that strides over the closing entries, the padding and the slot counts.  Cursor and ticket counter: the protocol of
-// csrc/triplet_stream.hip, on the same [HEAD | schedule] buffer.  One writer per word, plain vector stores (16 bytes wherever the
+// csrc/stream_protocol.h, on the same [HEAD | schedule] buffer.  One writer per word, plain vector stores (16 bytes wherever the
 // destination sits on 16 bytes: ea_copy, es_fill), the ticket counter is the only atomic.
 //
 // The number of pieces a schedule entry names is a template parameter of the body: 3 is the triplet launch above, 1 the ANCHOR launch of
@@ -28,6 +28,7 @@
 // graph_ptr_i[1] = the anchor's rows, bucket pointers sized for one graph, ids_out [1]; everything behind the anchor's own R_i / E_i
 // inert as above.
 #include "eigen_assemble_body.h"
+#include "stream_protocol.h"
 
 namespace {
 
@@ -60,13 +61,8 @@ __device__ __forceinline__ void es_gather_body(const EsArgs& a) {
   __shared__ EaPiece q_s;                     // this workgroup's piece (LDS: ea_piece_block indexes its levels at run time)
   const int tid = threadIdx.x;
   if (tid < NB) {
-    // (agent-scope load: the word is stored by the last workgroup of the previous launch, never through this CU's scalar cache)
-    const long long cur = __hip_atomic_load(reinterpret_cast<long long*>(a.state), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int64_t T = a.state[1];                                 // the loaded schedule's length: the host's word, kept inside the buffer
-    T = T < 1 ? 1 : (T > a.sched_cap ? a.sched_cap : T);
-    const int64_t c = (int64_t)((unsigned long long)cur % (unsigned long long)T);
-    int64_t id = a.sched[c * NB + tid];
-    id = id < 0 ? 0 : (id >= a.n_graphs ? a.n_graphs - 1 : id);      // (load() validated it; an index never leaves the records)
+    long long cur;
+    const int64_t id = stream_entry_id(a.state, a.sched, a.sched_cap, a.n_graphs, NB, tid, cur);
     const int4* r = reinterpret_cast<const int4*>(a.rec + id * ES_REC);
     const int4 r0 = r[0], r1 = r[1], r2 = r[2];
     int32_t* o = rec_s[tid];
@@ -75,15 +71,8 @@ __device__ __forceinline__ void es_gather_body(const EsArgs& a) {
     if (tid == 0) cur_s = cur;
   }
   __syncthreads();
-  // Every workgroup has READ the cursor by now (its value went through LDS), so it may draw its ticket: the workgroup that draws the
-  // last one knows that all have, leaves the counter at zero for the next launch and advances the cursor.
-  if (tid == 0) {
-    const unsigned t = atomicAdd(a.ticket, 1u);
-    if (t == gridDim.x * gridDim.y - 1) {
-      atomicExch(a.ticket, 0u);
-      __hip_atomic_store(reinterpret_cast<long long*>(a.state), cur_s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  // Every workgroup has READ the cursor by now (its value went through LDS), so it may draw its ticket
+  if (tid == 0) stream_ticket_flat(a.ticket, gridDim.x * gridDim.y, a.state, cur_s);
   const EaHead& h = a.h;
   const int nlev = h.nlev, L = nlev - 1;
   // where each piece goes, and the triplet's totals.  (The entry point checked the capacities against the arena's bounds; records

@@ -15,7 +15,7 @@
 //   graph_ptr[3] = R, iso_ptr[3] = I  the readout and the per-graph workgroups end at the last real row
 //   col, col_t, src_e_t, inv past E and the list past I are not written: every reader reaches them through the pointers above.
 // Grid: x = the chunk count of the largest piece (summed over its arrays), y = the three pieces + one row of workgroups that strides
-// over the padding.  Cursor and ticket counter: the protocol of csrc/triplet_stream.hip, on the same [HEAD | schedule] buffer.
+// over the padding.  Cursor and ticket counter: the protocol of csrc/stream_protocol.h, on the same [HEAD | schedule] buffer.
 // One writer per word, plain vector stores (16 bytes wherever the destination sits on 16 bytes: ga_copy_add, the padding feature
 // rows), the ticket counter is the only atomic.
 //
@@ -24,6 +24,7 @@
 // With one piece the schedule entries are one word, the grid is (chunks of the largest piece, 1 + 1), padding rows get row_graph 0,
 // graph_ptr[1] = R, iso_ptr[1] = I and ids_out[0] is the anchor's index.
 #include "gat_assemble_body.h"
+#include "stream_protocol.h"
 #include "../../include/tsgnn.h"
 
 namespace {
@@ -45,13 +46,8 @@ __device__ __forceinline__ void gs_gather_body(const GsArgs& a) {
   __shared__ long long cur_s;
   const int tid = threadIdx.x;
   if (tid < NB) {
-    // (agent-scope load: the word is stored by the last workgroup of the previous launch, never through this CU's scalar cache)
-    const long long cur = __hip_atomic_load(reinterpret_cast<long long*>(a.state), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int64_t T = a.state[1];                                 // the loaded schedule's length: the host's word, kept inside the buffer
-    T = T < 1 ? 1 : (T > a.sched_cap ? a.sched_cap : T);
-    const int64_t c = (int64_t)((unsigned long long)cur % (unsigned long long)T);
-    int64_t id = a.sched[c * NB + tid];
-    id = id < 0 ? 0 : (id >= a.n_graphs ? a.n_graphs - 1 : id);      // (load() validated it; an index never leaves the records)
+    long long cur;
+    const int64_t id = stream_entry_id(a.state, a.sched, a.sched_cap, a.n_graphs, NB, tid, cur);
     const int4 r0 = *reinterpret_cast<const int4*>(a.rec + id * GS_REC);
     const int4 r1 = *reinterpret_cast<const int4*>(a.rec + id * GS_REC + 4);
     rec_s[tid][0] = r0.x; rec_s[tid][1] = r0.y; rec_s[tid][2] = r0.z; rec_s[tid][3] = r0.w;
@@ -59,15 +55,8 @@ __device__ __forceinline__ void gs_gather_body(const GsArgs& a) {
     if (tid == 0) cur_s = cur;
   }
   __syncthreads();
-  // Every workgroup has READ the cursor by now (its value went through LDS), so it may draw its ticket: the workgroup that draws the
-  // last one knows that all have, leaves the counter at zero for the next launch and advances the cursor.
-  if (tid == 0) {
-    const unsigned t = atomicAdd(a.ticket, 1u);
-    if (t == gridDim.x * gridDim.y - 1) {
-      atomicExch(a.ticket, 0u);
-      __hip_atomic_store(reinterpret_cast<long long*>(a.state), cur_s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  // Every workgroup has READ the cursor by now (its value went through LDS), so it may draw its ticket
+  if (tid == 0) stream_ticket_flat(a.ticket, gridDim.x * gridDim.y, a.state, cur_s);
   // where each piece goes, and the batch's totals
   int row0[NB + 1], e0[NB + 1], i0[NB + 1];
   row0[0] = e0[0] = i0[0] = 0;

@@ -11,15 +11,15 @@
 //   gp [depth + 1][4]        the graph pointer of EVERY level: k_b = min(n_b, ceil(float32(ratio) * float32(n_b))) level after level,
 //                            what sag_stack.SagPlan computes on the host with np.float32
 //   ids_out [3]
-// Cursor and ticket counter: the protocol of csrc/triplet_stream.hip, on the same [HEAD | schedule] buffer.
+// Cursor and ticket counter: the protocol of csrc/stream_protocol.h, on the same [HEAD | schedule] buffer.
 // The number of graphs a schedule entry names is a template parameter of the body: 3 is the triplet launch above, 1 the ANCHOR launch of
 // the 2stg+ post-training step (Code/sag/train_triplet_pre_train.py:219-263: one optimiser step per graph at B = 1) — a schedule
 // [T, 1], capacities of ONE largest graph, gp rows (0, k_l, k_l, k_l) (still one 16-byte store: words 2 and 3 repeat the total),
 // ids_out [1].
-// One writer per word, plain vector stores (16 bytes wherever the destination's alignment is known: the feature rows, four rows'
-// row pointers and coefficients per store, a level's graph pointer; the columns land at a data-dependent offset and go out as
-// coalesced dwords), the ticket counter is the only atomic.
-#include "common.h"
+// The rows themselves: csrc/sag_gather_row.h (one writer per word, plain vector stores; a level's graph pointer is a 16-byte store
+// too); the ticket counter is the only atomic.
+#include "sag_gather_row.h"
+#include "stream_protocol.h"
 #include "../../include/tsgnn.h"
 
 namespace {
@@ -28,63 +28,50 @@ constexpr int SS_B = 3;                   // a triplet
 constexpr int SS_ANCHOR = 1;              // the anchor alone
 constexpr int SS_REC = 8;                 // int32 words of a record: n, nnz, first row, first entry, index, 0, 0, 0
 constexpr int SS_MAX_DEPTH = 7;
-constexpr int SS_EG = 8;                  // lanes per row
-constexpr int SS_ROWS = 256 / SS_EG;      // rows per workgroup
 
 struct SagGatherArgs {
   const int32_t* rec; int64_t n_graphs;
-  const int32_t *rowptr, *col;            // the arena's sections: graph g's n + 1 row pointers (graph-local) start at first row + g
-  const float* feats; int64_t ldf; int ld4;
   const int32_t* sched; int64_t sched_cap; int64_t* state; unsigned* ticket;      // state = {cursor, T}
-  int64_t row_cap, nnz_cap; float ratio; int depth;
-  int32_t *rowptr_out, *col_out; float* x; int64_t ldx; float *dinv, *self_w; int32_t *gp, *ids_out;
+  float ratio; int depth;
+  int32_t *gp, *ids_out;
+  SagRowIo io;
 };
 
-// 8 lanes per row, 32 rows per workgroup; the four rows of a 32-lane group leave their row pointers and coefficients as one
-// 16-byte store each through the group's first lane.
 template <int NB>
 __device__ __forceinline__ void sag_gather_body(const SagGatherArgs& a) {
   __shared__ int32_t rec_s[NB][SS_REC];
   __shared__ long long cur_s;
+  const SagRowIo& io = a.io;
   const int tid = threadIdx.x;
   if (tid < NB) {
-    // (agent-scope load: the word is stored by the last workgroup of the previous launch, never through this CU's scalar cache)
-    const long long cur = __hip_atomic_load(reinterpret_cast<long long*>(a.state), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    int64_t T = a.state[1];                                 // the loaded schedule's length: the host's word, kept inside the buffer
-    T = T < 1 ? 1 : (T > a.sched_cap ? a.sched_cap : T);
-    const int64_t c = (int64_t)((unsigned long long)cur % (unsigned long long)T);
-    int64_t id = a.sched[c * NB + tid];
-    id = id < 0 ? 0 : (id >= a.n_graphs ? a.n_graphs - 1 : id);      // (load() validated it; an index never leaves the records)
+    long long cur;
+    const int64_t id = stream_entry_id(a.state, a.sched, a.sched_cap, a.n_graphs, NB, tid, cur);
     const int4 r0 = *reinterpret_cast<const int4*>(a.rec + id * SS_REC);
     rec_s[tid][0] = r0.x; rec_s[tid][1] = r0.y; rec_s[tid][2] = r0.z; rec_s[tid][3] = r0.w;
     rec_s[tid][4] = (int32_t)id;
     if (tid == 0) cur_s = cur;
   }
   __syncthreads();
-  // Every workgroup has READ the cursor by now (its value went through LDS), so it may draw its ticket: the workgroup that draws the
-  // last one knows that all have, leaves the counter at zero for the next launch and advances the cursor.
-  if (tid == 0) {
-    const unsigned t = atomicAdd(a.ticket, 1u);
-    if (t == gridDim.x - 1) {
-      atomicExch(a.ticket, 0u);
-      __hip_atomic_store(reinterpret_cast<long long*>(a.state), cur_s + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-  }
+  // Every workgroup has READ the cursor by now (its value went through LDS), so it may draw its ticket
+  if (tid == 0) stream_ticket_flat(a.ticket, gridDim.x, a.state, cur_s);
 
-  const int64_t r = (int64_t)blockIdx.x * SS_ROWS + (tid >> 3);
-  const int sub = tid & (SS_EG - 1);
+  SagRow w;
+  w.r = (int64_t)blockIdx.x * SAG_ROWS + (tid >> 3);
+  w.sub = tid & (SAG_EG - 1);
+  w.lane = tid & 63;
   // the graph whose rows hold r, and the batch's totals: one pass over the three records, no data-dependent branch
   int n_tot = 0, e_tot = 0;
-  int b = NB, g0 = 0, eb = 0, row0 = 0, ent0 = 0, gid = 0;
+  int b = NB;
+  w.g0 = w.eb = w.row0 = w.ent0 = w.gid = 0;
   for (int k = 0; k < NB; ++k) {
     const int nk = rec_s[k][0], ek = rec_s[k][1];
-    const bool mine = r >= n_tot && r < (int64_t)n_tot + nk;
+    const bool mine = w.r >= n_tot && w.r < (int64_t)n_tot + nk;
     b = mine ? k : b;
-    g0 = mine ? n_tot : g0;
-    eb = mine ? e_tot : eb;
-    row0 = mine ? rec_s[k][2] : row0;
-    ent0 = mine ? rec_s[k][3] : ent0;
-    gid = mine ? rec_s[k][4] : gid;
+    w.g0 = mine ? n_tot : w.g0;
+    w.eb = mine ? e_tot : w.eb;
+    w.row0 = mine ? rec_s[k][2] : w.row0;
+    w.ent0 = mine ? rec_s[k][3] : w.ent0;
+    w.gid = mine ? rec_s[k][4] : w.gid;
     n_tot += nk;
     e_tot += ek;
   }
@@ -102,59 +89,12 @@ __device__ __forceinline__ void sag_gather_body(const SagGatherArgs& a) {
       *reinterpret_cast<int4*>(a.gp + 4 * tid) = make_int4(p[0], p[1], p[2], p[3]);
     }
     if (tid >= 32 && tid < 32 + NB) a.ids_out[tid - 32] = rec_s[tid - 32][4];
-    if (tid == 64) a.rowptr_out[a.row_cap] = e_tot;
+    if (tid == 64) io.rowptr_out[io.row_cap] = e_tot;
   }
-  const bool in_cap = r < a.row_cap;
-  const bool real = b < NB && in_cap;
-  const int lr = (int)(r - g0);
-  int e0 = 0, e1 = 0;
-  if (real) {
-    const int32_t* rp = a.rowptr + (int64_t)row0 + gid + lr;
-    e0 = rp[0]; e1 = rp[1];
-  }
-  bool has_self = false;
-  for (int e = e0 + sub; e < e1; e += SS_EG) {
-    const int c = a.col[(int64_t)ent0 + e];
-    has_self |= (c == lr);
-    const int64_t o = (int64_t)eb + e;
-    if (o < a.nnz_cap) a.col_out[o] = c + g0;
-  }
-  // (every lane of the wave is here: rows past row_cap only skip their stores)
-  const int lane = tid & 63;
-  has_self = ((unsigned)(__ballot(has_self) >> (lane & ~(SS_EG - 1))) & ((1u << SS_EG) - 1u)) != 0u;
-  float di = 0.f, sw = 0.f;
-  if (real) gcn_norm_coef(e1 - e0, has_self, di, sw);
-  const int rp_out = real ? eb + e0 : e_tot;
-  {
-    const int q0 = lane & ~31;                              // the 32-lane group's first lane: rows r .. r + 3 of a multiple of four
-    const int4 rp4 = make_int4(rp_out, __shfl(rp_out, q0 + 8, 64), __shfl(rp_out, q0 + 16, 64), __shfl(rp_out, q0 + 24, 64));
-    const float4 di4 = make_float4(di, __shfl(di, q0 + 8, 64), __shfl(di, q0 + 16, 64), __shfl(di, q0 + 24, 64));
-    const float4 sw4 = make_float4(sw, __shfl(sw, q0 + 8, 64), __shfl(sw, q0 + 16, 64), __shfl(sw, q0 + 24, 64));
-    if ((tid & 31) == 0 && in_cap) {
-      if (r + 3 < a.row_cap) {
-        *reinterpret_cast<int4*>(a.rowptr_out + r) = rp4;
-        *reinterpret_cast<float4*>(a.dinv + r) = di4;
-        *reinterpret_cast<float4*>(a.self_w + r) = sw4;
-      } else {                                              // the last rows of a capacity that is no multiple of four
-        const int rp_[4] = {rp4.x, rp4.y, rp4.z, rp4.w};
-        const float di_[4] = {di4.x, di4.y, di4.z, di4.w}, sw_[4] = {sw4.x, sw4.y, sw4.z, sw4.w};
-#pragma unroll
-        for (int u = 0; u < 4; ++u)
-          if (r + u < a.row_cap) {
-            a.rowptr_out[r + u] = rp_[u];
-            a.dinv[r + u] = di_[u];
-            a.self_w[r + u] = sw_[u];
-          }
-      }
-    }
-  }
-  if (in_cap) {
-    const float4* src = reinterpret_cast<const float4*>(a.feats + ((int64_t)row0 + lr) * a.ldf);
-    for (int c4 = sub; c4 < a.ld4; c4 += SS_EG) {
-      const float4 v = real ? src[c4] : make_float4(0.f, 0.f, 0.f, 0.f);
-      *reinterpret_cast<float4*>(a.x + r * a.ldx + 4 * c4) = v;
-    }
-  }
+  w.real = b < NB && w.r < io.row_cap;
+  w.e_tot = e_tot;
+  w.e_end = (int)((int64_t)e_tot < io.nnz_cap ? (int64_t)e_tot : io.nnz_cap);     // (= e_tot: the entry point's need_nnz check)
+  sag_gather_row(io, w);
 }
 
 __global__ __launch_bounds__(256) void sag_triplet_gather_kernel(SagGatherArgs a) { sag_gather_body<SS_B>(a); }
@@ -175,21 +115,21 @@ int sag_gather_launch(const int32_t* records, int64_t n_graphs, const int32_t* a
   // need_nnz are the caller's word, as the arena is (see tsgnn_triplet_gather_f32)
   if (row_cap < need_rows || nnz_cap < need_nnz) return TSGNN_EINVAL;
   if (off_rowptr < 0 || off_col < off_rowptr || arena_words < off_col) return TSGNN_EINVAL;
-  if (row_cap >= ((int64_t)1 << 31) - SS_ROWS || nnz_cap >= ((int64_t)1 << 31) || sched_cap >= ((int64_t)1 << 31) / NB)
+  if (row_cap >= ((int64_t)1 << 31) - SAG_ROWS || nnz_cap >= ((int64_t)1 << 31) || sched_cap >= ((int64_t)1 << 31) / NB)
     return TSGNN_EUNSUPPORTED;
   if ((ldf % 4) || ldx != ldf || ((off_rowptr | off_col) & 3)) return TSGNN_EUNSUPPORTED;
   const uintptr_t al = reinterpret_cast<uintptr_t>(records) | reinterpret_cast<uintptr_t>(arena) | reinterpret_cast<uintptr_t>(feats) |
                        reinterpret_cast<uintptr_t>(rowptr) | reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dinv) |
                        reinterpret_cast<uintptr_t>(self_w) | reinterpret_cast<uintptr_t>(graph_ptr) | reinterpret_cast<uintptr_t>(state);
   if (al & 15) return TSGNN_EUNSUPPORTED;
-  SagGatherArgs a{records, n_graphs, arena + off_rowptr, arena + off_col, feats, ldf, (int)(ldf / 4), sched, sched_cap, state, ticket,
-                  row_cap, nnz_cap, ratio, depth, rowptr, col, x, ldx, dinv, self_w, graph_ptr, ids_out};
+  SagGatherArgs a{records, n_graphs, sched, sched_cap, state, ticket, ratio, depth, graph_ptr, ids_out,
+                  {arena + off_rowptr, arena + off_col, feats, ldf, (int)(ldf / 4), row_cap, nnz_cap, rowptr, col, x, ldx, dinv, self_w}};
   if (NB == SS_B) {
     TSGNN_KNAME("sag_triplet_gather_kernel");
-    sag_triplet_gather_kernel<<<(unsigned)ceil_div64(row_cap, SS_ROWS), 256, 0, stream>>>(a);
+    sag_triplet_gather_kernel<<<(unsigned)ceil_div64(row_cap, SAG_ROWS), 256, 0, stream>>>(a);
   } else {
     TSGNN_KNAME("sag_anchor_gather_kernel");
-    sag_anchor_gather_kernel<<<(unsigned)ceil_div64(row_cap, SS_ROWS), 256, 0, stream>>>(a);
+    sag_anchor_gather_kernel<<<(unsigned)ceil_div64(row_cap, SAG_ROWS), 256, 0, stream>>>(a);
   }
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;

@@ -27,10 +27,9 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .triplet_stream import Arena, ArenaStream, HEAD, REC_WORDS, _align4, _graph_dict, check_schedule, pack_arena
+from .triplet_stream import Arena, ArenaStream, HEAD, REC_WORDS, TICKET_WORDS, _align4, _graph_dict, check_schedule, pack_arena
 
 MAX_BATCH = 128
-TICKET_WORDS = 33 * 32   # the launch's ticket counters: 32 shards and the top, each on 128 bytes of its own (csrc/batch_stream.hip)
 EAGER = "; use the eager route, MiniBatchStream.eager_loss(ids) / tu_data.TUDataset.collate + model.loss(model(x, g)[1], y)"
 
 
@@ -309,13 +308,6 @@ class MiniBatchStream(ArenaStream):
 
     def _checked(self, schedule):
         return check_fit(schedule, self.arena.records, self.B, self.row_cap, self.tail_cap)
-
-    def load(self, schedule):
-        """``ArenaStream.load`` behind the capacity check of every entry; the launch's ticket counters go back to zero with the cursor"""
-        T = super().load(schedule)
-        self._tickets.zero_()
-        torch.cuda.current_stream(self.device).synchronize()     # (a GraphedStep replays on a stream of its own)
-        return T
 
     def fits(self, schedule):
         return fits_mask(schedule, self.arena.records, self.B, self.row_cap, self.tail_cap)

@@ -27,7 +27,7 @@ import torch
 
 from . import _native as nat
 from .sag_triplet import _np, tail_ok
-from .triplet_stream import HEAD, ArenaStream, _align4, check_schedule, schedule_of  # noqa: F401  (the stream's vocabulary)
+from .triplet_stream import HEAD, TICKET_WORDS, ArenaStream, _align4, check_schedule, schedule_of  # noqa: F401  (the stream's vocabulary)
 
 REC_WORDS = 8          # int32 words of a graph's record: n, nnz, first row, first entry, index, 0, 0, 0
 EAGER = "; use the eager drop-in, tripletnet.forward(a, p, n)"
@@ -431,7 +431,6 @@ class PostTrainStream(SagArenaStream):
 
 # ----------------------------------------------------------------------------- the mini-batch stream (the "original" setting)
 MAX_BATCH = 128
-TICKET_WORDS = 33 * 32   # the launch's ticket counters: 32 shards and the top, each on 128 bytes of its own (csrc/sag_batch_stream.hip)
 BATCH_EAGER = "; use the eager route, MiniBatchStream.eager_loss(ids) / mp.nll_loss(Net(use_batch=True)(collated batch), y)"
 
 
@@ -614,13 +613,6 @@ class MiniBatchStream(SagArenaStream):
 
     def _checked(self, schedule):
         return check_fit(schedule, self.arena.records, self.B, self.row_cap, self.nnz_cap, self.level_caps, self.plan.ratio)
-
-    def load(self, schedule):
-        """``ArenaStream.load`` behind the capacity check of every entry; the launch's ticket counters go back to zero with the cursor"""
-        T = super().load(schedule)
-        self._tickets.zero_()
-        torch.cuda.current_stream(self.device).synchronize()     # (a GraphedStep replays on a stream of its own)
-        return T
 
     def fits(self, schedule):
         return fits_mask(schedule, self.arena.records, self.B, self.row_cap, self.nnz_cap, self.level_caps, self.plan.ratio)

@@ -10,7 +10,8 @@ replayed T times, trains the epoch with no host work per step beyond the replay.
 
 For the GraphSage-family step (``triplet.tripletnet`` over a ``GcnEncoderGraph`` whose conv stack runs as the fused node under
 per-graph statistics); DiffPool, SAGPool, GAT and EigenGCN have streams of their own on this module's protocol (``diffpool_stream``,
-``sag_stream``, ``gat_stream``, ``eigen_stream``).
+``sag_stream``, ``gat_stream``, ``eigen_stream``).  The protocol — the ``[HEAD | schedule]`` buffer, the cursor, the ticket counters —
+is owned here on the host (``HEAD``, ``TICKET_WORDS``, ``ArenaStream.load``) and by csrc/stream_protocol.h on the device.
 
 ``ArenaStream`` holds what does not depend on the number of graphs a schedule entry names; ``TripletStream`` (three) and
 ``post_train.PostTrainStream`` (one: the anchor of the 2stg+ post-training step) are its users.
@@ -22,6 +23,7 @@ from . import _native as nat
 from . import resident as R
 
 HEAD = 8               # int32 words in front of the schedule: cursor and T (two int64), the ticket counter, 3 spare
+TICKET_WORDS = 33 * 32   # the sharded ticket of the mini-batch launches: 32 shards and the top, each on 128 bytes of its own
 REC_WORDS = 8          # int32 words of a graph's record: n, nnz, ntail, first row, first entry, first tail entry, index, 0
 
 
@@ -216,8 +218,8 @@ class ArenaStream:
     def load(self, schedule):
         """validate on the host, ONE host-to-device copy ({cursor = 0, T, ticket counter = 0, schedule}), returns T.  An epoch
         boundary: it waits for the steps already enqueued (they read the buffer it overwrites).  The ticket counter goes up with it, so
-        a launch that was ever cut short cannot leave the cursor stuck for the next epoch.  (``minibatch_stream.MiniBatchStream``
-        keeps its launch's ticket counters in a tensor of its own and zeroes that in its ``load``, behind this one.)"""
+        a launch that was ever cut short cannot leave the cursor stuck for the next epoch; a stream that keeps sharded ticket counters
+        in a tensor of its own (``_tickets``, ``TICKET_WORDS``) has them zeroed here too."""
         s = self._checked(schedule)
         T = int(s.shape[0])
         if self._sched is None:
@@ -236,6 +238,9 @@ class ArenaStream:
         h[HEAD:HEAD + T * self.B] = s.reshape(-1)
         n = HEAD + T * self.B
         self._sched[:n].copy_(self._host[:n])
+        if getattr(self, "_tickets", None) is not None:
+            self._tickets.zero_()
+            torch.cuda.current_stream(self.device).synchronize()     # (a GraphedStep replays on a stream of its own)
         self.T = T
         return T
 
