@@ -391,7 +391,10 @@ int tsgnn_ragged_tn_direct_ro_f32(const float* s_mat, int64_t lds_, int K, const
 int tsgnn_wgrad_narrow_plan(int64_t rows, int K_in, int N, int64_t* ws_floats);
 int tsgnn_wgrad_narrow_f32(const float* z, int64_t ldz, const float* du, int64_t lddu, int64_t rows, int K_in, int N, float* ws,
                            float* dwb, tsgnn_stream_t stream);
-/* out[f] (+)= sum_r x[r,f] (bias gradients); ws >= ceil(rows/128)*F floats */
+/* out[f] (+)= sum_r x[r,f] (bias gradients); ws >= ceil(rows/128)*F floats.
+ * No rows (rows = 0 here and in tsgnn_linear_wgrad_f32 / _du_f32 with bias_only_rows = 0, K = 0 in tsgnn_gemm_splitk_f32): the row
+ * operands may be NULL (empty tensors have no storage), the outputs become zeros (or stay as they are under `accumulate`; the
+ * slabs become zeros when dw == NULL) and no product is launched, as in tsgnn_wgrad_narrow_f32. */
 int tsgnn_colsum_f32(const float* x, int64_t ld, int64_t rows, int F, float* out, float* ws, int accumulate,
                      tsgnn_stream_t stream);
 

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 from fp32_yardstick import _check
+from gemm_ref import _slab_ref
 from guard_buf import GUARD, PAT, Out, _du_ref, _owned  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -125,22 +126,6 @@ def test_gather_row_panels(rows, trans_b, K, N, normalize, fill):
              bias.cuda() if bias is not None else None, V.mat[:, c0:], ldc, R.mat if R is not None else None,
              Z.mat if Z is not None else None, Z.ld if Z is not None else 0, rows, K, N, normalize, fill)
     _check_panel("gather rows=%d tb=%d K=%d N=%d" % (rows, trans_b, K, N), rows, fill, K, N, c0, V, R, Z, ref64, ref32)
-
-
-def _slab_ref(z, du, rows, K_in, nslab, rps, bo, dtype):
-    """-> [nslab, K_in + 1, 128]: slab s = z[slab rows, :K_in]^T du[slab rows], row K_in = the column sums of du over the slab's rows and
-    its share of the bias-only rows behind `rows`"""
-    z, du = z.to(dtype), du.to(dtype)
-    out = torch.zeros(nslab, K_in + 1, 128, dtype=dtype)
-    per = -(-bo // nslab) if bo else 0
-    for s in range(nslab):
-        r0, r1 = s * rps, min(rows, (s + 1) * rps)
-        out[s, :K_in] = z[r0:r1, :K_in].t() @ du[r0:r1]
-        out[s, K_in] = du[r0:r1].sum(0)
-        if bo:
-            e0 = rows + s * per
-            out[s, K_in] += du[e0:max(e0, min(rows + bo, e0 + per))].sum(0)
-    return out
 
 
 @pytest.mark.parametrize("K_in", [89, 92, 128])

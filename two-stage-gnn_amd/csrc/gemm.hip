@@ -234,6 +234,21 @@ __global__ __launch_bounds__(256) void gemm_tn_rows_kernel(TnArgs g) {
   tn_rows_body<MT, NTt, NY>(g, tn_smem, blockIdx.x, blockIdx.y, gridDim.x);
 }
 
+// the ragged shapes with mt + nt > 8 ((1,8), (2,7), (2,8)) stage more than the 64 KB of dynamic LDS a launch gets without asking
+template <int MT, int NTt, int NY>
+void tn_rows_launch(dim3 grid, const TnArgs& g, tsgnn_stream_t stream) {
+  constexpr size_t lds = tn_rows_lds_bytes<MT, NTt>();
+  if (lds > 64 * 1024) {
+    static bool attr = false;
+    if (!attr) {
+      (void)hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_tn_rows_kernel<MT, NTt, NY>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                (int)lds);
+      attr = true;
+    }
+  }
+  gemm_tn_rows_kernel<MT, NTt, NY><<<grid, 256, lds, stream>>>(g);
+}
+
 // The fixed-order slab sum that every weight gradient of the library goes through: entry e of slabs[0 .. nslab) (stride per_slab).
 // Four wave groups take contiguous slab ranges, four accumulators each, and meet in LDS in group order: the same bits every run
 // (scripts/repeat_steps.py, repeat_diffpool.py).  All 256 threads of the block call it (it holds a barrier); every lane gets the sum.
@@ -415,11 +430,12 @@ int tsgnn_gemm_f32(const float* A, int64_t sam, int64_t sak, const float* B, int
                    int64_t scm, int64_t scn, int M, int N, int K, int batch, int64_t stride_a, int64_t stride_b,
                    int64_t stride_c, const int* seg_ptr, int ragged, int max_seg, float alpha, int accumulate,
                    tsgnn_stream_t stream) {
-  if (!A || !B || !C || M < 0 || N < 0 || K < 0 || batch <= 0) return TSGNN_EINVAL;
+  if (M < 0 || N < 0 || K < 0 || batch <= 0) return TSGNN_EINVAL;
   if (seg_ptr && ragged != 1 && ragged != 2) return TSGNN_EINVAL;
   if (!seg_ptr && ragged != 0) return TSGNN_EINVAL;
   const int Mgrid = (seg_ptr && ragged == 2) ? max_seg : M;
-  if (Mgrid <= 0 || N == 0) return TSGNN_OK;
+  if (Mgrid <= 0 || N == 0) return TSGNN_OK;               // no output elements (empty tensors have no storage)
+  if (!A || !B || !C) return TSGNN_EINVAL;
   GemmArgs g{A, B, C, sam, sak, sbk, sbn, scm, scn, stride_a, stride_b, stride_c, M, N, K, seg_ptr, ragged, 1, 0,
              alpha, accumulate};
   dim3 grid((unsigned)((N + BN - 1) / BN), (unsigned)((Mgrid + BM - 1) / BM), (unsigned)batch);
@@ -447,7 +463,12 @@ int tsgnn_gemm_splitk_plan(int M, int N, int K, int* ksplit, int64_t* ws_floats)
 int tsgnn_gemm_splitk_f32(const float* A, int64_t sam, int64_t sak, const float* B, int64_t sbk, int64_t sbn,
                           float* C, int M, int N, int K, int ksplit, float* ws, int accumulate,
                           tsgnn_stream_t stream) {
-  if (!A || !B || !C || M <= 0 || N <= 0 || K < 0 || ksplit < 1 || (ksplit > 1 && !ws)) return TSGNN_EINVAL;
+  if (!C || M <= 0 || N <= 0 || K < 0 || ksplit < 1) return TSGNN_EINVAL;
+  if (K == 0) {                                             // no rows: a zero product (empty tensors have no storage)
+    if (!accumulate) (void)hipMemsetAsync(C, 0, sizeof(float) * (size_t)M * N, stream);
+    return TSGNN_OK;
+  }
+  if (!A || !B || (ksplit > 1 && !ws)) return TSGNN_EINVAL;
   GemmArgs g{A, B, ksplit > 1 ? ws : C, sam, sak, sbk, sbn, (int64_t)N, 1, 0, 0, 0, M, N, K, nullptr, 0, ksplit,
              (int64_t)M * N, 1.f, accumulate};
   dim3 grid((unsigned)((N + BN - 1) / BN), (unsigned)(((M + BM - 1) / BM) * ksplit), 1);
@@ -506,7 +527,22 @@ int tsgnn_wgrad_reduce_multi_f32(const float* ws0, int nslab0, int K0, int N0, f
 static int linear_wgrad_launch(const float* z, int64_t ldz, const float* du, int64_t lddu, int64_t rows, int K_in, int N, int nslab,
                                int64_t rows_per_slab, int64_t bias_only_rows, float* ws, float* dw, float* db, float* du_part, int du_nb,
                                int du_F, float* du_dws, float* du_dbs, tsgnn_stream_t stream) {
-  if (!z || !du || !ws || rows < 0 || nslab <= 0 || rows_per_slab <= 0 || K_in <= 0 || N <= 0 || bias_only_rows < 0) return TSGNN_EINVAL;
+  if (!ws || rows < 0 || nslab <= 0 || rows_per_slab <= 0 || K_in <= 0 || N <= 0 || bias_only_rows < 0 || ldz < K_in || lddu < N)
+    return TSGNN_EINVAL;
+  if (rows == 0 && bias_only_rows == 0) {                   // no rows: zero gradients / zero slabs (empty tensors have no storage)
+    if (dw) {
+      (void)hipMemsetAsync(dw, 0, sizeof(float) * (size_t)K_in * N, stream);
+      if (db) (void)hipMemsetAsync(db, 0, sizeof(float) * (size_t)N, stream);
+      if (du_part) {                                        // the passenger still has rows to add up: its block alone
+        tn_rows_reduce_du<<<1, 256, 0, stream>>>(ws, 0, 0, 0, dw, db, du_part, du_nb, du_F, du_dws, du_dbs);
+        TSGNN_CHECK_LAUNCH();
+      }
+    } else {
+      (void)hipMemsetAsync(ws, 0, sizeof(float) * (size_t)nslab * (K_in + 1) * N, stream);
+    }
+    return TSGNN_OK;
+  }
+  if (!z || !du) return TSGNN_EINVAL;
   if (K_in > 128 || N > 128 || (ldz % 4) || (lddu % 4) || (N % 4) || (reinterpret_cast<uintptr_t>(z) & 15) ||
       (reinterpret_cast<uintptr_t>(du) & 15))
     return TSGNN_EUNSUPPORTED;
@@ -565,8 +601,7 @@ int tsgnn_ragged_tn_f32(const float* s_mat, int64_t lds_, const float* x, int64_
   TnArgs g{s_mat, lds_, x, ldx, 0, 0, K, N, ws, slab_row_ptr, 0};
   const unsigned ny = (mt * nt >= 8) ? 2u : 1u;
   const dim3 grid((unsigned)nslab, ny);
-#define TSGNN_RT(M_, N_) do { if (ny == 2) gemm_tn_rows_kernel<M_, N_, 2><<<grid, 256, 2 * TN_CH * 32 * (M_ + N_) * sizeof(float), stream>>>(g); \
-    else gemm_tn_rows_kernel<M_, N_, 1><<<grid, 256, 2 * TN_CH * 32 * (M_ + N_) * sizeof(float), stream>>>(g); } while (0)
+#define TSGNN_RT(M_, N_) do { if (ny == 2) tn_rows_launch<M_, N_, 2>(grid, g, stream); else tn_rows_launch<M_, N_, 1>(grid, g, stream); } while (0)
   switch (mt * 10 + nt) {
     case 11: TSGNN_RT(1, 1); break; case 12: TSGNN_RT(1, 2); break; case 13: TSGNN_RT(1, 3); break; case 14: TSGNN_RT(1, 4); break;
     case 15: TSGNN_RT(1, 5); break; case 16: TSGNN_RT(1, 6); break; case 17: TSGNN_RT(1, 7); break; case 18: TSGNN_RT(1, 8); break;
@@ -584,8 +619,7 @@ int tsgnn_ragged_tn_f32(const float* s_mat, int64_t lds_, const float* x, int64_
   return TSGNN_OK;
 }
 
-/* out[f] (+)= sum_r x[r,f];  ws >= nchunk*F floats with nchunk = ceil(rows/512) */
-/* floats of workspace for tsgnn_wgrad_narrow_f32 */
+/* floats of workspace for tsgnn_wgrad_narrow_f32: one [K_in + 1][N] partial per chunk of 128 rows (512 above 65,536 rows) */
 int tsgnn_wgrad_narrow_plan(int64_t rows, int K_in, int N, int64_t* ws_floats) {
   if (!ws_floats || rows < 0 || K_in <= 0 || N <= 0) return TSGNN_EINVAL;
   const int64_t rpc = rows > 65536 ? 512 : 128;
@@ -612,9 +646,15 @@ int tsgnn_wgrad_narrow_f32(const float* z, int64_t ldz, const float* du, int64_t
   return TSGNN_OK;
 }
 
+/* out[f] (+)= sum_r x[r,f];  ws >= nchunk*F floats with nchunk = ceil(rows/128) (ceil(rows/512) above 65,536 rows) */
 int tsgnn_colsum_f32(const float* x, int64_t ld, int64_t rows, int F, float* out, float* ws, int accumulate,
                      tsgnn_stream_t stream) {
-  if (!x || !out || !ws || rows < 0 || F <= 0 || ld < F) return TSGNN_EINVAL;
+  if (!out || rows < 0 || F <= 0 || ld < F) return TSGNN_EINVAL;
+  if (rows == 0) {                                          // no rows: a zero sum (empty tensors have no storage)
+    if (!accumulate) (void)hipMemsetAsync(out, 0, sizeof(float) * (size_t)F, stream);
+    return TSGNN_OK;
+  }
+  if (!x || !ws) return TSGNN_EINVAL;
   const int64_t rpc = rows > 65536 ? 512 : 128;          // short chunks: a bias gradient is a latency chain, not a stream
   const int nchunk = (int)(rows > 0 ? ceil_div64(rows, rpc) : 1);
   dim3 grid((unsigned)((F + 63) / 64), (unsigned)nchunk);
@@ -658,12 +698,22 @@ int tsgnn_wgrad_blocks_plan(int64_t rows, int K_in, int N, int64_t ldz, int64_t 
 
 static int wgrad_blocks_launch(const float* z, int64_t ldz, const float* du, int64_t lddu, int64_t rows, int K_in, int N, int nslab,
                                int64_t rows_per_slab, float* ws, float* dw, int64_t lddw, int oi, float* db, tsgnn_stream_t stream) {
-  if (!z || !du || !ws || rows < 0 || nslab <= 0 || rows_per_slab <= 0 || K_in <= 0 || N <= 0 || (dw && lddw < (oi ? K_in : N))) return TSGNN_EINVAL;
+  if (!ws || rows < 0 || nslab <= 0 || rows_per_slab <= 0 || K_in <= 0 || N <= 0 || (dw && lddw < (oi ? K_in : N))) return TSGNN_EINVAL;
+  if (rows > 0 && (!z || !du)) return TSGNN_EINVAL;
   if (K_in > 512 || N > 512 || (ldz % 4) || (lddu % 4) || (N % 4) || ldz < ((K_in + 3) / 4) * 4 || lddu < N ||
       ((reinterpret_cast<uintptr_t>(z) | reinterpret_cast<uintptr_t>(du)) & 15))
     return TSGNN_EUNSUPPORTED;
   const int KB = (K_in + 127) / 128, NB = (N + 127) / 128, nsets = KB * NB;
   if (nsets > WB_MAXSETS || (int64_t)nslab * rows_per_slab < rows) return TSGNN_EINVAL;
+  if (rows == 0) {                                          // no rows: zero gradients / zero slabs (empty tensors have no storage)
+    if (dw) {
+      (void)hipMemset2DAsync(dw, sizeof(float) * (size_t)lddw, 0, sizeof(float) * (size_t)(oi ? K_in : N), (size_t)(oi ? N : K_in), stream);
+      if (db) (void)hipMemsetAsync(db, 0, sizeof(float) * (size_t)N, stream);
+    } else {
+      (void)hipMemsetAsync(ws, 0, sizeof(float) * (size_t)nsets * nslab * WB_SET_FLOATS, stream);
+    }
+    return TSGNN_OK;
+  }
   WgradBlocks w{TnArgs{z, ldz, du, lddu, rows, rows_per_slab, K_in, N, ws, nullptr, 0}, NB, nsets, (int64_t)nslab * WB_SET_FLOATS};
   static bool attr = false;
   constexpr size_t lds = 2 * TN_CH * 32 * (4 + 4) * sizeof(float);
