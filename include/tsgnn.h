@@ -850,6 +850,22 @@ int tsgnn_gat_triplet_gather_f32(const int32_t* records, int64_t n_graphs, const
 int tsgnn_gat_anchor_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words, int64_t max_nr,
                                 int64_t max_nnz, int64_t max_k, const int32_t* sched, int64_t sched_cap, int64_t* state,
                                 unsigned* ticket, const int64_t* desc, int32_t* ids_out, tsgnn_stream_t stream);
+/* The same launch for 1 <= B <= 128 pieces per schedule entry: the mini-batch of the classification loop (train.py:104-131 with
+ * --method=GAT; gat_batch_stream.hip; host side: gat_stream.MiniBatchStream).  The schedule is [T, B], desc's B = B, and the capacities
+ * R, E, I of desc need only cover ONE largest piece of the arena: whether an entry fits is the uploader's check, and an entry that does
+ * not (R' > R or E' > E or I' > I), or that names a record whose sizes exceed max_nr / max_nnz / max_k or whose piece leaves the arena
+ * or does not start on 16 bytes, writes nothing and still advances the cursor.  Behind the entry's own [:R'] / [:E'] / [:I'] the padding
+ * as above with row_graph B - 1, graph_ptr[B] = R', iso_ptr[B] = I'.  labels int32[n_graphs]: the graphs' classes; ids_out[B] = the
+ * entry, label_out int64[B] = labels[ids_out].  ticket: the sharded ticket words (32 shards + the top, each on 128 bytes: 33 * 32
+ * words, zero before the first launch) in place of the flat ticket word; the grid is 1-D, (chunks of the largest piece) x (B + 1)
+ * workgroups.
+ * TSGNN_EINVAL without a launch: a null pointer, B outside 1..128, a header tsgnn_gat_assemble_f32 refuses or whose B differs, a
+ * capacity below the arena's largest piece; TSGNN_EUNSUPPORTED without a launch: records / arena / state off 16 bytes, label_out off
+ * 8 bytes, sizes past 2^31 (arena_words, B sched_cap, R ldf, B max_nr, B max_nnz), a grid of 2^31 workgroups or more. */
+int tsgnn_gat_batch_gather_f32(const int32_t* records, int64_t n_graphs, const int32_t* arena, int64_t arena_words, int64_t max_nr,
+                               int64_t max_nnz, int64_t max_k, const int32_t* labels, const int32_t* sched, int64_t sched_cap,
+                               int64_t* state, unsigned* ticket, int B, const int64_t* desc, int32_t* ids_out, int64_t* label_out,
+                               tsgnn_stream_t stream);
 /* Resident one-graph pieces of the EigenGCN encoder -> the complete EigenBatch of a chunk (eigen_pool.concat_batches of the same
  * one-graph batches, word for word): per level graph i = 0..L rowptr [R_i + Nmax + 1] (the Nmax ghost-slot rows empty), col, val,
  * graph_ptr [B + 1], row_graph, row_slot, slot_count [Nmax]; per pooling level i < L cluster_of [R_i] (-1 kept), coef [R_i, J],

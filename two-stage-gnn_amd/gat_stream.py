@@ -13,7 +13,10 @@ triplet tail run unchanged on that batch: its host-side sizes are the capacities
 ``graph_ptr`` and ``iso_ptr`` on the device.
 
 ``PostTrainStream`` is the same machinery at ONE piece per schedule entry (``tsgnn_gat_anchor_gather_f32``): the anchor steps of the
-2stg+ post-training phase (train_triplet_pre_train.py:233-262), with the loss on the readout row.  ``GatArenaStream`` holds what the two
+2stg+ post-training phase (train_triplet_pre_train.py:233-262), with the loss on the readout row.  ``MiniBatchStream`` is the
+classification loop of train.py --method=GAT (train.py:104-131): a NEW batch of 1..128 graphs per replay
+(``tsgnn_gat_batch_gather_f32``, csrc/gat_batch_stream.hip), at capacities that default to the sums of the ``batch`` largest pieces and
+are checked per entry at ``load`` (``default_caps``, ``schedule_capacity``, ``check_fit``).  ``GatArenaStream`` holds what the three
 share.
 
 No dropout (a ghost representative is exact only while its copies stay identical); anything the stream does not take is a TypeError
@@ -25,7 +28,7 @@ from . import _native as nat
 from . import gat_triplet as gt
 from . import resident as R
 from .graph import GraphBatch
-from .triplet_stream import HEAD, ArenaStream, check_schedule, schedule_of  # noqa: F401  (the stream's vocabulary)
+from .triplet_stream import HEAD, TICKET_WORDS, ArenaStream, check_schedule, schedule_of  # noqa: F401  (the stream's vocabulary)
 
 REC_WORDS = 8          # int32 words of a graph's record: piece offset (words), n, nr, nnz, k, Nmax - n, index, 0
 EAGER = "; use the eager drop-in, tripletnet.forward(a, p, n)"
@@ -128,16 +131,19 @@ class GatArenaStream(ArenaStream):
         if any(hd.dropout > 0 for hd in model.modules() if isinstance(hd, DGATHead)) or any(l.dropout > 0 for l in _layers(model)):
             self._refuse("takes no attention or input dropout (a ghost representative is exact only while its copies stay identical)")
 
-    def _build(self, model, dev, heads, graphs, batch, max_steps):
-        """the arena, the capacity batch and the uploads, once the model passed the refusals"""
+    def _build(self, model, dev, heads, graphs, batch, max_steps, caps=None, arena=None):
+        """the arena, the capacity batch and the uploads, once the model passed the refusals.  ``caps``: (rows, entries, listed
+        columns) in place of ``batch`` times the largest piece, ``arena``: ``pack_arena(graphs, batch=batch)`` where the caller has
+        packed already (``MiniBatchStream``, which reads its capacities off the records and whose ``load`` checks every entry
+        against them)"""
         from . import gat_fused as gf
         from .gat_encoders import _fused_layer_ok
-        ar = self.arena = pack_arena(graphs, batch=batch)
+        ar = self.arena = pack_arena(graphs, batch=batch) if arena is None else arena
         if ar.fin != int(model.conv_first.attentions[0].input_dim):
             raise ValueError("%s: the dataset has %d features per node, the model takes %d"
                              % (self.NAME, ar.fin, model.conv_first.attentions[0].input_dim))
         self.model, self.device, self.B, self.heads = model, dev, int(batch), heads
-        self.row_cap, self.nnz_cap, self.iso_cap = ar.caps
+        self.row_cap, self.nnz_cap, self.iso_cap = ar.caps if caps is None else caps
         self._allocate()
         if not all(_fused_layer_ok(l.attentions, self.g, self.row_cap) for l in _layers(model)) or not gf.readout_ok(self.g, self.row_cap):
             self._refuse("needs the fused GAT node on the gathered batch (the dataset's graphs list up to %d edge-less columns per %s)"
@@ -297,3 +303,241 @@ class PostTrainStream(GatArenaStream):
         def step():
             return self.step(with_out=False)[0]
         return step
+
+
+# ----------------------------------------------------------------------------- the mini-batch stream (the classification loop)
+MAX_BATCH = 128
+BATCH_EAGER = ("; use the eager route, MiniBatchStream.eager_loss(ids): gat_triplet.assemble of the resident pieces, gat_triplet.readout_rows, "
+               "model.head and model.loss")
+
+
+def size_records(graphs):
+    """int64 [G, 3] of (nr, nnz, k) per graph object — rows with the ghost representative, entries, listed edge-less columns
+    (``gat_triplet.pack_host``'s numbers): what the capacity helpers below read of an arena's records, without packing one
+    (``schedule_capacity`` in front of the stream's constructor)"""
+    out = np.zeros((len(graphs), 3), dtype=np.int64)
+    for i, o in enumerate(graphs):
+        p = gt.pack_host(o)
+        out[i] = (p["nr"], p["nnz"], p["k"])
+    return out
+
+
+def _sizes3(records):
+    """(nr, nnz, k) int64 [G, 3] of ``size_records``' rows or of an arena's records [G, 8]"""
+    rec = np.asarray(records, dtype=np.int64)
+    if rec.ndim != 2 or rec.shape[1] not in (3, REC_WORDS) or rec.shape[0] < 1:
+        raise ValueError("records are size_records' [G, 3] or an arena's [G, %d]; got shape %s" % (REC_WORDS, rec.shape))
+    return rec if rec.shape[1] == 3 else rec[:, 2:5]
+
+
+def entry_sums(records, schedule):
+    """rows, entries and listed columns of every schedule entry: int64 [T, 3] (a graph counts as often as the entry names it)"""
+    return _sizes3(records)[np.asarray(schedule, dtype=np.int64)].sum(axis=1)
+
+
+def _top_sum(v, batch):
+    s = np.sort(np.asarray(v, dtype=np.int64))[::-1][:int(batch)]
+    return int(s.sum() + (int(batch) - s.size) * s[0])
+
+
+def default_caps(records, batch):
+    """(row_cap, nnz_cap, iso_cap) no entry of ``batch`` DISTINCT graphs exceeds: the sums of the ``batch`` largest nr / nnz / k over
+    the dataset, each on its own (a dataset of fewer graphs: the largest stands in for the missing ones)"""
+    s = _sizes3(records)
+    return tuple(_top_sum(s[:, c], batch) for c in range(3))
+
+
+def schedule_capacity(records, schedule):
+    """the schedule's own maxima -> {row_cap, nnz_cap, iso_cap}, the constructor's keywords: the smallest capacities every entry of
+    ``schedule`` fits (never below the dataset's largest piece).  The default capacity has to cover the ``batch`` largest graphs in one
+    entry, which a shuffled epoch hardly ever draws; a loop that knows its schedules passes these instead"""
+    s3 = _sizes3(records)
+    s = np.asarray(schedule)
+    s = check_schedule(s, len(s3), s.shape[1] if s.ndim == 2 else 1)
+    caps = np.maximum(entry_sums(s3, s).max(axis=0), s3.max(axis=0))
+    return {"row_cap": int(caps[0]), "nnz_cap": int(caps[1]), "iso_cap": int(caps[2])}
+
+
+def fits_mask(schedule, records, batch, row_cap, nnz_cap, iso_cap):
+    """bool [T]: the entry's rows, entries and listed columns lie within the capacities (duplicates inside an entry count as often as
+    they appear).  ``check_schedule``'s ValueError for a wrong shape, a wrong dtype or an index out of range"""
+    s3 = _sizes3(records)
+    s = check_schedule(schedule, len(s3), int(batch))
+    return (entry_sums(s3, s) <= np.array([int(row_cap), int(nnz_cap), int(iso_cap)], dtype=np.int64)).all(axis=1)
+
+
+def check_fit(schedule, records, batch, row_cap, nnz_cap, iso_cap):
+    """-> the checked int32 schedule; ValueError naming the first entry that exceeds a capacity, and the eager route"""
+    s3 = _sizes3(records)
+    s = check_schedule(schedule, len(s3), int(batch))
+    need = entry_sums(s3, s)
+    bad = np.flatnonzero((need > np.array([int(row_cap), int(nnz_cap), int(iso_cap)], dtype=np.int64)).any(axis=1))
+    if bad.size:
+        k = int(bad[0])
+        raise ValueError("schedule entry %d has %d rows, %d entries and %d listed edge-less columns: more than this stream's capacity "
+                         "(row_cap %d, nnz_cap %d, iso_cap %d)%s" % (k, need[k, 0], need[k, 1], need[k, 2], int(row_cap), int(nnz_cap),
+                                                                      int(iso_cap), BATCH_EAGER))
+    return s
+
+
+class MiniBatchStream(GatArenaStream):
+    """An epoch of the GAT classification loop (Code/sage+gat+diffpool/train.py:104-131 with --method=GAT:
+    ``DGATEncoderGraph(final_dim='number_classes')``, ``model.loss(ypred, label)``, clip 2.0, Adam) from ONE hipGraph: the arena of
+    ``pack_arena``, a device label table, and per replay the batch gather launch (``tsgnn_gat_batch_gather_f32``,
+    csrc/gat_batch_stream.hip: the ``batch`` pieces of "schedule entry number cursor" as one packed batch at the stream's capacities,
+    ``label_out`` int64 [batch]), the fused GAT layers and the readout on that batch (``gat_triplet.readout_rows``) and the fused
+    head with the cross-entropy folded into its backward (``model.head``, ``model.loss``):
+
+        st = MiniBatchStream(model, graphs, 32, max_steps=len(graphs) // 32)
+        gs = GraphedStep(FlatTrainer(model, lr=1e-3, clip=2.0), st.loss())
+        for epoch in ...:
+            full, rest = minibatch_stream.epoch_schedule(len(graphs), 32, rng)
+            st.load(full)
+            for _ in range(len(full)): gs.step()
+            gs.synchronize()
+            ... st.eager_loss(rest) ...                          # the epoch's remainder: an exact batch
+
+    What a batch means: at ``batch`` = 1 this is exactly the reference's loop (its default ``batch_size`` is 1).  At ``batch`` > 1 the
+    reference's GAT reads graph 0's features for every graph of the batch (encoders_GAT.py:32, trap T4), so the stream runs the
+    project's ``per_graph_features`` extension, as ``gat_triplet.readout_rows`` / ``own_rows`` do for the three graphs of a triplet:
+    every graph reads its own rows, ONE batched step equals ``batch`` independent B = 1 reference forwards, and ``loss`` is the
+    mean of their ``batch`` cross-entropies.
+
+    ``model``: a bare ``gat_encoders.DGATEncoderGraph`` with ``final_dim != 'output_dim'`` (``ypred = pred_model(readout)`` has
+    ``label_dim`` columns); the layer, head-count and dropout refusals of ``TripletStream``, and a head that ``DGATEncoderGraph.head``
+    would run through library GEMMs instead of its fused launches is refused too; TypeErrors end in the eager route.  Labels:
+    ``post_train.label_table(graphs, model.label_dim)``.  ``row_cap`` / ``nnz_cap`` / ``iso_cap``: the capacities (default: the sums of
+    the ``batch`` largest nr / nnz / k over the dataset — any entry of distinct graphs fits; ``schedule_capacity`` gives a
+    schedule's own); ``load`` checks every entry against them on the host and refuses, naming the entry, one that does not fit (the
+    launch itself writes nothing for such an entry).  ``load(schedule [T, batch])``, ``fits(schedule)``, ``gather``,
+    ``step() -> (loss, ypred [batch, label_dim])``, ``loss()`` (the callable for ``GraphedStep``), ``eager_step(ids)`` /
+    ``eager_loss(ids)``: the same step on the exact batch of 1..``batch`` resident pieces through ``gat_triplet.assemble``, for the
+    epoch's remainder (``minibatch_stream.epoch_schedule``) and entries that do not fit.  ``max_steps`` as ``TripletStream`` (the
+    warm-up entry: ``batch`` copies of the smallest graph whose copies fit).  ``mine()`` refuses: an entry names a mini-batch."""
+
+    NAME = "gat_stream.MiniBatchStream"
+    EAGER = BATCH_EAGER
+
+    def __init__(self, model, graphs, batch, row_cap=None, nnz_cap=None, iso_cap=None, max_steps=None):
+        from . import post_train as PT
+        from .gat_encoders import DGATEncoderGraph
+        B = int(batch)
+        if not 1 <= B <= MAX_BATCH:
+            raise ValueError("%s: batch = %d lies outside 1..%d%s" % (self.NAME, B, MAX_BATCH, self.EAGER))
+        if not isinstance(model, DGATEncoderGraph):
+            self._refuse("takes a bare gat_encoders.DGATEncoderGraph")
+        if model.final_dim == "output_dim":
+            self._refuse("takes a model with final_dim != 'output_dim' (train.py's constructor: final_dim = 'number_classes', whose ypred "
+                         "has label_dim columns)")
+        self._refuse_dropout(model)
+        graphs = list(graphs)
+        labels = PT.label_table(graphs, model.label_dim)
+        dev = self._refuse_device(model)
+        heads = self._refuse_layers(model)
+        self._refuse_head(model, B, dev)
+        ar = pack_arena(graphs, batch=B)                            # (once: the capacities come off its records)
+        top = ar.top
+        caps = [int(c) if c is not None else d for c, d in zip((row_cap, nnz_cap, iso_cap), default_caps(ar.records, B))]
+        if any(c < t for c, t in zip(caps, top)):
+            raise ValueError("%s: row_cap %d / nnz_cap %d / iso_cap %d lie below the dataset's largest piece (%d rows, %d entries, %d listed "
+                             "edge-less columns)%s" % (self.NAME, caps[0], caps[1], caps[2], top[0], top[1], top[2], self.EAGER))
+        self._build(model, dev, heads, graphs, B, max_steps, caps=tuple(caps), arena=ar)
+        if self.row_cap * self.arena.ldf >= 1 << 31:
+            raise ValueError("%s: %d rows x %d floats reach 2^31 (int32 offsets)%s" % (self.NAME, self.row_cap, self.arena.ldf, self.EAGER))
+        self.n_classes = int(model.label_dim)
+        self.graphs, self._host_labels = graphs, labels
+        self.labels = torch.from_numpy(labels).to(dev)
+        self.label = torch.zeros(B, dtype=torch.int64, device=dev)   # int64 [B]: what mp.cross_entropy takes
+        self._tickets = torch.zeros(TICKET_WORDS, dtype=torch.int32, device=dev)
+        self._cache = R.cache_for(model)
+        self._warm_up_schedule()
+
+    def _refuse_head(self, model, B, dev):
+        """``DGATEncoderGraph.head`` on [B, embedding_dim] readout rows must take one of its fused routes (``mp.head2`` for two
+        Linears, the W2 = I form for the reference's Identity ``map2_model``): its last branch is library GEMMs without the folded
+        cross-entropy, which the stream does not fall back to"""
+        from . import gat_encoders as ge
+        from . import message_passing as mp
+        import torch.nn as nn
+        r = torch.empty(B, int(model.pred_input_dim), dtype=torch.float32, device=dev)
+        lin1 = model.pred_model
+        fused = mp.head2_ok(r, lin1, model.map2_model) or (
+            ge.FUSED_HEAD and isinstance(model.map2_model, nn.Identity) and isinstance(lin1, nn.Linear) and r.size(1) % 4 == 0
+            and r.size(0) <= 1024 and lin1.out_features <= 256 and lin1.weight.data_ptr() % 16 == 0)
+        if not fused:
+            self._refuse("needs a head the fused head launches take at %d rows (pred_model a Linear on an embedding_dim that is a "
+                         "multiple of 4, label_dim <= 256, map2_model the Identity or a Linear)" % B)
+
+    def _warm_up_schedule(self):
+        """with ``max_steps``: a one-entry schedule for the ``GraphedStep``'s warm-up steps — ``batch`` copies of ONE graph, the
+        smallest whose copies fit every capacity.  ValueError, naming ``max_steps``, when no graph's copies fit: the caller then builds
+        the step after the first ``load``"""
+        if self.max_steps is not None:
+            if self.max_steps < 1:
+                raise ValueError("max_steps must be at least 1")
+            rec = self.arena.records.astype(np.int64)
+            one = np.arange(len(rec), dtype=np.int64).reshape(-1, 1).repeat(self.B, axis=1)
+            ok = np.flatnonzero(self.fits(one))
+            if not ok.size:
+                raise ValueError("%s: max_steps asks for a warm-up entry, and %d copies of no graph fit the capacities (row_cap %d, nnz_cap "
+                                 "%d, iso_cap %d); leave max_steps out and build the step after the first load(schedule)"
+                                 % (self.NAME, self.B, self.row_cap, self.nnz_cap, self.iso_cap))
+            g = int(ok[np.argmin(rec[ok, 2])])
+            self.load(np.full((1, self.B), g, dtype=np.int64))
+
+    def _checked(self, schedule):
+        return check_fit(schedule, self.arena.records, self.B, self.row_cap, self.nnz_cap, self.iso_cap)
+
+    def fits(self, schedule):
+        return fits_mask(schedule, self.arena.records, self.B, self.row_cap, self.nnz_cap, self.iso_cap)
+
+    def mine(self, *args, **kwargs):
+        raise RuntimeError("%s: a schedule entry names a mini-batch, not a triplet: there is no negative to mine" % self.NAME)
+
+    def gather(self):
+        """enqueue (current stream; capturable) the launch that writes the batch and the labels of the cursor's entry and advances the
+        cursor"""
+        if self._sched is None:
+            raise RuntimeError("%s: load(schedule) before the first step" % self.NAME)
+        ar = self.arena
+        if self._parts is None or self._parts[0] is not self._sched:        # (a view of the schedule buffer, made once: load() keeps it)
+            self._parts = (self._sched, self._sched[HEAD:])
+        nat.call("gat_batch_gather_f32", self.records, ar.n_graphs, self.buf, ar.words, ar.top[0], ar.top[1], ar.top[2], self.labels,
+                 self._parts[1], self.max_steps, self._sched, self._tickets, self.B, self._desc.ctypes.data, self.ids_out, self.label)
+
+    def _head(self, x, g, label):
+        r = gt.readout_rows(self.model, x, g)
+        ypred = self.model.head(r)
+        return self.model.loss(ypred, label), ypred
+
+    def step(self):
+        """gather launch + the encoder's readout rows + the head + the loss -> (loss, ypred [batch, label_dim]) of the cursor's entry"""
+        if gt.dropout_active(self.model):
+            raise RuntimeError("%s: dropout became active on the model after the stream was built%s" % (self.NAME, self.EAGER))
+        self.gather()
+        return self._head(self.x, self.g, self.label)
+
+    def loss(self):
+        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
+        def step():
+            return self.step()[0]
+        return step
+
+    # ------------------------------------------------------------------ the eager route
+    def eager_step(self, ids):
+        """the same step on the exact batch of ``ids`` (1 to ``batch`` graphs): the resident pieces through ``gat_triplet.assemble``
+        (one launch per 8 pieces, host-known sizes), the same readout, head and loss -> (loss, ypred)"""
+        ids = np.asarray(ids)
+        if ids.ndim != 1 or not 1 <= ids.size <= self.B or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError("eager_loss takes 1 to %d integer indices; got shape %s of %s" % (self.B, ids.shape, ids.dtype))
+        if int(ids.min()) < 0 or int(ids.max()) >= self.arena.n_graphs:
+            raise ValueError("indices must lie in [0, %d)" % self.arena.n_graphs)
+        if gt.dropout_active(self.model):
+            raise RuntimeError("%s: dropout became active on the model after the stream was built" % self.NAME)
+        parts = [gt.resident_piece(self.graphs[int(i)], self.device, self._cache) for i in ids]
+        x, g = gt.assemble(parts, self.device, self.heads)
+        y = torch.from_numpy(self._host_labels[ids].astype(np.int64)).to(self.device)
+        return self._head(x, g, y)
+
+    def eager_loss(self, ids):
+        return self.eager_step(ids)[0]
