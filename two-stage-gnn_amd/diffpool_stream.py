@@ -17,7 +17,7 @@ import torch
 
 from . import _native as nat
 from . import post_train as PT
-from .triplet_stream import ArenaStream, _graph_dict, check_schedule, pack_arena, schedule_of  # noqa: F401  (the stream's vocabulary)
+from .triplet_stream import SageArenaStream, TripletSteps, _graph_dict, check_schedule, pack_arena, schedule_of  # noqa: F401  (the stream's vocabulary)
 
 EAGER = "; use the eager drop-in, tripletnet.forward(a, p, n)"
 # SoftPoolingGcnEncoder.forward derives `masked` from ``batch_num_nodes is not None`` and make_batch ignores the argument for a
@@ -74,7 +74,7 @@ class DiffPoolChecks:
         return True
 
 
-class TripletStream(DiffPoolChecks, ArenaStream):
+class TripletStream(TripletSteps, DiffPoolChecks, SageArenaStream):
     """``net``: a ``triplet.tripletnet`` over a ``SoftPoolingGcnEncoder`` with concat and bn, num_pooling >= 1 and
     final_dim == "output_dim"; ``graphs``: the dataset's graph objects.  The interface of ``triplet_stream.TripletStream``: ``load``,
     ``gather``, ``embed``, ``loss(criterion, target)``, ``position``, ``len``.  TypeError (ending in the eager drop-in) for a model
@@ -83,18 +83,17 @@ class TripletStream(DiffPoolChecks, ArenaStream):
 
     NAME = "diffpool_stream.TripletStream"
     EAGER = EAGER
+    TAKES = "takes a tripletnet over a SoftPoolingGcnEncoder with concat and bn, num_pooling >= 1 and final_dim == \"output_dim\""
 
     def __init__(self, net, graphs, nmax=None, max_steps=None):
         graphs = list(graphs)
         model = getattr(net, "model", None)
-        if not self._model_ok(model):
-            raise TypeError("%s %s%s" % (self.NAME, self._TAKES, EAGER))
+        if not self._model_ok(model):                   # (before the graphs are read; the base's constructor asks again)
+            self._refuse(self.TAKES)
         check_assign_feats(graphs)
-        super().__init__(model, graphs, 3, nmax, max_steps, name=self.NAME, takes=self._TAKES, eager=EAGER)
+        super().__init__(model, graphs, 3, nmax, max_steps)
         self.net = net
         self._warm_up_schedule()
-
-    _TAKES = "takes a tripletnet over a SoftPoolingGcnEncoder with concat and bn, num_pooling >= 1 and final_dim == \"output_dim\""
 
     def _model_ok(self, model):
         return self._family_ok(model) and model.final_dim == "output_dim"
@@ -104,15 +103,8 @@ class TripletStream(DiffPoolChecks, ArenaStream):
         self.gather()
         return self.net._embed(self.x, self.g, SIZES_ON_DEVICE, self.x)
 
-    def loss(self, criterion, target):
-        """-> callable for ``GraphedStep``: gather launch + ``net._embed`` on the gathered batch + ``criterion(dist_p, dist_n, target)``"""
-        def step():
-            out = self.embed()
-            return criterion(out[0], out[1], target)
-        return step
 
-
-class PostTrainStream(PT.PostTrainSteps, DiffPoolChecks, ArenaStream):
+class PostTrainStream(PT.PostTrainSteps, DiffPoolChecks, SageArenaStream):
     """An epoch of the 2stg+ post-training steps with --method=soft-assign from ONE hipGraph: ``post_train.PostTrainStream`` for a
     ``SoftPoolingGcnEncoder(final_dim='pretrain')`` with concat and bn and num_pooling >= 1 under the installed head
     (``post_train.install_head``).  Per replay: the gather launch at one graph, ``TripletStream``'s fused levels on it, every level's
@@ -123,18 +115,18 @@ class PostTrainStream(PT.PostTrainSteps, DiffPoolChecks, ArenaStream):
     NAME = "diffpool_stream.PostTrainStream"
     EAGER = PT.EAGER
     SIZES = SIZES_ON_DEVICE
-    _TAKES = "takes a SoftPoolingGcnEncoder with concat and bn, num_pooling >= 1 and final_dim == \"pretrain\""
+    TAKES = "takes a SoftPoolingGcnEncoder with concat and bn, num_pooling >= 1 and final_dim == \"pretrain\""
 
     def __init__(self, model, graphs, nmax=None, max_steps=None):
         graphs = list(graphs)
-        if not self._model_ok(model):
-            raise TypeError("%s %s%s" % (self.NAME, self._TAKES, self.EAGER))
+        if not self._model_ok(model):                   # (before the graphs are read; the base's constructor asks again)
+            self._refuse(self.TAKES)
         check_assign_feats(graphs)
         layers = PT.head_layers(model)
         if layers is not None:                     # (a label the head has no class for: named before anything is packed or uploaded)
             PT.label_table(graphs, layers[3].out_features)
-        super().__init__(model, graphs, 1, nmax, max_steps, name=self.NAME, takes=self._TAKES, eager=self.EAGER)
-        self._init_post_train(model, graphs, self.NAME, self.EAGER)
+        super().__init__(model, graphs, 1, nmax, max_steps)
+        self._init_post_train(model, graphs)
 
     def _model_ok(self, model):
         return self._family_ok(model) and model.final_dim == "pretrain"

@@ -30,15 +30,20 @@ from . import eigen_pool as ep
 from . import eigen_triplet as et
 from . import resident as R
 from .graph import GraphBatch
-from .triplet_stream import HEAD, ArenaStream, check_schedule, schedule_of  # noqa: F401  (the stream's vocabulary)
+from .post_train import AnchorSteps
+from .triplet_stream import HEAD, Arena, ArenaStream, TripletSteps, check_schedule, schedule_of  # noqa: F401  (the stream's vocabulary)
 
 REC_WORDS = 12         # int32 words of a graph's record: piece offset (words), index, n[0..3], nnz[0..3], 0, 0
 LMAX = 4               # level graphs a record holds (max_levels() + 1)
 EAGER = "; use the eager drop-in, tripletnet.forward(a, p, n)"
 
 
-class Arena:
-    """host arrays of a packed dataset (``pack_arena``):
+def pack_arena(graphs, L, J, Jf, limit=1 << 31, batch=3):
+    """graph objects (``.graph`` = {'adj', 'feats', 'num_nodes', 'adj_pool_i', 'num_nodes_i', 'pool_adj_i_j'} as cross_val.py prepares
+    them, or bare dicts) -> ``Arena``.  ValueError, naming the graph's index (and the level where one is at fault), for whatever
+    ``check_dict`` / ``pack_host`` reject, for an Nmax, a feature width or (L, J, Jf) that differs from the other graphs', for a level
+    adjacency that is not symmetric, for more levels than the assembler takes and for offsets that reach ``limit`` (the records are
+    int32).  Host work only: no GPU is touched.  The arena's fields:
       records  int32 [G, 12]   the piece's word offset in ``buf``, the graph's index, n[0..3], nnz[0..3] (unused levels 0), 0, 0
       buf      int32 [words]   every graph's ``eigen_triplet.piece_buffer`` (sections at ``tsgnn_eigen_assemble_layout``'s offsets,
                                piece-local indices), one behind the other, each piece on 16 bytes
@@ -48,17 +53,6 @@ class Arena:
                                negative's positive; the three largest DISTINCT graphs would not cover that)
       nmax, fin, ldf, L, J, Jf   what every graph shares: the padded size, the feature width, the 16-byte row stride of the feature
                                rows, the pooling levels and the pooling / final matrices per level"""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-
-def pack_arena(graphs, L, J, Jf, limit=1 << 31, batch=3):
-    """graph objects (``.graph`` = {'adj', 'feats', 'num_nodes', 'adj_pool_i', 'num_nodes_i', 'pool_adj_i_j'} as cross_val.py prepares
-    them, or bare dicts) -> ``Arena``.  ValueError, naming the graph's index (and the level where one is at fault), for whatever
-    ``check_dict`` / ``pack_host`` reject, for an Nmax, a feature width or (L, J, Jf) that differs from the other graphs', for a level
-    adjacency that is not symmetric, for more levels than the assembler takes and for offsets that reach ``limit`` (the records are
-    int32).  Host work only: no GPU is touched."""
     graphs = list(graphs)
     L, J, Jf = int(L), int(J), int(Jf)
     if not graphs:
@@ -122,9 +116,6 @@ class EigenArenaStream(ArenaStream):
     EAGER = EAGER
     GATHER = "eigen_triplet_gather_f32"
 
-    def _refuse(self, what):
-        raise TypeError("%s %s%s" % (self.NAME, what, self.EAGER))
-
     def _check_model(self, model, L):
         """the refusals every EigenGCN stream shares -> the model's device"""
         dev = next(model.parameters()).device
@@ -140,19 +131,12 @@ class EigenArenaStream(ArenaStream):
 
     def _init_arena(self, model, graphs, dev, shape, batch, max_steps):
         """pack and upload the dataset, allocate the batch at ``batch`` times the largest piece per level; ``shape`` = (L, J, Jf)"""
-        ar = self.arena = pack_arena(graphs, *shape, batch=batch)
+        ar = pack_arena(graphs, *shape, batch=batch)
         if ar.fin != int(model.conv_first.input_dim):
             raise ValueError("%s: the dataset has %d features per node, the model takes %d" % (self.NAME, ar.fin, model.conv_first.input_dim))
-        self.model, self.device, self.B = model, dev, int(batch)
         self.row_caps, self.nnz_caps = ar.caps
         self._top = (np.array(ar.top[0], dtype=np.int64), np.array(ar.top[1], dtype=np.int64))
-        self._allocate()
-        self.records = torch.from_numpy(ar.records).to(dev)
-        self.buf = torch.from_numpy(ar.buf).to(dev)
-        self.ids_out = torch.zeros(self.B, dtype=torch.int32, device=dev)
-        self.max_steps = int(max_steps) if max_steps is not None else None
-        self._sched = self._host = self._parts = None
-        self.T = 0
+        self._init_protocol(model, dev, batch, ar, max_steps, self._allocate)
 
     def layout(self, guard=0):
         """(ioff, isz, foff, fsz): ``eigen_triplet.assemble``'s two-buffer layout with R_i, E_i = the capacities; ``guard`` words behind
@@ -219,16 +203,13 @@ class EigenArenaStream(ArenaStream):
 
     def gather(self):
         """enqueue (current stream; capturable) the launch that writes the batch of the cursor's entry and advances the cursor"""
-        if self._sched is None:
-            raise RuntimeError("%s: load(schedule) before the first step" % self.NAME)
+        entries, ticket = self._loaded(self.NAME)
         ar = self.arena
-        if self._parts is None or self._parts[0] is not self._sched:        # (views of the schedule buffer, made once: load() keeps it)
-            self._parts = (self._sched, self._sched[HEAD:], self._sched[4:HEAD])
         nat.call(self.GATHER, self.records, ar.n_graphs, self.buf, ar.words, self._top[0].ctypes.data,
-                 self._top[1].ctypes.data, self._parts[1], self.max_steps, self._sched, self._parts[2], self._desc.ctypes.data, self.ids_out)
+                 self._top[1].ctypes.data, entries, self.max_steps, self._sched, ticket, self._desc.ctypes.data, self.ids_out)
 
 
-class TripletStream(EigenArenaStream):
+class TripletStream(TripletSteps, EigenArenaStream):
     """``net``: an ``eigen_triplet.tripletnet``; ``graphs``: the dataset's graph objects (they are packed once).  The interface of
     ``triplet_stream.TripletStream``: ``load(schedule)`` (``[T, 3]`` indices into ``graphs``), ``gather``, ``embed``,
     ``loss(criterion, target)`` (the step for ``GraphedStep``: every call, every replay, consumes the next entry), ``position``,
@@ -256,19 +237,12 @@ class TripletStream(EigenArenaStream):
         self.gather()
         return self.net.embed(self.batch)
 
-    def loss(self, criterion, target):
-        """-> callable for ``GraphedStep``: gather launch + the encoder + the tail + ``criterion(dist_p, dist_n, target)``"""
-        def step():
-            out = self.embed()
-            return criterion(out[0], out[1], target)
-        return step
-
 
 # ----------------------------------------------------------------------------- the post-training phase of 2stg+ (streamed)
 POST_EAGER = "; use the eager drop-in, eigen_stream.post_train_step(model, graph)"
 
 
-class PostTrainStream(EigenArenaStream):
+class PostTrainStream(AnchorSteps, EigenArenaStream):
     """An epoch of EigenGCN post-training steps (Code/eigengcn/train_triplet_pre_train.py:192-247: one optimiser step on the sampler's
     ANCHOR at B = 1, ``loss = model.loss(model(...), label)``) from ONE hipGraph: the arena of ``pack_arena(..., batch=1)``, a device
     label table, and per replay the anchor gather launch (``tsgnn_eigen_anchor_gather_f32``: the whole one-graph ``EigenBatch`` of
@@ -303,10 +277,6 @@ class PostTrainStream(EigenArenaStream):
         self.labels = torch.from_numpy(table).to(dev)
         self._warm_up_schedule()
 
-    def _checked(self, anchors):
-        from .post_train import check_anchors
-        return check_anchors(anchors, self.arena.n_graphs)
-
     def step(self):
         """gather launch + the encoder's readout row + ``pred_model`` and the loss -> (loss, ypred) of the cursor's entry"""
         from . import post_train as PT
@@ -316,12 +286,6 @@ class PostTrainStream(EigenArenaStream):
         with R.per_graph_statistics(self.model):
             r = self.model(self.x, self.eb, readout_only=True)
         return PT.apply_mlp2_ce(self.model, r, self.ids_out, self.labels)
-
-    def step_loss(self):
-        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
-        def step():
-            return self.step()[0]
-        return step
 
 
 # ----------------------------------------------------------------------------- the post-training phase of 2stg+ (eager)

@@ -28,24 +28,12 @@ from . import _native as nat
 from . import gat_triplet as gt
 from . import resident as R
 from .graph import GraphBatch
-from .triplet_stream import HEAD, TICKET_WORDS, ArenaStream, check_schedule, schedule_of  # noqa: F401  (the stream's vocabulary)
+from .minibatch_stream import MAX_BATCH, MiniBatchSteps, compare, top_sum
+from .post_train import AnchorSteps
+from .triplet_stream import HEAD, TICKET_WORDS, Arena, ArenaStream, TripletSteps, check_schedule, schedule_of  # noqa: F401  (the stream's vocabulary)
 
 REC_WORDS = 8          # int32 words of a graph's record: piece offset (words), n, nr, nnz, k, Nmax - n, index, 0
 EAGER = "; use the eager drop-in, tripletnet.forward(a, p, n)"
-
-
-class Arena:
-    """host arrays of a packed dataset (``pack_arena``):
-      records  int32 [G, 8]    the piece's word offset in ``buf``, n, nr, nnz, k, mult = Nmax - n, the graph's index, 0
-      buf      int32 [words]   every graph's ``gat_triplet.piece_buffer`` (sections at ``tsgnn_gat_assemble_layout``'s offsets, piece-local
-                               indices), one behind the other, each piece on 16 bytes
-      top      (nr, nnz, k)    the largest of each over the dataset
-      caps     (rows, nnz, k)  ``batch`` (3) times ``top``: no triplet needs more, also when one object fills all three places (a sampler may
-                               draw an anchor as its own negative's positive; the three largest DISTINCT graphs would not cover that)
-      nmax, fin, ldf           what every graph shares: the padded size, the feature width, the 16-byte row stride of the feature rows"""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
 
 
 def pack_arena(graphs, limit=1 << 31, batch=3):
@@ -53,7 +41,15 @@ def pack_arena(graphs, limit=1 << 31, batch=3):
     ValueError, naming the graph's index, for what one ghost representative cannot stand for (``pack_host``'s ``exact`` is False: the
     padded feature rows differ, or ``adj`` is positive outside ``[:n, :n]``), for an Nmax or a feature width that differs from the
     other graphs', and for offsets that reach ``limit`` (the records are int32).  ``batch``: the pieces a schedule entry names (3: a
-    triplet; 1: the anchor of a post-training step); ``caps = batch * top``.  Host work only: no GPU is touched."""
+    triplet; 1: the anchor of a post-training step); ``caps = batch * top``.  Host work only: no GPU is touched.
+    The arena's fields:
+      records  int32 [G, 8]    the piece's word offset in ``buf``, n, nr, nnz, k, mult = Nmax - n, the graph's index, 0
+      buf      int32 [words]   every graph's ``gat_triplet.piece_buffer`` (sections at ``tsgnn_gat_assemble_layout``'s offsets, piece-local
+                               indices), one behind the other, each piece on 16 bytes
+      top      (nr, nnz, k)    the largest of each over the dataset
+      caps     (rows, nnz, k)  ``batch`` (3) times ``top``: no triplet needs more, also when one object fills all three places (a sampler may
+                               draw an anchor as its own negative's positive; the three largest DISTINCT graphs would not cover that)
+      nmax, fin, ldf           what every graph shares: the padded size, the feature width, the 16-byte row stride of the feature rows"""
     graphs = list(graphs)
     if not graphs:
         raise ValueError("pack_arena: no graphs")
@@ -104,9 +100,6 @@ class GatArenaStream(ArenaStream):
     EAGER = EAGER
     ENTRY = {3: "gat_triplet_gather_f32", 1: "gat_anchor_gather_f32"}
 
-    def _refuse(self, what):
-        raise TypeError("%s %s%s" % (self.NAME, what, self.EAGER))
-
     def _refuse_device(self, model):
         dev = next(model.parameters()).device
         if dev.type != "cuda":
@@ -131,29 +124,28 @@ class GatArenaStream(ArenaStream):
         if any(hd.dropout > 0 for hd in model.modules() if isinstance(hd, DGATHead)) or any(l.dropout > 0 for l in _layers(model)):
             self._refuse("takes no attention or input dropout (a ghost representative is exact only while its copies stay identical)")
 
-    def _build(self, model, dev, heads, graphs, batch, max_steps, caps=None, arena=None):
+    def _build(self, model, dev, heads, graphs, batch, max_steps, caps=None, arena=None, tickets=False):
         """the arena, the capacity batch and the uploads, once the model passed the refusals.  ``caps``: (rows, entries, listed
         columns) in place of ``batch`` times the largest piece, ``arena``: ``pack_arena(graphs, batch=batch)`` where the caller has
         packed already (``MiniBatchStream``, which reads its capacities off the records and whose ``load`` checks every entry
         against them)"""
-        from . import gat_fused as gf
-        from .gat_encoders import _fused_layer_ok
-        ar = self.arena = pack_arena(graphs, batch=batch) if arena is None else arena
+        ar = pack_arena(graphs, batch=batch) if arena is None else arena
         if ar.fin != int(model.conv_first.attentions[0].input_dim):
             raise ValueError("%s: the dataset has %d features per node, the model takes %d"
                              % (self.NAME, ar.fin, model.conv_first.attentions[0].input_dim))
-        self.model, self.device, self.B, self.heads = model, dev, int(batch), heads
+        self.heads = heads
         self.row_cap, self.nnz_cap, self.iso_cap = ar.caps if caps is None else caps
+        self._init_protocol(model, dev, batch, ar, max_steps, self._allocate_checked, tickets)
+
+    def _allocate_checked(self):
+        """the capacity batch, and the fused node's check on it"""
+        from . import gat_fused as gf
+        from .gat_encoders import _fused_layer_ok
+        model = self.model
         self._allocate()
         if not all(_fused_layer_ok(l.attentions, self.g, self.row_cap) for l in _layers(model)) or not gf.readout_ok(self.g, self.row_cap):
             self._refuse("needs the fused GAT node on the gathered batch (the dataset's graphs list up to %d edge-less columns per %s)"
                          % (self.iso_cap, "triplet" if self.B == 3 else "entry"))
-        self.records = torch.from_numpy(ar.records).to(dev)
-        self.buf = torch.from_numpy(ar.buf).to(dev)
-        self.ids_out = torch.zeros(self.B, dtype=torch.int32, device=dev)
-        self.max_steps = int(max_steps) if max_steps is not None else None
-        self._sched = self._host = self._parts = None
-        self.T = 0
 
     def _allocate(self):
         """the persistent batch: every array ``gat_fused`` / ``attention`` look up on a ``GraphBatch``, once, at capacity (two
@@ -200,16 +192,13 @@ class GatArenaStream(ArenaStream):
 
     def gather(self):
         """enqueue (current stream; capturable) the launch that writes the batch of the cursor's entry and advances the cursor"""
-        if self._sched is None:
-            raise RuntimeError("%s: load(schedule) before the first step" % self.NAME)
+        entries, ticket = self._loaded(self.NAME)
         ar = self.arena
-        if self._parts is None or self._parts[0] is not self._sched:        # (views of the schedule buffer, made once: load() keeps it)
-            self._parts = (self._sched, self._sched[HEAD:], self._sched[4:HEAD])
         nat.call(self.ENTRY[self.B], self.records, ar.n_graphs, self.buf, ar.words, ar.top[0], ar.top[1], ar.top[2],
-                 self._parts[1], self.max_steps, self._sched, self._parts[2], self._desc.ctypes.data, self.ids_out)
+                 entries, self.max_steps, self._sched, ticket, self._desc.ctypes.data, self.ids_out)
 
 
-class TripletStream(GatArenaStream):
+class TripletStream(TripletSteps, GatArenaStream):
     """``net``: a ``gat_triplet.tripletnet``; ``graphs``: the dataset's graph objects (they are packed once).  The interface of
     ``triplet_stream.TripletStream``: ``load(schedule)`` (``[T, 3]`` indices into ``graphs``), ``gather``, ``embed``,
     ``loss(criterion, target)`` (the step for ``GraphedStep``: every call, every replay, consumes the next entry), ``position``,
@@ -238,15 +227,8 @@ class TripletStream(GatArenaStream):
         self.gather()
         return self.net.embed((self.x, self.g))
 
-    def loss(self, criterion, target):
-        """-> callable for ``GraphedStep``: gather launch + the encoder + the tail + ``criterion(dist_p, dist_n, target)``"""
-        def step():
-            out = self.embed()
-            return criterion(out[0], out[1], target)
-        return step
 
-
-class PostTrainStream(GatArenaStream):
+class PostTrainStream(AnchorSteps, GatArenaStream):
     """An epoch of the 2stg+ post-training steps with --method=GAT (train_triplet_pre_train.py:233-262) from ONE hipGraph: per replay
     the one-piece gather launch (the anchor of "schedule entry number cursor"), the fused GAT layers and the readout over ONE graph's
     capacity, and the loss on the readout row.
@@ -266,6 +248,7 @@ class PostTrainStream(GatArenaStream):
 
     NAME = "gat_stream.PostTrainStream"
     EAGER = "; use the eager drop-in, post_train.post_train_step(model, graph)"
+    STEP_ARGS = {"with_out": False}
 
     def __init__(self, model, graphs, max_steps=None):
         from . import post_train as PT
@@ -284,10 +267,6 @@ class PostTrainStream(GatArenaStream):
         self.labels = torch.from_numpy(labels).to(dev)
         self._warm_up_schedule()
 
-    def _checked(self, anchors):
-        from . import post_train as PT
-        return PT.check_anchors(anchors, self.arena.n_graphs)
-
     def step(self, with_out=True):
         """gather launch + the encoder's readout row + the loss on it -> (loss, pred, out) of the cursor's entry"""
         from . import post_train as PT
@@ -298,15 +277,8 @@ class PostTrainStream(GatArenaStream):
         loss = PT.row_loss(pred, self.ids_out, self.labels)
         return loss, pred, (PT.readout_out(self.model, pred) if with_out else None)
 
-    def step_loss(self):
-        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
-        def step():
-            return self.step(with_out=False)[0]
-        return step
-
 
 # ----------------------------------------------------------------------------- the mini-batch stream (the classification loop)
-MAX_BATCH = 128
 BATCH_EAGER = ("; use the eager route, MiniBatchStream.eager_loss(ids): gat_triplet.assemble of the resident pieces, gat_triplet.readout_rows, "
                "model.head and model.loss")
 
@@ -335,16 +307,11 @@ def entry_sums(records, schedule):
     return _sizes3(records)[np.asarray(schedule, dtype=np.int64)].sum(axis=1)
 
 
-def _top_sum(v, batch):
-    s = np.sort(np.asarray(v, dtype=np.int64))[::-1][:int(batch)]
-    return int(s.sum() + (int(batch) - s.size) * s[0])
-
-
 def default_caps(records, batch):
     """(row_cap, nnz_cap, iso_cap) no entry of ``batch`` DISTINCT graphs exceeds: the sums of the ``batch`` largest nr / nnz / k over
     the dataset, each on its own (a dataset of fewer graphs: the largest stands in for the missing ones)"""
     s = _sizes3(records)
-    return tuple(_top_sum(s[:, c], batch) for c in range(3))
+    return tuple(top_sum(s[:, c], batch) for c in range(3))
 
 
 def schedule_capacity(records, schedule):
@@ -358,29 +325,29 @@ def schedule_capacity(records, schedule):
     return {"row_cap": int(caps[0]), "nnz_cap": int(caps[1]), "iso_cap": int(caps[2])}
 
 
+def _compare(schedule, records, batch, row_cap, nnz_cap, iso_cap):
+    s3 = _sizes3(records)
+    return compare(schedule, len(s3), batch, lambda s: entry_sums(s3, s), (row_cap, nnz_cap, iso_cap))
+
+
 def fits_mask(schedule, records, batch, row_cap, nnz_cap, iso_cap):
     """bool [T]: the entry's rows, entries and listed columns lie within the capacities (duplicates inside an entry count as often as
     they appear).  ``check_schedule``'s ValueError for a wrong shape, a wrong dtype or an index out of range"""
-    s3 = _sizes3(records)
-    s = check_schedule(schedule, len(s3), int(batch))
-    return (entry_sums(s3, s) <= np.array([int(row_cap), int(nnz_cap), int(iso_cap)], dtype=np.int64)).all(axis=1)
+    return ~_compare(schedule, records, batch, row_cap, nnz_cap, iso_cap)[2]
 
 
 def check_fit(schedule, records, batch, row_cap, nnz_cap, iso_cap):
     """-> the checked int32 schedule; ValueError naming the first entry that exceeds a capacity, and the eager route"""
-    s3 = _sizes3(records)
-    s = check_schedule(schedule, len(s3), int(batch))
-    need = entry_sums(s3, s)
-    bad = np.flatnonzero((need > np.array([int(row_cap), int(nnz_cap), int(iso_cap)], dtype=np.int64)).any(axis=1))
-    if bad.size:
-        k = int(bad[0])
+    s, need, over = _compare(schedule, records, batch, row_cap, nnz_cap, iso_cap)
+    if over.any():
+        k = int(np.argmax(over))
         raise ValueError("schedule entry %d has %d rows, %d entries and %d listed edge-less columns: more than this stream's capacity "
                          "(row_cap %d, nnz_cap %d, iso_cap %d)%s" % (k, need[k, 0], need[k, 1], need[k, 2], int(row_cap), int(nnz_cap),
                                                                       int(iso_cap), BATCH_EAGER))
     return s
 
 
-class MiniBatchStream(GatArenaStream):
+class MiniBatchStream(MiniBatchSteps, GatArenaStream):
     """An epoch of the GAT classification loop (Code/sage+gat+diffpool/train.py:104-131 with --method=GAT:
     ``DGATEncoderGraph(final_dim='number_classes')``, ``model.loss(ypred, label)``, clip 2.0, Adam) from ONE hipGraph: the arena of
     ``pack_arena``, a device label table, and per replay the batch gather launch (``tsgnn_gat_batch_gather_f32``,
@@ -417,13 +384,12 @@ class MiniBatchStream(GatArenaStream):
 
     NAME = "gat_stream.MiniBatchStream"
     EAGER = BATCH_EAGER
+    SORT_COLUMN = 2                                                 # (nr: the rows with the ghost representative)
 
     def __init__(self, model, graphs, batch, row_cap=None, nnz_cap=None, iso_cap=None, max_steps=None):
         from . import post_train as PT
         from .gat_encoders import DGATEncoderGraph
-        B = int(batch)
-        if not 1 <= B <= MAX_BATCH:
-            raise ValueError("%s: batch = %d lies outside 1..%d%s" % (self.NAME, B, MAX_BATCH, self.EAGER))
+        B = self._batch_in_range(batch)
         if not isinstance(model, DGATEncoderGraph):
             self._refuse("takes a bare gat_encoders.DGATEncoderGraph")
         if model.final_dim == "output_dim":
@@ -441,14 +407,12 @@ class MiniBatchStream(GatArenaStream):
         if any(c < t for c, t in zip(caps, top)):
             raise ValueError("%s: row_cap %d / nnz_cap %d / iso_cap %d lie below the dataset's largest piece (%d rows, %d entries, %d listed "
                              "edge-less columns)%s" % (self.NAME, caps[0], caps[1], caps[2], top[0], top[1], top[2], self.EAGER))
-        self._build(model, dev, heads, graphs, B, max_steps, caps=tuple(caps), arena=ar)
+        self._build(model, dev, heads, graphs, B, max_steps, caps=tuple(caps), arena=ar, tickets=True)
         if self.row_cap * self.arena.ldf >= 1 << 31:
             raise ValueError("%s: %d rows x %d floats reach 2^31 (int32 offsets)%s" % (self.NAME, self.row_cap, self.arena.ldf, self.EAGER))
         self.n_classes = int(model.label_dim)
         self.graphs, self._host_labels = graphs, labels
-        self.labels = torch.from_numpy(labels).to(dev)
-        self.label = torch.zeros(B, dtype=torch.int64, device=dev)   # int64 [B]: what mp.cross_entropy takes
-        self._tickets = torch.zeros(TICKET_WORDS, dtype=torch.int32, device=dev)
+        self._init_labels(labels)                                   # (label: what mp.cross_entropy takes)
         self._cache = R.cache_for(model)
         self._warm_up_schedule()
 
@@ -468,22 +432,8 @@ class MiniBatchStream(GatArenaStream):
             self._refuse("needs a head the fused head launches take at %d rows (pred_model a Linear on an embedding_dim that is a "
                          "multiple of 4, label_dim <= 256, map2_model the Identity or a Linear)" % B)
 
-    def _warm_up_schedule(self):
-        """with ``max_steps``: a one-entry schedule for the ``GraphedStep``'s warm-up steps — ``batch`` copies of ONE graph, the
-        smallest whose copies fit every capacity.  ValueError, naming ``max_steps``, when no graph's copies fit: the caller then builds
-        the step after the first ``load``"""
-        if self.max_steps is not None:
-            if self.max_steps < 1:
-                raise ValueError("max_steps must be at least 1")
-            rec = self.arena.records.astype(np.int64)
-            one = np.arange(len(rec), dtype=np.int64).reshape(-1, 1).repeat(self.B, axis=1)
-            ok = np.flatnonzero(self.fits(one))
-            if not ok.size:
-                raise ValueError("%s: max_steps asks for a warm-up entry, and %d copies of no graph fit the capacities (row_cap %d, nnz_cap "
-                                 "%d, iso_cap %d); leave max_steps out and build the step after the first load(schedule)"
-                                 % (self.NAME, self.B, self.row_cap, self.nnz_cap, self.iso_cap))
-            g = int(ok[np.argmin(rec[ok, 2])])
-            self.load(np.full((1, self.B), g, dtype=np.int64))
+    def _capacity_words(self):
+        return "the capacities (row_cap %d, nnz_cap %d, iso_cap %d)" % (self.row_cap, self.nnz_cap, self.iso_cap)
 
     def _checked(self, schedule):
         return check_fit(schedule, self.arena.records, self.B, self.row_cap, self.nnz_cap, self.iso_cap)
@@ -491,19 +441,13 @@ class MiniBatchStream(GatArenaStream):
     def fits(self, schedule):
         return fits_mask(schedule, self.arena.records, self.B, self.row_cap, self.nnz_cap, self.iso_cap)
 
-    def mine(self, *args, **kwargs):
-        raise RuntimeError("%s: a schedule entry names a mini-batch, not a triplet: there is no negative to mine" % self.NAME)
-
     def gather(self):
         """enqueue (current stream; capturable) the launch that writes the batch and the labels of the cursor's entry and advances the
         cursor"""
-        if self._sched is None:
-            raise RuntimeError("%s: load(schedule) before the first step" % self.NAME)
+        entries, _ = self._loaded(self.NAME)
         ar = self.arena
-        if self._parts is None or self._parts[0] is not self._sched:        # (a view of the schedule buffer, made once: load() keeps it)
-            self._parts = (self._sched, self._sched[HEAD:])
         nat.call("gat_batch_gather_f32", self.records, ar.n_graphs, self.buf, ar.words, ar.top[0], ar.top[1], ar.top[2], self.labels,
-                 self._parts[1], self.max_steps, self._sched, self._tickets, self.B, self._desc.ctypes.data, self.ids_out, self.label)
+                 entries, self.max_steps, self._sched, self._tickets, self.B, self._desc.ctypes.data, self.ids_out, self.label)
 
     def _head(self, x, g, label):
         r = gt.readout_rows(self.model, x, g)
@@ -514,30 +458,19 @@ class MiniBatchStream(GatArenaStream):
         """gather launch + the encoder's readout rows + the head + the loss -> (loss, ypred [batch, label_dim]) of the cursor's entry"""
         if gt.dropout_active(self.model):
             raise RuntimeError("%s: dropout became active on the model after the stream was built%s" % (self.NAME, self.EAGER))
-        self.gather()
-        return self._head(self.x, self.g, self.label)
+        return super().step()
 
-    def loss(self):
-        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
-        def step():
-            return self.step()[0]
-        return step
+    def _gathered(self):
+        return self.x, self.g
 
     # ------------------------------------------------------------------ the eager route
     def eager_step(self, ids):
         """the same step on the exact batch of ``ids`` (1 to ``batch`` graphs): the resident pieces through ``gat_triplet.assemble``
         (one launch per 8 pieces, host-known sizes), the same readout, head and loss -> (loss, ypred)"""
-        ids = np.asarray(ids)
-        if ids.ndim != 1 or not 1 <= ids.size <= self.B or not np.issubdtype(ids.dtype, np.integer):
-            raise ValueError("eager_loss takes 1 to %d integer indices; got shape %s of %s" % (self.B, ids.shape, ids.dtype))
-        if int(ids.min()) < 0 or int(ids.max()) >= self.arena.n_graphs:
-            raise ValueError("indices must lie in [0, %d)" % self.arena.n_graphs)
+        ids = self._checked_ids(ids)
         if gt.dropout_active(self.model):
             raise RuntimeError("%s: dropout became active on the model after the stream was built" % self.NAME)
         parts = [gt.resident_piece(self.graphs[int(i)], self.device, self._cache) for i in ids]
         x, g = gt.assemble(parts, self.device, self.heads)
         y = torch.from_numpy(self._host_labels[ids].astype(np.int64)).to(self.device)
         return self._head(x, g, y)
-
-    def eager_loss(self, ids):
-        return self.eager_step(ids)[0]

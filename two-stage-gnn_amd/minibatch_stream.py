@@ -27,7 +27,8 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .triplet_stream import Arena, ArenaStream, HEAD, REC_WORDS, TICKET_WORDS, _align4, _graph_dict, check_schedule, pack_arena
+from .triplet_stream import HEAD, TICKET_WORDS, ArenaStream  # noqa: F401  (the stream's vocabulary)
+from .triplet_stream import Arena, REC_WORDS, SageArenaStream, _align4, _graph_dict, check_schedule, pack_arena
 
 MAX_BATCH = 128
 EAGER = "; use the eager route, MiniBatchStream.eager_loss(ids) / tu_data.TUDataset.collate + model.loss(model(x, g)[1], y)"
@@ -178,13 +179,27 @@ def epoch_schedule(n_graphs, batch, rng):
     return perm[:T * batch].reshape(T, batch), perm[T * batch:]
 
 
+def top_sum(v, batch):
+    """the sum of the ``batch`` largest values of ``v`` (fewer values than ``batch``: the largest stands in for the missing ones): what
+    no entry of ``batch`` DISTINCT graphs exceeds"""
+    s = np.sort(np.asarray(v, dtype=np.int64))[::-1][:int(batch)]
+    return int(s.sum() + (int(batch) - s.size) * s[0])
+
+
+def compare(schedule, n_graphs, batch, need_of, caps):
+    """the one need-versus-capacity comparison behind every family's ``fits_mask`` / ``check_fit``: ``check_schedule``'s ValueError
+    for a wrong shape, a wrong dtype or an index out of range, then ``need_of(checked schedule)`` (int64 [T, C]: what every entry
+    needs, duplicates inside an entry counted as often as they appear) against ``caps`` [C] -> (the checked int32 schedule, need,
+    bool [T]: the entry exceeds a capacity)"""
+    s = check_schedule(schedule, n_graphs, int(batch))
+    need = np.asarray(need_of(s), dtype=np.int64)
+    return s, need, (need > np.asarray([int(c) for c in caps], dtype=np.int64)).any(axis=1)
+
+
 def default_capacity(records, batch):
     """(rows, tail entries) no entry of ``batch`` DISTINCT graphs exceeds: the sums of the ``batch`` largest n and ntail of the dataset
     (a dataset of fewer graphs: the largest stands in for the missing ones)"""
-    def top(v):
-        s = np.sort(np.asarray(v, dtype=np.int64))[::-1][:int(batch)]
-        return int(s.sum() + (int(batch) - s.size) * s[0])
-    return top(records[:, 0]), top(records[:, 2])
+    return top_sum(records[:, 0], batch), top_sum(records[:, 2], batch)
 
 
 def entry_sums(records, schedule):
@@ -193,28 +208,94 @@ def entry_sums(records, schedule):
     return rec[schedule, 0].sum(axis=1), rec[schedule, 2].sum(axis=1)
 
 
+def _compare(schedule, records, batch, row_cap, tail_cap):
+    return compare(schedule, len(records), batch, lambda s: np.stack(entry_sums(records, s), axis=1), (row_cap, tail_cap))
+
+
 def fits_mask(schedule, records, batch, row_cap, tail_cap):
     """bool [T]: the entry's row and tail sums lie within the capacities (duplicates inside an entry count as often as they appear).
     ``check_schedule``'s ValueError for a wrong shape, a wrong dtype or an index out of range"""
-    s = check_schedule(schedule, len(records), int(batch))
-    rows, tail = entry_sums(records, s)
-    return (rows <= int(row_cap)) & (tail <= int(tail_cap))
+    return ~_compare(schedule, records, batch, row_cap, tail_cap)[2]
 
 
 def check_fit(schedule, records, batch, row_cap, tail_cap):
     """-> the checked int32 schedule; ValueError naming the first entry that exceeds a capacity"""
-    s = check_schedule(schedule, len(records), int(batch))
-    rows, tail = entry_sums(records, s)
-    bad = np.flatnonzero((rows > int(row_cap)) | (tail > int(tail_cap)))
-    if bad.size:
-        k = int(bad[0])
+    s, need, over = _compare(schedule, records, batch, row_cap, tail_cap)
+    if over.any():
+        k = int(np.argmax(over))
         raise ValueError("schedule entry %d has %d rows and %d tail entries: more than this stream's capacity (row_cap %d, tail_cap %d)%s"
-                         % (k, rows[k], tail[k], int(row_cap), int(tail_cap), EAGER))
+                         % (k, need[k, 0], need[k, 1], int(row_cap), int(tail_cap), EAGER))
     return s
 
 
+# ----------------------------------------------------------------------------- what the families' mini-batch streams share
+class MiniBatchSteps:
+    """The mini-batch layer over an ``ArenaStream``, whatever the family: the batch range, the label buffers, the ``mine()`` refusal,
+    the warm-up entry, the ``ids`` of the eager route, ``step``, ``loss()`` and ``eager_loss()``.  A family supplies ``SORT_COLUMN`` (the
+    record column the warm-up candidates are sorted by), ``_capacity_words()`` (how the warm-up ValueError names its capacities),
+    ``fits`` / ``_checked`` over its own capacities, ``_gathered()`` (what ``_head`` takes of the gathered batch), ``_head(..., label)
+    -> (loss, predictions)`` and ``eager_step(ids)``."""
+
+    SORT_COLUMN = 0
+
+    def _batch_in_range(self, batch):
+        B = int(batch)
+        if not 1 <= B <= MAX_BATCH:
+            raise ValueError("%s: batch = %d lies outside 1..%d%s" % (self.NAME, B, MAX_BATCH, self.EAGER))
+        return B
+
+    def _init_labels(self, table, label=None):
+        """the device label table and ``label``, the int64 [B] the gather launch writes and the loss takes (one that exists already,
+        or a new one)"""
+        self.labels = torch.from_numpy(table).to(self.device)
+        self.label = label if label is not None else torch.zeros(self.B, dtype=torch.int64, device=self.device)
+
+    def mine(self, *args, **kwargs):
+        raise RuntimeError("%s: a schedule entry names a mini-batch, not a triplet: there is no negative to mine" % self.NAME)
+
+    def _warm_up_schedule(self):
+        """with ``max_steps``: a one-entry schedule for the ``GraphedStep``'s warm-up steps — ``batch`` copies of ONE graph, the
+        smallest (by ``SORT_COLUMN``) whose copies fit every capacity.  ValueError, naming ``max_steps``, when no graph's copies fit:
+        the caller then builds the step after the first ``load``"""
+        if self.max_steps is not None:
+            if self.max_steps < 1:
+                raise ValueError("max_steps must be at least 1")
+            rec = self.arena.records.astype(np.int64)
+            one = np.arange(len(rec), dtype=np.int64).reshape(-1, 1).repeat(self.B, axis=1)
+            ok = np.flatnonzero(self.fits(one))
+            if not ok.size:
+                raise ValueError("%s: max_steps asks for a warm-up entry, and %d copies of no graph fit %s; leave max_steps out and "
+                                 "build the step after the first load(schedule)" % (self.NAME, self.B, self._capacity_words()))
+            g = int(ok[np.argmin(rec[ok, self.SORT_COLUMN])])
+            self.load(np.full((1, self.B), g, dtype=np.int64))
+
+    def _checked_ids(self, ids):
+        """the ``ids`` of ``eager_step``: 1 to ``batch`` integer indices into the dataset -> the array; ValueError otherwise"""
+        ids = np.asarray(ids)
+        if ids.ndim != 1 or not 1 <= ids.size <= self.B or not np.issubdtype(ids.dtype, np.integer):
+            raise ValueError("eager_loss takes 1 to %d integer indices; got shape %s of %s" % (self.B, ids.shape, ids.dtype))
+        if int(ids.min()) < 0 or int(ids.max()) >= self.arena.n_graphs:
+            raise ValueError("indices must lie in [0, %d)" % self.arena.n_graphs)
+        return ids
+
+    def step(self):
+        """gather launch + the family's forward, head and loss on the gathered batch -> (loss, predictions [batch, classes]) of the
+        cursor's entry"""
+        self.gather()
+        return self._head(*self._gathered(), self.label)
+
+    def loss(self):
+        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
+        def step():
+            return self.step()[0]
+        return step
+
+    def eager_loss(self, ids):
+        return self.eager_step(ids)[0]
+
+
 # ----------------------------------------------------------------------------- the stream
-class MiniBatchStream(ArenaStream):
+class MiniBatchStream(MiniBatchSteps, SageArenaStream):
     """``model``: a plain ``GcnEncoderGraph`` with concat, bn and a head (``final_dim`` other than 'output_dim') on the GPU; ``dataset``:
     a ``tu_data.TUDataset`` or a list of graph objects (``.graph`` = {'adj', 'feats', 'num_nodes', 'label'[, 'node_label']}).
     ``features``: "table" (a device feature table) or "node-label" (the launch writes the one-hot rows).  ``row_cap`` / ``tail_cap``:
@@ -226,20 +307,26 @@ class MiniBatchStream(ArenaStream):
     step on the exact, unpadded batch of ``ids`` (any size up to ``batch``) built by ``TUDataset.collate``: for entries that do not
     fit and the epoch's remainder.  ``max_steps`` as ``TripletStream`` (the warm-up entry: ``batch`` copies of the smallest graph)."""
 
+    NAME = "MiniBatchStream"
+    TAKES = "takes a GcnEncoderGraph with concat, bn and a head (final_dim other than 'output_dim') under batch statistics"
+    EAGER = EAGER
+
     def __init__(self, model, dataset, batch, nmax=None, row_cap=None, tail_cap=None, features="table", max_steps=None):
+        B = self._batch_in_range(batch)
+        if features not in ("table", "node-label"):
+            raise ValueError("%s: features must be 'table' or 'node-label'%s" % (self.NAME, EAGER))
+        self.features = features
+        super().__init__(model, None, B, nmax, max_steps, pack=lambda: self._pack(model, dataset, B, nmax, row_cap, tail_cap), tickets=True)
+        self._init_labels(self.arena.labels, self.batch.label)      # (label: what model.loss takes)
+        self.node_label = torch.from_numpy(self.arena.node_label).to(self.device) if features == "node-label" else None
+        self._table = None
+        self._warm_up_schedule()
+
+    def _pack(self, model, dataset, B, nmax, row_cap, tail_cap):
+        """once the model and its device have passed: the arena of ``dataset`` and the capacities -> (arena, row_cap, tail_cap)"""
         from .ingest import ELL_W
         from .tu_data import TUDataset
-        name = "MiniBatchStream"
-        B = int(batch)
-        if not 1 <= B <= MAX_BATCH:
-            raise ValueError("%s: batch = %d lies outside 1..%d%s" % (name, B, MAX_BATCH, EAGER))
-        if features not in ("table", "node-label"):
-            raise ValueError("%s: features must be 'table' or 'node-label'%s" % (name, EAGER))
-        takes = "takes a GcnEncoderGraph with concat, bn and a head (final_dim other than 'output_dim') under batch statistics"
-        if not self._model_ok(model):
-            raise TypeError("%s %s%s" % (name, takes, EAGER))
-        if next(model.parameters()).device.type != "cuda":
-            raise TypeError("%s runs on the GPU only%s" % (name, EAGER))
+        name, features = self.NAME, self.features
         try:
             if isinstance(dataset, TUDataset):
                 self.dataset = dataset
@@ -266,15 +353,7 @@ class MiniBatchStream(ArenaStream):
         if row_cap < self.max_n or tail_cap < self.max_tail:
             raise ValueError("%s: row_cap %d / tail_cap %d lie below the dataset's largest graph (%d rows, %d tail entries)%s"
                              % (name, row_cap, tail_cap, self.max_n, self.max_tail, EAGER))
-        self.features = features
-        super().__init__(model, None, B, nmax, max_steps, name=name, takes=takes, eager=EAGER, arena=arena, row_cap=row_cap,
-                         tail_cap=tail_cap)
-        self.labels = torch.from_numpy(arena.labels).to(self.device)
-        self.node_label = torch.from_numpy(arena.node_label).to(self.device) if features == "node-label" else None
-        self.label = self.batch.label                            # int64 [B]: what model.loss takes
-        self._table = None
-        self._tickets = torch.zeros(TICKET_WORDS, dtype=torch.int32, device=self.device)
-        self._warm_up_schedule()
+        return arena, row_cap, tail_cap
 
     def _model_ok(self, model):
         from .dense_encoders import GcnEncoderGraph
@@ -291,20 +370,8 @@ class MiniBatchStream(ArenaStream):
                             "(sage_stack.eligible / head_ok) on this dataset%s" % EAGER)
         return True
 
-    def _warm_up_schedule(self):
-        """with ``max_steps``: a one-entry schedule for the ``GraphedStep``'s warm-up steps — ``batch`` copies of ONE graph, the
-        smallest whose copies fit both capacities (no entry has fewer rows than ``batch`` copies of the smallest graph).  ValueError,
-        naming ``max_steps``, when no graph's copies fit: the caller then builds the step after the first ``load``"""
-        if self.max_steps is not None:
-            if self.max_steps < 1:
-                raise ValueError("max_steps must be at least 1")
-            rec = self.arena.records.astype(np.int64)
-            ok = np.flatnonzero((self.B * rec[:, 0] <= self.row_cap) & (self.B * rec[:, 2] <= self.tail_cap))
-            if not ok.size:
-                raise ValueError("MiniBatchStream: max_steps asks for a warm-up entry, and %d copies of no graph fit row_cap %d / tail_cap %d; "
-                                 "leave max_steps out and build the step after the first load(schedule)" % (self.B, self.row_cap, self.tail_cap))
-            g = int(ok[np.argmin(rec[ok, 0])])
-            self.load(np.full((1, self.B), g, dtype=np.int64))
+    def _capacity_words(self):
+        return "row_cap %d / tail_cap %d" % (self.row_cap, self.tail_cap)
 
     def _checked(self, schedule):
         return check_fit(schedule, self.arena.records, self.B, self.row_cap, self.tail_cap)
@@ -312,33 +379,25 @@ class MiniBatchStream(ArenaStream):
     def fits(self, schedule):
         return fits_mask(schedule, self.arena.records, self.B, self.row_cap, self.tail_cap)
 
-    def mine(self, *args, **kwargs):
-        raise RuntimeError("MiniBatchStream: a schedule entry names a mini-batch, not a triplet: there is no negative to mine")
-
     def gather(self):
         """enqueue (current stream; capturable) the launch that writes the batch and the labels of the cursor's entry and advances
         the cursor"""
-        if self._sched is None:
-            raise RuntimeError("MiniBatchStream: load(schedule) before the first step")
+        entries, _ = self._loaded()
         ar, g, b = self.arena, self.g, self.batch
         ell, ell_w, (tail_ptr, tail_col) = g._ell
         nat.call("batch_gather_f32", self.records, ar.n_graphs, self.buf, ar.off["rowptr"], ar.off["col"], ar.off["tail_ptr"],
                  ar.off["tail_col"], ar.words, self.feats, ar.ld, self.node_label, ar.fin, self.labels, self.max_n, self.max_tail,
-                 self._sched[HEAD:], self.max_steps, self._sched, self._tickets, self.B, ar.nmax, self.row_cap, self.tail_cap, ell_w,
+                 entries, self.max_steps, self._sched, self._tickets, self.B, ar.nmax, self.row_cap, self.tail_cap, ell_w,
                  g.graph_ptr, g.slot_count, g.row_graph, g.row_slot, ell, tail_ptr, tail_col, b.ell_slots, b.tail_slots, self.x,
                  self.x.stride(0), self.ids_out, self.label)
 
-    def step(self):
-        """gather launch + the model on the gathered batch -> (loss, ypred [batch, classes]) of the cursor's entry"""
-        self.gather()
-        ypred = self.model(self.x, self.g)[1]
-        return self.model.loss(ypred, self.label), ypred
+    def _gathered(self):
+        return self.x, self.g
 
-    def loss(self):
-        """-> callable for ``GraphedStep``: gather launch, then ``model.loss(model(x, g)[1], label)``"""
-        def step():
-            return self.step()[0]
-        return step
+    def _head(self, x, g, label):
+        """the model on a batch -> (loss, ypred [batch, classes])"""
+        ypred = self.model(x, g)[1]
+        return self.model.loss(ypred, label), ypred
 
     # ------------------------------------------------------------------ the eager route
     def _host_table(self):
@@ -355,14 +414,6 @@ class MiniBatchStream(ArenaStream):
     def eager_step(self, ids):
         """the same step on the exact, unpadded batch of ``ids`` (1 to ``batch`` graphs) built by ``TUDataset.collate`` ->
         (loss, ypred)"""
-        ids = np.asarray(ids)
-        if ids.ndim != 1 or not 1 <= ids.size <= self.B or not np.issubdtype(ids.dtype, np.integer):
-            raise ValueError("eager_loss takes 1 to %d integer indices; got shape %s of %s" % (self.B, ids.shape, ids.dtype))
-        if int(ids.min()) < 0 or int(ids.max()) >= self.arena.n_graphs:
-            raise ValueError("indices must lie in [0, %d)" % self.arena.n_graphs)
+        ids = self._checked_ids(ids)
         g, x, y = self.dataset.collate(ids.astype(np.int64), self.arena.nmax, self._host_table(), self.device)
-        ypred = self.model(x, g)[1]
-        return self.model.loss(ypred, y), ypred
-
-    def eager_loss(self, ids):
-        return self.eager_step(ids)[0]
+        return self._head(x, g, y)

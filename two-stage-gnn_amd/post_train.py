@@ -34,7 +34,7 @@ import torch.nn.functional as F
 from . import _native as nat
 from . import message_passing as mp
 from . import resident as R
-from .triplet_stream import ArenaStream, _graph_dict, check_schedule
+from .triplet_stream import SageArenaStream, _graph_dict, check_schedule
 
 EAGER = "; use the eager drop-in, post_train.post_train_step(model, graph)"
 
@@ -444,11 +444,27 @@ def check_anchors(anchors, n_graphs):
     return check_schedule(s, n_graphs, 1)
 
 
-class PostTrainSteps:
-    """What the post-training streams over an ``ArenaStream`` at ``batch=1`` share (this module's for the plain ``GcnEncoderGraph``,
-    ``diffpool_stream.PostTrainStream`` for DiffPool): the final_dim and head refusals, the device label table, ``check_anchors`` and
-    the step — the model's concatenated readout rows under per-graph statistics with ``_defer_map``, then the fused head, whose
-    label is ``labels[ids_out[0]]`` read on the device.  ``SIZES``: what the model's forward gets as ``batch_num_nodes``;
+class AnchorSteps:
+    """What every family's post-training stream shares: a schedule entry names ONE graph (``check_anchors``), and the callable for
+    ``GraphedStep`` is the loss of the family's ``step()``.  ``STEP_ARGS``: what ``step_loss()`` passes to ``step``."""
+
+    STEP_ARGS = {}
+
+    def _checked(self, anchors):
+        return check_anchors(anchors, self.arena.n_graphs)
+
+    def step_loss(self):
+        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
+        def step():
+            return self.step(**self.STEP_ARGS)[0]
+        return step
+
+
+class PostTrainSteps(AnchorSteps):
+    """What the post-training streams over a ``SageArenaStream`` at ``batch=1`` share (this module's for the plain ``GcnEncoderGraph``,
+    ``diffpool_stream.PostTrainStream`` for DiffPool): the final_dim and head refusals, the device label table and the step — the
+    model's concatenated readout rows under per-graph statistics with ``_defer_map``, then the fused head, whose label is
+    ``labels[ids_out[0]]`` read on the device.  ``SIZES``: what the model's forward gets as ``batch_num_nodes``;
     ``_readout_width(model)``: the columns of its concatenated readout rows."""
 
     SIZES = None
@@ -456,37 +472,28 @@ class PostTrainSteps:
     def _readout_width(self, model):
         return int(model.pred_input_dim)
 
-    def _init_post_train(self, model, graphs, name, eager):
-        self._pt_name, self._pt_eager = name, eager
+    def _init_post_train(self, model, graphs):
         if model.final_dim != "pretrain":
-            raise TypeError("%s takes a model with final_dim = 'pretrain'%s" % (name, eager))
+            self._refuse("takes a model with final_dim = 'pretrain'")
         layers = head_layers(model)
         P = self._readout_width(model)
         if not _layers_fit(layers, 1, self.device) or layers[0].in_features != P or P % 4:
-            raise TypeError("%s: map_model / map2_model are not the head the fused launches take (post_train.install_head)%s" % (name, eager))
+            raise TypeError("%s: map_model / map2_model are not the head the fused launches take (post_train.install_head)%s"
+                            % (self.NAME, self.EAGER))
         self.n_classes = int(layers[3].out_features)
         self.labels = torch.from_numpy(label_table(graphs, self.n_classes)).to(self.device)
         self._warm_up_schedule()
-
-    def _checked(self, anchors):
-        return check_anchors(anchors, self.arena.n_graphs)
 
     def step(self):
         """gather launch + the stack's readout row + the head -> (loss, pred, out) of the cursor's entry"""
         self.gather()
         r = _readout(self.model, self.x, self.g, self.SIZES, self.x)
         if not head_ok(self.model, r):
-            raise RuntimeError("%s: the fused head does not take this model's readout rows%s" % (self._pt_name, self._pt_eager))
+            raise RuntimeError("%s: the fused head does not take this model's readout rows%s" % (self.NAME, self.EAGER))
         return apply_head(self.model, r, self.ids_out, self.labels)
 
-    def step_loss(self):
-        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
-        def step():
-            return self.step()[0]
-        return step
 
-
-class PostTrainStream(PostTrainSteps, ArenaStream):
+class PostTrainStream(PostTrainSteps, SageArenaStream):
     """An epoch of post-training steps from ONE hipGraph: the arena of ``triplet_stream.pack_arena(..., batch=1)``, a device label
     table, and per replay the gather launch (the anchor of "schedule entry number cursor"), the fused per-graph conv stack on the
     gathered capacity-padded batch and the fused head, whose label is ``labels[ids_out[0]]`` read on the device.
@@ -497,11 +504,13 @@ class PostTrainStream(PostTrainSteps, ArenaStream):
     reference's epoch).  ``step_loss()`` is the callable for ``GraphedStep``.  ``max_steps``: as ``TripletStream``.
     ``gat_stream.PostTrainStream`` and ``diffpool_stream.PostTrainStream`` are the same phase for the other two methods of the driver."""
 
+    NAME = "PostTrainStream"
+    EAGER = EAGER
+
     def __init__(self, model, graphs, nmax=None, max_steps=None):
         graphs = list(graphs)
-        super().__init__(model, graphs, 1, nmax, max_steps, name="PostTrainStream",
-                         takes="takes a GcnEncoderGraph with concat and bn", eager=EAGER)
-        self._init_post_train(model, graphs, "PostTrainStream", EAGER)
+        super().__init__(model, graphs, 1, nmax, max_steps)
+        self._init_post_train(model, graphs)
 
 
 # ----------------------------------------------------------------------------- evaluate() of a model whose `pred` is its readout row

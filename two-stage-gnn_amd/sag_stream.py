@@ -26,15 +26,22 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .minibatch_stream import MAX_BATCH, MiniBatchSteps, compare, top_sum
+from .post_train import AnchorSteps
 from .sag_triplet import _np, tail_ok
-from .triplet_stream import HEAD, TICKET_WORDS, ArenaStream, _align4, check_schedule, schedule_of  # noqa: F401  (the stream's vocabulary)
+from .triplet_stream import HEAD, TICKET_WORDS, Arena, ArenaStream, TripletSteps, _align4, check_schedule, schedule_of  # noqa: F401  (the stream's vocabulary)
 
 REC_WORDS = 8          # int32 words of a graph's record: n, nnz, first row, first entry, index, 0, 0, 0
 EAGER = "; use the eager drop-in, tripletnet.forward(a, p, n)"
 
 
-class Arena:
-    """host arrays of a packed dataset (``pack_arena``):
+def pack_arena(datas, batch=3, limit=1 << 31, n_classes=None, labels=None):
+    """``Data``-like objects (``.x [n, F]``, ``.edge_index [2, E]``: row 0 = source, row 1 = target) -> ``Arena``.  ValueError, naming
+    the graph's index, for what the fused SAGPool node cannot take on a gathered batch: n < 1, n above
+    ``tsgnn_sag_pool_graph_max_nodes()``, an edge id outside the graph, a graph that is not symmetric as a multiset (the in-kernel
+    filter needs it), feature widths that differ; and for offsets that reach ``limit`` (the records are int32).  With ``n_classes``
+    the arena carries ``labels`` (int32 [G]: ``label_table`` of ``data.y`` or of ``labels``).  Pure numpy: no GPU is touched.
+    The arena's fields:
       records  int32 [G, 8]          n, nnz, first row, first entry, the graph's index, 0, 0, 0
       buf      int32 [words]         sections ``rowptr`` | ``col`` at the word offsets ``off[...]`` (each on 16 bytes); graph i's n + 1
                                      row pointers (graph-local) start at ``first row + i``, its columns (graph-local, rows are
@@ -43,17 +50,6 @@ class Arena:
       caps     (rows, nnz)           ``batch`` (3: a triplet, 1: the anchor of the post-training step) times the largest n / nnz: no
                                      entry needs more, also when one object fills every place
       largest  the largest n"""
-
-    def __init__(self, **kw):
-        self.__dict__.update(kw)
-
-
-def pack_arena(datas, batch=3, limit=1 << 31, n_classes=None, labels=None):
-    """``Data``-like objects (``.x [n, F]``, ``.edge_index [2, E]``: row 0 = source, row 1 = target) -> ``Arena``.  ValueError, naming
-    the graph's index, for what the fused SAGPool node cannot take on a gathered batch: n < 1, n above
-    ``tsgnn_sag_pool_graph_max_nodes()``, an edge id outside the graph, a graph that is not symmetric as a multiset (the in-kernel
-    filter needs it), feature widths that differ; and for offsets that reach ``limit`` (the records are int32).  With ``n_classes``
-    the arena carries ``labels`` (int32 [G]: ``label_table`` of ``data.y`` or of ``labels``).  Pure numpy: no GPU is touched."""
     datas = list(datas)
     if not datas:
         raise ValueError("pack_arena: no graphs")
@@ -167,9 +163,6 @@ class SagArenaStream(ArenaStream):
     GATHER = "sag_triplet_gather_f32"
     DEPTH = 3
 
-    def _refuse(self, what):
-        raise TypeError("%s %s%s" % (self.NAME, what, self.EAGER))
-
     def _check_model(self, model):
         """the refusals every SAGPool stream shares -> the model's device"""
         from . import sag_stack
@@ -187,13 +180,17 @@ class SagArenaStream(ArenaStream):
             self._refuse("needs sag_stack's per-graph level kernels with the in-kernel filter")
         return dev
 
-    def _init_arena(self, model, datas, dev, batch, max_steps, arena=None, row_cap=None, nnz_cap=None, level_caps=None):
+    def _init_arena(self, model, datas, dev, batch, max_steps, arena=None, row_cap=None, nnz_cap=None, level_caps=None, tickets=False):
         """pack and upload the dataset (or ``arena``, packed by the caller), allocate the batch at ``batch`` times the largest graph
         (or at ``row_cap`` / ``nnz_cap`` / ``level_caps``: ``MiniBatchStream``, whose ``load`` checks every entry against them)"""
-        ar = self.arena = pack_arena(datas, batch=batch) if arena is None else arena
+        ar = pack_arena(datas, batch=batch) if arena is None else arena
         if ar.fin != int(model.num_features):
             raise ValueError("%s: the dataset has %d features per node, the model takes %d" % (self.NAME, ar.fin, model.num_features))
-        self.model, self.device, self.B = model, dev, int(batch)
+        self._init_protocol(model, dev, batch, ar, max_steps, lambda: self._allocate(row_cap, nnz_cap, level_caps), tickets)
+
+    def _allocate(self, row_cap, nnz_cap, level_caps):
+        """the capacity buffers the gather launch writes and the ``CapacityPlan`` over them"""
+        ar, model, dev = self.arena, self.model, self.device
         self.row_cap = ar.caps[0] if row_cap is None else int(row_cap)
         self.nnz_cap = max(ar.caps[1] if nnz_cap is None else int(nnz_cap), 1)
         self.plan = CapacityPlan(ar.largest, model.pooling_ratio, self.DEPTH, dev, batch=self.B, level_caps=level_caps)
@@ -204,21 +201,13 @@ class SagArenaStream(ArenaStream):
         self._x = f32(self.row_cap, ar.ld)
         self.x = self._x[:, :ar.fin]                        # the node reads fin columns at the row stride ld
         self.g = _CapGraph(self.rowptr, self.col, self.dinv, self.self_w, self.row_cap)
-        self.records = torch.from_numpy(ar.records).to(dev)
-        self.buf = torch.from_numpy(ar.buf).to(dev)
-        self.feats = torch.from_numpy(ar.feats).to(dev)
-        self.ids_out = torch.zeros(self.B, dtype=torch.int32, device=dev)
-        self.max_steps = int(max_steps) if max_steps is not None else None
-        self._sched = self._host = None
-        self.T = 0
 
     def gather(self):
         """enqueue (current stream; capturable) the launch that writes the batch of the cursor's entry and advances the cursor"""
-        if self._sched is None:
-            raise RuntimeError("%s: load(schedule) before the first step" % self.NAME)
+        entries, ticket = self._loaded(self.NAME)
         ar = self.arena
         nat.call(self.GATHER, self.records, ar.n_graphs, self.buf, ar.off["rowptr"], ar.off["col"], ar.words, self.feats,
-                 ar.ld, ar.caps[0], ar.caps[1], self._sched[HEAD:], self.max_steps, self._sched, self._sched[4:HEAD], self.row_cap,
+                 ar.ld, ar.caps[0], ar.caps[1], entries, self.max_steps, self._sched, ticket, self.row_cap,
                  self.nnz_cap, float(self.plan.ratio), self.plan.depth, self.rowptr, self.col, self._x, self._x.stride(0), self.dinv,
                  self.self_w, self.plan.gp_all, self.ids_out)
 
@@ -235,7 +224,7 @@ class SagArenaStream(ArenaStream):
         return sag_stack.sag_stack(self.x, self.g, self.plan, self._params())
 
 
-class TripletStream(SagArenaStream):
+class TripletStream(TripletSteps, SagArenaStream):
     """``net``: a ``sag_triplet.tripletnet`` over a ``sag_layers.Net`` with ``conv="gcn"``; ``datas``: the dataset's ``Data`` objects
     (host or device tensors; they are packed once).  The interface of ``triplet_stream.TripletStream``: ``load(schedule)`` (``[T, 3]``
     indices into ``datas``), ``gather``, ``embed``, ``loss(criterion, target)`` (the step for ``GraphedStep``: every call, every replay,
@@ -260,13 +249,6 @@ class TripletStream(SagArenaStream):
         ``tripletnet.forward`` returns"""
         self.gather()
         return self.net._tail(self.readout())
-
-    def loss(self, criterion, target):
-        """-> callable for ``GraphedStep``: gather launch + the node + the tail + ``criterion(dist_p, dist_n, target)``"""
-        def step():
-            out = self.embed()
-            return criterion(out[0], out[1], target)
-        return step
 
 
 # ----------------------------------------------------------------------------- the post-training phase of 2stg+ (eager)
@@ -375,7 +357,7 @@ def label_table(datas, n_classes, labels=None):
     return out
 
 
-class PostTrainStream(SagArenaStream):
+class PostTrainStream(AnchorSteps, SagArenaStream):
     """An epoch of the SAGPool fine-tuning steps (Code/sag/train_triplet_pre_train.py:219-263: ``F.nll_loss(model(data), data.y)`` on
     ONE graph per optimiser step) from ONE hipGraph: the arena of ``pack_arena(datas, batch=1)``, a device label table, and per replay
     the anchor gather launch (``tsgnn_sag_anchor_gather_f32``: the graph of "schedule entry number cursor" at capacities of one
@@ -409,10 +391,6 @@ class PostTrainStream(SagArenaStream):
         _in_kernel_dropout(max(float(model.dropout_ratio), 0.0), dev)         # (creates the seed and the device counter)
         self._warm_up_schedule()
 
-    def _checked(self, anchors):
-        from .post_train import check_anchors
-        return check_anchors(anchors, self.arena.n_graphs)
-
     def step(self):
         """gather launch + the fused node's readout row + the head -> (loss, out) of the cursor's entry"""
         from . import post_train as PT
@@ -422,15 +400,8 @@ class PostTrainStream(SagArenaStream):
             raise RuntimeError("%s: the fused head does not take this model's readout rows%s" % (self.NAME, self.EAGER))
         return PT.apply_mlp3_nll(self.model, r, self.ids_out, self.labels)
 
-    def step_loss(self):
-        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
-        def step():
-            return self.step()[0]
-        return step
-
 
 # ----------------------------------------------------------------------------- the mini-batch stream (the "original" setting)
-MAX_BATCH = 128
 BATCH_EAGER = "; use the eager route, MiniBatchStream.eager_loss(ids) / mp.nll_loss(Net(use_batch=True)(collated batch), y)"
 
 
@@ -460,21 +431,16 @@ def nnz_sums(records, schedule):
     return np.asarray(records, dtype=np.int64)[:, 1][np.asarray(schedule, dtype=np.int64)].sum(axis=1)
 
 
-def _top_sum(v, batch):
-    s = np.sort(np.asarray(v, dtype=np.int64))[::-1][:int(batch)]
-    return int(s.sum() + (int(batch) - s.size) * s[0])
-
-
 def default_level_caps(records, batch, ratio, depth=3):
     """rows no entry of ``batch`` DISTINCT graphs exceeds, per level: the sum of the ``batch`` largest k^l(n) (k is monotone in n, so
     these are the ``batch`` largest graphs at every level; a dataset of fewer graphs: the largest stands in for the missing ones)"""
     K = k_levels(np.asarray(records, dtype=np.int64)[:, 0], ratio, depth)
-    return [_top_sum(K[:, l], batch) for l in range(int(depth) + 1)]
+    return [top_sum(K[:, l], batch) for l in range(int(depth) + 1)]
 
 
 def default_nnz_cap(records, batch):
     """CSR entries no entry of ``batch`` DISTINCT graphs exceeds (at least 1)"""
-    return max(_top_sum(np.asarray(records, dtype=np.int64)[:, 1], batch), 1)
+    return max(top_sum(np.asarray(records, dtype=np.int64)[:, 1], batch), 1)
 
 
 def schedule_capacity(records, schedule, ratio, depth=3):
@@ -489,24 +455,28 @@ def schedule_capacity(records, schedule, ratio, depth=3):
     return {"row_cap": int(caps[0]), "nnz_cap": int(max(nnz_sums(rec, s).max(), rec[:, 1].max(), 1)), "level_caps": [int(c) for c in caps]}
 
 
+def _compare(schedule, records, batch, row_cap, nnz_cap, level_caps, ratio):
+    """need [T, depth + 3]: the rows of every level, the rows of level 0 once more (against ``row_cap``), the CSR entries"""
+    def need(s):
+        lv = level_sums(records, s, ratio, len(level_caps) - 1)
+        return np.concatenate([lv, lv[:, :1], nnz_sums(records, s).reshape(-1, 1)], axis=1)
+    return compare(schedule, len(records), batch, need, list(level_caps) + [row_cap, nnz_cap])
+
+
 def fits_mask(schedule, records, batch, row_cap, nnz_cap, level_caps, ratio):
     """bool [T]: the entry's rows at every level and its CSR entries lie within the capacities (duplicates inside an entry count as often
     as they appear).  ``check_schedule``'s ValueError for a wrong shape, a wrong dtype or an index out of range"""
-    s = check_schedule(schedule, len(records), int(batch))
-    lv = level_sums(records, s, ratio, len(level_caps) - 1)
-    return (lv <= np.asarray(level_caps, dtype=np.int64)).all(axis=1) & (lv[:, 0] <= int(row_cap)) & (nnz_sums(records, s) <= int(nnz_cap))
+    return ~_compare(schedule, records, batch, row_cap, nnz_cap, level_caps, ratio)[2]
 
 
 def check_fit(schedule, records, batch, row_cap, nnz_cap, level_caps, ratio):
     """-> the checked int32 schedule; ValueError naming the first entry that exceeds a capacity, and the eager route"""
-    s = check_schedule(schedule, len(records), int(batch))
-    lv, nz = level_sums(records, s, ratio, len(level_caps) - 1), nnz_sums(records, s)
-    caps = np.asarray(level_caps, dtype=np.int64)
-    bad = np.flatnonzero((lv > caps).any(axis=1) | (lv[:, 0] > int(row_cap)) | (nz > int(nnz_cap)))
-    if bad.size:
-        k = int(bad[0])
+    s, need, over = _compare(schedule, records, batch, row_cap, nnz_cap, level_caps, ratio)
+    if over.any():
+        k = int(np.argmax(over))
         raise ValueError("schedule entry %d has %s rows (level by level) and %d CSR entries: more than this stream's capacity (row_cap %d, "
-                         "nnz_cap %d, level_caps %s)%s" % (k, lv[k].tolist(), nz[k], int(row_cap), int(nnz_cap), caps.tolist(), BATCH_EAGER))
+                         "nnz_cap %d, level_caps %s)%s" % (k, need[k, :-2].tolist(), need[k, -1], int(row_cap), int(nnz_cap),
+                                                           [int(c) for c in level_caps], BATCH_EAGER))
     return s
 
 
@@ -519,7 +489,7 @@ class _DeviceData:
         self.edge_index = torch.as_tensor(_np(d.edge_index)).long().reshape(2, -1).to(dev)
 
 
-class MiniBatchStream(SagArenaStream):
+class MiniBatchStream(MiniBatchSteps, SagArenaStream):
     """An epoch of the SAGPool family's "original" setting (Code/sag/train.py:181-198: ``DataLoader(batch_size=128, shuffle=True)``,
     ``F.nll_loss(model(data), data.y)``, Adam) from ONE hipGraph: the arena of ``pack_arena(datas, batch=B)``, a device label table, and
     per replay the batch gather launch (``tsgnn_sag_batch_gather_f32``: the B graphs of "schedule entry number cursor" as one batch at
@@ -555,9 +525,7 @@ class MiniBatchStream(SagArenaStream):
     def __init__(self, model, datas, batch, labels=None, row_cap=None, nnz_cap=None, level_caps=None, max_steps=None):
         from . import message_passing as mp
         from .sag_triplet import _in_kernel_dropout, tripletnet
-        B = int(batch)
-        if not 1 <= B <= MAX_BATCH:
-            raise ValueError("%s: batch = %d lies outside 1..%d%s" % (self.NAME, B, MAX_BATCH, self.EAGER))
+        B = self._batch_in_range(batch)
         dev = self._check_model(model)
         if B > 1 and not model.use_batch:
             self._refuse("pools every graph of a mini-batch on its own, which is Net(use_batch=True): use_batch=False keeps the "
@@ -585,31 +553,15 @@ class MiniBatchStream(SagArenaStream):
         if len(caps) != self.DEPTH + 1 or any(c < s for c, s in zip(caps, chain)) or nnz_cap < max(self.max_nnz, 1):
             raise ValueError("%s: level_caps %s / nnz_cap %d lie below the dataset's largest graph (%s rows level by level, %d CSR entries)%s"
                              % (self.NAME, caps, nnz_cap, chain, self.max_nnz, self.EAGER))
-        self._init_arena(model, datas, dev, B, max_steps, arena=ar, row_cap=caps[0], nnz_cap=nnz_cap, level_caps=caps)
+        self._init_arena(model, datas, dev, B, max_steps, arena=ar, row_cap=caps[0], nnz_cap=nnz_cap, level_caps=caps, tickets=True)
         self.level_caps = np.asarray(caps, dtype=np.int64)          # (host: the launch reads it at enqueue time)
-        self.labels = torch.from_numpy(ar.labels).to(dev)
-        self.label = torch.zeros(B, dtype=torch.int64, device=dev)  # int64 [B]: what mp.nll_loss takes
-        self._tickets = torch.zeros(TICKET_WORDS, dtype=torch.int32, device=dev)
+        self._init_labels(ar.labels)                                # (label: what mp.nll_loss takes)
         self.datas, self._dev_datas, self._net = datas, {}, tripletnet(model)
         _in_kernel_dropout(max(float(model.dropout_ratio), 0.0), dev)         # (creates the seed and the device counter)
         self._warm_up_schedule()
 
-    def _warm_up_schedule(self):
-        """with ``max_steps``: a one-entry schedule for the ``GraphedStep``'s warm-up steps — ``batch`` copies of ONE graph, the
-        smallest whose copies fit every capacity.  ValueError, naming ``max_steps``, when no graph's copies fit: the caller then builds
-        the step after the first ``load``"""
-        if self.max_steps is not None:
-            if self.max_steps < 1:
-                raise ValueError("max_steps must be at least 1")
-            rec = self.arena.records.astype(np.int64)
-            one = np.arange(len(rec), dtype=np.int64).reshape(-1, 1).repeat(self.B, axis=1)
-            ok = np.flatnonzero(self.fits(one))
-            if not ok.size:
-                raise ValueError("%s: max_steps asks for a warm-up entry, and %d copies of no graph fit the capacities (level_caps %s, "
-                                 "nnz_cap %d); leave max_steps out and build the step after the first load(schedule)"
-                                 % (self.NAME, self.B, self.level_caps.tolist(), self.nnz_cap))
-            g = int(ok[np.argmin(rec[ok, 0])])
-            self.load(np.full((1, self.B), g, dtype=np.int64))
+    def _capacity_words(self):
+        return "the capacities (level_caps %s, nnz_cap %d)" % (self.level_caps.tolist(), self.nnz_cap)
 
     def _checked(self, schedule):
         return check_fit(schedule, self.arena.records, self.B, self.row_cap, self.nnz_cap, self.level_caps, self.plan.ratio)
@@ -617,17 +569,13 @@ class MiniBatchStream(SagArenaStream):
     def fits(self, schedule):
         return fits_mask(schedule, self.arena.records, self.B, self.row_cap, self.nnz_cap, self.level_caps, self.plan.ratio)
 
-    def mine(self, *args, **kwargs):
-        raise RuntimeError("%s: a schedule entry names a mini-batch, not a triplet: there is no negative to mine" % self.NAME)
-
     def gather(self):
         """enqueue (current stream; capturable) the launch that writes the batch, the graph pointers and the labels of the cursor's
         entry and advances the cursor"""
-        if self._sched is None:
-            raise RuntimeError("%s: load(schedule) before the first step" % self.NAME)
+        entries, _ = self._loaded(self.NAME)
         ar = self.arena
         nat.call(self.GATHER, self.records, ar.n_graphs, self.buf, ar.off["rowptr"], ar.off["col"], ar.words, self.feats, ar.ld,
-                 self.labels, self.max_n, self.max_nnz, self._sched[HEAD:], self.max_steps, self._sched, self._tickets, self.B,
+                 self.labels, self.max_n, self.max_nnz, entries, self.max_steps, self._sched, self._tickets, self.B,
                  self.row_cap, self.nnz_cap, self.level_caps.ctypes.data, float(self.plan.ratio), self.plan.depth, self.rowptr, self.col,
                  self._x, self._x.stride(0), self.dinv, self.self_w, self.plan.gp_all, self.plan.ldg, self.ids_out, self.label)
 
@@ -639,16 +587,8 @@ class MiniBatchStream(SagArenaStream):
         logp = mp.mlp3_log_softmax(r, m.lin1, m.lin2, m.lin3, m.dropout_ratio, m.training)
         return mp.nll_loss(logp, label), logp
 
-    def step(self):
-        """gather launch + the fused node's readout rows + the head -> (loss, logp [batch, C]) of the cursor's entry"""
-        self.gather()
-        return self._head(self.readout(), self.label)
-
-    def loss(self):
-        """-> callable for ``GraphedStep``: every call (every replay) consumes the next entry and returns its loss"""
-        def step():
-            return self.step()[0]
-        return step
+    def _gathered(self):
+        return (self.readout(),)
 
     # ------------------------------------------------------------------ the eager route
     def _device_data(self, i):
@@ -662,14 +602,7 @@ class MiniBatchStream(SagArenaStream):
     def eager_step(self, ids):
         """the same step on the exact, unpadded batch of ``ids`` (1 to ``batch`` graphs): cached structure concatenated on the device,
         ``Net``'s fused forward with host-known sizes, the same head -> (loss, logp)"""
-        ids = np.asarray(ids)
-        if ids.ndim != 1 or not 1 <= ids.size <= self.B or not np.issubdtype(ids.dtype, np.integer):
-            raise ValueError("eager_loss takes 1 to %d integer indices; got shape %s of %s" % (self.B, ids.shape, ids.dtype))
-        if int(ids.min()) < 0 or int(ids.max()) >= self.arena.n_graphs:
-            raise ValueError("indices must lie in [0, %d)" % self.arena.n_graphs)
+        ids = self._checked_ids(ids)
         r = self._net.readout(self._net.batch_of([self._device_data(int(i)) for i in ids]))
         y = torch.from_numpy(self.arena.labels[ids].astype(np.int64)).to(self.device)
         return self._head(r, y)
-
-    def eager_loss(self, ids):
-        return self.eager_step(ids)[0]

@@ -13,8 +13,10 @@ per-graph statistics); DiffPool, SAGPool, GAT and EigenGCN have streams of their
 ``sag_stream``, ``gat_stream``, ``eigen_stream``).  The protocol — the ``[HEAD | schedule]`` buffer, the cursor, the ticket counters —
 is owned here on the host (``HEAD``, ``TICKET_WORDS``, ``ArenaStream.load``) and by csrc/stream_protocol.h on the device.
 
-``ArenaStream`` holds what does not depend on the number of graphs a schedule entry names; ``TripletStream`` (three) and
-``post_train.PostTrainStream`` (one: the anchor of the 2stg+ post-training step) are its users.
+``ArenaStream`` is that protocol on the host and nothing else: every family's stream derives from it.  ``SageArenaStream`` adds the
+GraphSage family's capacity batch and gather launch, whatever the number of graphs a schedule entry names; ``TripletStream`` (three),
+``post_train.PostTrainStream`` (one: the anchor of the 2stg+ post-training step), ``minibatch_stream.MiniBatchStream`` (1..128) and the
+two DiffPool streams are its users.  ``TripletSteps`` is the step every family's triplet stream shares.
 """
 import numpy as np
 import torch
@@ -28,18 +30,8 @@ REC_WORDS = 8          # int32 words of a graph's record: n, nnz, ntail, first r
 
 
 class Arena:
-    """host arrays of a packed dataset (``pack_arena``):
-      records  int32 [G, 8]          n, nnz, ntail, first row, first entry, first tail entry, the graph's index, 0
-      buf      int32 [words]         sections ``rowptr`` | ``col`` | ``tail_ptr`` | ``tail_col`` at the word offsets ``off[...]`` (each on
-                                     16 bytes); graph i's n + 1 row pointers (graph-local) start at ``first row + i``, its tail
-                                     pointers likewise
-      feats    float32 [nodes, ld]   ld = fin rounded up to 4, zero in the pad columns
-      caps     (rows, nnz, tail)     ``batch`` times the largest n / nnz / ntail: no batch of that many graphs needs more, also when
-                                     one object fills several of its places (a sampler may draw an anchor as its own negative's
-                                     positive; the sum of the ``batch`` largest DISTINCT graphs would not cover that)
-      largest  the largest n
-    and, from ``minibatch_stream.pack_arena_tu`` / its graph-object route only: ``labels`` int32 [G] (the graphs' classes) and
-    ``node_label`` int32 [nodes] or None; ``feats`` is None where the gather launch writes one-hot rows from ``node_label``"""
+    """host arrays of a packed dataset: a record of named fields, whatever the family (each ``pack_arena`` says which its arena
+    carries).  Every arena has ``records`` int32 [G, words], ``buf`` int32 [words], ``n_graphs`` and ``batch``."""
 
     def __init__(self, **kw):
         self.__dict__.update(kw)
@@ -57,7 +49,18 @@ def pack_arena(graphs, nmax, ell_w=16, batch=3, limit=1 << 31):
     """graph objects (``.graph`` = {'adj', 'feats', 'num_nodes', ...} as cross_val.split_train_val prepares them, or bare dicts) ->
     ``Arena``.  ValueError, naming the graph's index, for whatever the fused per-graph stack cannot take: num_nodes outside 1..nmax, a
     weight other than 0 / 1 in adj[:n, :n], an adjacency that is not symmetric, feature widths that differ; and for offsets that
-    reach ``limit`` (the records are int32)."""
+    reach ``limit`` (the records are int32).  The arena's fields:
+      records  int32 [G, 8]          n, nnz, ntail, first row, first entry, first tail entry, the graph's index, 0
+      buf      int32 [words]         sections ``rowptr`` | ``col`` | ``tail_ptr`` | ``tail_col`` at the word offsets ``off[...]`` (each on
+                                     16 bytes); graph i's n + 1 row pointers (graph-local) start at ``first row + i``, its tail
+                                     pointers likewise
+      feats    float32 [nodes, ld]   ld = fin rounded up to 4, zero in the pad columns
+      caps     (rows, nnz, tail)     ``batch`` times the largest n / nnz / ntail: no batch of that many graphs needs more, also when
+                                     one object fills several of its places (a sampler may draw an anchor as its own negative's
+                                     positive; the sum of the ``batch`` largest DISTINCT graphs would not cover that)
+      largest  the largest n
+    and, from ``minibatch_stream.pack_arena_tu`` / its graph-object route only: ``labels`` int32 [G] (the graphs' classes) and
+    ``node_label`` int32 [nodes] or None; ``feats`` is None where the gather launch writes one-hot rows from ``node_label``"""
     if ell_w not in (4, 8, 16):
         raise ValueError("ell_w must be 4, 8 or 16")
     graphs = list(graphs)
@@ -147,60 +150,36 @@ def schedule_of(sampler, graphs):
 
 
 class ArenaStream:
-    """What the streams over a packed dataset share, whatever the number ``batch`` of graphs a schedule entry names (3: a triplet,
-    ``TripletStream``; 1: the anchor of the 2stg+ post-training step, ``post_train.PostTrainStream``): the eligibility checks, the arena
-    upload, the capacity-padded batch the gather launch writes, the schedule buffer with cursor and ticket counter, ``load``,
-    ``gather`` and ``position``.  ``model``: a plain ``GcnEncoderGraph`` with concat and bn whose conv stack runs as the fused
-    per-graph node on the gathered batch; anything else is a TypeError that ends in ``eager`` (where the caller's eager drop-in is).
-    The two checks are methods (``_model_ok``, ``_stacks_ok``): a stream for another encoder family (``diffpool_stream.TripletStream``)
-    overrides them.  ``arena``: an ``Arena`` packed by the caller in place of ``pack_arena(graphs, ...)``; ``row_cap`` / ``tail_cap``:
-    capacities in place of the arena's bounds (``minibatch_stream.MiniBatchStream``, whose ``load`` checks every entry against them).
-    A feature table the arena does not carry (``arena.feats`` None) is not uploaded."""
+    """The stream protocol and nothing else, whatever the encoder family and whatever the number ``B`` of graphs a schedule entry names:
+    the uploads of a packed dataset, the ``[HEAD | schedule]`` buffer with cursor and ticket counter, ``load``, ``mine``, ``position``
+    and the views of the loaded schedule every ``gather()`` hands to its launch (``_loaded``).  A family's stream passes its model
+    refusals (``_refuse``: a TypeError that starts with ``NAME`` and ends in ``EAGER``, where the caller's eager drop-in is), packs its
+    arena and calls ``_init_protocol``, handing it the allocation of the capacity batch its gather launch writes; ``SageArenaStream`` below is the
+    GraphSage family's."""
 
-    def __init__(self, model, graphs, batch, nmax=None, max_steps=None, name="ArenaStream", takes="takes a GcnEncoderGraph with concat and bn",
-                 eager="", arena=None, row_cap=None, tail_cap=None):
-        from .ingest import CapacityBatch, ELL_W
-        if not self._model_ok(model):
-            raise TypeError("%s %s%s" % (name, takes, eager))
-        dev = next(model.parameters()).device
-        if dev.type != "cuda":
-            raise TypeError("%s runs on the GPU only%s" % (name, eager))
-        self.model, self.device, self.B = model, dev, int(batch)
-        if arena is None:
-            graphs = list(graphs)
-            if nmax is None:
-                nmax = int(np.asarray(_graph_dict(graphs[0])["adj"]).shape[0])
-            arena = pack_arena(graphs, nmax, ELL_W, batch=self.B)
-        ar = self.arena = arena
-        rows, _, tail = ar.caps
-        self.row_cap = ((rows if row_cap is None else int(row_cap)) + 31) // 32 * 32
-        self.tail_cap = _align4(max(tail if tail_cap is None else int(tail_cap), 1))
-        ghost = min(ar.nmax, ar.largest + 1)
-        # (edge_cap: the compact staging layout's CSR columns, which this path never fills)
-        self.batch = CapacityBatch(self.B, ar.nmax, self.row_cap, 4, ar.fin, dev, ghost_slots=ghost, tail_cap=self.tail_cap)
-        self.g, self.x = self.batch.g, self.batch.x
-        if not self._stacks_ok(model):
-            raise TypeError("%s: the model's conv stack does not run as the fused per-graph node on this dataset%s" % (name, eager))
-        self.records = torch.from_numpy(ar.records).to(dev)
-        self.buf = torch.from_numpy(ar.buf).to(dev)
-        self.feats = torch.from_numpy(ar.feats).to(dev) if ar.feats is not None else None
-        self.ids_out = torch.zeros(self.B, dtype=torch.int32, device=dev)
+    NAME = "ArenaStream"
+    EAGER = ""
+
+    def _refuse(self, what):
+        raise TypeError("%s %s%s" % (self.NAME, what, self.EAGER))
+
+    def _init_protocol(self, model, device, batch, arena, max_steps, allocate, tickets=False):
+        """the state every family's stream has: ``model``, ``device``, ``B`` and ``arena``, then ``allocate()`` (the family's capacity
+        batch and the refusals that need it: device memory is laid out batch first, and a model refused there uploads nothing), the
+        arena's uploads (``feats`` where the arena carries a table), the index output of the gather launch, the empty schedule and,
+        with ``tickets``, the sharded ticket counters of a mini-batch launch"""
+        self.model, self.device, self.B, self.arena = model, device, int(batch), arena
+        allocate()
+        self.records = torch.from_numpy(arena.records).to(device)
+        self.buf = torch.from_numpy(arena.buf).to(device)
+        feats = getattr(arena, "feats", None)
+        self.feats = torch.from_numpy(feats).to(device) if feats is not None else None
+        self.ids_out = torch.zeros(self.B, dtype=torch.int32, device=device)
         self.max_steps = int(max_steps) if max_steps is not None else None
         # int32 [HEAD + max_steps * B]: {cursor, T} as two int64, the ticket counter (+ 3 spare words), then the schedule
-        self._sched = self._host = None
+        self._sched = self._host = self._parts = None
         self.T = 0
-
-    def _model_ok(self, model):
-        """the model check, before anything is packed (a subclass for another encoder family overrides both checks)"""
-        from .dense_encoders import GcnEncoderGraph
-        return type(model) is GcnEncoderGraph and bool(model.concat) and bool(model.bn)
-
-    def _stacks_ok(self, model):
-        """... and on the gathered batch (self.g, self.x, self.arena exist): do the model's stacks run as the fused per-graph node?"""
-        from . import dense_encoders as E, sage_stack
-        convs = model.conv_stack()
-        return bool(sage_stack.eligible(self.g, convs, model.bn, self.x) and E.per_graph_node_ok(self.g, convs)
-                    and convs[0].input_dim == self.arena.fin)
+        self._tickets = torch.zeros(TICKET_WORDS, dtype=torch.int32, device=device) if tickets else None
 
     def _warm_up_schedule(self):
         """with ``max_steps``: the one-entry schedule of graph 0, so that a ``GraphedStep`` can be built before the first epoch's exists"""
@@ -228,6 +207,7 @@ class ArenaStream:
             words = HEAD + self.max_steps * self.B
             self._host = torch.zeros(words, dtype=torch.int32).pin_memory()
             self._sched = torch.zeros(words, dtype=torch.int32, device=self.device)
+            self._parts = (self._sched[HEAD:], self._sched[4:HEAD])           # (made once: every later load keeps the buffer)
         if T > self.max_steps:
             raise ValueError("a schedule of %d entries exceeds this stream's buffer of %d (max_steps: captured steps hold its address)"
                              % (T, self.max_steps))
@@ -238,11 +218,19 @@ class ArenaStream:
         h[HEAD:HEAD + T * self.B] = s.reshape(-1)
         n = HEAD + T * self.B
         self._sched[:n].copy_(self._host[:n])
-        if getattr(self, "_tickets", None) is not None:
+        if self._tickets is not None:
             self._tickets.zero_()
             torch.cuda.current_stream(self.device).synchronize()     # (a GraphedStep replays on a stream of its own)
         self.T = T
         return T
+
+    def _loaded(self, name=None):
+        """what every ``gather()`` starts with: RuntimeError before the first ``load``, else the views of the schedule buffer its launch
+        takes -> (the entries behind ``HEAD``, the ticket words ``[4:HEAD]``).  ``name``: what the error starts with (default: the
+        class's name)"""
+        if self._sched is None:
+            raise RuntimeError("%s: load(schedule) before the first step" % (name or type(self).__name__))
+        return self._parts
 
     def mine(self, emb, index, hardness, count=False):
         """hard / semi-hard negative mining of the LOADED schedule, in place on the device (``mining.mine_negatives`` on
@@ -275,17 +263,6 @@ class ArenaStream:
         torch.cuda.current_stream(self.device).synchronize()
         return cnt
 
-    def gather(self):
-        """enqueue (current stream; capturable) the launch that writes the batch of the cursor's entry and advances the cursor"""
-        if self._sched is None:
-            raise RuntimeError("%s: load(schedule) before the first step" % type(self).__name__)
-        ar, g, b = self.arena, self.g, self.batch
-        ell, ell_w, (tail_ptr, tail_col) = g._ell
-        nat.call("triplet_gather_f32", self.records, ar.n_graphs, self.buf, ar.off["rowptr"], ar.off["col"], ar.off["tail_ptr"],
-                 ar.off["tail_col"], ar.words, self.feats, ar.ld, ar.caps[0], ar.caps[2], self._sched[HEAD:], self.max_steps, self._sched,
-                 self._sched[4:HEAD], self.B, ar.nmax, self.row_cap, self.tail_cap, ell_w, g.graph_ptr, g.slot_count, g.row_graph, g.row_slot,
-                 ell, tail_ptr, tail_col, b.ell_slots, b.tail_slots, self.x, self.x.stride(0), self.ids_out)
-
     def position(self):
         """the cursor: entries consumed since ``load``.  Waits for everything enqueued on the device, whichever stream the steps
         were replayed on (a ``GraphedStep`` has a stream of its own); for tests and epoch boundaries"""
@@ -295,7 +272,85 @@ class ArenaStream:
         return int(self._sched[:2].cpu().numpy().view(np.int64)[0])
 
 
-class TripletStream(ArenaStream):
+class TripletSteps:
+    """the step of a triplet stream, over the family's ``embed()``"""
+
+    def loss(self, criterion, target):
+        """-> callable for ``GraphedStep``: ``embed()`` (the gather launch, the encoder on the gathered batch, the triplet tail) +
+        ``criterion(dist_p, dist_n, target)``; every call (every replay) consumes the next entry"""
+        def step():
+            out = self.embed()
+            return criterion(out[0], out[1], target)
+        return step
+
+
+class SageArenaStream(ArenaStream):
+    """What the GraphSage-family streams share, whatever the number ``batch`` of graphs a schedule entry names (3: ``TripletStream``
+    and ``diffpool_stream.TripletStream``; 1: the anchor of the 2stg+ post-training step, ``post_train.PostTrainStream``; 1..128:
+    ``minibatch_stream.MiniBatchStream``): the eligibility checks, the capacity-padded batch (``ingest.CapacityBatch``) and the gather
+    launch that writes it.  ``model``: a plain ``GcnEncoderGraph`` with concat and bn (``TAKES``) whose conv stack runs as the fused
+    per-graph node on the gathered batch.  The two checks are methods (``_model_ok``, ``_stacks_ok``): a stream for another encoder
+    family (``diffpool_stream.TripletStream``) overrides them.  ``pack``: a callable -> (``Arena``, row capacity, tail capacity) in
+    place of ``pack_arena(graphs, ...)`` and the arena's bounds, run once the model and its device have passed
+    (``minibatch_stream.MiniBatchStream``, whose ``load`` checks every entry against the capacities).  A feature table the arena does
+    not carry (``arena.feats`` None) is not uploaded."""
+
+    TAKES = "takes a GcnEncoderGraph with concat and bn"
+
+    def __init__(self, model, graphs, batch, nmax=None, max_steps=None, pack=None, tickets=False):
+        from .ingest import ELL_W
+        if not self._model_ok(model):
+            self._refuse(self.TAKES)
+        dev = next(model.parameters()).device
+        if dev.type != "cuda":
+            self._refuse("runs on the GPU only")
+        if pack is None:
+            graphs = list(graphs)
+            if nmax is None:
+                nmax = int(np.asarray(_graph_dict(graphs[0])["adj"]).shape[0])
+            ar = pack_arena(graphs, nmax, ELL_W, batch=int(batch))
+            rows, _, tail = ar.caps
+        else:
+            ar, rows, tail = pack()
+        self._init_protocol(model, dev, batch, ar, max_steps, lambda: self._allocate(rows, tail), tickets)
+
+    def _allocate(self, rows, tail):
+        """the capacity-padded batch the gather launch writes, and the model's check on it"""
+        from .ingest import CapacityBatch
+        ar = self.arena
+        self.row_cap = (int(rows) + 31) // 32 * 32
+        self.tail_cap = _align4(max(int(tail), 1))
+        ghost = min(ar.nmax, ar.largest + 1)
+        # (edge_cap: the compact staging layout's CSR columns, which this path never fills)
+        self.batch = CapacityBatch(self.B, ar.nmax, self.row_cap, 4, ar.fin, self.device, ghost_slots=ghost, tail_cap=self.tail_cap)
+        self.g, self.x = self.batch.g, self.batch.x
+        if not self._stacks_ok(self.model):
+            raise TypeError("%s: the model's conv stack does not run as the fused per-graph node on this dataset%s" % (self.NAME, self.EAGER))
+
+    def _model_ok(self, model):
+        """the model check, before anything is packed (a subclass for another encoder family overrides both checks)"""
+        from .dense_encoders import GcnEncoderGraph
+        return type(model) is GcnEncoderGraph and bool(model.concat) and bool(model.bn)
+
+    def _stacks_ok(self, model):
+        """... and on the gathered batch (self.g, self.x, self.arena exist): do the model's stacks run as the fused per-graph node?"""
+        from . import dense_encoders as E, sage_stack
+        convs = model.conv_stack()
+        return bool(sage_stack.eligible(self.g, convs, model.bn, self.x) and E.per_graph_node_ok(self.g, convs)
+                    and convs[0].input_dim == self.arena.fin)
+
+    def gather(self):
+        """enqueue (current stream; capturable) the launch that writes the batch of the cursor's entry and advances the cursor"""
+        entries, ticket = self._loaded()
+        ar, g, b = self.arena, self.g, self.batch
+        ell, ell_w, (tail_ptr, tail_col) = g._ell
+        nat.call("triplet_gather_f32", self.records, ar.n_graphs, self.buf, ar.off["rowptr"], ar.off["col"], ar.off["tail_ptr"],
+                 ar.off["tail_col"], ar.words, self.feats, ar.ld, ar.caps[0], ar.caps[2], entries, self.max_steps, self._sched,
+                 ticket, self.B, ar.nmax, self.row_cap, self.tail_cap, ell_w, g.graph_ptr, g.slot_count, g.row_graph, g.row_slot,
+                 ell, tail_ptr, tail_col, b.ell_slots, b.tail_slots, self.x, self.x.stride(0), self.ids_out)
+
+
+class TripletStream(TripletSteps, SageArenaStream):
     """``net``: a ``triplet.tripletnet`` over a ``GcnEncoderGraph``; ``graphs``: the dataset's graph objects.  Packs and uploads the
     arena once.  ``load(schedule)`` uploads an epoch's triplets ([T, 3] indices into ``graphs``) and sets the cursor to 0;
     ``loss(criterion, target)`` is the step for ``GraphedStep``: every call (every replay) consumes the next entry.  The schedule
@@ -303,10 +358,12 @@ class TripletStream(ArenaStream):
     stream starts on the one-entry schedule [0, 0, 0], so a ``GraphedStep`` can be built (its warm-up steps run) before the first epoch's
     schedule exists."""
 
+    NAME = "TripletStream"
+    TAKES = "takes a tripletnet over a GcnEncoderGraph with concat and bn"
+    EAGER = "; use the eager drop-in, tripletnet.forward(a, p, n)"
+
     def __init__(self, net, graphs, nmax=None, max_steps=None):
-        super().__init__(getattr(net, "model", None), graphs, 3, nmax, max_steps, name="TripletStream",
-                         takes="takes a tripletnet over a GcnEncoderGraph with concat and bn",
-                         eager="; use the eager drop-in, tripletnet.forward(a, p, n)")
+        super().__init__(getattr(net, "model", None), graphs, 3, nmax, max_steps)
         self.net = net
         self._warm_up_schedule()
 
@@ -314,10 +371,3 @@ class TripletStream(ArenaStream):
         """gather + the model on the gathered batch -> (dist_p, dist_n, embed_a, embed_p, embed_n), as ``tripletnet.forward`` returns"""
         self.gather()
         return self.net._embed(self.x, self.g, None, self.x)
-
-    def loss(self, criterion, target):
-        """-> callable for ``GraphedStep``: gather launch + ``net._embed`` on the gathered batch + ``criterion(dist_p, dist_n, target)``"""
-        def step():
-            out = self.embed()
-            return criterion(out[0], out[1], target)
-        return step
