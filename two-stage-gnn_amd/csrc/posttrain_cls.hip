@@ -16,29 +16,16 @@
 // Every output element is written once, every sum runs in a fixed order (rows 0 .. R - 1, the partial sums of a column in order), no
 // read-modify-write anywhere: two runs give the same bits.  Rows R .. RT - 1 of the LDS tiles repeat row R - 1 (forward) or hold
 // zeros (backward), so the row loops have a compile-time length and the accumulators stay in registers.
+// The loops are csrc/head_rows_body.h's bodies at RT = 1, 2, 4, 8: rows_dense16 / rows_dense1 (the EigenGCN head's two layers),
+// rows_chain / rows_dh1, rows_input_columns, rows_outer_tail.  Two stay here: p3_dense, the SAGPool head's 16-byte dense layer,
+// whose pairwise dot product  (wx ax + wy ay) + (wz az + ww aw)  is left to the compiler's contraction, so its bits belong to this
+// very instantiation (as a call of a shared body the forward's outputs changed in the last place); and the mlp3 backward's tail.
 #include "common.h"
+#include "head_rows_body.h"
 #include "mlp3_drop.h"
 #include "../../include/tsgnn.h"
 
 namespace {
-
-constexpr int PC_MAXR = 8;
-
-__device__ __forceinline__ float4 pc_ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
-// a row index of the forward's input rows.  Eight rows: kept in a vector register, so that the eight row addresses are formed per
-// lane (as eight scalar pointers they do not fit the scalar registers beside the kernel's arguments and would be spilled)
-template <int RT>
-__device__ __forceinline__ int pc_row(int i) {
-  if (RT == 8) asm volatile("" : "+v"(i));
-  return i;
-}
-
-// label of row i: labels[ids[i]], both clamped into their tables (the host validates what it can see; these live on the device)
-__device__ __forceinline__ int pc_label(const int* ids, const int* labels, int n_labels, int C, int i) {
-  const int id = min(max(ids[i], 0), n_labels - 1);
-  return min(max(labels[id], 0), C - 1);
-}
 
 // ================================================================================================ SAGPool: mlp3 + nll
 constexpr int P3_WAVES = 8;                  // forward: 512 threads
@@ -84,11 +71,11 @@ __device__ __forceinline__ void p3_dense(const float* in, int64_t ldin, int rows
 #pragma unroll
       for (int u = 0; u < EPW; ++u) {                                      // rows past N: a mapped row, result dropped
         const int j = j0 + P3_WAVES * u;
-        wv[u] = pc_ld4(w + (int64_t)(j < N ? j : 0) * K + 4 * k4);
+        wv[u] = ld4(w + (int64_t)(j < N ? j : 0) * K + 4 * k4);
       }
 #pragma unroll
       for (int i = 0; i < RT; ++i) {
-        const float4 x = pc_ld4(in + (int64_t)pc_row<RT>(min(i, rows - 1)) * ldin + 4 * k4);
+        const float4 x = ld4(in + (int64_t)rows_row<RT>(min(i, rows - 1)) * ldin + 4 * k4);
 #pragma unroll
         for (int u = 0; u < EPW; ++u) s[u][i] += (wv[u].x * x.x + wv[u].y * x.y) + (wv[u].z * x.z + wv[u].w * x.w);
       }
@@ -111,7 +98,7 @@ __device__ __forceinline__ void p3_dense(const float* in, int64_t ldin, int rows
 template <int RT>
 __global__ __launch_bounds__(64 * P3_WAVES) void posttrain_mlp3_nll_fwd_kernel(const P3Fwd a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ float li[PC_MAXR];
+  __shared__ float li[ROWS_MAXR];
   const int R = a.R, D0 = a.D0, D1 = a.D1, D2 = a.D2, C = a.C;
   float* v1 = smem;                      // [RT][D1]
   float* v2 = v1 + RT * D1;              // [RT][D2]
@@ -146,7 +133,7 @@ __global__ __launch_bounds__(64 * P3_WAVES) void posttrain_mlp3_nll_fwd_kernel(c
     s = wave_sum(s);
     const float lse = m + logf(s);
     for (int c = lane; c < C; c += 64) a.logp[wid * C + c] = row[c] - lse;
-    if (lane == 0) li[wid] = lse - row[pc_label(a.ids, a.labels, a.n_labels, C, wid)];
+    if (lane == 0) li[wid] = lse - row[row_label(a.ids, a.labels, a.n_labels, C, wid)];
   }
   __syncthreads();
   if (tid == 0) {
@@ -160,90 +147,10 @@ __global__ __launch_bounds__(64 * P3_WAVES) void posttrain_mlp3_nll_fwd_kernel(c
   }
 }
 
-// out[i][n] = gate(i, n) * sum_q g[i][q] W[q, n]  for i < RT, n < N   (W [Q, N] row-major; g [RT][Q], act [RT][N], out [RT][N],
-// part [RT][4][64] in LDS; gate = scale where act[i][n] > 0, else 0).  64 columns x 4 row lanes per pass.
-template <int RT>
-__device__ __forceinline__ void p3_chain(const float* g, int Q, const float* __restrict__ W, int N, const float* act, float scale,
-                                         float* out, float* part) {
-  const int tid = threadIdx.x, j = tid & 63, k = tid >> 6;
-  for (int n0 = 0; n0 < N; n0 += 64) {
-    const int n = n0 + j;
-    const int nc = n < N ? n : 0;
-    float s[RT];
-#pragma unroll
-    for (int i = 0; i < RT; ++i) s[i] = 0.f;
-#pragma unroll 8
-    for (int q = k; q < Q; q += 4) {
-      const float wv = W[(int64_t)q * N + nc];
-#pragma unroll
-      for (int i = 0; i < RT; ++i) s[i] = fmaf(g[i * Q + q], wv, s[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < RT; ++i) part[(i * 4 + k) * 64 + j] = s[i];
-    __syncthreads();
-    for (int t = tid; t < RT * 64; t += P3_BT) {
-      const int i = t >> 6, jj = t & 63, nn = n0 + jj;
-      if (nn < N) {
-        const float v = (part[(i * 4 + 0) * 64 + jj] + part[(i * 4 + 1) * 64 + jj]) + (part[(i * 4 + 2) * 64 + jj] + part[(i * 4 + 3) * 64 + jj]);
-        out[i * N + nn] = act[i * N + nn] > 0.f ? v * scale : 0.f;
-      }
-    }
-    __syncthreads();
-  }
-}
-
-// this workgroup's 32 columns [32 bx, 32 bx + 32) of r: dr = dz W, dW = dz^T r (W, dW [N, D] row-major; dz [RT][N] in LDS, zero rows
-// past R; part [RT][8][32] in LDS).  Thread (j = tid & 31, k = tid >> 5): column j, rows k, k + 8, ... of W.
-template <int RT>
-__device__ __forceinline__ void pc_input_columns(const float* __restrict__ r, int64_t ldr, int R, int D, const float* __restrict__ w, int N,
-                                                 const float* dz, float* __restrict__ dr, int64_t lddr, float* __restrict__ dw, float* part) {
-  const int tid = threadIdx.x, j = tid & 31, k = tid >> 5;
-  const int d = 32 * (int)blockIdx.x + j;
-  const bool ok = d < D;
-  const int dc = ok ? d : 0;
-  float rv[RT], acc[RT];
-#pragma unroll
-  for (int i = 0; i < RT; ++i) {
-    rv[i] = (ok && i < R) ? r[(int64_t)i * ldr + d] : 0.f;
-    acc[i] = 0.f;
-  }
-  for (int o0 = k; o0 < N; o0 += 64) {                                       // eight rows of W per pass, requested together
-    float wv[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) wv[u] = w[(int64_t)min(o0 + 8 * u, N - 1) * D + dc];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-      const int o = o0 + 8 * u;
-      if (ok && o < N) {
-        float s = 0.f;
-#pragma unroll
-        for (int i = 0; i < RT; ++i) {
-          const float gi = dz[i * N + o];
-          acc[i] = fmaf(gi, wv[u], acc[i]);
-          s = fmaf(gi, rv[i], s);
-        }
-        dw[(int64_t)o * D + d] = s;
-      }
-    }
-  }
-  if (dr) {
-#pragma unroll
-    for (int i = 0; i < RT; ++i) part[(i * 8 + k) * 32 + j] = acc[i];
-    __syncthreads();
-    for (int t = tid; t < RT * 32; t += P3_BT) {
-      const int i = t >> 5, jj = t & 31, dd = 32 * (int)blockIdx.x + jj;
-      float s = 0.f;
-#pragma unroll
-      for (int q = 0; q < 8; ++q) s += part[(i * 8 + q) * 32 + jj];
-      if (i < R && dd < D) dr[(int64_t)i * lddr + dd] = s;
-    }
-  }
-}
-
 template <int RT>
 __global__ __launch_bounds__(P3_BT) void posttrain_mlp3_nll_bwd_kernel(const P3Bwd p) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
-  __shared__ int ys[PC_MAXR];
+  __shared__ int ys[ROWS_MAXR];
   const int tid = threadIdx.x;
   const int R = p.R, D0 = p.D0, D1 = p.D1, D2 = p.D2, C = p.C;
   float* dlg = smem;                     // [RT][C]
@@ -252,7 +159,7 @@ __global__ __launch_bounds__(P3_BT) void posttrain_mlp3_nll_bwd_kernel(const P3B
   float* a1s = dz2 + RT * D2;            // [RT][D1]
   float* dz1 = a1s + RT * D1;            // [RT][D1]
   float* part = dz1 + RT * D1;           // [RT][4][64] (chain) / [RT][8][32] (dr)
-  if (tid < RT) ys[tid] = tid < R ? pc_label(p.ids, p.labels, p.n_labels, C, tid) : -1;
+  if (tid < RT) ys[tid] = tid < R ? row_label(p.ids, p.labels, p.n_labels, C, tid) : -1;
   __syncthreads();
   const float scale = (p.g ? p.g[0] : 1.f) / (float)R;
   for (int k = tid; k < RT * C; k += P3_BT) {                                // dlogits = g (softmax - onehot) / R
@@ -262,10 +169,12 @@ __global__ __launch_bounds__(P3_BT) void posttrain_mlp3_nll_bwd_kernel(const P3B
   for (int k = tid; k < RT * D2; k += P3_BT) a2s[k] = k < R * D2 ? p.a2[k] : 0.f;
   for (int k = tid; k < RT * D1; k += P3_BT) a1s[k] = k < R * D1 ? p.a1[k] : 0.f;
   __syncthreads();
-  p3_chain<RT>(dlg, C, p.w3, D2, a2s, 1.f, dz2, part);                       // dz2 = [a2 > 0] dlogits W3
-  p3_chain<RT>(dz2, D2, p.w2, D1, a1s, p.keep_scale, dz1, part);             // dz1 = keep_scale [a1 > 0] dz2 W2
-  pc_input_columns<RT>(p.r, p.ldr, R, D0, p.w1, D1, dz1, p.dr, p.lddr, p.dw1, part);
-  // dW2 = dz2^T a1, dW3 = dlogits^T a2 and the bias gradients: outer products of LDS vectors, dealt out over the grid
+  rows_chain<RT, P3_BT>(dlg, C, p.w3, D2, a2s, 1.f, dz2, part);               // dz2 = [a2 > 0] dlogits W3
+  rows_chain<RT, P3_BT>(dz2, D2, p.w2, D1, a1s, p.keep_scale, dz1, part);     // dz1 = keep_scale [a1 > 0] dz2 W2
+  rows_input_columns<RT, P3_BT>(p.r, p.ldr, R, D0, p.w1, D0, D1, dz1, p.dr, p.lddr, p.dw1, D0, part);
+  // dW2 = dz2^T a1, dW3 = dlogits^T a2 and the bias gradients: outer products of LDS vectors, dealt out over the grid.  This is
+  // rows_outer_tail's loop, kept here: as a call it costs the RT = 4 instantiation two vector registers (66) and with them the eighth
+  // wave per SIMD (-Rpass-analysis=kernel-resource-usage)
   const int n2 = D2 * D1, n3 = C * D2;
   const int total = n2 + n3 + D1 + D2 + C;
   for (int idx = (int)blockIdx.x * P3_BT + tid; idx < total; idx += (int)gridDim.x * P3_BT) {
@@ -325,74 +234,14 @@ template <int RT>
 __global__ __launch_bounds__(1024) void posttrain_mlp2_ce_fwd_kernel(const P2Fwd a) {
   __shared__ float hs[RT][P2_MAX];
   __shared__ float zs[RT][P2_MAX];
-  __shared__ float li[PC_MAXR];
+  __shared__ float li[ROWS_MAXR];
   constexpr int RPW = RT <= 2 ? 8 : 4;                                      // weight rows per wave and pass
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int R = a.R, D = a.D, H = a.H, C = a.C;
-  const int D4 = D >> 2;
-  for (int h0 = wid * RPW; h0 < H; h0 += 16 * RPW) {
-    float s[RPW][RT];
-#pragma unroll
-    for (int j = 0; j < RPW; ++j)
-#pragma unroll
-      for (int i = 0; i < RT; ++i) s[j][i] = 0.f;
-    for (int c = lane; c < D4; c += 64) {
-      float4 wv[RPW];
-#pragma unroll
-      for (int j = 0; j < RPW; ++j)                                          // rows past H: a mapped row, result dropped
-        wv[j] = reinterpret_cast<const float4*>(a.w1 + (int64_t)min(h0 + j, H - 1) * D)[c];
-#pragma unroll
-      for (int i = 0; i < RT; ++i) {                                         // rows past R: the last row again
-        const float4 rv = reinterpret_cast<const float4*>(a.r + (int64_t)pc_row<RT>(min(i, R - 1)) * a.ldr)[c];
-#pragma unroll
-        for (int j = 0; j < RPW; ++j)
-          s[j][i] = fmaf(wv[j].x, rv.x, fmaf(wv[j].y, rv.y, fmaf(wv[j].z, rv.z, fmaf(wv[j].w, rv.w, s[j][i]))));
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < RPW; ++j)
-#pragma unroll
-      for (int i = 0; i < RT; ++i) {
-        const float t = wave_sum(s[j][i]);
-        const int k = h0 + j;
-        if (lane == 0 && k < H) {
-          const float v = fmaxf(t + (a.b1 ? a.b1[k] : 0.f), 0.f);
-          hs[i][k] = v;
-          if (i < R) a.h[i * H + k] = v;
-        }
-      }
-  }
+  rows_dense16<RT, RPW, 16, true>(a.r, a.ldr, R, D, a.w1, D, a.b1, H, &hs[0][0], P2_MAX, a.h, R);
   __syncthreads();
-  for (int e0 = wid * RPW; e0 < C; e0 += 16 * RPW) {                         // W2's rows are H floats: scalar loads, lanes along the row
-    float s[RPW][RT];
-#pragma unroll
-    for (int j = 0; j < RPW; ++j)
-#pragma unroll
-      for (int i = 0; i < RT; ++i) s[j][i] = 0.f;
-    for (int k = lane; k < H; k += 64) {
-      float wv[RPW];
-#pragma unroll
-      for (int j = 0; j < RPW; ++j) wv[j] = a.w2[(int64_t)min(e0 + j, C - 1) * H + k];
-#pragma unroll
-      for (int i = 0; i < RT; ++i) {
-        const float hv = hs[i][k];
-#pragma unroll
-        for (int j = 0; j < RPW; ++j) s[j][i] = fmaf(wv[j], hv, s[j][i]);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < RPW; ++j)
-#pragma unroll
-      for (int i = 0; i < RT; ++i) {
-        const float t = wave_sum(s[j][i]);
-        const int e = e0 + j;
-        if (lane == 0 && e < C && i < R) {
-          const float v = t + (a.b2 ? a.b2[e] : 0.f);
-          zs[i][e] = v;
-          a.z[i * C + e] = v;
-        }
-      }
-  }
+  // W2's rows are H floats: scalar loads, lanes along the row
+  rows_dense1<RT, RPW, 16>(&hs[0][0], P2_MAX, H, a.w2, a.b2, C, R, false, 0.f, a.z, &zs[0][0], P2_MAX);
   __syncthreads();
   if (wid < R) {                                                            // soft-max and the row's loss: one wave per row
     const float* row = zs[wid];
@@ -404,7 +253,7 @@ __global__ __launch_bounds__(1024) void posttrain_mlp2_ce_fwd_kernel(const P2Fwd
     s = wave_sum(s);
     const float inv = 1.f / s;
     for (int c = lane; c < C; c += 64) a.p[wid * C + c] = expf(row[c] - m) * inv;
-    if (lane == 0) li[wid] = (m + logf(s)) - row[pc_label(a.ids, a.labels, a.n_labels, C, wid)];
+    if (lane == 0) li[wid] = (m + logf(s)) - row[row_label(a.ids, a.labels, a.n_labels, C, wid)];
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -420,10 +269,10 @@ __global__ __launch_bounds__(P3_BT) void posttrain_mlp2_ce_bwd_kernel(const P2Bw
   __shared__ float dh[RT * P2_MAX];          // [RT][H]
   __shared__ float hs[RT * P2_MAX];          // [RT][H]
   __shared__ float part[RT * 256];
-  __shared__ int ys[PC_MAXR];
+  __shared__ int ys[ROWS_MAXR];
   const int tid = threadIdx.x;
   const int R = a.R, D = a.D, H = a.H, C = a.C;
-  if (tid < RT) ys[tid] = tid < R ? pc_label(a.ids, a.labels, a.n_labels, C, tid) : -1;
+  if (tid < RT) ys[tid] = tid < R ? row_label(a.ids, a.labels, a.n_labels, C, tid) : -1;
   __syncthreads();
   const float scale = (a.g ? a.g[0] : 1.f) / (float)R;
   for (int k = tid; k < RT * C; k += P3_BT) {                                // dz = g (softmax - onehot) / R
@@ -432,86 +281,18 @@ __global__ __launch_bounds__(P3_BT) void posttrain_mlp2_ce_bwd_kernel(const P2Bw
   }
   for (int k = tid; k < RT * H; k += P3_BT) hs[k] = k < R * H ? a.h[k] : 0.f;
   __syncthreads();
-  // dh[i, k] = (h[i, k] > 0) sum_c dz[i, c] W2[c, k]: threads along a row of W2, eight rows requested together
-  for (int k = tid; k < H; k += P3_BT) {
-    float s[RT];
-#pragma unroll
-    for (int i = 0; i < RT; ++i) s[i] = 0.f;
-    for (int c0 = 0; c0 < C; c0 += 8) {
-      float wv[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) wv[q] = a.w2[(int64_t)min(c0 + q, C - 1) * H + k];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        if (c0 + q < C) {
-#pragma unroll
-          for (int i = 0; i < RT; ++i) s[i] = fmaf(dz[i * C + c0 + q], wv[q], s[i]);
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < RT; ++i) dh[i * H + k] = hs[i * H + k] > 0.f ? s[i] : 0.f;
-  }
+  rows_dh1<RT, P3_BT>(dz, C, a.w2, H, hs, dh);                                // dh = [h > 0] dz W2
   __syncthreads();
-  pc_input_columns<RT>(a.r, a.ldr, R, D, a.w1, H, dh, a.dr, a.lddr, a.dw1, part);
-  // this workgroup's share of dW2[c, k] = sum_i dz[i, c] h[i, k] and of the bias gradients
-  const int n2 = C * H, total = n2 + H + C;
-  for (int idx = (int)blockIdx.x * P3_BT + tid; idx < total; idx += (int)gridDim.x * P3_BT) {
-    float s = 0.f;
-    if (idx < n2) {
-      const int c = idx / H, k = idx - c * H;
-#pragma unroll
-      for (int i = 0; i < RT; ++i) s = fmaf(dz[i * C + c], hs[i * H + k], s);
-      a.dw2[idx] = s;
-    } else if (idx < n2 + H) {
-      const int k = idx - n2;
-#pragma unroll
-      for (int i = 0; i < RT; ++i) s += dh[i * H + k];
-      if (a.db1) a.db1[k] = s;
-    } else {
-      const int c = idx - n2 - H;
-#pragma unroll
-      for (int i = 0; i < RT; ++i) s += dz[i * C + c];
-      if (a.db2) a.db2[c] = s;
-    }
-  }
-}
-
-inline int pc_rt(int R) { return R <= 1 ? 1 : R <= 2 ? 2 : R <= 4 ? 4 : 8; }
-
-// LDS above 64 KB, the kernel's few static words included, has to be asked for (R = 8 at the envelope's corner: 120 KB of the 160 KB a
-// workgroup may have on gfx950).  Asked ONCE per instantiation, for the most any call of it needs, at the first call that needs it; a
-// refusal is remembered and every such call is TSGNN_EUNSUPPORTED before anything is launched.
-constexpr int PC_MAX_DYN_LDS = 128 * 1024;
-template <typename K>
-inline bool pc_allow_lds(K kernel) {
-  return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, PC_MAX_DYN_LDS) == hipSuccess;
+  rows_input_columns<RT, P3_BT>(a.r, a.ldr, R, D, a.w1, D, H, dh, a.dr, a.lddr, a.dw1, D, part);
+  rows_outer_tail<RT, P3_BT>(dh, dz, nullptr, hs, nullptr, H, C, 0, a.dw2, nullptr, a.db1, a.db2, nullptr);   // dW2 = dz^T h | db1 | db2
 }
 
 }  // namespace
 
 extern "C" {
 
-#define TSGNN_PC_LAUNCH(KERNEL, RT, GRID, BLOCK, LDS)                            \
-  do {                                                                           \
-    if ((LDS) + 1024 > 64 * 1024) {                                              \
-      static const bool allowed_ = pc_allow_lds(KERNEL<RT>);                     \
-      if (!allowed_) return TSGNN_EUNSUPPORTED;                                  \
-    }                                                                            \
-    KERNEL<RT><<<GRID, BLOCK, LDS, stream>>>(a);                                 \
-  } while (0)
-
-#define TSGNN_PC_DISPATCH(KERNEL, GRID, BLOCK, LDS)                              \
-  do {                                                                           \
-    TSGNN_KNAME(#KERNEL "<%d>", rt);                                             \
-    if (rt == 1) TSGNN_PC_LAUNCH(KERNEL, 1, GRID, BLOCK, LDS);                   \
-    else if (rt == 2) TSGNN_PC_LAUNCH(KERNEL, 2, GRID, BLOCK, LDS);              \
-    else if (rt == 4) TSGNN_PC_LAUNCH(KERNEL, 4, GRID, BLOCK, LDS);              \
-    else TSGNN_PC_LAUNCH(KERNEL, 8, GRID, BLOCK, LDS);                           \
-  } while (0)
-
 int tsgnn_posttrain_mlp3_nll_supported(int D0, int D1, int D2, int C, int R) {
-  return (tsgnn_mlp3_triplet_supported(D0, D1, D2, C) && C >= 2 && R >= 1 && R <= PC_MAXR) ? 1 : 0;
+  return (tsgnn_mlp3_triplet_supported(D0, D1, D2, C) && C >= 2 && R >= 1 && R <= ROWS_MAXR) ? 1 : 0;
 }
 
 int tsgnn_posttrain_mlp3_nll_fwd_f32(const float* r, int64_t ldr, int R, const float* w1, const float* b1, float p, uint64_t seed,
@@ -520,12 +301,12 @@ int tsgnn_posttrain_mlp3_nll_fwd_f32(const float* r, int64_t ldr, int R, const f
                                      const int32_t* labels, int64_t n_labels, float* a1, float* a2, float* logp, float* loss,
                                      tsgnn_stream_t stream) {
   if (!r || !w1 || !w2 || !w3 || !ids || !labels || !a1 || !a2 || !logp || !loss || n_labels < 1 || n_labels > 0x7fffffff || R < 1 ||
-      R > PC_MAXR || D0 < 1 || D1 < 1 || D2 < 1 || C < 2 || ldr < D0 || !(p >= 0.f) || !(p < 1.f) || (p > 0.f && (!state || !used)))
+      R > ROWS_MAXR || D0 < 1 || D1 < 1 || D2 < 1 || C < 2 || ldr < D0 || !(p >= 0.f) || !(p < 1.f) || (p > 0.f && (!state || !used)))
     return TSGNN_EINVAL;
   if (!tsgnn_posttrain_mlp3_nll_supported(D0, D1, D2, C, R) || (ldr % 4) ||
       ((reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(w1) | reinterpret_cast<uintptr_t>(w2) | reinterpret_cast<uintptr_t>(w3)) & 15))
     return TSGNN_EUNSUPPORTED;
-  const int rt = pc_rt(R);
+  const int rt = rt_of(R);
   P3Fwd a;
   a.r = r; a.ldr = ldr;
   a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2; a.w3 = w3; a.b3 = b3;
@@ -536,7 +317,7 @@ int tsgnn_posttrain_mlp3_nll_fwd_f32(const float* r, int64_t ldr, int R, const f
   if (p > 0.f) a.drop = Mlp3Drop{mlp3_thresh(p), (unsigned)(seed & 0xffffffffull), (unsigned)(seed >> 32), state, used};
   a.a1 = a1; a.a2 = a2; a.logp = logp; a.loss = loss;
   const size_t lds = sizeof(float) * rt * ((size_t)D1 + D2 + C);                 // <= 64 KB inside _supported
-  TSGNN_PC_DISPATCH(posttrain_mlp3_nll_fwd_kernel, 1, 64 * P3_WAVES, lds);
+  TSGNN_ROWS_DISPATCH(posttrain_mlp3_nll_fwd_kernel, R, 1, 64 * P3_WAVES, lds);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -546,10 +327,10 @@ int tsgnn_posttrain_mlp3_nll_bwd_f32(const float* r, int64_t ldr, int R, const f
                                      const float* a1, const float* a2, const float* logp, const float* g_loss, float* dr, int64_t lddr,
                                      float* dw1, float* db1, float* dw2, float* db2, float* dw3, float* db3, tsgnn_stream_t stream) {
   if (!r || !w1 || !w2 || !w3 || !ids || !labels || !a1 || !a2 || !logp || !dw1 || !dw2 || !dw3 || n_labels < 1 || n_labels > 0x7fffffff ||
-      R < 1 || R > PC_MAXR || D0 < 1 || D1 < 1 || D2 < 1 || C < 2 || ldr < D0 || (dr && lddr < D0))
+      R < 1 || R > ROWS_MAXR || D0 < 1 || D1 < 1 || D2 < 1 || C < 2 || ldr < D0 || (dr && lddr < D0))
     return TSGNN_EINVAL;
   if (!tsgnn_posttrain_mlp3_nll_supported(D0, D1, D2, C, R)) return TSGNN_EUNSUPPORTED;
-  const int rt = pc_rt(R);
+  const int rt = rt_of(R);
   P3Bwd a;
   a.r = r; a.ldr = ldr;
   a.w1 = w1; a.w2 = w2; a.w3 = w3; a.a1 = a1; a.a2 = a2; a.logp = logp;
@@ -559,32 +340,31 @@ int tsgnn_posttrain_mlp3_nll_bwd_f32(const float* r, int64_t ldr, int R, const f
   a.dr = dr; a.lddr = lddr;
   a.dw1 = dw1; a.db1 = db1; a.dw2 = dw2; a.db2 = db2; a.dw3 = dw3; a.db3 = db3;
   const size_t lds = sizeof(float) * rt * ((size_t)C + 2 * D2 + 2 * D1 + 256);   // <= 124 KB inside _supported
-  TSGNN_PC_DISPATCH(posttrain_mlp3_nll_bwd_kernel, (unsigned)((D0 + 31) / 32), P3_BT, lds);
+  TSGNN_ROWS_DISPATCH(posttrain_mlp3_nll_bwd_kernel, R, (unsigned)((D0 + 31) / 32), P3_BT, lds);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
 
 int tsgnn_posttrain_mlp2_ce_supported(int D, int H, int C, int R) {
-  return (tsgnn_mlp2_triplet_supported(D, H, C) && C >= 2 && R >= 1 && R <= PC_MAXR) ? 1 : 0;
+  return (tsgnn_mlp2_triplet_supported(D, H, C) && C >= 2 && R >= 1 && R <= ROWS_MAXR) ? 1 : 0;
 }
 
 int tsgnn_posttrain_mlp2_ce_fwd_f32(const float* r, int64_t ldr, int R, const float* w1, const float* b1, const float* w2, const float* b2,
                                     int D, int H, int C, const int32_t* ids, const int32_t* labels, int64_t n_labels, float* h, float* z,
                                     float* p, float* loss, tsgnn_stream_t stream) {
-  if (!r || !w1 || !w2 || !ids || !labels || !h || !z || !p || !loss || n_labels < 1 || n_labels > 0x7fffffff || R < 1 || R > PC_MAXR ||
+  if (!r || !w1 || !w2 || !ids || !labels || !h || !z || !p || !loss || n_labels < 1 || n_labels > 0x7fffffff || R < 1 || R > ROWS_MAXR ||
       D < 1 || H < 1 || C < 2 || ldr < D)
     return TSGNN_EINVAL;
   if (!tsgnn_posttrain_mlp2_ce_supported(D, H, C, R) || (ldr % 4) ||
       ((reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(w1)) & 15))
     return TSGNN_EUNSUPPORTED;
-  const int rt = pc_rt(R);
   P2Fwd a;
   a.r = r; a.ldr = ldr;
   a.w1 = w1; a.b1 = b1; a.w2 = w2; a.b2 = b2;
   a.ids = ids; a.labels = labels; a.n_labels = (int)n_labels;
   a.R = R; a.D = D; a.H = H; a.C = C;
   a.h = h; a.z = z; a.p = p; a.loss = loss;
-  TSGNN_PC_DISPATCH(posttrain_mlp2_ce_fwd_kernel, 1, 1024, 0);
+  TSGNN_ROWS_DISPATCH(posttrain_mlp2_ce_fwd_kernel, R, 1, 1024, 0);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -593,11 +373,10 @@ int tsgnn_posttrain_mlp2_ce_bwd_f32(const float* r, int64_t ldr, int R, const fl
                                     const int32_t* ids, const int32_t* labels, int64_t n_labels, const float* h, const float* p,
                                     const float* g_loss, float* dr, int64_t lddr, float* dw1, float* db1, float* dw2, float* db2,
                                     tsgnn_stream_t stream) {
-  if (!r || !w1 || !w2 || !ids || !labels || !h || !p || !dw1 || !dw2 || n_labels < 1 || n_labels > 0x7fffffff || R < 1 || R > PC_MAXR ||
+  if (!r || !w1 || !w2 || !ids || !labels || !h || !p || !dw1 || !dw2 || n_labels < 1 || n_labels > 0x7fffffff || R < 1 || R > ROWS_MAXR ||
       D < 1 || H < 1 || C < 2 || ldr < D || (dr && lddr < D))
     return TSGNN_EINVAL;
   if (!tsgnn_posttrain_mlp2_ce_supported(D, H, C, R)) return TSGNN_EUNSUPPORTED;
-  const int rt = pc_rt(R);
   P2Bwd a;
   a.r = r; a.ldr = ldr;
   a.w1 = w1; a.w2 = w2; a.h = h; a.p = p;
@@ -605,12 +384,9 @@ int tsgnn_posttrain_mlp2_ce_bwd_f32(const float* r, int64_t ldr, int R, const fl
   a.R = R; a.D = D; a.H = H; a.C = C;
   a.dr = dr; a.lddr = lddr;
   a.dw1 = dw1; a.db1 = db1; a.dw2 = dw2; a.db2 = db2;
-  TSGNN_PC_DISPATCH(posttrain_mlp2_ce_bwd_kernel, (unsigned)((D + 31) / 32), P3_BT, 0);
+  TSGNN_ROWS_DISPATCH(posttrain_mlp2_ce_bwd_kernel, R, (unsigned)((D + 31) / 32), P3_BT, 0);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
-
-#undef TSGNN_PC_DISPATCH
-#undef TSGNN_PC_LAUNCH
 
 }  // extern "C"

@@ -15,14 +15,19 @@
 // (at most 8 * 64 * 512 multiply-adds on W1 out of the L2: cheaper than a launch of its own), then owns its columns of dr and dW0 and
 // a grid-strided share of the three small weight gradients and the four bias gradients.  Every output element is written once, every
 // sum runs in a fixed order (rows 0 .. R - 1, classes 0 .. C - 1, the eight partial sums of a column in order): two runs give the same
-// bits.  Rows R .. RT - 1 of the LDS tiles hold zeros, so the row loops have a compile-time length and the accumulators stay in
-// registers (no private segment in any variant: -Rpass-analysis=kernel-resource-usage).
+// bits.  Rows R .. RT - 1 of the LDS tiles hold zeros (backward) or what row R - 1 gives, never stored to memory (forward), so the
+// row loops have a compile-time length and the accumulators stay in registers (no private segment in any variant:
+// -Rpass-analysis=kernel-resource-usage).
+// map_model's layer, the three small layers and the backward's block of 32 columns are csrc/head_rows_body.h's rows_dense16,
+// rows_dense1 (one weight row per wave) and rows_input_columns; the soft-max taken twice, the chain through the leaky layers and the
+// index range of the small gradients are this head's own.
 #include "common.h"
+#include "head_rows_body.h"
 #include "../../include/tsgnn.h"
 
 namespace {
 
-constexpr int PT_MAXP = 2048, PT_MAXE = 512, PT_MAXH = 64, PT_MAXC = 64, PT_MAXR = 8;
+constexpr int PT_MAXP = 2048, PT_MAXE = 512, PT_MAXH = 64, PT_MAXC = 64;
 
 struct PtFwd {
   const float* r;
@@ -47,92 +52,26 @@ struct PtBwd {
   float *dw0, *db0, *dw1, *db1, *dw2, *db2, *dw3, *db3;
 };
 
-__device__ __forceinline__ float pt_leaky(float v, float slope) { return v > 0.f ? v : slope * v; }
 __device__ __forceinline__ float pt_leaky_grad(float v, float slope) { return v > 0.f ? 1.f : slope; }   // at exactly 0: slope (torch)
-
-// label of row i: labels[ids[i]], both clamped into their tables (the host validates what it can see; these live on the device)
-__device__ __forceinline__ int pt_label(const int* ids, const int* labels, int n_labels, int C, int i) {
-  const int id = min(max(ids[i], 0), n_labels - 1);
-  return min(max(labels[id], 0), C - 1);
-}
-
-// one small layer for all rows: a wave per output unit n, lanes along the unit's K weights; pre-activations to memory, the
-// (activated) values to the LDS tile of the next layer
-template <int RT>
-__device__ __forceinline__ void pt_small_layer(const float* __restrict__ w, const float* __restrict__ b, int K, int N, int R,
-                                               const float* in, int ldin, float slope, bool act, float* __restrict__ zg, float* aout) {
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  for (int n = wid; n < N; n += 16) {
-    float s[RT];
-#pragma unroll
-    for (int i = 0; i < RT; ++i) s[i] = 0.f;
-    for (int k = lane; k < K; k += 64) {
-      const float wv = w[(int64_t)n * K + k];
-#pragma unroll
-      for (int i = 0; i < RT; ++i) s[i] = fmaf(wv, in[i * ldin + k], s[i]);
-    }
-#pragma unroll
-    for (int i = 0; i < RT; ++i) {
-      const float t = wave_sum(s[i]);
-      if (lane == 0 && i < R) {
-        const float v = t + b[n];
-        zg[i * N + n] = v;
-        aout[i * PT_MAXH + n] = act ? pt_leaky(v, slope) : v;
-      }
-    }
-  }
-}
 
 template <int RT>
 __global__ __launch_bounds__(1024) void posttrain_head_fwd_kernel(const PtFwd a) {
   __shared__ float outs[RT][PT_MAXE];
   __shared__ float act1[RT][PT_MAXH], act2[RT][PT_MAXH], zs[RT][PT_MAXH];
-  __shared__ float li[PT_MAXR];
+  __shared__ float li[ROWS_MAXR];
   constexpr int RPW = RT <= 2 ? 8 : 4;                                  // rows of W0 per wave and pass
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const int R = a.R, P = a.P, E = a.E, h1 = a.h1, h2 = a.h2, C = a.C;
-  const int P4 = P >> 2;
-  for (int j = threadIdx.x; j < RT * PT_MAXE; j += 1024) (&outs[0][0])[j] = 0.f;      // (rows R .. RT - 1 are read by the layers below)
+  for (int j = threadIdx.x; j < RT * PT_MAXE; j += 1024) (&outs[0][0])[j] = 0.f;      // (every word of the tiles is read by the layers below)
   for (int j = threadIdx.x; j < RT * PT_MAXH; j += 1024) (&act1[0][0])[j] = (&act2[0][0])[j] = 0.f;
   __syncthreads();
-  for (int e0 = wid * RPW; e0 < E; e0 += 16 * RPW) {
-    float s[RPW][RT];
-#pragma unroll
-    for (int j = 0; j < RPW; ++j)
-#pragma unroll
-      for (int i = 0; i < RT; ++i) s[j][i] = 0.f;
-    for (int c = lane; c < P4; c += 64) {
-      float4 wv[RPW];
-#pragma unroll
-      for (int j = 0; j < RPW; ++j)                                      // rows past E: a mapped row, result dropped
-        wv[j] = reinterpret_cast<const float4*>(a.w0 + (int64_t)min(e0 + j, E - 1) * P)[c];
-#pragma unroll
-      for (int i = 0; i < RT; ++i) {                                     // rows past R: the last row again, result dropped
-        const float4 rv = reinterpret_cast<const float4*>(a.r + (int64_t)min(i, R - 1) * a.ldr)[c];
-#pragma unroll
-        for (int j = 0; j < RPW; ++j)
-          s[j][i] = fmaf(wv[j].x, rv.x, fmaf(wv[j].y, rv.y, fmaf(wv[j].z, rv.z, fmaf(wv[j].w, rv.w, s[j][i]))));
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < RPW; ++j)
-#pragma unroll
-      for (int i = 0; i < RT; ++i) {
-        const float t = wave_sum(s[j][i]);
-        const int e = e0 + j;
-        if (lane == 0 && e < E && i < R) {
-          const float v = t + a.b0[e];
-          outs[i][e] = v;
-          a.out[i * E + e] = v;
-        }
-      }
-  }
+  rows_dense16<RT, RPW, 16, false>(a.r, a.ldr, R, P, a.w0, P, a.b0, E, &outs[0][0], PT_MAXE, a.out, R);
   __syncthreads();
-  pt_small_layer<RT>(a.w1, a.b1, E, h1, R, &outs[0][0], PT_MAXE, a.slope, true, a.z1, &act1[0][0]);
+  // the three small layers: a wave per output unit, lanes along the unit's weight row
+  rows_dense1<RT, 1, 16>(&outs[0][0], PT_MAXE, E, a.w1, a.b1, h1, R, true, a.slope, a.z1, &act1[0][0], PT_MAXH);
   __syncthreads();
-  pt_small_layer<RT>(a.w2, a.b2, h1, h2, R, &act1[0][0], PT_MAXH, a.slope, true, a.z2, &act2[0][0]);
+  rows_dense1<RT, 1, 16>(&act1[0][0], PT_MAXH, h1, a.w2, a.b2, h2, R, true, a.slope, a.z2, &act2[0][0], PT_MAXH);
   __syncthreads();
-  pt_small_layer<RT>(a.w3, a.b3, h2, C, R, &act2[0][0], PT_MAXH, a.slope, false, a.z, &zs[0][0]);
+  rows_dense1<RT, 1, 16>(&act2[0][0], PT_MAXH, h2, a.w3, a.b3, C, R, false, a.slope, a.z, &zs[0][0], PT_MAXH);
   __syncthreads();
   if (threadIdx.x < R) {
     const int i = threadIdx.x;
@@ -155,7 +94,7 @@ __global__ __launch_bounds__(1024) void posttrain_head_fwd_kernel(const PtFwd a)
     }
     float sp = 0.f;
     for (int c = 0; c < C; ++c) sp += expf(zi[c] - pm);
-    li[i] = (pm + logf(sp)) - zi[pt_label(a.ids, a.labels, a.n_labels, C, i)];
+    li[i] = (pm + logf(sp)) - zi[row_label(a.ids, a.labels, a.n_labels, C, i)];
   }
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -165,13 +104,12 @@ __global__ __launch_bounds__(1024) void posttrain_head_fwd_kernel(const PtFwd a)
   }
 }
 
-// workgroup = 32 columns [32 bx, 32 bx + 32) of r; thread (j = tid & 31, k = tid >> 5): column j, rows k, k + 8, ... of W0
 template <int RT>
 __global__ __launch_bounds__(256) void posttrain_head_bwd_kernel(const PtBwd a) {
   __shared__ float outs[RT][PT_MAXE];
-  __shared__ float douts[RT][PT_MAXE];
+  __shared__ float douts[RT * PT_MAXE];      // [RT][E]
   __shared__ float dzs[RT][PT_MAXC], dz2s[RT][PT_MAXH], dz1s[RT][PT_MAXH], z1s[RT][PT_MAXH], z2s[RT][PT_MAXH];
-  __shared__ float part[RT][8][32];
+  __shared__ float part[RT * 256];
   const int tid = threadIdx.x;
   const int R = a.R, P = a.P, E = a.E, h1 = a.h1, h2 = a.h2, C = a.C;
   const float slope = a.slope;
@@ -194,7 +132,7 @@ __global__ __launch_bounds__(256) void posttrain_head_bwd_kernel(const PtBwd a) 
     float* const d = dzs[i];
     if (i < R) {
       const float* const pi = a.p + i * C;
-      const int y = pt_label(a.ids, a.labels, a.n_labels, C, i);
+      const int y = row_label(a.ids, a.labels, a.n_labels, C, i);
       const float scale = (a.g ? a.g[0] : 1.f) / (float)R;
       float pm = 0.f;
       for (int c = 0; c < C; ++c) pm = fmaxf(pm, pi[c]);
@@ -241,50 +179,10 @@ __global__ __launch_bounds__(256) void posttrain_head_bwd_kernel(const PtBwd a) 
       for (int i = 0; i < RT; ++i) s[i] = fmaf(dz1s[i][j], wv, s[i]);
     }
 #pragma unroll
-    for (int i = 0; i < RT; ++i) douts[i][e] = s[i];
+    for (int i = 0; i < RT; ++i) douts[i * E + e] = s[i];
   }
   __syncthreads();
-  {
-    const int j = tid & 31, k = tid >> 5;
-    const int d = 32 * (int)blockIdx.x + j;
-    const bool ok = d < P;
-    const int dc = ok ? d : 0;
-    float rv[RT], acc[RT];
-#pragma unroll
-    for (int i = 0; i < RT; ++i) {
-      rv[i] = (ok && i < R) ? a.r[(int64_t)i * a.ldr + d] : 0.f;
-      acc[i] = 0.f;
-    }
-    for (int e0 = k; e0 < E; e0 += 64) {                               // eight rows of W0 per pass, requested together
-      float wv[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) wv[q] = a.w0[(int64_t)min(e0 + 8 * q, E - 1) * P + dc];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) {
-        const int e = e0 + 8 * q;
-        if (ok && e < E) {
-          float dw = 0.f;
-#pragma unroll
-          for (int i = 0; i < RT; ++i) {
-            const float gi = douts[i][e];
-            acc[i] = fmaf(gi, wv[q], acc[i]);
-            dw = fmaf(gi, rv[i], dw);
-          }
-          a.dw0[(int64_t)e * P + d] = dw;
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < RT; ++i) part[i][k][j] = acc[i];
-  }
-  __syncthreads();
-  if (a.dr && tid < RT * 32) {
-    const int i = tid >> 5, jj = tid & 31, dd = 32 * (int)blockIdx.x + jj;
-    float s = 0.f;
-#pragma unroll
-    for (int q = 0; q < 8; ++q) s += part[i][q][jj];
-    if (i < R && dd < P) a.dr[(int64_t)i * a.lddr + dd] = s;
-  }
+  rows_input_columns<RT, 256>(a.r, a.ldr, R, P, a.w0, P, E, douts, a.dr, a.lddr, a.dw0, P, part);
   // this workgroup's share of the small gradients: dW1 | dW2 | dW3 | db0 | db1 | db2 | db3 as one index range
   const int n1 = h1 * E, n2 = n1 + h2 * h1, n3 = n2 + C * h2, n4 = n3 + E, n5 = n4 + h1, n6 = n5 + h2, n7 = n6 + C;
   for (int idx = (int)blockIdx.x * 256 + tid; idx < n7; idx += (int)gridDim.x * 256) {
@@ -297,16 +195,16 @@ __global__ __launch_bounds__(256) void posttrain_head_bwd_kernel(const PtBwd a) 
     } else if (idx < n2) {
       const int t = idx - n1, k = t / h1, j = t - k * h1;
 #pragma unroll
-      for (int i = 0; i < RT; ++i) s = fmaf(dz2s[i][k], pt_leaky(z1s[i][j], slope), s);
+      for (int i = 0; i < RT; ++i) s = fmaf(dz2s[i][k], rows_leaky(z1s[i][j], slope), s);
       a.dw2[t] = s;
     } else if (idx < n3) {
       const int t = idx - n2, c = t / h2, k = t - c * h2;
 #pragma unroll
-      for (int i = 0; i < RT; ++i) s = fmaf(dzs[i][c], pt_leaky(z2s[i][k], slope), s);
+      for (int i = 0; i < RT; ++i) s = fmaf(dzs[i][c], rows_leaky(z2s[i][k], slope), s);
       a.dw3[t] = s;
     } else if (idx < n4) {
 #pragma unroll
-      for (int i = 0; i < RT; ++i) s += douts[i][idx - n3];
+      for (int i = 0; i < RT; ++i) s += douts[i * E + idx - n3];
       a.db0[idx - n3] = s;
     } else if (idx < n5) {
 #pragma unroll
@@ -368,7 +266,7 @@ __global__ __launch_bounds__(64) void posttrain_rowloss_fwd_kernel(const PtRowLo
     float sp = 0.f;
     for (int c = lane; c < C; c += 64) sp += expf(expf(zi[c] - m) * inv - pm);
     sp = wave_sum(sp);
-    const int y = pt_label(a.ids, a.labels, a.n_labels, C, i);
+    const int y = row_label(a.ids, a.labels, a.n_labels, C, i);
     total += (pm + logf(sp)) - expf(zi[y] - m) * inv;
   }
   if (lane == 0) a.loss[0] = total / (float)a.R;
@@ -381,7 +279,7 @@ __global__ __launch_bounds__(64) void posttrain_rowloss_bwd_kernel(const PtRowLo
   const float scale = (a.g ? a.g[0] : 1.f) / (float)a.R;
   for (int i = 0; i < a.R; ++i) {
     const float* const pi = a.p + i * C;
-    const int y = pt_label(a.ids, a.labels, a.n_labels, C, i);
+    const int y = row_label(a.ids, a.labels, a.n_labels, C, i);
     float pm = 0.f;
     for (int c = lane; c < C; c += 64) pm = fmaxf(pm, pi[c]);
     pm = wave_max(pm);
@@ -398,7 +296,7 @@ __global__ __launch_bounds__(64) void posttrain_rowloss_bwd_kernel(const PtRowLo
 
 bool pt_dims_ok(int P, int E, int h1, int h2, int C, int R) {
   return P >= 4 && P % 4 == 0 && P <= PT_MAXP && E >= 1 && E <= PT_MAXE && h1 >= 1 && h1 <= PT_MAXH && h2 >= 1 && h2 <= PT_MAXH && C >= 2 &&
-         C <= PT_MAXC && R >= 1 && R <= PT_MAXR;
+         C <= PT_MAXC && R >= 1 && R <= ROWS_MAXR;
 }
 
 }  // namespace
@@ -407,22 +305,12 @@ extern "C" {
 
 int tsgnn_posttrain_head_supported(int P, int E, int h1, int h2, int C, int R) { return pt_dims_ok(P, E, h1, h2, C, R) ? 1 : 0; }
 
-#define TSGNN_PT_DISPATCH(KERNEL, GRID, BLOCK)                                   \
-  do {                                                                           \
-    const int rt = R <= 1 ? 1 : R <= 2 ? 2 : R <= 4 ? 4 : 8;                     \
-    TSGNN_KNAME(#KERNEL "<%d>", rt);                                             \
-    if (rt == 1) KERNEL<1><<<GRID, BLOCK, 0, stream>>>(a);                       \
-    else if (rt == 2) KERNEL<2><<<GRID, BLOCK, 0, stream>>>(a);                  \
-    else if (rt == 4) KERNEL<4><<<GRID, BLOCK, 0, stream>>>(a);                  \
-    else KERNEL<8><<<GRID, BLOCK, 0, stream>>>(a);                               \
-  } while (0)
-
 int tsgnn_posttrain_head_fwd_f32(const float* r, int64_t ldr, int R, int P, const float* w0, const float* b0, int E, const float* w1,
                                  const float* b1, int h1, const float* w2, const float* b2, int h2, const float* w3, const float* b3, int C,
                                  float negative_slope, const int32_t* ids, const int32_t* labels, int64_t n_labels, float* out, float* z1,
                                  float* z2, float* z, float* p, float* loss, hipStream_t stream) {
   if (!r || !w0 || !b0 || !w1 || !b1 || !w2 || !b2 || !w3 || !b3 || !ids || !labels || !out || !z1 || !z2 || !z || !p || !loss ||
-      n_labels < 1 || n_labels > 0x7fffffff || R < 1 || R > PT_MAXR || P < 1 || E < 1 || h1 < 1 || h2 < 1 || C < 2 || ldr < P)
+      n_labels < 1 || n_labels > 0x7fffffff || R < 1 || R > ROWS_MAXR || P < 1 || E < 1 || h1 < 1 || h2 < 1 || C < 2 || ldr < P)
     return TSGNN_EINVAL;
   if (!pt_dims_ok(P, E, h1, h2, C, R) || (ldr % 4) || ((reinterpret_cast<uintptr_t>(r) | reinterpret_cast<uintptr_t>(w0)) & 15))
     return TSGNN_EUNSUPPORTED;
@@ -433,7 +321,7 @@ int tsgnn_posttrain_head_fwd_f32(const float* r, int64_t ldr, int R, int P, cons
   a.R = R; a.P = P; a.E = E; a.h1 = h1; a.h2 = h2; a.C = C;
   a.slope = negative_slope;
   a.out = out; a.z1 = z1; a.z2 = z2; a.z = z; a.p = p; a.loss = loss;
-  TSGNN_PT_DISPATCH(posttrain_head_fwd_kernel, 1, 1024);
+  TSGNN_ROWS_DISPATCH(posttrain_head_fwd_kernel, R, 1, 1024, 0);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
@@ -444,7 +332,7 @@ int tsgnn_posttrain_head_bwd_f32(const float* r, int64_t ldr, int R, int P, cons
                                  float* dr, int64_t lddr, float* dw0, float* db0, float* dw1, float* db1, float* dw2, float* db2, float* dw3,
                                  float* db3, hipStream_t stream) {
   if (!r || !w0 || !w1 || !w2 || !w3 || !ids || !labels || !out || !z1 || !z2 || !p || !dw0 || !db0 || !dw1 || !db1 || !dw2 || !db2 ||
-      !dw3 || !db3 || n_labels < 1 || n_labels > 0x7fffffff || R < 1 || R > PT_MAXR || P < 1 || E < 1 || h1 < 1 || h2 < 1 || C < 2 ||
+      !dw3 || !db3 || n_labels < 1 || n_labels > 0x7fffffff || R < 1 || R > ROWS_MAXR || P < 1 || E < 1 || h1 < 1 || h2 < 1 || C < 2 ||
       ldr < P || (dr && lddr < P))
     return TSGNN_EINVAL;
   if (!pt_dims_ok(P, E, h1, h2, C, R)) return TSGNN_EUNSUPPORTED;
@@ -456,14 +344,12 @@ int tsgnn_posttrain_head_bwd_f32(const float* r, int64_t ldr, int R, int P, cons
   a.slope = negative_slope;
   a.dr = dr; a.lddr = lddr;
   a.dw0 = dw0; a.db0 = db0; a.dw1 = dw1; a.db1 = db1; a.dw2 = dw2; a.db2 = db2; a.dw3 = dw3; a.db3 = db3;
-  TSGNN_PT_DISPATCH(posttrain_head_bwd_kernel, (unsigned)((P + 31) / 32), 256);
+  TSGNN_ROWS_DISPATCH(posttrain_head_bwd_kernel, R, (unsigned)((P + 31) / 32), 256, 0);
   TSGNN_CHECK_LAUNCH();
   return TSGNN_OK;
 }
 
-#undef TSGNN_PT_DISPATCH
-
-int tsgnn_posttrain_rowloss_supported(int C, int R) { return (C >= 2 && C <= PT_ROW_MAXC && R >= 1 && R <= PT_MAXR) ? 1 : 0; }
+int tsgnn_posttrain_rowloss_supported(int C, int R) { return (C >= 2 && C <= PT_ROW_MAXC && R >= 1 && R <= ROWS_MAXR) ? 1 : 0; }
 
 int tsgnn_posttrain_rowloss_fwd_f32(const float* z, int64_t ldz, int R, int C, const int32_t* ids, const int32_t* labels, int64_t n_labels,
                                     float* p, float* loss, hipStream_t stream) {
